@@ -7,7 +7,12 @@ Adam, fp32.  N > 1 (launched by torch.distributed.run, one rank per GPU) is weak
 runs the same per-GPU batch and gradients are all-reduced over RCCL; `value` counts the batch-32 steps
 completed by ALL ranks per second.  Inputs are resident in HBM before the timed region.
 
-Besides the contract line it reports
+A plain run sets up, warms up, times EXACTLY --steps steps (one block; --min-seconds S repeats the block until S seconds
+have been measured and reports the median block), writes the generated frames of the last timed step with --dump-outputs
+DIR (DIR/generated_frames.npy, float32: what Trainer.train_g returns to its caller; a fixed seeded sample above 48 MiB)
+and prints the result line.  Inputs are seeded: the same arguments give the same inputs from run to run.
+
+With --full the result line also reports
   roofline      every conv/deconv fwd, dgrad, wgrad launch of the step (+ their split-K reductions): algorithmic
                 FLOPs (2*B*OH*OW*KH*KW*Cin*Cout per contraction) / their duration IN SITU, against the
                 fp32 matrix-core peak (157.3 TFLOP/s; 2.5 PFLOP/s with --dtype bf16);
@@ -21,7 +26,8 @@ Besides the contract line it reports
                 2-20 % faster; it is kept as the labelled second field `hot_relaunch` and is the fallback (said so in
                 `timing`) when no in-situ profile of the workload is committed;
   cpu_baseline  the CPU restatement of the reference step (oracle/, torch-CPU fp32; TF-1.0 itself cannot
-                run here) on this host's cores, on a bounded sample of the same workload.
+                run here) on this host's cores, on a bounded sample of the same workload;
+  eval_rollout, api_rates, op_ms_per_step, kernel_ms_per_step_insitu   (each null in a plain run).
 """
 import argparse
 import json
@@ -38,6 +44,7 @@ import torch         # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md chip table
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # dense
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: larger frame batches are written as a seeded sample of this size
 
 
 def slab_mode(v):
@@ -65,6 +72,9 @@ def parse():
     ap.add_argument('--no-adv', action='store_true')
     ap.add_argument('--no-graphs', action='store_true', help='eager launches instead of HIP-graph replay')
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='conv arithmetic: exact fp32 MFMA (BASELINE config 2) or bf16 MFMA operands with fp32 storage/accumulation (configs 3, 5)')
+    ap.add_argument('--full', action='store_true', help='also the side measurements after the timed region: roofline (instrumented pass), eval rollout, '
+                                                         'API rates, CPU baseline; a plain run reports the headline only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the generated frames of the last timed step to DIR/generated_frames.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-dgrad-limit', action='store_true', help='experiment: input gradients also compute the columns of the tiled action channels (acg_conv_desc dgrad_c unset)')
     ap.add_argument('--profile-repeats', type=int, default=3)
@@ -76,10 +86,10 @@ def parse():
     ap.add_argument('--no-pair', action='store_true', help='experiment: a layer\'s dgrad and wgrad as two launches instead of one')
     ap.add_argument('--dp-collectives', default=None, choices=['stream', 'side'], help='gradient all-reduces (ncclAllReduce captured into the step\'s HIP graph) on the compute stream in program order, or on a side HIP stream overlapping the rest of backward; default: side with more than one rank')
     ap.add_argument('--buckets', type=int, default=0, help='gradient all-reduce buckets per optimizer (data parallel); 0 = 1 for in-order collectives, 2 for side-stream ones')
-    ap.add_argument('--min-seconds', type=float, default=1.0, help='the timed K-step block is repeated until this much time has been measured; the median block is reported')
+    ap.add_argument('--min-seconds', type=float, default=0.0, help='the timed K-step block is repeated until this much time has been measured; the median block is reported (default: one block)')
     ap.add_argument('--exact-global-batch', action='store_true', help='data parallel that reproduces one device at the global batch: SyncBN + GDL scaling + global state-loss norm')
     ap.add_argument('--sync-bn', action='store_true', help='data parallel with BatchNorm statistics of the global batch (one small all-reduce per BatchNorm layer and direction)')
-    ap.add_argument('--trace-run', action='store_true', help='nothing but training steps (no rollout, no instrumented pass, no CPU baseline): the run tools/insitu_times.py reduces a rocprofv3 kernel trace of')
+    ap.add_argument('--trace-run', action='store_true', help='nothing but training steps, even with --full (no rollout, no instrumented pass, no CPU baseline): the run tools/insitu_times.py reduces a rocprofv3 kernel trace of')
     ap.add_argument('--force-dp', action='store_true', help='run the data-parallel machinery (RCCL all-reduce buckets, graph segments) even on one rank')
     ap.add_argument('--bn-grid-exchange', default='auto', choices=['auto', 'on', 'off', 'not-beside-collectives'],
                     help="the one-launch BatchNorm kernels (all blocks of a grid resident at once): 'auto' = with more than one rank under side-stream collectives "
@@ -266,8 +276,8 @@ def main():
             dt = float(t.item())
         return dt, out
 
-    # a K-step block can be a few tens of milliseconds: repeat it until --min-seconds have been measured (every rank
-    # derives the same count from the max-reduced first block) and report the median block
+    # one block of exactly --steps steps; with --min-seconds the block is repeated until that much time has been measured
+    # (every rank derives the same count from the max-reduced first block) and the median block is reported
     first, frames = timed_block()
     blocks = [first]
     repeats = int(min(max(np.ceil(args.min_seconds / max(first, 1e-6)), 1), 200))
@@ -276,11 +286,20 @@ def main():
         blocks.append(dt)
     elapsed = float(np.median(blocks))
     assert torch.isfinite(frames).all(), 'generated frames are not finite'
+    if args.dump_outputs and rank == 0:
+        # copied before anything else runs (--full's side measurements replay the same programs and their output buffers)
+        out = frames.detach().float().cpu().numpy()
+        if out.nbytes > DUMP_MAX_BYTES:      # a fixed, seeded sample of the flattened frames (same elements every run)
+            pick = np.random.default_rng(0).choice(out.size, DUMP_MAX_BYTES // 4, replace=False)
+            out = out.reshape(-1)[np.sort(pick)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'generated_frames.npy'), out)
+    extras = args.full and not args.trace_run      # the side measurements below; a plain run goes straight to the result line
 
     # ---- eval rollout: Trainer.test_sequence, T-1 recursive G-only steps through the
     # reference's numpy-in / numpy-out API (train.py:157-176), after the timed region ---------------------------
     rollout = None
-    if rank == 0 and dna and world == 1 and not args.trace_run:      # a one-GPU side metric; multi-GPU runs go straight to the result line
+    if rank == 0 and dna and world == 1 and extras:      # a one-GPU side metric; multi-GPU runs go straight to the result line
         r_img = rng.uniform(-1, 1, (B, args.seq_len, S, S, 3)).astype(np.float32)
         r_act = rng.standard_normal((B, args.seq_len, 10)).astype(np.float32)
         for _ in range(3):
@@ -299,7 +318,7 @@ def main():
     # (no look-ahead: what `value` was up to round 4), and through the reference's own API exactly as train() drives it
     # (train.py:241-263: host numpy sequences, pair selection, numpy feeds, generated frames fetched to the host every step)
     api_rates = None
-    if not args.trace_run and not args.no_api_rates and world == 1:      # (time-bounded loops: with several ranks the step counts - and with them the collectives - would differ per rank)
+    if extras and not args.no_api_rates and world == 1:      # (time-bounded loops: with several ranks the step counts - and with them the collectives - would differ per rank)
         def rate(fn, seconds=0.5):
             for i in range(4):
                 fn(i)
@@ -331,7 +350,7 @@ def main():
     roof, roof_dna, kernel_ms, insitu = None, None, {}, None
     # EVERY rank runs the instrumented pass: with world > 1 the programs contain gradient all-reduces, and a
     # collective issued by rank 0 alone would never complete.  Only rank 0 reports.
-    if not args.trace_run:
+    if extras:
         d_in0, g_in0, pair0, _ = pool[0]
         zero_state = torch.zeros(B, 5, device=device)
         recs = []
@@ -474,7 +493,7 @@ def main():
         _leave_distributed(sess)
         return
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.trace_run:
+    if world == 1 and not args.no_cpu_baseline and extras:
         cpu = cpu_baseline(args, n_critic)
     # which BASELINE.json configuration this run is: config 2 itself (the headline), or the per-GPU shard of configs 3 / 4
     # (global batch 256 / 128 over 8 / 4 GPUs = 32 per GPU) or config 5's geometry at 32 per GPU (its per-GPU batch is not stated)
@@ -513,7 +532,7 @@ def main():
         # per kernel family, in situ (same source as `roofline.timing`); null without a committed profile of this workload
         'kernel_ms_per_step_insitu': ({k: round(v / 1e3, 4) for k, v in insitu['family_us_per_step'].items()} if insitu else None),
         # per op kind, this process: an event pair around every eager launch (includes the ~4 us the event records open per op)
-        'op_ms_per_step': {k: round(v, 4) for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1])},
+        'op_ms_per_step': {k: round(v, 4) for k, v in sorted(kernel_ms.items(), key=lambda kv: -kv[1])} if extras else None,
     }
     result_out.write(json.dumps(line) + '\n')
     result_out.flush()

@@ -5,8 +5,8 @@ OUT=$1; LIB=$2; mkdir -p $OUT
 for rep in 1 2; do
 for v in new old; do
   if [ $v = old ]; then L="--lib $LIB"; else L=""; fi
-  python3 bench.py --dtype bf16 --no-cpu-baseline $L > $OUT/c3_${rep}_$v.json 2>$OUT/err.txt
-  python3 bench.py --dtype bf16 --img 128 --ksize 11 --seq_len 16 --steps 10 --no-cpu-baseline $L > $OUT/c5_${rep}_$v.json 2>>$OUT/err.txt
+  python3 bench.py --full --min-seconds 1 --dtype bf16 --no-cpu-baseline $L > $OUT/c3_${rep}_$v.json 2>$OUT/err.txt
+  python3 bench.py --full --min-seconds 1 --dtype bf16 --img 128 --ksize 11 --seq_len 16 --steps 10 --no-cpu-baseline $L > $OUT/c5_${rep}_$v.json 2>>$OUT/err.txt
 done; done
 python3 - <<PY
 import json,glob

@@ -3,9 +3,9 @@
 set -e
 OUT=$1; shift; mkdir -p $OUT
 for rep in 1 2 3; do
-  python3 bench.py --no-cpu-baseline > $OUT/f32_${rep}_new.json 2>$OUT/err.txt
+  python3 bench.py --full --min-seconds 1 --no-cpu-baseline > $OUT/f32_${rep}_new.json 2>$OUT/err.txt
   i=0
-  for LIB in "$@"; do i=$((i+1)); python3 bench.py --no-cpu-baseline --lib $LIB > $OUT/f32_${rep}_lib$i.json 2>>$OUT/err.txt; done
+  for LIB in "$@"; do i=$((i+1)); python3 bench.py --full --min-seconds 1 --no-cpu-baseline --lib $LIB > $OUT/f32_${rep}_lib$i.json 2>>$OUT/err.txt; done
 done
 python3 - <<PY
 import json,glob

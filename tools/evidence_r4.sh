@@ -32,7 +32,7 @@ pmc bf16_b32_s64_k5 $W_C3
 pmc bf16_b32_s128_k11 --dtype bf16 --img 128 --ksize 11 --seq_len 16
 l2() {      # tag flags... : L2 (TCC) hits / misses per kernel family of the step - where the conv kernels' memory-side traffic comes from
   local tag=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/l2_$tag -- python3 bench.py --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --profile-repeats 1 "$@" > $OUT/l2_$tag.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/l2_$tag -- python3 bench.py --full --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --profile-repeats 1 "$@" > $OUT/l2_$tag.log 2>&1
   python3 - $OUT/l2_$tag > $OUT/j_l2_hit_miss_$tag.txt <<'PY'
 import csv, glob, os, re, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); disp = collections.defaultdict(set)
@@ -53,9 +53,9 @@ l2 f32_b32_s64_k5 $W_F32
 l2 bf16_b32_s128_k11 --dtype bf16 --img 128 --ksize 11 --seq_len 16
 find $OUT -name "*counter_collection.csv" -delete; find $OUT -name "*kernel_trace.csv" -delete
 echo pmc done
-python3 bench.py $W_F32 > $OUT/d_bench_f32_config2.json 2>$OUT/bench_err.txt
-python3 bench.py $W_C3 > $OUT/d_bench_bf16_config3_b32.json 2>>$OUT/bench_err.txt
-python3 bench.py $W_C5 > $OUT/d_bench_bf16_config5_geometry.json 2>>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_F32 > $OUT/d_bench_f32_config2.json 2>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_C3 > $OUT/d_bench_bf16_config3_b32.json 2>>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_C5 > $OUT/d_bench_bf16_config5_geometry.json 2>>$OUT/bench_err.txt
 echo bench done
 python3 tools/conv_table.py > $OUT/h_conv_table_f32_config2.txt 2>/dev/null
 python3 tools/conv_table.py --other > $OUT/h_other_ops_f32_config2.txt 2>/dev/null
@@ -65,7 +65,7 @@ python3 tools/conv_table.py --dtype bf16 --img 128 --ksize 11 > $OUT/h_conv_tabl
 python3 tools/conv_table.py --dtype bf16 --img 128 --ksize 11 --other > $OUT/h_other_ops_bf16_config5.txt 2>/dev/null
 echo tables done
 ( for flags in "--loss wass --opt rmsprop" "--loss wass --opt rmsprop --dtype bf16" "--img 128 --ksize 11 --seq_len 16 --steps 10" "--plain" "--plain --dtype bf16" "--batch 64" "--dtype bf16 --batch 256 --steps 10"; do
-    echo "== bench.py $flags"; python3 bench.py --no-cpu-baseline $flags 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'steps/s', d['ms_per_step'], 'ms/step  conv', d['roofline']['achieved'], 'TFLOP/s (', d['roofline']['timing'][:12], ') dna', (d['roofline_dna'] or {}).get('frac'), '|', d['config']['workload'])"
+    echo "== bench.py $flags"; python3 bench.py --full --min-seconds 1 --no-cpu-baseline $flags 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'steps/s', d['ms_per_step'], 'ms/step  conv', d['roofline']['achieved'], 'TFLOP/s (', d['roofline']['timing'][:12], ') dna', (d['roofline_dna'] or {}).get('frac'), '|', d['config']['workload'])"
   done ) > $OUT/q_other_configs.txt 2>&1
 echo other configs done
 rm -rf $OUT/prof_*/ $OUT/pmc_*/ $OUT/l2_*/

@@ -32,7 +32,7 @@ pmc bf16_b32_s64_k5 $W_C3
 pmc bf16_b32_s128_k11 --dtype bf16 --img 128 --ksize 11 --seq_len 16
 l2() {      # tag flags... : L2 (TCC) hits / misses per kernel family of the step - where the conv kernels' memory-side traffic comes from
   local tag=$1; shift
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/l2_$tag -- python3 bench.py --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --profile-repeats 1 "$@" > $OUT/l2_$tag.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/l2_$tag -- python3 bench.py --full --steps 4 --warmup 1 --min-seconds 0 --no-cpu-baseline --profile-repeats 1 "$@" > $OUT/l2_$tag.log 2>&1
   python3 - $OUT/l2_$tag > $OUT/j_l2_hit_miss_$tag.txt <<'PY'
 import csv, glob, os, re, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); disp = collections.defaultdict(set)
@@ -53,9 +53,9 @@ l2 f32_b32_s64_k5 $W_F32
 l2 bf16_b32_s128_k11 --dtype bf16 --img 128 --ksize 11 --seq_len 16
 find $OUT -name "*counter_collection.csv" -delete; find $OUT -name "*kernel_trace.csv" -delete
 echo pmc done
-python3 bench.py $W_F32 > $OUT/d_bench_f32_config2.json 2>$OUT/bench_err.txt
-python3 bench.py $W_C3 > $OUT/d_bench_bf16_config3_b32.json 2>>$OUT/bench_err.txt
-python3 bench.py $W_C5 > $OUT/d_bench_bf16_config5_geometry.json 2>>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_F32 > $OUT/d_bench_f32_config2.json 2>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_C3 > $OUT/d_bench_bf16_config3_b32.json 2>>$OUT/bench_err.txt
+python3 bench.py --full --min-seconds 1 $W_C5 > $OUT/d_bench_bf16_config5_geometry.json 2>>$OUT/bench_err.txt
 echo bench done
 rm -rf $OUT/prof_*/ $OUT/pmc_*/ $OUT/l2_*/
 ls $OUT | head -60

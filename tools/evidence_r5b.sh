@@ -17,7 +17,7 @@ python3 tools/conv_table.py --dtype bf16 --img 128 --ksize 11 > $OUT/h_conv_tabl
 python3 tools/conv_table.py --dtype bf16 --img 128 --ksize 11 --other > $OUT/h_other_ops_bf16_config5.txt 2>/dev/null
 echo tables done
 ( for flags in "--loss wass --opt rmsprop" "--loss wass --opt rmsprop --dtype bf16" "--img 128 --ksize 11 --seq_len 16 --steps 10" "--plain" "--plain --dtype bf16" "--batch 64" "--dtype bf16 --batch 256 --steps 10"; do
-    echo "== bench.py $flags"; python3 bench.py --no-cpu-baseline $flags 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'steps/s', d['ms_per_step'], 'ms/step  conv', d['roofline']['achieved'], 'TFLOP/s (', d['roofline']['timing'][:12], ') dna', (d['roofline_dna'] or {}).get('frac'), '|', d['config']['workload'])"
+    echo "== bench.py $flags"; python3 bench.py --full --min-seconds 1 --no-cpu-baseline $flags 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], 'steps/s', d['ms_per_step'], 'ms/step  conv', d['roofline']['achieved'], 'TFLOP/s (', d['roofline']['timing'][:12], ') dna', (d['roofline_dna'] or {}).get('frac'), '|', d['config']['workload'])"
   done ) > $OUT/q_other_configs.txt 2>&1
 echo other configs done
 rm -rf $OUT/prof_*/ $OUT/pmc_*/ $OUT/l2_*/
