@@ -71,6 +71,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16(const float* __restric
   }
 }
 
+// A split FWD / DGRAD output with channels the contraction does not compute (pad channels of a pitched tensor; channels at or
+// beyond dgrad_c / adj_dgrad_c): only the first `cols` channels of every `pitch`-channel row are summed and stored - the slabs
+// hold nothing beyond them, and acgan_hip.h leaves those channels untouched.  Same z order, same values as the kernels above.
+template <typename T>
+__global__ __launch_bounds__(256) void splitk_reduce_cols(const float* __restrict__ slabs, T* __restrict__ out, long long numel, int splits,
+                                                          int pitch, int cols) {
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < numel; i += stride) {
+    if (i % pitch >= cols) continue;
+    float s = 0.f;
+#pragma unroll 8
+    for (int z = 0; z < splits; ++z) s += slabs[(long long)z * numel + i];
+    out[i] = (T)s;
+  }
+}
+
 // fp32 master weights [taps][A][B] -> the two bf16 operand layouts of the bf16 conv kernels, zero padded to multiples
 // of 8: rm [taps][A][B8] (k-fast along B) and tr [taps][B][A8] (k-fast along A).  All filters of a scope in ONE launch:
 // entry e owns blocks [first_block[e], first_block[e+1]); the first n_rm[e] of them write rm - one 16-byte oct per
@@ -229,16 +245,18 @@ Plan make_plan(const acg_conv_desc& d, int which, bool bf16 = false, bool wide_o
   const long long cin_p = (d.in_c + pad) & ~pad, cout_p = (d.out_c + pad) & ~pad;
   if (which == ACG_CONV_FWD) {
     pl.M = (long long)d.batch * d.out_h * d.out_w; pl.N = d.adj_dgrad_c > 0 ? d.adj_dgrad_c : d.out_c; K = (long long)d.kh * d.kw * cin_p; pl.classes = 1;
-    pl.out_numel = pl.M * (bf16 ? cout_p : (d.out_pitch > 0 ? d.out_pitch : d.out_c));
+    pl.out_pitch = (int)(bf16 ? cout_p : (d.out_pitch > 0 ? d.out_pitch : d.out_c)); pl.out_cols = (int)pl.N;
+    pl.out_numel = pl.M * pl.out_pitch;
   } else if (which == ACG_CONV_DGRAD) {
     const int hc = (d.in_h + d.stride_h - 1) / d.stride_h, wc = (d.in_w + d.stride_w - 1) / d.stride_w;
     pl.M = (long long)d.batch * hc * wc; pl.N = d.dgrad_c > 0 ? d.dgrad_c : d.in_c;
     K = (long long)((d.kh + d.stride_h - 1) / d.stride_h) * ((d.kw + d.stride_w - 1) / d.stride_w) * cout_p;
     pl.classes = d.stride_h * d.stride_w;
-    pl.out_numel = (long long)d.batch * d.in_h * d.in_w * (bf16 ? cin_p : (d.in_pitch > 0 ? d.in_pitch : d.in_c));
+    pl.out_pitch = (int)(bf16 ? cin_p : (d.in_pitch > 0 ? d.in_pitch : d.in_c)); pl.out_cols = (int)pl.N;
+    pl.out_numel = (long long)d.batch * d.in_h * d.in_w * pl.out_pitch;
   } else {
     pl.M = (long long)d.kh * d.kw * cin_p; pl.N = d.out_c; K = (long long)d.batch * d.out_h * d.out_w; pl.classes = 1;
-    pl.out_numel = (long long)d.kh * d.kw * d.in_c * d.out_c;
+    pl.out_numel = (long long)d.kh * d.kw * d.in_c * d.out_c; pl.out_pitch = pl.out_cols = (int)d.out_c;
   }
   // channel pitch of the gathered tensor decides whether its quads are 16-byte loads
   const int ky = d.out_pitch > 0 ? d.out_pitch : d.out_c;
@@ -448,6 +466,15 @@ int launch(const Job& j, hipStream_t st) {
 }
 
 int reduce(const Job& j, hipStream_t st) {
+  if (j.pl.splits > 1 && !j.slabs_only && j.which != ACG_CONV_WGRAD && j.pl.out_cols < j.pl.out_pitch) {
+    if (j.pl.bf16 && !j.a.out_f32)
+      ACG_LAUNCH(splitk_reduce_cols<__bf16>, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, (__bf16*)j.out, j.pl.out_numel,
+                 j.pl.splits, j.pl.out_pitch, j.pl.out_cols);
+    else
+      ACG_LAUNCH(splitk_reduce_cols<float>, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, (float*)j.out, j.pl.out_numel,
+                 j.pl.splits, j.pl.out_pitch, j.pl.out_cols);
+    return acg::check_launch("splitk_reduce_cols");
+  }
   if (j.pl.splits > 1 && !j.slabs_only && j.pl.bf16 && j.which != ACG_CONV_WGRAD && !j.a.out_f32) {
     ACG_LAUNCH(splitk_reduce_bf16, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, (__bf16*)j.out, j.pl.out_numel, j.pl.splits);
     return acg::check_launch("splitk_reduce_bf16");
@@ -522,7 +549,7 @@ int run_merged(const Merged& m, const float* dy, const float* w, float* out, con
   Job j;
   // the forward problem as prepare() plans it; its result tensor is then redirected to dx (pixel-shuffle epilogue, ConvArgs::shuf_c)
   if (int rc = prepare(j, ACG_CONV_FWD, dy, wm, out, 0.f, &m.syn, dtype, ws, (size_t)1 << 40, who, slabs_only)) return rc;
-  j.pl.out_numel = m.out_numel; j.a.out_numel = m.out_numel;
+  j.pl.out_numel = m.out_numel; j.a.out_numel = m.out_numel; j.pl.out_pitch = m.pitch; j.pl.out_cols = d->in_c;
   j.a.shuf_c = d->in_c; j.a.shuf_w = d->in_w; j.a.shuf_pitch = m.pitch;
   if (int rc = launch(j, st)) return rc;
   return reduce(j, st);

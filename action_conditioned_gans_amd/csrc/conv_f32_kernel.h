@@ -954,6 +954,8 @@ struct Plan {
   bool ragged, nvec, bf16;
   bool direct;     // a few-MFLOP float32 contraction with at most 8 output channels: the direct kernels of conv_direct.hip, one launch, no slabs
   long long tiles, out_numel;
+  int out_pitch, out_cols;   // FWD / DGRAD: channel pitch of the output tensor and the channels the contraction computes (the rest of a
+                             // row - pad channels, channels at or beyond dgrad_c / adj_dgrad_c - is never written, by the reduction neither)
 };
 
 // conv_direct.hip

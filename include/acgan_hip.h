@@ -18,7 +18,8 @@
  *     from acg_last_error() (thread-local).  No global mutable state besides that.
  *   - `dtype` is the STORAGE type of the activation-class tensors of a call (x, y, dy, dx ...): ACG_F32, or
  *     ACG_BF16 = bfloat16 in memory (BASELINE configs 3 and 5).  bf16 activations are stored at the channel pitch
- *     round8(C) with zero pad channels, so that every 16-byte unit is 8 channels of one pixel.  The conv entry
+ *     round8(C) with zero pad channels, so that every 16-byte unit is 8 channels of one pixel (the caller stores those zeros
+ *     once: no conv entry writes a pad channel of its output, nor a channel at or beyond dgrad_c / adj_dgrad_c).  The conv entry
  *     points then contract on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16, float32 accumulation) and take
  *     their filter operand from the bf16 copies made by acg_weights_prepare_bf16; weight gradients, BatchNorm
  *     statistics, losses and optimizer state stay float32.  Where a call has two activation tensors of different
@@ -79,8 +80,9 @@ typedef struct acg_conv_desc {
   int32_t out_pitch; /* same for y / dy (0 = dense = out_c): the 138- and 266-channel action-concatenated maps feeding
                         d/conv3 and g/tconv1 are stored at a pitch of 140 / 268.  Pad channels of dy must be zero. */
   int32_t dgrad_c;   /* acg_conv2d_dgrad, acg_conv2d_dgrad_slabs, acg_conv2d_bwd_pair: only the first dgrad_c channels of dx
-                        are computed and written (0 = all in_c).  The last channels of those action-concatenated maps are tiled
-                        inputs (train.py:48-50): nothing reads their gradient, and 138 columns cost a third 64-column tile. */
+                        are computed and written (0 = all in_c; a split-K reduction leaves the others untouched as well).  The
+                        last channels of those action-concatenated maps are tiled inputs (train.py:48-50): nothing reads their
+                        gradient, and 138 columns cost a third 64-column tile. */
   int32_t adj_dgrad_c; /* the same on the ADJOINT descriptor of a transposed layer: acg_deconv2d_dgrad, _dgrad_slabs and
                           acg_deconv2d_bwd_pair compute the first adj_dgrad_c of the out_c channels of dx (0 = all).  Leave 0
                           on descriptors handed to acg_conv2d_fwd. */

@@ -268,6 +268,88 @@ class Abi:
         rl.step_inc = step.data_ptr() if step is not None else None
         self.lib.splitk_reduce_many(ctypes.byref(rl), len(entries), self.stream())
 
+    # ---- one entry point on a FULL descriptor (pitches, dgrad_c, adj_dgrad_c as given): the caller lays the tensors out at the
+    # pitches the descriptor names (bf16: round8).  ``w`` is the float32 master filter; bf16 calls read its prepared copy.
+    # Each returns the workspace(s) it used, whose canaries the caller checks.
+    def _wop(self, w, kind):
+        if not self.half:
+            return w
+        rm, tr = self.prep_weights(w)
+        return rm if kind == 'rm' else tr
+
+    def conv_ws(self, d, which, dtype=None):
+        return self.ws(self.lib.conv2d_workspace_bytes(ctypes.byref(d), which, self.conv_dtype if dtype is None else dtype))
+
+    def fwd_d(self, d, transposed, x, w, y, dtype=None):
+        """acg_conv2d_fwd / acg_deconv2d_fwd; ``dtype`` e.g. ACG_DTYPE2(ACG_BF16, ACG_F32) for a float32 head output."""
+        dt = self.conv_dtype if dtype is None else dtype
+        ws, n = self.conv_ws(d, L.CONV_DGRAD if transposed else L.CONV_FWD, dt)
+        fn = self.lib.deconv2d_fwd if transposed else self.lib.conv2d_fwd
+        fn(_p(x), _p(self._wop(w, 'rm' if transposed else 'tr')), _p(y), ctypes.byref(d), dt, _p(ws), n, self.stream())
+        return ws
+
+    def fwd_stats_d(self, d, transposed, x, w, y, groups):
+        """acg_(de)conv2d_fwd_stats -> (partials, nblk, block_rows, run_rows, workspace); None when the shape leaves none."""
+        which = L.CONV_DGRAD if transposed else L.CONV_FWD
+        brows, rrows = ctypes.c_int32(0), ctypes.c_int32(0)
+        nblk = self.lib.conv2d_stats_layout(ctypes.byref(d), which, self.conv_dtype, groups, ctypes.byref(brows), ctypes.byref(rrows))
+        if nblk <= 0:
+            return None
+        c = d.in_c if transposed else d.out_c
+        part = torch.full((groups * nblk * 2 * c,), float('nan'), device=self.device)
+        ws, n = self.conv_ws(d, which)
+        fn = self.lib.deconv2d_fwd_stats if transposed else self.lib.conv2d_fwd_stats
+        fn(_p(x), _p(self._wop(w, 'rm' if transposed else 'tr')), _p(y), ctypes.byref(d), self.conv_dtype, _p(ws), n, _p(part), groups,
+           self.stream())
+        return part, nblk, brows.value, rrows.value, ws
+
+    def fwd_slabs_d(self, d, transposed, x, w, layout):
+        """acg_(de)conv2d_fwd_slabs -> (slab workspace, splits)."""
+        which = L.CONV_DGRAD if transposed else L.CONV_FWD
+        ws, n = self.conv_ws(d, which)
+        fn = self.lib.deconv2d_fwd_slabs if transposed else self.lib.conv2d_fwd_slabs
+        fn(_p(x), _p(self._wop(w, 'rm' if transposed else 'tr')), ctypes.byref(d), self.conv_dtype, layout, _p(ws), n, self.stream())
+        return ws, self.lib.conv2d_splits(ctypes.byref(d), which, self.conv_dtype)
+
+    def fwd_bias_act_d(self, d, x, w, bias, y, act, leak):
+        self.lib.deconv2d_fwd_bias_act(_p(x), _p(self._wop(w, 'rm')), _p(bias), _p(y), ctypes.byref(d), ACT[act], leak, self.conv_dtype,
+                                       self.stream())
+
+    def dgrad_d(self, d, transposed, dy, w, dx):
+        ws, n = self.conv_ws(d, L.CONV_FWD if transposed else L.CONV_DGRAD)
+        fn = self.lib.deconv2d_dgrad if transposed else self.lib.conv2d_dgrad
+        fn(_p(dy), _p(self._wop(w, 'tr' if transposed else 'rm')), _p(dx), ctypes.byref(d), self.conv_dtype, _p(ws), n, self.stream())
+        return ws
+
+    def dgrad_slabs_d(self, d, transposed, dy, w, layout):
+        which = L.CONV_FWD if transposed else L.CONV_DGRAD
+        ws, n = self.conv_ws(d, which)
+        fn = self.lib.deconv2d_dgrad_slabs if transposed else self.lib.conv2d_dgrad_slabs
+        fn(_p(dy), _p(self._wop(w, 'tr' if transposed else 'rm')), ctypes.byref(d), self.conv_dtype, layout, _p(ws), n, self.stream())
+        return ws, self.lib.conv2d_splits(ctypes.byref(d), which, self.conv_dtype)
+
+    def wgrad_d(self, d, transposed, x, dy, dw, accumulate):
+        """``x``: the layer's input (a transposed layer: the deconv input, on the descriptor's out side)."""
+        ws, n = self.conv_ws(d, L.CONV_WGRAD)
+        fn = self.lib.deconv2d_wgrad if transposed else self.lib.conv2d_wgrad
+        fn(_p(x), _p(dy), _p(dw), accumulate, ctypes.byref(d), self.conv_dtype, _p(ws), n, self.stream())
+        return ws
+
+    def wgrad_slabs_d(self, d, transposed, x, dy):
+        ws, n = self.conv_ws(d, L.CONV_WGRAD)
+        fn = self.lib.deconv2d_wgrad_slabs if transposed else self.lib.conv2d_wgrad_slabs
+        fn(_p(x), _p(dy), ctypes.byref(d), self.conv_dtype, _p(ws), n, self.stream())
+        return ws, self.lib.conv2d_splits(ctypes.byref(d), L.CONV_WGRAD, self.conv_dtype)
+
+    def bwd_pair_d(self, d, transposed, dy, w, x, dx, dw, accumulate, flags):
+        """acg_(de)conv2d_bwd_pair with its flag word -> (input-gradient workspace, weight-gradient workspace)."""
+        wsd, nd = self.conv_ws(d, L.CONV_FWD if transposed else L.CONV_DGRAD)
+        wsw, nw = self.conv_ws(d, L.CONV_WGRAD)
+        fn = self.lib.deconv2d_bwd_pair if transposed else self.lib.conv2d_bwd_pair
+        fn(_p(dy), _p(self._wop(w, 'tr' if transposed else 'rm')), _p(x), _p(dx), _p(dw), accumulate, ctypes.byref(d), self.conv_dtype,
+           _p(wsd), nd, _p(wsw), nw, flags, self.stream())
+        return wsd, wsw
+
     # ---- bn / bias
     def bn_act_fwd(self, x, beta, act, groups=1, eps=1e-3, leak=0.2, y_dtype=None, c=None):
         """Storage types follow the tensors: x float32 or bfloat16, y like x unless ``y_dtype`` says otherwise.

@@ -92,6 +92,32 @@ def case_conv(abi, shape, tol, seed=0):
     close(got, 0.5 * dw0.double().cpu() + dw_ref, tol, tag + ' wgrad accumulate')
 
 
+def case_dgrad_limit_split_reduction(abi, tol):
+    """g/tconv1's input gradient (adj_dgrad_c 256 of 266 channels at a pitch of 268, split over K): the split-K reduction must
+    leave the channels at or beyond the limit and the pad channels as they were, like the unsplit kernels do - dx starts at a
+    sentinel.  (The reduction used to store all 268 channels of every pixel, the ones the slabs hold nothing for included.)"""
+    import ctypes
+    from action_conditioned_gans_amd import _lib as L
+    dev = abi.device
+    r = (lambda t: t.bfloat16().float()) if abi.half else (lambda t: t)
+    store = torch.bfloat16 if abi.half else torch.float32
+    xs, ws_, keep = (4, 4, 4, 268), (5, 5, 128, 266), 256
+    d = abi._adj(xs, ws_, 2)
+    d.adj_dgrad_c = keep
+    pitch = 272 if abi.half else 268
+    if abi.half:
+        d.out_pitch = 0
+    assert abi.lib.conv2d_splits(ctypes.byref(d), L.CONV_FWD, abi.conv_dtype) > 1, 'test premise: the input gradient is split over K'
+    dy, w = randn((4, 8, 8, 128), 1130), randn(ws_, 1131, 0.1)
+    want = T.conv2d(r(dy).double(), r(w).double(), 2, 'SAME')
+    dx = torch.full(xs[:3] + (pitch,), -777.0, dtype=store, device=dev)
+    ws = abi.dgrad_d(d, True, dy.to(dev).to(store), w.to(dev), dx)
+    abi.sync()
+    type(abi).canary_intact(ws)
+    close(dx[..., :keep].float(), want[..., :keep], tol, 'split limited dgrad')
+    assert bool((dx[..., keep:].cpu() == torch.tensor(-777.0, dtype=store)).all()), 'split limited dgrad: channels beyond the limit were written'
+
+
 MERGED_LAYERS = [   # (x shape, w shape, stride, padding, transposed, merged?)
     ((4, 16, 16, 6), (5, 5, 6, 64), 2, 'SAME', False, True),       # d/conv1-like: 3 x 3 window, N = 24
     ((2, 16, 12, 3), (3, 3, 3, 16), 2, 'SAME', False, True),       # 3 x 3 filter, pad 0 / 1: a 2 x 2 window (8 output channels would take the direct kernels)
@@ -434,6 +460,10 @@ BASELINE_LAYERS = [
     ('c', 64, 64, 64, 6, 64, 5, 2, 'SAME'), ('c', 64, 32, 32, 64, 128, 5, 2, 'SAME'), ('c', 64, 16, 16, 138, 128, 5, 2, 'SAME'),
     ('c', 64, 8, 8, 128, 256, 5, 2, 'SAME'), ('c', 64, 4, 4, 256, 512, 5, 2, 'SAME'), ('c', 64, 2, 2, 512, 1, 2, 1, 'SAME'),
     ('d', 32, 64, 64, 128, 121, 5, 2, 'SAME'), ('c', 32, 128, 128, 6, 64, 5, 2, 'SAME'),
+    # the look-ahead generator pass of the bench step (train.py Trainer(lookahead=True)): the generator at batch 2 B = 64
+    ('c', 64, 64, 64, 3, 32, 5, 2, 'SAME'), ('c', 64, 32, 32, 32, 64, 5, 2, 'SAME'), ('c', 64, 16, 16, 64, 128, 5, 2, 'SAME'),
+    ('c', 64, 8, 8, 128, 256, 5, 2, 'SAME'), ('d', 64, 4, 4, 266, 128, 5, 2, 'SAME'), ('d', 64, 8, 8, 128, 128, 5, 2, 'SAME'),
+    ('d', 64, 16, 16, 128, 128, 5, 2, 'SAME'), ('d', 64, 32, 32, 128, 25, 5, 2, 'SAME'), ('d', 64, 64, 64, 128, 121, 5, 2, 'SAME'),
 ]
 
 

@@ -77,6 +77,14 @@ def test_dgrad_channel_limit_bf16(hip_abi_bf16):
     C.case_dgrad_channel_limit(hip_abi_bf16, TOL_BF16)
 
 
+def test_dgrad_channel_limit_split_reduction(hip_abi):
+    C.case_dgrad_limit_split_reduction(hip_abi, TOL_CONV)
+
+
+def test_dgrad_channel_limit_split_reduction_bf16(hip_abi_bf16):
+    C.case_dgrad_limit_split_reduction(hip_abi_bf16, TOL_BF16)
+
+
 def test_slab_handoff_layouts(hip_abi):
     C.case_slab_handoff(hip_abi, 2e-5)
 
