@@ -155,6 +155,14 @@ SIGNATURES = {
     'acg_step_inc': (c_int32, [_P, _P]),
 }
 
+# include/acgan_metrics.h: an addition under ABI version 8, bound as a table of its own - the C oracle (oracle/cbind) does not
+# implement it and is never asked for it; the HIP library must export it (get() / load_tuning() pass it as `extra`)
+METRICS_SIGNATURES = {
+    'acg_frame_metrics_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32]),
+    'acg_frame_metrics': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                    _P, c_size_t, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -221,7 +229,7 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH)
+        _LIB = Library(LIB_PATH, extra=METRICS_SIGNATURES)
     return _LIB
 
 
@@ -237,5 +245,5 @@ def load_tuning():
         # build at call time would also run under whatever preload (rocprofv3) the calling tool was started with
         raise RuntimeError('%s not found: build it first, before any profiler or GPU process starts: '
                            '`make -s -j16 -C %s tuning`' % (TUNING_LIB_PATH, os.path.dirname(LIB_PATH)))
-    _LIB = Library(TUNING_LIB_PATH, extra={'acg_debug_conv_plan': (c_int32, [c_int32, c_int32])})
+    _LIB = Library(TUNING_LIB_PATH, extra=dict(METRICS_SIGNATURES, acg_debug_conv_plan=(c_int32, [c_int32, c_int32])))
     return _LIB

@@ -1,0 +1,208 @@
+"""Checkpoint evaluation: ``python -m action_conditioned_gans_amd.evaluate MODEL_PATH INPUT OUTPUT [options]``.
+
+The reference's test.py (restore the latest checkpoint, recursive rollout on ``.npy`` frames and actions, GIF samples through
+util.save_samples), made to run (defect D5), plus the numbers its report publishes: SSIM and PSNR per rollout step for the
+model and for the identity baseline (Fig. 4), scored on the GPU (metrics.frame_metrics).
+
+INPUT: a ``.npy`` of frames [N, T, H, W, 3] (float in [-1, 1], or uint8 read as x / 127.5 - 1) with ``--actions`` [N, T, 10];
+a push TFRecord directory (its validation split, read once in sorted file order); or ``synthetic`` (seeded random sequences).
+``--num_sequences`` caps any of them.  The rollout runs ``--batch_size`` sequences at a time; the last batch is padded by
+repeating its last sequence and the padded rows enter no sum.
+
+OUTPUT/metrics.json: the checkpoint, sequences, steps, the SSIM definition, per step the mean SSIM over sequences and the PSNR
+of the whole set by the reference's formula (10 log10(1 / MSE), MSE over all sequences' frames of that step - for a single
+batch the train loop's ``rollout_psnr``), the same two curves for the identity baseline, and the rollout rate in frames/s.
+"""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+
+ACTION_DIM = 10
+
+
+def _flag(v):
+    from .train import _flag as f
+    return f(v)
+
+
+def load_frames(path):
+    """A frames ``.npy`` [N, T, H, W, 3] -> float32 in [-1, 1] (uint8 is read as x / 127.5 - 1)."""
+    arr = np.load(path, mmap_mode='r')
+    if arr.ndim != 5 or arr.shape[-1] != 3:
+        raise ValueError('%s: expected frames [N, T, H, W, 3], got %s' % (path, arr.shape))
+    return arr
+
+
+def _as_float(frames):
+    frames = np.asarray(frames)
+    if frames.dtype == np.uint8:
+        return frames.astype(np.float32) / 127.5 - 1.0
+    return np.array(frames, dtype=np.float32)          # (a writable copy: the .npy is memory-mapped read-only)
+
+
+def _batches(input_path, actions_path, batch_size, img_size, seq_len, num_sequences):
+    """-> generator of (frames [b, T, S, S, 3] float32, actions [b, T, 10] float32), b <= batch_size, at most num_sequences rows."""
+    left = num_sequences if num_sequences is not None else float('inf')
+    if input_path == 'synthetic':
+        from .train import SyntheticPush
+        data = SyntheticPush(batch_size, seq_len, img_size, seed=1007)
+        if num_sequences is None:
+            raise ValueError('the synthetic source needs --num_sequences')
+        while left > 0:
+            img, _, acts, _ = data.get_batch()
+            b = int(min(left, batch_size))
+            yield img[:b], acts[:b]
+            left -= b
+    elif os.path.isdir(input_path):
+        from .push_data import PushDataset
+        with PushDataset(input_path, batch_size, training=False, img_size=img_size, one_pass=True) as data:
+            for img, _, acts, _ in data:
+                if left <= 0:
+                    break
+                b = int(min(left, img.shape[0]))
+                yield np.asarray(img[:b], np.float32), np.asarray(acts[:b], np.float32)
+                left -= b
+    else:
+        frames, actions = load_frames(input_path), np.load(actions_path, mmap_mode='r')
+        n = int(min(left, frames.shape[0]))
+        for s in range(0, n, batch_size):
+            e = min(s + batch_size, n)
+            yield _as_float(frames[s:e]), np.array(actions[s:e], dtype=np.float32)
+
+
+def _pad(x, batch_size):
+    if x.shape[0] == batch_size:
+        return x
+    return np.concatenate([x, np.repeat(x[-1:], batch_size - x.shape[0], axis=0)], axis=0)
+
+
+def set_psnr(sqerr, valid, count_per_frame):
+    """PSNR of a set by the reference's formula: ``sqerr`` [N, steps] sums of squared errors per frame, ``valid`` [N] bool (False:
+    a padding row) -> [steps] 10 log10(1 / (sum over valid rows / (rows * count_per_frame)))."""
+    from .metrics import psnr_from_sqerr
+    sqerr = np.asarray(sqerr, np.float64)[np.asarray(valid, bool)]
+    return psnr_from_sqerr(sqerr.sum(axis=0), sqerr.shape[0] * count_per_frame)
+
+
+def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
+             seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0'):
+    """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
+    ``dna`` / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of ``input_path`` and write
+    ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs with ``gif``) and with
+    ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  -> the metrics dict."""
+    from . import graph as G
+    from .metrics import SSIM_DEFINITION
+    from .saver import Saver, latest_checkpoint
+    from .train import Trainer
+    from .util import save_samples
+
+    ckpt = latest_checkpoint(model_path) if os.path.isdir(model_path) else model_path
+    if ckpt is None:
+        raise FileNotFoundError('no checkpoint under %s' % model_path)
+    os.makedirs(output_path, exist_ok=True)
+    G.reset_default_graph()
+    sess = G.Session(device=device, dtype=dtype)
+    try:
+        trainer = Trainer(sess, False, 'bce', 'adam', dna, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False)
+        sess.run(G.global_variables_initializer())
+        Saver().restore(sess, ckpt)
+        keys = ('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
+        acc = {k: [] for k in keys}
+        valid, kept_frames, kept_pred, dumped = [], [], [], []
+        rollout_s, n_seq, steps, hw = 0.0, 0, None, None
+        for frames, acts in _batches(input_path, actions_path, batch_size, img_size, seq_len, num_sequences):
+            b = frames.shape[0]
+            if frames.shape[2:4] != (img_size, img_size):
+                raise ValueError('frames of %s x %s, the model is built for --img_size %d' % (frames.shape[2], frames.shape[3], img_size))
+            steps, hw = frames.shape[1] - 1, frames.shape[2:]
+            want = dump or len(kept_pred) < samples
+            t0 = time.perf_counter()
+            m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want)
+            rollout_s += time.perf_counter() - t0
+            for k in keys:
+                acc[k].append(m[k])
+            valid.append(np.arange(batch_size) < b)
+            if want:
+                pred = m['frames'][:b]
+                if dump:
+                    dumped.append(pred)
+                take = min(samples - len(kept_pred), b)
+                kept_pred.extend(pred[:take])
+                kept_frames.extend(frames[:take])
+            n_seq += b
+        if n_seq == 0:
+            raise ValueError('%s holds no sequences' % input_path)
+        valid = np.concatenate(valid)
+        acc = {k: np.concatenate(v) for k, v in acc.items()}
+        count = int(np.prod(hw))        # H * W * 3 values per frame
+        result = {
+            'checkpoint': os.path.abspath(ckpt),
+            'sequences': n_seq,
+            'steps': int(steps),
+            'ssim_definition': SSIM_DEFINITION + ' (data_range 2 for frames in [-1, 1])',
+            'psnr_definition': '10 log10(1 / MSE) on [-1, 1] frames (reference build_psnr): 6.02 dB below a [0, 1]-range PSNR; '
+                               'MSE over all sequences of the step',
+            'ssim': [float(v) for v in acc['ssim'][valid].mean(axis=0, dtype=np.float64)],
+            'psnr': [float(v) for v in set_psnr(acc['sqerr'], valid, count)],
+            'identity_ssim': [float(v) for v in acc['identity_ssim'][valid].mean(axis=0, dtype=np.float64)],
+            'identity_psnr': [float(v) for v in set_psnr(acc['identity_sqerr'], valid, count)],
+            'frames_per_s': float(valid.size * steps / rollout_s),
+        }
+        with open(os.path.join(output_path, 'metrics.json'), 'w') as f:
+            json.dump(result, f, indent=1)
+        if dump:
+            np.save(os.path.join(output_path, 'predictions.npy'), np.concatenate(dumped))
+        if kept_pred:
+            seqs = np.stack(kept_frames)
+            save_samples(output_path, seqs, np.stack(kept_pred), seqs[:, 1:], 0, gif=gif)
+        return result
+    finally:
+        sess.close()
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='evaluate a checkpoint: rollout SSIM / PSNR per step, model and identity baseline')
+    parser.add_argument('model_path', type=str, help='checkpoint directory (its latest checkpoint) or checkpoint prefix')
+    parser.add_argument('input', type=str, help="frames .npy [N,T,H,W,3], push TFRecord directory, or 'synthetic'")
+    parser.add_argument('output', type=str)
+    parser.add_argument('--actions', type=str, default=None, help='actions .npy [N,T,10] (with a frames .npy)')
+    parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
+    parser.add_argument('--ksize', type=int, default=5)
+    parser.add_argument('--img_size', type=int, default=64)
+    parser.add_argument('--dtype', type=str, default='f32', choices=['f32', 'bf16'])
+    parser.add_argument('--batch_size', type=int, default=32)
+    parser.add_argument('--seq_len', type=int, default=8, help='sequence length of the synthetic source')
+    parser.add_argument('--num_sequences', type=int, default=None)
+    parser.add_argument('--samples', type=int, default=16, help='sample videos written (train.py:300-305 writes 16)')
+    parser.add_argument('--gif', action='store_true')
+    parser.add_argument('--dump', action='store_true', help='save the predictions as predictions.npy')
+    parser.add_argument('--device', type=str, default='cuda:0')
+    args = parser.parse_args(argv)
+    if args.batch_size < 1:
+        parser.error('--batch_size must be >= 1')
+    if args.num_sequences is not None and args.num_sequences < 1:
+        parser.error('--num_sequences must be >= 1')
+    if args.input == 'synthetic':
+        if args.num_sequences is None:
+            parser.error('the synthetic source needs --num_sequences')
+    elif not os.path.isdir(args.input):
+        if args.actions is None:
+            parser.error('a frames .npy needs --actions ACTIONS.npy')
+        try:
+            frames, actions = load_frames(args.input), np.load(args.actions, mmap_mode='r')
+        except (OSError, ValueError) as e:
+            parser.error(str(e))
+        if actions.ndim != 3 or actions.shape[2] != ACTION_DIM:
+            parser.error('%s: expected actions [N, T, %d], got %s' % (args.actions, ACTION_DIM, actions.shape))
+        if actions.shape[:2] != frames.shape[:2]:
+            parser.error('frames %s and actions %s disagree in N or T' % (frames.shape[:2], actions.shape[:2]))
+    return evaluate(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, ksize=args.ksize,
+                    img_size=args.img_size, dtype=args.dtype, batch_size=args.batch_size, seq_len=args.seq_len,
+                    num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device)
+
+
+if __name__ == '__main__':
+    main()

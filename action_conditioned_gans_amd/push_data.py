@@ -509,11 +509,15 @@ class PushDataset:
         training set) is served from memory: no file read, no worker task.  What is kept is what the decoder produced - same
         bits.  First come, first kept (no eviction: under a cyclic stream an LRU of less than the whole set never hits).
       * ``decode='dct'`` - opt-in, approximate: the 8x reduction inside libjpeg's inverse DCT (``decode_frame``).
+
+    ``one_pass=True`` (opt-in; evaluation): the files are read ONCE in sorted order, unshuffled - every record of the split once -
+    and then the stream ends: the last ``get_batch`` may return fewer than ``batch_size`` rows, the one after it raises
+    ``StopIteration``; iterating the dataset yields its batches.
     """
 
     def __init__(self, data_dir, batch_size, train_val_split=0.95, use_state=True, training=True, img_size=IMG_HEIGHT,
                  seed=7, rank=0, world_size=1, verify_crc=False, num_threads=None, capacity=None, workers='thread', decode='exact',
-                 cache_bytes=0):
+                 cache_bytes=0, one_pass=False):
         files = sorted(glob.glob(os.path.join(data_dir, '*')))
         if not files:
             raise RuntimeError('No data files found.')                          # ops.py:159
@@ -524,6 +528,7 @@ class PushDataset:
         self.batch_size, self.use_state, self.img_size = batch_size, use_state, img_size
         self.rng = np.random.default_rng(seed)
         self.rank, self.world_size, self.verify_crc = rank, world_size, verify_crc
+        self.one_pass = bool(one_pass)
         self.seq_len = len(FRAME_IDS)
         if num_threads is None:
             try:
@@ -556,7 +561,7 @@ class PushDataset:
         n = 0
         while True:
             seen = False
-            for k in self.rng.permutation(len(self.files)):
+            for k in (range(len(self.files)) if self.one_pass else self.rng.permutation(len(self.files))):
                 path = self.files[k]
                 if self.verify_crc:
                     recs = read_records(path, True)
@@ -571,6 +576,8 @@ class PushDataset:
                     n += 1
             if not seen:
                 raise RuntimeError('the data files hold no records')
+            if self.one_pass:
+                return
 
     def _items(self):
         """(payload, tag) in stream order for the prefetcher: payload = (record, frames to decode) or None when the cache holds
@@ -644,13 +651,34 @@ class PushDataset:
         """-> (frames, frames, action||state [B,T,10], state [B,T,5]), the tuple the training loop consumes.  ``frames``: the
         ``[B, 7, S, S, 3]`` array, or a ``SparseFrames`` when only announced frames were decoded."""
         self._start()
-        rows, acts, states = zip(*[self._next_record() for _ in range(self.batch_size)])
+        if self.one_pass:
+            got = []
+            try:
+                while len(got) < self.batch_size:
+                    got.append(self._next_record())
+            except StopIteration:
+                if not got:
+                    raise
+            rows, acts, states = zip(*got)
+        else:
+            rows, acts, states = zip(*[self._next_record() for _ in range(self.batch_size)])
         if all(len(r) == self.seq_len for r in rows):
             img = np.stack([np.stack([r[j] for j in range(self.seq_len)]) for r in rows])
         else:
             img = SparseFrames(list(rows), self.seq_len, self.img_size)
         action_state = np.concatenate([np.stack(acts), np.stack(states)], axis=2)
         return img, img, action_state, action_state[:, :, STATE_DIM:].copy()
+
+    def __iter__(self):
+        """The batches of a ``one_pass`` dataset, the last one possibly partial."""
+        if not self.one_pass:
+            raise TypeError('only a one_pass PushDataset ends: call get_batch() on a training stream')
+        while True:
+            try:
+                batch = self.get_batch()
+            except StopIteration:
+                return
+            yield batch
 
     def close(self):
         self._closed = True

@@ -23,6 +23,7 @@ from . import graph as G
 from . import models as M
 from . import ops as O
 from . import optim
+from .metrics import frame_metrics
 from .saver import Saver
 from .util import build_all_mask
 
@@ -281,22 +282,8 @@ class Trainer:
         if device_loop is None:
             device_loop = self.sess.rt.is_cuda
         if device_loop and steps >= 1:
-            out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32))
-            acts = self.sess.upload(np.asarray(test_actions[:, :steps + 1], np.float32))          # [B, steps + 1, 10], once
-            frame = self.sess.upload(out)
-            state = self.sess.upload(st) if st is not None else acts[:, 1, 5:]
-            frames = [frame]
-            fetches = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else [])
-            for j in range(1, steps):
-                acs = torch.cat([acts[:, j, :5], state], dim=1).contiguous()
-                fd = self._feed(frame, test_next_frame[:, j + 1], acs)      # (next_frame is not read by this program: checked, not uploaded)
-                self._announced = None
-                res = self.sess.run(fetches, fd, device_fetch=True)
-                frame = res[0].float().clone()                             # the fetch is the tensor's own buffer: the next step overwrites it
-                state = res[1].float().clone() if self.g_state_out is not None else acts[:, j + 1, 5:]
-                frames.append(frame)
-            predicted = torch.stack(frames, dim=1).cpu().numpy()
-            return predicted, summ0
+            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps)
+            return predicted.cpu().numpy(), summ0
         predicted, summ0 = [], None
         current_frame = input_images[:, 0]
         current_state = test_actions[:, 0, 5:]
@@ -308,6 +295,50 @@ class Trainer:
             current_frame = out
             current_state = st if st is not None else test_actions[:, j + 1, 5:]
         return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), summ0
+
+    def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps):
+        """The device loop of ``test_sequence``: -> (predicted [B, steps, H, W, 3] float32 on the device, summaries of step 0)."""
+        out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32))
+        acts = self.sess.upload(np.asarray(test_actions[:, :steps + 1], np.float32))          # [B, steps + 1, 10], once
+        frame = self.sess.upload(out)
+        state = self.sess.upload(st) if st is not None else acts[:, 1, 5:]
+        frames = [frame]
+        fetches = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else [])
+        for j in range(1, steps):
+            acs = torch.cat([acts[:, j, :5], state], dim=1).contiguous()
+            fd = self._feed(frame, test_next_frame[:, j + 1], acs)      # (next_frame is not read by this program: checked, not uploaded)
+            self._announced = None
+            res = self.sess.run(fetches, fd, device_fetch=True)
+            frame = res[0].float().clone()                             # the fetch is the tensor's own buffer: the next step overwrites it
+            state = res[1].float().clone() if self.g_state_out is not None else acts[:, j + 1, 5:]
+            frames.append(frame)
+        return torch.stack(frames, dim=1), summ0
+
+    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False):
+        """Quality of the recursive rollout, scored on the GPU (metrics.frame_metrics; no reference counterpart - the curves of
+        its report).  Rollout as ``test_sequence``'s default on the device loop: ``steps`` (default T-1) steps,
+        step j commanded by ``actions[:, j]`` with the generator's own predicted state (defect D7) and scored against
+        ``images[:, j + 1]``.  The predictions stay on the device; all B * steps frames are scored in one launch.  ``identity``:
+        also score the identity baseline - ``images[:, 0]`` carried forward - against the same targets.
+        -> dict of numpy arrays [B, steps]: ``ssim``, ``sqerr`` (sum of squared errors of the frame), and ``identity_ssim``,
+        ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames)."""
+        from . import metrics
+        if not self.sess.rt.is_cuda:
+            raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
+        steps = steps if steps is not None else images.shape[1] - 1
+        if steps < 1 or steps + 1 > images.shape[1]:
+            raise ValueError('rollout_metrics: %d steps need %d frames per sequence, got %d' % (steps, steps + 1, images.shape[1]))
+        predicted, _ = self._rollout_on_device(images, images, actions, steps)
+        seq = self.sess.upload(np.asarray(images[:, :steps + 1], np.float32))                # [B, steps + 1, H, W, 3], once
+        truth = seq[:, 1:]
+        ssim, sqerr = metrics.frame_metrics(predicted, truth)
+        out = {'ssim': ssim, 'sqerr': sqerr}
+        if identity:
+            out['identity_ssim'], out['identity_sqerr'] = metrics.frame_metrics(seq[:, :1].expand_as(truth), truth)
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        if return_frames:
+            out['frames'] = predicted.cpu().numpy()
+        return out
 
     def _named(self, values):
         return {k: float(np.asarray(v).reshape(-1)[0]) for k, v in zip(self._summary_names, values)}
@@ -551,7 +582,10 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             psnr = [float(10.0 * np.log10(1.0 / max(np.mean((predicted[:, j] - t_img[:, j + 1]) ** 2), 1e-30)))
                     for j in range(predicted.shape[1])]
             if log_file:
-                _log_jsonl(os.path.join(log_dir, 'test.jsonl'), dict(e_summ or {}, iteration=i, rollout_psnr=psnr))
+                # SSIM per step (mean over the batch) by the GPU kernel (metrics.frame_metrics) on the same predictions
+                ssim, _ = frame_metrics(sess.upload(predicted), sess.upload(np.asarray(t_img[:, 1:predicted.shape[1] + 1], np.float32)))
+                ssim = [float(v) for v in ssim.mean(dim=0, dtype=torch.float64).cpu().numpy()]
+                _log_jsonl(os.path.join(log_dir, 'test.jsonl'), dict(e_summ or {}, iteration=i, rollout_psnr=psnr, rollout_ssim=ssim))
     if hasattr(eval_data, 'close'):
         eval_data.close()
     saver.wait()                     # the last checkpoints are on disk when train() returns
