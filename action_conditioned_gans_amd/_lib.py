@@ -163,6 +163,15 @@ METRICS_SIGNATURES = {
                                     _P, c_size_t, _P]),
 }
 
+# include/acgan_cdna.h: the CDNA generator's fused transform-and-composite, an addition under ABI version 8 bound as a table of
+# its own like METRICS_SIGNATURES (the C oracle does not implement it: ops.CdnaCompositeOp raises a RuntimeError there)
+CDNA_SIGNATURES = {
+    'acg_cdna_composite_workspace_bytes': (c_size_t, [c_int32] * 6),
+    'acg_cdna_composite_fwd': (c_int32, [_P, _P, _P, _P, c_int32, _P, _P] + [c_int32] * 6 + [c_float, _P]),
+    'acg_cdna_composite_bwd': (c_int32, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 6
+                               + [c_float, _P, c_size_t, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -229,7 +238,7 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH, extra=METRICS_SIGNATURES)
+        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES))
     return _LIB
 
 

@@ -1,0 +1,307 @@
+// Fused CDNA transform-and-composite (include/acgan_cdna.h): the output stage of the CDNA generator.
+//
+// Forward, one launch: a block owns a 16x16 pixel tile of one sample and stages, as cdna_fwd_k does, the sample's
+// normalised kernels and the image window (SAME zeros) in LDS.  Every thread computes the C*M transformed values of its
+// pixel from registers and folds each one straight into the softmax-weighted composite (max-subtracted, the tconv4 bias
+// folded in): the M transformed images never reach HBM.  Algorithmic bytes: the image, the M+1 mask logits and the frame.
+//
+// Backward: the transformed values are recomputed, not stored.  Per pixel g_0 = <dout, image>, g_{j+1} = <dout, T_j> and
+// dz_j = s_j (g_j - sum_l s_l g_l); the kernel gradient takes dT_j = s_{j+1} dout.  The tile pass leaves per-(sample, tile)
+// partials of the kernel gradient and of the bias gradient in the workspace (cdna_bwd_kern_partial_k's scheme); a final
+// pass sums them in a fixed order and goes through the normalisation and the relu.  No atomics.
+#include <hip/hip_runtime.h>
+
+#include "../../include/acgan_cdna.h"
+#include "cdna_common.h"
+#include "common.h"
+
+namespace {
+
+using namespace acg_cdna;
+
+constexpr int kPix = kTile * kTile;
+constexpr int kMaxZ = kMaxM + 1;                                   // mask channels: the image and the M transforms
+constexpr int kWin = (kTile + kMaxK - 1) * (kTile + kMaxK - 1) * kMaxC;
+constexpr int kBig = kMaxZ * kPix;                                 // bwd: g_j / dz_j per pixel, then the dd chunks
+
+// softmax weight of channel j of a pixel (zp its logits, zb the bias in LDS) given its max and 1 / sum
+__device__ __forceinline__ float weight(const float* zp, const float* zb, int j, float zmax, float inv) {
+  return expf(zp[j] + zb[j] - zmax) * inv;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void cdna_comp_fwd_k(const float* __restrict__ params, const float* __restrict__ z,
+                                                       const float* __restrict__ zbias, const float* __restrict__ img,
+                                                       float* __restrict__ out, float* __restrict__ kern_norm, Geo g,
+                                                       float shift) {
+  __shared__ float kn[kMaxK * kMaxK * kMaxM];
+  __shared__ float S[kMaxM];
+  __shared__ float win[kWin];
+  __shared__ float zb[kMaxZ];
+  const int b = blockIdx.z, y0 = blockIdx.y * kTile, x0 = blockIdx.x * kTile, nz = g.M + 1;
+  constexpr int kk = K * K, ww = kTile + K - 1;
+  if ((int)threadIdx.x < nz) zb[threadIdx.x] = zbias ? zbias[threadIdx.x] : 0.f;
+  stage_kernels(params, b, g, shift, kn, S);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && kern_norm)
+    for (int i = threadIdx.x; i < kk * g.M; i += blockDim.x) kern_norm[(long long)b * kk * g.M + i] = kn[i];
+  stage_window(img + (long long)b * g.H * g.W * g.pitch, g.C, g.pitch, y0, x0, g, win);
+  __syncthreads();
+  const int ly = threadIdx.x / kTile, lx = threadIdx.x % kTile;
+  const int y = y0 + ly, x = x0 + lx;
+  if (y >= g.H || x >= g.W) return;
+  const long long pix = ((long long)b * g.H + y) * g.W + x;
+  const float* zp = z + pix * nz;
+  float zmax = -INFINITY, sum = 0.f;
+  for (int j = 0; j < nz; ++j) zmax = fmaxf(zmax, zp[j] + zb[j]);
+  for (int j = 0; j < nz; ++j) sum += expf(zp[j] + zb[j] - zmax);
+  const float inv = 1.f / sum;
+  const float* centre = win + ((ly + g.pad) * ww + lx + g.pad) * g.C;           // the pixel itself
+  const float s0 = weight(zp, zb, 0, zmax, inv);
+  float f[kMaxC];
+#pragma unroll
+  for (int i = 0; i < kMaxC; ++i) f[i] = i < g.C ? s0 * centre[i] : 0.f;
+  for (int c = 0; c < g.C; ++c) {
+    float w[kk];                                                                // the pixel's window of colour c, in registers
+#pragma unroll
+    for (int u = 0; u < K; ++u)
+#pragma unroll
+      for (int v = 0; v < K; ++v) w[u * K + v] = win[((ly + u) * ww + lx + v) * g.C + c];
+    for (int m = 0; m < g.M; ++m) {
+      float acc = 0.f;
+#pragma unroll
+      for (int t = 0; t < kk; ++t) acc += w[t] * kn[t * g.M + m];              // LDS broadcast reads
+      const int q = c * g.M + m, j = q / g.C, i = q - j * g.C;                  // piece j, channel i
+      const float v = weight(zp, zb, j + 1, zmax, inv) * acc;
+#pragma unroll
+      for (int ii = 0; ii < kMaxC; ++ii)                                         // (a select, not a dynamic register index)
+        if (ii == i) f[ii] += v;
+    }
+  }
+  float* o = out + pix * g.C;
+#pragma unroll
+  for (int i = 0; i < kMaxC; ++i)
+    if (i < g.C) o[i] = f[i];
+}
+
+// The tile pass of the backward: dz for every pixel; part_n[b][tile][(u*K+v)*M + m] = sum over the tile's pixels and the
+// colours of dT_q * image(pixel + (u,v) - pad, c) with q = c*M + m; part_b[b][tile][j] = sum over the tile's pixels of dz_j.
+template <int K>
+__global__ __launch_bounds__(256) void cdna_comp_bwd_tile_k(const float* __restrict__ kern_norm, const float* __restrict__ z,
+                                                            const float* __restrict__ zbias, const float* __restrict__ img,
+                                                            const float* __restrict__ dout, float* __restrict__ dz,
+                                                            float* __restrict__ part_n, float* __restrict__ part_b, Geo g) {
+  __shared__ float kn[kMaxK * kMaxK * kMaxM];
+  __shared__ float win[kWin];
+  __shared__ float zb[kMaxZ];
+  __shared__ float big[kBig];     // phase 1: g_j, then dz_j, of pixel p at big[j * kPix + p]; phase 2: dd[pixel][mask][colour]
+  __shared__ float red[kPix];
+  const int b = blockIdx.z, ty = blockIdx.y, tx = blockIdx.x, y0 = ty * kTile, x0 = tx * kTile;
+  constexpr int kk = K * K, ww = kTile + K - 1;
+  const int nz = g.M + 1, n = kk * g.M, tid = threadIdx.x;
+  if (tid < nz) zb[tid] = zbias ? zbias[tid] : 0.f;
+  for (int i = tid; i < n; i += blockDim.x) kn[i] = kern_norm[(long long)b * n + i];
+  stage_window(img + (long long)b * g.H * g.W * g.pitch, g.C, g.pitch, y0, x0, g, win);
+  __syncthreads();
+  const int ly = tid / kTile, lx = tid % kTile;
+  const bool inside = y0 + ly < g.H && x0 + lx < g.W;
+  // (a thread outside the image works on the last pixel of its row / column and contributes zeros)
+  const long long pix = ((long long)b * g.H + min(y0 + ly, g.H - 1)) * g.W + min(x0 + lx, g.W - 1);
+  const float* zp = z + pix * nz;
+  float d[kMaxC];
+#pragma unroll
+  for (int i = 0; i < kMaxC; ++i) d[i] = (inside && i < g.C) ? dout[pix * g.C + i] : 0.f;
+  float zmax = -INFINITY, sum = 0.f;
+  for (int j = 0; j < nz; ++j) zmax = fmaxf(zmax, zp[j] + zb[j]);
+  for (int j = 0; j < nz; ++j) sum += expf(zp[j] + zb[j] - zmax);
+  const float inv = 1.f / sum;
+
+  // ---- phase 1: g_j in big[j][pixel], then dz_j
+  const float* centre = win + ((ly + g.pad) * ww + lx + g.pad) * g.C;
+  float g0 = 0.f;
+#pragma unroll
+  for (int i = 0; i < kMaxC; ++i)
+    if (i < g.C) g0 += d[i] * centre[i];
+  big[tid] = g0;
+  for (int j = 1; j < nz; ++j) big[j * kPix + tid] = 0.f;
+  for (int c = 0; c < g.C; ++c) {
+    float w[kk];
+#pragma unroll
+    for (int u = 0; u < K; ++u)
+#pragma unroll
+      for (int v = 0; v < K; ++v) w[u * K + v] = win[((ly + u) * ww + lx + v) * g.C + c];
+    for (int m = 0; m < g.M; ++m) {
+      float acc = 0.f;
+#pragma unroll
+      for (int t = 0; t < kk; ++t) acc += w[t] * kn[t * g.M + m];
+      const int q = c * g.M + m, j = q / g.C, i = q - j * g.C;
+      float di = 0.f;
+#pragma unroll
+      for (int ii = 0; ii < kMaxC; ++ii)
+        if (ii == i) di = d[ii];
+      big[(j + 1) * kPix + tid] += di * acc;
+    }
+  }
+  float gbar = 0.f;
+  for (int j = 0; j < nz; ++j) gbar += weight(zp, zb, j, zmax, inv) * big[j * kPix + tid];
+  float* dzp = dz + pix * nz;
+  for (int j = 0; j < nz; ++j) {
+    const float v = inside ? weight(zp, zb, j, zmax, inv) * (big[j * kPix + tid] - gbar) : 0.f;
+    big[j * kPix + tid] = v;
+    if (inside) dzp[j] = v;
+  }
+  __syncthreads();
+  // bias-gradient partial of the tile: 4 lanes per channel, 64 pixels each, then the 4 in order
+  if (tid < nz * 4) {
+    const int j = tid >> 2, r = tid & 3;
+    float s = 0.f;
+    for (int p = r * 64; p < r * 64 + 64; ++p) s += big[j * kPix + p];
+    red[tid] = s;
+  }
+  __syncthreads();
+  const long long tile = ((long long)b * g.tiles_y + ty) * g.tiles_x + tx;
+  if (tid < nz) part_b[tile * nz + tid] = red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3];
+
+  // ---- phase 2: kernel-gradient partials.  dd[(p*nm + mm)*C + c] = dT_q of pixel p, q = c*M + m0 + mm, for as many masks
+  // as fit `big`; then 4 pixel groups x 64 tap slots: a thread sums its tap over 64 pixels, the groups fold through LDS
+  float* dd = big;
+  float* o = part_n + tile * n;
+  const int mc = min(g.M, kBig / (kPix * g.C));
+  const int t = tid & 63, pg = tid >> 6, u = t / K, v = t % K;
+  for (int m0 = 0; m0 < g.M; m0 += mc) {
+    const int nm = min(mc, g.M - m0);
+    __syncthreads();                                 // every read of big (dz sums, previous chunk) is done
+    for (int mm = 0; mm < nm; ++mm)
+      for (int c = 0; c < g.C; ++c) {
+        const int q = c * g.M + m0 + mm, j = q / g.C, i = q - j * g.C;
+        float di = 0.f;
+#pragma unroll
+        for (int ii = 0; ii < kMaxC; ++ii)
+          if (ii == i) di = d[ii];                  // (zero outside the image)
+        dd[(tid * nm + mm) * g.C + c] = di * weight(zp, zb, j + 1, zmax, inv);
+      }
+    __syncthreads();
+    for (int mm = 0; mm < nm; ++mm) {
+      float acc = 0.f;
+      if (t < kk) {
+        for (int p = pg * 64; p < pg * 64 + 64; ++p) {
+          const float* wsrc = win + ((p / kTile + u) * ww + p % kTile + v) * g.C;
+          const float* dsrc = dd + (p * nm + mm) * g.C;
+#pragma unroll
+          for (int c = 0; c < kMaxC; ++c)
+            if (c < g.C) acc += dsrc[c] * wsrc[c];
+        }
+      }
+      __syncthreads();                               // red[] of the previous mask has been consumed
+      red[tid] = acc;
+      __syncthreads();
+      if (tid < kk) o[tid * g.M + m0 + mm] = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
+    }
+  }
+}
+
+// blocks 0..B-1: dn = sum of the sample's tile partials; through the normalisation dk = (dn - sum_uv(dn * n)) / S and the
+// relu, dp = dk * [p - shift > 0] (cdna_bwd_kern_final_k).  Block B (when dbias is wanted): dbias over all the partials.
+__global__ __launch_bounds__(256) void cdna_comp_bwd_final_k(const float* __restrict__ params, const float* __restrict__ kern_norm,
+                                                             const float* __restrict__ part_n, const float* __restrict__ part_b,
+                                                             float* __restrict__ dparams, float* __restrict__ dbias, float dbias_acc,
+                                                             Geo g, float shift) {
+  __shared__ float dn[kMaxK * kMaxK * kMaxM];
+  __shared__ float dot[kMaxM], S[kMaxM];
+  __shared__ double scratch[16];
+  const int b = blockIdx.x, kk = g.K * g.K, n = kk * g.M, ntile = g.tiles_x * g.tiles_y, nz = g.M + 1;
+  if (b == g.B) {
+    const int rows = g.B * ntile;
+    for (int j = 0; j < nz; ++j) {
+      double s = 0.0;
+      for (int r = threadIdx.x; r < rows; r += blockDim.x) s += part_b[(long long)r * nz + j];
+      s = acg::block_sum(s, scratch);
+      if (threadIdx.x == 0) dbias[j] = (dbias_acc != 0.f ? dbias_acc * dbias[j] : 0.f) + (float)s;
+    }
+    return;
+  }
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    double s = 0.0;
+    for (int t = 0; t < ntile; ++t) s += part_n[((long long)b * ntile + t) * n + i];
+    dn[i] = (float)s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < g.M) {
+    const int m = threadIdx.x;
+    float d = 0.f, s = 0.f;
+    for (int t = 0; t < kk; ++t) {
+      d += dn[t * g.M + m] * kern_norm[(long long)b * n + t * g.M + m];
+      s += fmaxf(params[(long long)b * n + t * g.M + m] - shift, 0.f) + shift;
+    }
+    dot[m] = d; S[m] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int m = i % g.M;
+    const float dk = (dn[i] - dot[m]) / S[m];
+    dparams[(long long)b * n + i] = params[(long long)b * n + i] - shift > 0.f ? dk : 0.f;
+  }
+}
+
+int make_geo(const char* who, int B, int H, int W, int C, int M, int K, int pitch, Geo* g) {
+  ACG_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && M > 0 && K > 0, ACG_ERR_INVALID_ARG, "%s: non-positive size", who);
+  ACG_REQUIRE(C <= kMaxC && M <= kMaxM, ACG_ERR_UNSUPPORTED, "%s: supports C <= %d, masks <= %d", who, kMaxC, kMaxM);
+  ACG_REQUIRE(K == 3 || K == 5 || K == 7, ACG_ERR_UNSUPPORTED, "%s: kernel size %d (3, 5 or 7)", who, K);
+  ACG_REQUIRE(B <= 65535, ACG_ERR_UNSUPPORTED, "%s: batch too large", who);
+  ACG_REQUIRE(pitch == 0 || (pitch >= C && pitch <= 64), ACG_ERR_INVALID_ARG, "%s: image pitch %d for %d channels", who, pitch, C);
+  g->B = B; g->H = H; g->W = W; g->C = C; g->M = M; g->K = K;
+  g->pad = (K - 1) / 2;                              // SAME, stride 1: pad_before = (k-1)//2
+  g->tiles_x = (W + kTile - 1) / kTile; g->tiles_y = (H + kTile - 1) / kTile;
+  g->pitch = pitch ? pitch : C;
+  return ACG_OK;
+}
+
+size_t partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.K * g.K * g.M; }     // floats of part_n
+
+}  // namespace
+
+extern "C" {
+
+size_t acg_cdna_composite_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t M, int32_t K) {
+  Geo g;
+  if (make_geo("cdna_composite_workspace_bytes", B, H, W, C, M, K, 0, &g) != ACG_OK) return 0;
+  return (partials(g) + (size_t)B * g.tiles_x * g.tiles_y * (M + 1)) * sizeof(float);
+}
+
+int32_t acg_cdna_composite_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                               int32_t image_pitch, float* out, float* kern_norm, int32_t B, int32_t H, int32_t W, int32_t C,
+                               int32_t M, int32_t K, float relu_shift, acg_stream_t stream) {
+  Geo g;
+  if (int rc = make_geo("cdna_composite_fwd", B, H, W, C, M, K, image_pitch, &g)) return rc;
+  ACG_REQUIRE(params && mask_logits && image && out, ACG_ERR_INVALID_ARG, "cdna_composite_fwd: null pointer");
+  const dim3 grid(g.tiles_x, g.tiles_y, B);
+  hipStream_t st = acg::to_stream(stream);
+  if (K == 3) ACG_LAUNCH(cdna_comp_fwd_k<3>, grid, dim3(256), 0, st, params, mask_logits, mask_bias, image, out, kern_norm, g, relu_shift);
+  else if (K == 5) ACG_LAUNCH(cdna_comp_fwd_k<5>, grid, dim3(256), 0, st, params, mask_logits, mask_bias, image, out, kern_norm, g, relu_shift);
+  else ACG_LAUNCH(cdna_comp_fwd_k<7>, grid, dim3(256), 0, st, params, mask_logits, mask_bias, image, out, kern_norm, g, relu_shift);
+  return acg::check_launch("cdna_composite_fwd");
+}
+
+int32_t acg_cdna_composite_bwd(const float* params, const float* kern_norm, const float* mask_logits, const float* mask_bias,
+                               const float* image, int32_t image_pitch, const float* dout, float* dparams, float* dmask_logits,
+                               float* dmask_bias, float dmask_bias_accumulate, int32_t B, int32_t H, int32_t W, int32_t C,
+                               int32_t M, int32_t K, float relu_shift, void* ws, size_t wsb, acg_stream_t stream) {
+  Geo g;
+  if (int rc = make_geo("cdna_composite_bwd", B, H, W, C, M, K, image_pitch, &g)) return rc;
+  ACG_REQUIRE(params && kern_norm && mask_logits && image && dout && dparams && dmask_logits, ACG_ERR_INVALID_ARG,
+              "cdna_composite_bwd: null pointer");
+  ACG_REQUIRE(ws && wsb >= acg_cdna_composite_workspace_bytes(B, H, W, C, M, K), ACG_ERR_WORKSPACE,
+              "cdna_composite_bwd: workspace too small");
+  hipStream_t st = acg::to_stream(stream);
+  float* part_n = (float*)ws;
+  float* part_b = part_n + partials(g);
+  const dim3 grid(g.tiles_x, g.tiles_y, B);
+  if (K == 3) ACG_LAUNCH(cdna_comp_bwd_tile_k<3>, grid, dim3(256), 0, st, kern_norm, mask_logits, mask_bias, image, dout, dmask_logits, part_n, part_b, g);
+  else if (K == 5) ACG_LAUNCH(cdna_comp_bwd_tile_k<5>, grid, dim3(256), 0, st, kern_norm, mask_logits, mask_bias, image, dout, dmask_logits, part_n, part_b, g);
+  else ACG_LAUNCH(cdna_comp_bwd_tile_k<7>, grid, dim3(256), 0, st, kern_norm, mask_logits, mask_bias, image, dout, dmask_logits, part_n, part_b, g);
+  if (int rc = acg::check_launch("cdna_composite_bwd tile")) return rc;
+  ACG_LAUNCH(cdna_comp_bwd_final_k, dim3(B + (dmask_bias ? 1 : 0)), dim3(256), 0, st, params, kern_norm, (const float*)part_n,
+             (const float*)part_b, dparams, dmask_bias, dmask_bias_accumulate, g, relu_shift);
+  return acg::check_launch("cdna_composite_bwd final");
+}
+
+}  // extern "C"

@@ -23,11 +23,6 @@ import numpy as np
 ACTION_DIM = 10
 
 
-def _flag(v):
-    from .train import _flag as f
-    return f(v)
-
-
 def load_frames(path):
     """A frames ``.npy`` [N, T, H, W, 3] -> float32 in [-1, 1] (uint8 is read as x / 127.5 - 1)."""
     arr = np.load(path, mmap_mode='r')
@@ -88,11 +83,14 @@ def set_psnr(sqerr, valid, count_per_frame):
 
 
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
-             seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0'):
+             seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
-    ``dna`` / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of ``input_path`` and write
-    ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs with ``gif``) and with
-    ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  -> the metrics dict."""
+    ``dna`` / ``cdna`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
+    ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
+    with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  -> the metrics dict."""
+    if dna and cdna:
+        raise ValueError('dna and cdna name two different generators')
+    transform = 'cdna' if cdna else dna
     from . import graph as G
     from .metrics import SSIM_DEFINITION
     from .saver import Saver, latest_checkpoint
@@ -106,7 +104,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
     try:
-        trainer = Trainer(sess, False, 'bce', 'adam', dna, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False)
+        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False,
+                          num_masks=num_masks)
         sess.run(G.global_variables_initializer())
         Saver().restore(sess, ckpt)
         keys = ('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
@@ -140,6 +139,9 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         count = int(np.prod(hw))        # H * W * 3 values per frame
         result = {
             'checkpoint': os.path.abspath(ckpt),
+            'model': trainer.model,
+            'num_masks': num_masks if trainer.model == 'cdna' else None,
+            'ksize': ksize if trainer.model != 'plain' else None,
             'sequences': n_seq,
             'steps': int(steps),
             'ssim_definition': SSIM_DEFINITION + ' (data_range 2 for frames in [-1, 1])',
@@ -169,7 +171,8 @@ def main(argv=None):
     parser.add_argument('input', type=str, help="frames .npy [N,T,H,W,3], push TFRecord directory, or 'synthetic'")
     parser.add_argument('output', type=str)
     parser.add_argument('--actions', type=str, default=None, help='actions .npy [N,T,10] (with a frames .npy)')
-    parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
+    from .train import add_model_args, check_model_args
+    add_model_args(parser)
     parser.add_argument('--ksize', type=int, default=5)
     parser.add_argument('--img_size', type=int, default=64)
     parser.add_argument('--dtype', type=str, default='f32', choices=['f32', 'bf16'])
@@ -181,6 +184,7 @@ def main(argv=None):
     parser.add_argument('--dump', action='store_true', help='save the predictions as predictions.npy')
     parser.add_argument('--device', type=str, default='cuda:0')
     args = parser.parse_args(argv)
+    check_model_args(parser, args)
     if args.batch_size < 1:
         parser.error('--batch_size must be >= 1')
     if args.num_sequences is not None and args.num_sequences < 1:
@@ -201,7 +205,8 @@ def main(argv=None):
             parser.error('frames %s and actions %s disagree in N or T' % (frames.shape[:2], actions.shape[:2]))
     return evaluate(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, ksize=args.ksize,
                     img_size=args.img_size, dtype=args.dtype, batch_size=args.batch_size, seq_len=args.seq_len,
-                    num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device)
+                    num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
+                    cdna=args.cdna, num_masks=args.num_masks)
 
 
 if __name__ == '__main__':

@@ -86,6 +86,52 @@ def build_generator_transform(images, actions, batch_size=None, reuse=False, col
         return frame, state
 
 
+def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10, ksize=5):
+    """CDNA generator: the DNA generator's trunk with the reference's ``cdna_transformation`` (ops.py:52-98, which none of
+    its models calls) as the motion model.  Returns ``(frame, state)``.
+
+    ``cdna_params``, a linear layer (bias, no BatchNorm or activation) on the action-conditioned bottleneck h0
+    [B, S/16, S/16, 266] - stored as a VALID S/16 x S/16 conv, ``g/cdna_params/weights`` [S/16, S/16, 266, k*k*M], the same
+    numbers as slim's [S/16 * S/16 * 266, k*k*M] in reshape order - predicts M = ``num_masks`` k x k kernels per sample.
+    tconv1, tconv2, the state head and tconv3 are the DNA generator's; ``tconv4`` (5x5/2, bias only) gives M+1 mask logits.
+    The frame is s_0 * images + sum_j s_{j+1} * T_j with s = softmax over the M+1 channels and T_j the pieces of
+    cdna_transformation (its channel split kept as written), in one fused kernel (ops.cdna_composite).
+
+    Two differences from the CDNA model of the paper the push dataset comes from: there is no image generated from
+    scratch among the composited candidates, and the masks come from the 5x5/2 ``tconv4`` instead of a 1x1 layer.
+    float32 only; ``ksize`` 3, 5 or 7, 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
+    if batch_size is not None and batch_size != images.shape[0]:
+        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
+    if images.shape[3] != color_channels:
+        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
+    if ksize not in (3, 5, 7) or not 1 <= num_masks <= 32:
+        raise ValueError('CDNA generator: ksize must be 3, 5 or 7 and num_masks 1..32 (got %r, %r)' % (ksize, num_masks))
+    if images.shape[1] % 16 or images.shape[2] % 16:
+        raise ValueError('CDNA generator: image size %s is not a multiple of 16' % (images.shape[1:3],))
+    if O.half_mode():
+        raise NotImplementedError('the CDNA generator is float32 only')
+    with O.variable_scope('g', reuse=reuse), \
+            O.arg_scope([O.conv2d, O.deconv2d], activation_fn=O.relu, stride=2, padding='SAME',
+                        normalizer_fn=O.batch_norm, reuse=reuse):
+        net = _stack(getattr(images, 'padded', images), G_DNA['encoder'], O.conv2d)
+        net = _with_actions(net, actions, 'actions')
+        nk = ksize * ksize * num_masks
+        params = O.conv2d(net, nk, [net.shape[1], net.shape[2]], activation_fn=None, stride=1, padding='VALID',
+                          normalizer_fn=None, scope='cdna_params')
+        params = params.reshape((images.shape[0], nk))
+        net = _stack(net, G_DNA['decoder_a'], O.deconv2d)
+        with G.get_default_graph().side_branch():
+            state = _stack(net, G_DNA['state'], O.conv2d, size=3)
+            sk = state.shape[1]
+            state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
+                             scope='sconv5')
+            state = O.squeeze(state)
+        net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
+        logits = O.deconv2d(net, num_masks + 1, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
+        frame = O.cdna_composite(logits, images, params, num_masks, ksize)
+        return frame, state
+
+
 def build_discriminator(inputs, actions, reuse=False):
     """Discriminator (models.py:76-89): 5 x [conv5x5/2 + BN + lrelu], actions after conv2, 2x2 logit conv + BN."""
     with O.variable_scope('d', reuse=reuse), \

@@ -924,6 +924,79 @@ class CdnaBwdOp(G.Op):
         return launch
 
 
+def _cdna_entry(rt, name):
+    """An entry of include/acgan_cdna.h (_lib.CDNA_SIGNATURES); a library without it (the C oracle) is a clear error."""
+    fn = getattr(rt.lib, name, None)
+    if fn is None:
+        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_cdna.h): the CDNA generator runs on the HIP library only'
+                            % (getattr(rt.lib, 'path', rt.lib), name))
+    return fn
+
+
+class CdnaCompositeOp(G.Op):
+    """The CDNA generator's output stage in one kernel (acg_cdna_composite_fwd): normalise the per-sample kernels ``params``,
+    transform the image with each (cdna_transformation's M pieces, kept in registers) and composite s_0 * image +
+    sum_j s_{j+1} * T_j under s = softmax(logits + bias) over the M + 1 mask channels.  ``bias`` (may be None) is the bias
+    variable of the layer that produced the logits, folded in as DnaOp does.  Outputs: the frame, and the normalised kernels
+    the backward pass reads."""
+
+    def __init__(self, logits, image, params, masks, ksize, relu_shift, name, bias=None):
+        b, h, w, c = image.shape
+        self.masks, self.ksize, self.relu_shift = int(masks), int(ksize), float(relu_shift)
+        self.has_bias = bias is not None
+        self.kern_norm = _new((b, self.ksize * self.ksize * self.masks), name + ':kern_norm')
+        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
+                         [_new(image.shape, name + ':0'), self.kern_norm])
+
+    def bind(self, rt):
+        lg, img, par = self.inputs[:3]
+        b, h, w, c = img.shape
+        fn = _cdna_entry(rt, 'cdna_composite_fwd')
+        pb = _p(self.inputs[3].buf) if self.has_bias else None
+        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), _p(self.kern_norm.buf), b, h, w, c,
+                self.masks, self.ksize, self.relu_shift)
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        if needs[1]:
+            raise NotImplementedError('cdna_composite: gradient w.r.t. the image is not implemented (the image is a network '
+                                      'input, train.py:53-54)')
+        dst, acc = (None, 0.0)
+        if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
+            dst, acc = ctx.slot(self.inputs[3])
+        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
+            return [None] * len(self.inputs)
+        op = CdnaCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
+        if dst is not None:
+            ctx.wrote(self.inputs[3], op)
+        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
+
+
+class CdnaCompositeBwdOp(G.Op):
+    """acg_cdna_composite_bwd: d logits, d params (through the normalisation and the relu) and, into the bias variable's
+    gradient window, d bias."""
+
+    def __init__(self, fwd, dout, dbias_dst, accumulate, name):
+        self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
+        lg, img, par = fwd.inputs[:3]
+        super().__init__(G.get_default_graph(), name, [lg, img, par, fwd.kern_norm, dout] + list(fwd.inputs[3:]),
+                         [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
+                         + ([dbias_dst] if dbias_dst is not None else []))
+
+    def bind(self, rt):
+        lg, img, par, kn, dout = self.inputs[:5]
+        f = self.fwd
+        b, h, w, c = img.shape
+        fn = _cdna_entry(rt, 'cdna_composite_bwd')
+        ws, n = rt.workspace(_cdna_entry(rt, 'cdna_composite_workspace_bytes')(b, h, w, c, f.masks, f.ksize))
+        self._keep = ws
+        pb = _p(self.inputs[5].buf) if f.has_bias else None
+        args = (_p(par.buf), _p(kn.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf), _p(self.outputs[0].buf),
+                _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c, f.masks, f.ksize, f.relu_shift,
+                _p(ws), n)
+        return lambda s: fn(*args, s)
+
+
 DGRAD_CHANNEL_LIMIT = True     # A/B switch (bench.py --no-dgrad-limit): input gradients skip the columns of tiled action channels
 
 
@@ -1338,6 +1411,30 @@ def cdna_transformation(prev_image, cdna_input, num_masks, color_channels, ksize
     params = fully_connected(cdna_input, ksize * ksize * num_masks, activation_fn=None, scope='cdna_params', reuse=reuse)
     op = CdnaOp(params, prev_image, num_masks, ksize, RELU_SHIFT, _scope_name('cdna'))
     return list(op.outputs[:num_masks])
+
+
+def cdna_composite(mask_logits, image, params, num_masks, ksize=DNA_KERN_SIZE, name='cdna'):
+    """The CDNA generator's frame in one op (CdnaCompositeOp): the ``num_masks`` kernels ``params`` [B, k*k*M] transform
+    ``image`` [B,H,W,C] as cdna_transformation does, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
+    the M transformed images through a per-pixel softmax.  When the logits come from a layer with a bias and neither
+    BatchNorm nor activation, that bias is folded into the kernel (as dna_gather does)."""
+    _check_nhwc(mask_logits, 'cdna_composite')
+    _check_nhwc(image, 'cdna_composite')
+    if ksize not in (3, 5, 7) or not 1 <= num_masks <= 32:
+        raise ValueError('cdna_composite: supports ksize 3/5/7 and 1..32 masks, got ksize %r, %r masks' % (ksize, num_masks))
+    if not 1 <= image.shape[3] <= 4:
+        raise ValueError('cdna_composite: image channels outside 1..4')
+    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
+        raise ValueError('cdna_composite: mask logits %s do not match image %s with %d masks' % (mask_logits.shape, image.shape, num_masks))
+    if params.shape != (image.shape[0], ksize * ksize * num_masks):
+        raise ValueError('cdna_composite: params %s, expected [%d, %d]' % (params.shape, image.shape[0], ksize * ksize * num_masks))
+    if half_mode() or image.dtype != torch.float32:
+        raise NotImplementedError('cdna_composite is float32 only')
+    bias = None
+    prod = mask_logits.op
+    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
+        mask_logits, bias = prod.inputs[0], prod.inputs[1]
+    return CdnaCompositeOp(mask_logits, image, params, num_masks, ksize, RELU_SHIFT, _scope_name(name), bias=bias).outputs[0]
 
 
 def concat_actions(x, actions, name='concat_actions'):

@@ -38,14 +38,18 @@ ACTION_DIM, STATE_DIM = 10, 5
 
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
-                 seed=0, batched_d=True, lookahead=True):
+                 seed=0, batched_d=True, lookahead=True, num_masks=10):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
         inputs then finds its generator forward pass done.  The two passes read the same generator weights (the D step does not
         touch them), so this is the reference's arithmetic - one D step, then one G step (train.py:241-263) - with the two
-        generator forward passes of an iteration sharing their launches at twice the GEMM height."""
+        generator forward passes of an iteration sharing their launches at twice the GEMM height.
+        ``arg_transform``: False - the plain generator; True or 'dna' - the DNA generator (the reference's ``--dna``); 'cdna' -
+        the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses."""
         self.sess = sess
+        self.model = model_kind(arg_transform)
+        self.num_masks = num_masks
         self.batch_size, self.img_size, self.ksize = batch_size, img_size, ksize
         self.arg_adv, self.arg_loss, self.arg_opt, self.arg_transform = arg_adv, arg_loss, arg_opt, arg_transform
         if arg_loss not in ('bce', 'wass'):
@@ -67,6 +71,8 @@ class Trainer:
         self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn)
 
         def build_g(images, actions, batch, reuse):
+            if self.model == 'cdna':
+                return M.build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse)
             if arg_transform:
                 return M.build_generator_transform(images, actions, batch_size=batch, ksize=ksize, reuse=reuse)
             return M.build_generator(images, actions, reuse=reuse), None
@@ -344,6 +350,15 @@ class Trainer:
         return {k: float(np.asarray(v).reshape(-1)[0]) for k, v in zip(self._summary_names, values)}
 
 
+def model_kind(arg_transform):
+    """The generator an ``arg_transform`` names: 'plain' (False), 'dna' (True or 'dna') or 'cdna'."""
+    if isinstance(arg_transform, str):
+        if arg_transform in ('dna', 'cdna'):
+            return arg_transform
+        raise ValueError("unexpected transform argument %r (False, True / 'dna' or 'cdna')" % arg_transform)
+    return 'dna' if arg_transform else 'plain'
+
+
 def _join(first, second):
     """[first ; second] along the batch axis, numpy arrays or (device) torch tensors."""
     if torch.is_tensor(first):
@@ -460,7 +475,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           batch_size=64, img_size=64, seq_len=8, ksize=5, train_iter=TRAIN_ITER, pretrain_iter=PRETRAIN_ITER,
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
-          data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0):
+          data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
+          num_masks=10):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -475,7 +491,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     as the reference's queue runners do).  ``data_decode``: 'exact' (decode -> crop -> box mean, the reference's arithmetic) or
     'dct' (opt-in, approximate: the reduction inside libjpeg's inverse DCT, push_data.decode_frame).  ``data_cache_gb``: keep up to
     that many GiB of decoded frames in host memory - a record that comes round again in a later epoch is not decoded again (same
-    bits; 0 = off, as the reference).  ``synthetic_pool``: SyntheticPush(pool=...)."""
+    bits; 0 = off, as the reference).  ``synthetic_pool``: SyntheticPush(pool=...).  ``arg_transform`` / ``num_masks``: the
+    generator, as Trainer takes them ('cdna': the CDNA generator with ``num_masks`` kernels of ``ksize``)."""
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
     np.random.seed(7)                                           # train.py:14
@@ -497,7 +514,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     try:
         trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
-                              select_frames=data_frames == 'selected')
+                              select_frames=data_frames == 'selected', num_masks=num_masks)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -511,8 +528,9 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
-                img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True):
-    trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize)
+                img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
+                num_masks=10):
+    trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks)
     sess.run(G.global_variables_initializer())
     saver = Saver()                                                           # train.py:215
     if resume:
@@ -602,6 +620,29 @@ def _flag(v):
     raise argparse.ArgumentTypeError('boolean expected')
 
 
+def add_model_args(parser):
+    """The generator flags shared by this CLI and evaluate's: --dna (the reference's), --cdna and --num_masks."""
+    parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
+    parser.add_argument('--cdna', nargs='?', const=True, default=False, type=_flag,
+                        help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7')
+    parser.add_argument('--num_masks', type=int, default=10, help='CDNA kernels / masks (1..32)')
+
+
+def check_model_args(parser, args):
+    """parser.error for generator flags that do not go together (before anything is created); -> Trainer's arg_transform."""
+    if args.dna and args.cdna:
+        parser.error('--dna and --cdna name two different generators')
+    if not 1 <= args.num_masks <= 32:
+        parser.error('--num_masks must be in 1..32')
+    if args.cdna:
+        if args.dtype == 'bf16':
+            parser.error('the CDNA generator is float32 only (--dtype bf16)')
+        if args.ksize not in (3, 5, 7):
+            parser.error('--cdna takes --ksize 3, 5 or 7')
+        return 'cdna'
+    return args.dna
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='action-conditioned video-prediction GAN on MI355X')
     parser.add_argument('input_path', type=str)
@@ -609,7 +650,7 @@ def main(argv=None):
     parser.add_argument('--adv', nargs='?', const=True, default=False, type=_flag)
     parser.add_argument('--loss', type=str, default='bce')
     parser.add_argument('--opt', type=str, default='adam')
-    parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
+    add_model_args(parser)
     parser.add_argument('--batch_size', type=int, default=64)
     parser.add_argument('--img_size', type=int, default=64)
     parser.add_argument('--seq_len', type=int, default=8)
@@ -641,6 +682,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
+    transform = check_model_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
     log_dir = os.path.join(args.output_path, 'logs')
     os.makedirs(args.output_path)
@@ -653,12 +695,12 @@ def main(argv=None):
         torch.cuda.set_device(local_rank)
         torch.distributed.init_process_group('gloo')
     trainer = train(args.input_path, os.path.join(args.output_path, 'train_output'), os.path.join(args.output_path, 'test_output'),
-                    log_dir, model_dir, args.adv, args.loss, args.opt, args.dna, batch_size=args.batch_size, img_size=args.img_size,
+                    log_dir, model_dir, args.adv, args.loss, args.opt, transform, batch_size=args.batch_size, img_size=args.img_size,
                     seq_len=args.seq_len, ksize=args.ksize, train_iter=args.train_iter, pretrain_iter=args.pretrain_iter,
                     n_critic=args.n_critic, device='cuda:%d' % local_rank, world_size=world_size, rank=rank, dtype=args.dtype,
                     sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
-                    data_cache_gb=args.data_cache_gb)
+                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

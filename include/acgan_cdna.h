@@ -1,0 +1,55 @@
+/*
+ * acgan_cdna.h - the CDNA generator's output stage in libacgan_hip.so: normalised per-sample kernels, the M transformed
+ * images and their masked composite with the previous image, in one kernel per direction (the M transformed images never
+ * reach memory).
+ *
+ * An addition under ACG_ABI_VERSION 8: it changes no signature of acgan_hip.h, whose conventions it follows - device
+ * pointers are borrowed (NHWC, float32), scratch comes in through (workspace, workspace_bytes) sized by the query below,
+ * calls are asynchronous on `stream`, return ACG_OK or an ACG_ERR_* code with the message in acg_last_error().  The Python
+ * binding keeps these entries in a table of their own (_lib.CDNA_SIGNATURES): the C oracle does not implement them.
+ *
+ * Definitions (B samples of H x W, C colours, M masks, k x k kernels; 1 <= C <= 4, 1 <= M <= 32, k in {3, 5, 7}):
+ *   params      [B, k*k*M]   read as [B, k, k, 1, M] (index (u*k + v)*M + m), as acg_cdna_fwd reads them;
+ *   kern_norm   [B, k*k*M]   n = (relu(p - relu_shift) + relu_shift) / sum over the k*k taps of one mask;
+ *   T_j         j = 0..M-1   the pieces of acg_cdna_fwd: the depthwise SAME correlation of the image with the normalised
+ *                            kernels, channel q = c*M + m, split into M pieces of C channels - piece j, channel i is
+ *                            colour (j*C + i) / M under mask (j*C + i) % M;
+ *   mask_logits [B, H, W, M+1] z; mask_bias [M+1] b (NULL = zero);
+ *   s           softmax over the M+1 channels of z + b, per pixel (max-subtracted);
+ *   out         [B, H, W, C] = s_0 * image + sum_j s_{j+1} * T_j.
+ * image_pitch: channel pitch of `image` (0 = C; C..64).  The output is dense.
+ */
+#ifndef ACGAN_CDNA_H
+#define ACGAN_CDNA_H
+
+#include "acgan_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Bytes of workspace acg_cdna_composite_bwd needs (0 for an unsupported geometry). */
+size_t acg_cdna_composite_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks, int32_t ksize);
+
+/* out (and kern_norm, when not NULL, for the backward pass) as defined above.  One launch. */
+int32_t acg_cdna_composite_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                               int32_t image_pitch, float* out, float* kern_norm, int32_t batch, int32_t h, int32_t w, int32_t c,
+                               int32_t masks, int32_t ksize, float relu_shift, acg_stream_t stream);
+
+/* Gradients of the composite from dout [B, H, W, C] (no image gradient: the image is an input of the model):
+ *   dmask_logits [B, H, W, M+1]: dz_j = s_j (g_j - sum_l s_l g_l), g_0 = <dout, image>, g_{j+1} = <dout, T_j>;
+ *   dmask_bias [M+1] (may be NULL): dmask_bias = (accumulate != 0 ? accumulate * dmask_bias : 0) + sum over pixels of dz;
+ *   dparams [B, k*k*M]: through T, the normalisation and the relu (zero where p - relu_shift <= 0).
+ * kern_norm is the forward's.  Two launches: a per-tile pass that writes dmask_logits and per-(sample, tile) partials into the
+ * workspace, and a final pass that sums the partials in a fixed order.  No atomics: the same call gives the same bits. */
+int32_t acg_cdna_composite_bwd(const float* params, const float* kern_norm, const float* mask_logits, const float* mask_bias,
+                               const float* image, int32_t image_pitch, const float* dout, float* dparams, float* dmask_logits,
+                               float* dmask_bias, float dmask_bias_accumulate, int32_t batch, int32_t h, int32_t w, int32_t c,
+                               int32_t masks, int32_t ksize, float relu_shift, void* workspace, size_t workspace_bytes,
+                               acg_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* ACGAN_CDNA_H */

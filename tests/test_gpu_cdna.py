@@ -1,0 +1,298 @@
+"""GPU: the CDNA generator and its fused transform-and-composite kernels (include/acgan_cdna.h) against float64
+restatements (tests/cdna_ref.py), through every call path the DNA generator runs on."""
+import ctypes
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cdna_ref as R
+import train_cases as TC
+from action_conditioned_gans_amd import _lib
+from action_conditioned_gans_amd import evaluate as E
+from action_conditioned_gans_amd import graph as G
+from action_conditioned_gans_amd import models as MB
+from action_conditioned_gans_amd import optim
+from action_conditioned_gans_amd import train as T
+from action_conditioned_gans_amd.saver import Saver
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda:0'
+SHAPES = [(1, 20, 36, 3, 1, 3), (3, 17, 33, 4, 32, 7), (2, 64, 64, 3, 10, 5), (32, 64, 64, 3, 10, 5), (4, 128, 128, 3, 10, 5),
+          (2, 24, 40, 1, 6, 5)]
+
+
+def _p(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _case(shape, seed=0):
+    """params with whole masks clamped (every tap <= shift) and logits of +-30 in places."""
+    b, h, w, c, m, k = shape
+    g = torch.Generator().manual_seed(seed)
+    params = torch.randn(b, k * k * m, generator=g) * 0.7 + 0.3
+    params.view(b, k * k, m)[:, :, 0] = -0.5
+    z = torch.randn(b, h, w, m + 1, generator=g) * 2
+    z[:, 0, :, 0], z[:, -1, :, -1] = 30.0, -30.0
+    bias = torch.randn(m + 1, generator=g)
+    img = torch.rand(b, h, w, c, generator=g) * 2 - 1
+    dout = torch.randn(b, h, w, c, generator=g)
+    return params.float(), z.float(), bias.float(), img.float(), dout.float()
+
+
+def fwd(lib, params, z, bias, img, m, k, pitch=0, c=None):
+    b, h, w = img.shape[:3]
+    c = c or img.shape[3]
+    out = torch.empty(b, h, w, c, device=DEV)
+    kn = torch.empty(b, k * k * m, device=DEV)
+    lib.cdna_composite_fwd(_p(params), _p(z), _p(bias), _p(img), pitch, _p(out), _p(kn), b, h, w, c, m, k, R.RELU_SHIFT, _stream())
+    torch.cuda.synchronize()
+    return out, kn
+
+
+def bwd(lib, params, kn, z, bias, img, dout, m, k, dbias=None, acc=0.0):
+    b, h, w, c = img.shape
+    dpar, dz = torch.empty_like(params), torch.empty_like(z)
+    nb = lib.cdna_composite_workspace_bytes(b, h, w, c, m, k)
+    ws = torch.zeros(nb + 512, dtype=torch.uint8, device=DEV)
+    ws[nb:] = 0xA5
+    lib.cdna_composite_bwd(_p(params), _p(kn), _p(z), _p(bias), _p(img), 0, _p(dout), _p(dpar), _p(dz), _p(dbias), acc, b, h, w, c,
+                           m, k, R.RELU_SHIFT, _p(ws), nb, _stream())
+    torch.cuda.synchronize()
+    assert bool((ws[nb:] == 0xA5).all()), 'the backward wrote past its workspace'
+    return dpar, dz
+
+
+def nrel(got, want):
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    return float((got - want).norm() / max(float(want.norm()), 1e-30))
+
+
+@pytest.mark.parametrize('shape', SHAPES, ids=str)
+def test_composite_forward_matches_float64(hip_abi, shape):
+    b, h, w, c, m, k = shape
+    lib = hip_abi.lib
+    params, z, bias, img, _ = _case(shape)
+    want = R.composite(z.double() + bias.double(), img.double(), params.double(), m, k)
+    d = lambda t: t.to(DEV)     # noqa: E731
+    out, kn = fwd(lib, d(params), d(z), d(bias), d(img), m, k)
+    assert (out.cpu().double() - want).abs().max().item() <= 1e-5
+    kern = torch.relu(params.double() - R.RELU_SHIFT).view(b, k * k, m) + R.RELU_SHIFT
+    kern = (kern / kern.sum(dim=1, keepdim=True)).view(b, -1)
+    assert ((kn.cpu().double() - kern).abs() <= 1e-6 * kern.abs()).all()
+    # the unfused path: acg_cdna_fwd's M pieces, composited in float32 by torch
+    pieces, _ = hip_abi.cdna_fwd(d(params), d(img), m, k)
+    s = torch.softmax(d(z) + d(bias), dim=-1)
+    ref = s[..., :1] * d(img) + sum(s[..., j + 1:j + 2] * pieces[j] for j in range(m))
+    assert (out - ref).abs().max().item() <= 1e-5
+    if c == 3:                 # the image at a channel pitch of 4 gives the same bits
+        img4 = torch.zeros(b, h, w, 4)
+        img4[..., :3] = img
+        out4, _ = fwd(lib, d(params), d(z), d(bias), d(img4), m, k, pitch=4, c=3)
+        assert torch.equal(out4, out)
+
+
+@pytest.mark.parametrize('shape', SHAPES, ids=str)
+def test_composite_backward_matches_float64(hip_abi, shape):
+    b, h, w, c, m, k = shape
+    lib = hip_abi.lib
+    params, z, bias, img, dout = _case(shape, seed=1)
+    pd, zd, bd = (t.double().requires_grad_(True) for t in (params, z, bias))
+    R.composite(zd + bd, img.double(), pd, m, k).backward(dout.double())
+    d = lambda t: t.to(DEV)     # noqa: E731
+    _, kn = fwd(lib, d(params), d(z), d(bias), d(img), m, k)
+    dbias = torch.full((m + 1,), 123.0, device=DEV)
+    dpar, dz = bwd(lib, d(params), kn, d(z), d(bias), d(img), d(dout), m, k, dbias=dbias, acc=0.0)
+    assert nrel(dz, zd.grad) <= 1e-4 and nrel(dpar, pd.grad) <= 1e-4 and nrel(dbias, bd.grad) <= 1e-4, (
+        nrel(dz, zd.grad), nrel(dpar, pd.grad), nrel(dbias, bd.grad))
+    assert (dpar.cpu()[params <= R.RELU_SHIFT] == 0).all(), 'clamped parameters must have zero gradient'
+    dbias2 = dbias.clone()
+    dpar2, dz2 = bwd(lib, d(params), kn, d(z), d(bias), d(img), d(dout), m, k, dbias=dbias2, acc=1.0)
+    assert torch.equal(dpar2, dpar) and torch.equal(dz2, dz), 'two launches differ'
+    assert torch.equal(dbias2, dbias + dbias), 'accumulate = 1 must add'
+    dpar3, dz3 = bwd(lib, d(params), kn, d(z), d(bias), d(img), d(dout), m, k)       # no bias gradient asked for
+    assert torch.equal(dpar3, dpar) and torch.equal(dz3, dz)
+
+
+def _gen_graph(B, S, M=10, K=5, seed=3):
+    G.reset_default_graph()
+    optim.set_data_parallel(1)
+    sess = G.Session(device=DEV)
+    img, act = G.placeholder((B, S, S, 3), name='img'), G.placeholder((B, 10), name='act')
+    frame, state = MB.build_generator_cdna(img, act, num_masks=M, ksize=K)
+    sess.run(G.global_variables_initializer())
+    params = R.init_params_cdna(batch=B, img=S, ksize=K, num_masks=M, seed=seed)
+    for n, v in G.get_default_graph().variables.items():
+        sess.set_value(v, params[n])
+    return sess, img, act, frame, state, params
+
+
+@pytest.mark.parametrize('B,S', [(2, 64), (32, 64), (2, 128)])
+def test_generator_forward_matches_float64(B, S):
+    sess, img, act, frame, state, params = _gen_graph(B, S)
+    rng = np.random.default_rng(B + S)
+    x = rng.uniform(-1, 1, (B, S, S, 3)).astype(np.float32)
+    a = rng.standard_normal((B, 10)).astype(np.float32)
+    got_f, got_s = sess.run([frame, state], {img: x, act: a})
+    with torch.no_grad():
+        wf, ws = R.generator_cdna({k: v.double() for k, v in params.items()}, torch.from_numpy(x).double(), torch.from_numpy(a).double())
+    assert TC.rel(got_f, wf.numpy()) <= 1e-3 and TC.rel(got_s, ws.numpy()) <= 1e-3, (TC.rel(got_f, wf.numpy()), TC.rel(got_s, ws.numpy()))
+    sess.close()
+
+
+def _trainer(B, loss='bce', opt='adam', seed=9, **kw):
+    G.reset_default_graph()
+    optim.set_data_parallel(1)
+    sess = G.Session(device=DEV, **{k: v for k, v in kw.items() if k == 'use_hip_graphs'})
+    tr = T.Trainer(sess, True, loss, opt, 'cdna', batch_size=B, img_size=64, ksize=5, **{k: v for k, v in kw.items() if k != 'use_hip_graphs'})
+    sess.run(G.global_variables_initializer())
+    params = R.init_params_cdna(batch=B, seed=seed)
+    for n, v in G.get_default_graph().variables.items():
+        sess.set_value(v, params[n])
+    return sess, tr, params
+
+
+def _data(B, seed=21):
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1, 1, (B, 64, 64, 3)).astype(np.float32)
+    y = np.clip(np.roll(x, 2, axis=2) + 0.05 * rng.standard_normal(x.shape).astype(np.float32), -1, 1)
+    return x, y, rng.standard_normal((B, 10)).astype(np.float32), rng.standard_normal((B, 5)).astype(np.float32)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize('loss,opt', [('bce', 'adam'), ('wass', 'rmsprop')])
+def test_full_size_step_matches_oracle_live(loss, opt):
+    """Batch 32, 64x64: the test pass, one D step and one G step against CdnaOracleTrainer in float64 - losses and per-variable
+    gradient norms to 1e-3; for RMSProp the weights after both updates."""
+    B = 32
+    sess, tr, params = _trainer(B, loss, opt)
+    x, y, a, s = _data(B)
+    td = lambda t: torch.from_numpy(t).double()     # noqa: E731
+    torch.set_num_threads(16)
+    ot = R.CdnaOracleTrainer({k: v.double() for k, v in params.items()}, True, loss, opt)
+    frame, state, _ = tr.test(x, y, a)
+    oframe, ostate, _ = ot.test(td(x), td(y), td(a))
+    assert TC.rel(frame, oframe.numpy()) <= 1e-3 and TC.rel(state, ostate.numpy()) <= 1e-3
+    dsumm = tr.train_d(x, y, a, summarize=True)
+    od = ot.train_d(td(x), td(y), td(a), return_all=True)
+    assert abs(dsumm['discriminator_loss'] - float(od['d_loss'])) <= 1e-3 * max(abs(float(od['d_loss'])), 1.0)
+    TC.check_norms(TC.flat_grad_norms(sess, tr.d_opt_op), {'dgrad_norm/' + k: v.norm() for k, v in ot.last_grads.items()},
+                   'dgrad_norm/', 1e-3, 'D grad')
+    res = sess.run([tr.g_opt_op, tr.g_loss], tr._feed(x, y, a, s))
+    og = ot.train_g(td(x), td(y), td(a), td(s), return_all=True)
+    assert abs(res[1][0] - float(og['g_loss'])) <= 1e-3 * abs(float(og['g_loss']))
+    TC.check_norms(TC.flat_grad_norms(sess, tr.g_opt_op), {'ggrad_norm/' + k: v.norm() for k, v in ot.last_grads.items()},
+                   'ggrad_norm/', 1e-3, 'G grad')
+    if opt == 'rmsprop':
+        for n, v in G.get_default_graph().variables.items():
+            got, want = sess.get_value(v).double(), ot.p[n]
+            assert (got - want).abs().max().item() <= 1e-3 * max(want.abs().max().item(), 1e-3) + 2e-6, n
+    sess.close()
+
+
+def test_pretrain_steps_stay_finite_and_lower_the_loss():
+    sess, tr, _ = _trainer(32)
+    x, y, a, s = _data(32, seed=7)
+    losses = [tr.pretrain_g(x, y, a, s) for _ in range(8)]
+    assert all(np.isfinite(losses)) and losses[-1] < losses[0], losses
+    sess.close()
+
+
+def test_lookahead_equals_the_plain_call_path_and_replay_equals_eager():
+    """As test_lookahead_equals_the_plain_call_path_on_the_gpu (batch 8, four iterations; after one: frames 1e-5, D gradient
+    1e-4, G gradient 5e-3); and the same four iterations without HIP graphs give the same bits as the captured run."""
+    x, y, a, s = TC.MG.inputs(8)
+    xb, yb, ab, sb = [np.ascontiguousarray(np.roll(t, 3, axis=0)[::-1]) for t in (y, x, a, s)]
+    n = lambda got, want: float(np.linalg.norm(np.asarray(got, np.float64) - np.asarray(want, np.float64)) / np.linalg.norm(np.asarray(want, np.float64)))  # noqa: E731
+
+    def run(use, graphs=True):
+        sess, tr, _ = _trainer(8, 'bce', 'rmsprop', use_hip_graphs=graphs)
+        grad = lambda name: [sess._materialize(t).clone().cpu().double() for t in G.get_default_graph().state if t.name == name][0]   # noqa: E731
+        first = None
+        for it in range(4):
+            tr.train_d(x, y, a, next_g=(xb, ab) if use else None)
+            dg = grad('d_opt/flat_grad') if it == 0 else None
+            frames = tr.train_g(xb, yb, ab, sb)
+            if it == 0:
+                first = (np.array(frames, copy=True), dg, grad('g_opt/flat_grad'))
+        final = {k: sess.get_value(v).clone() for k, v in G.get_default_graph().variables.items()}
+        if use and graphs:
+            assert all(p.graphs is not None for p in sess._programs.values())
+        sess.close()
+        return first, np.array(frames, copy=True), final
+    (f0, dg0, gg0), _, _ = run(False)
+    (f1, dg1, gg1), fl1, w1 = run(True)
+    assert n(f1, f0) <= 1e-5 and n(dg1, dg0) <= 1e-4 and n(gg1, gg0) <= 5e-3, (n(f1, f0), n(dg1, dg0), n(gg1, gg0))
+    _, fl2, w2 = run(True, graphs=False)
+    assert np.array_equal(fl1, fl2) and all(torch.equal(w1[k], w2[k]) for k in w1), 'HIP-graph replay differs from eager launches'
+
+
+def test_rollout_matches_float64_and_rollout_metrics_runs():
+    B, Tn = 4, 7
+    sess, tr, params = _trainer(B)
+    rng = np.random.default_rng(5)
+    frames = rng.uniform(-1, 1, (B, Tn, 64, 64, 3)).astype(np.float32)
+    acts = rng.standard_normal((B, Tn, 10)).astype(np.float32)
+    pred, _ = tr.test_sequence(frames, frames, acts)
+    ot = R.CdnaOracleTrainer({k: v.double() for k, v in params.items()}, True, 'bce', 'adam')
+    want, _ = ot.test_sequence(torch.from_numpy(frames).double(), torch.from_numpy(frames).double(), torch.from_numpy(acts).double())
+    assert pred.shape == (B, Tn - 1, 64, 64, 3)
+    for j in range(Tn - 1):
+        assert TC.rel(pred[:, j], want[:, j].numpy()) <= 1e-3, (j, TC.rel(pred[:, j], want[:, j].numpy()))
+    m = tr.rollout_metrics(frames, acts)
+    assert m['ssim'].shape == (B, Tn - 1) and all(np.isfinite(v).all() for v in m.values())
+    sess.close()
+
+
+def test_checkpoint_round_trip_and_cross_model_restore(tmp_path):
+    x, y, a, s = _data(8, seed=3)
+    sess, tr, _ = _trainer(8)
+    for _ in range(2):
+        tr.train_d(x, y, a)
+        tr.train_g(x, y, a, s)
+    path = str(tmp_path / 'cdna')
+    Saver().save(sess, path)
+    tr.train_d(x, y, a)
+    want = tr.train_g(x, y, a, s)
+    sess.close()
+    sess, tr, _ = _trainer(8, seed=1)
+    Saver().restore(sess, path)
+    tr.train_d(x, y, a)
+    assert np.array_equal(tr.train_g(x, y, a, s), want), 'the restored run does not continue bit-identically'
+    sess.close()
+    # a DNA checkpoint into the CDNA graph (missing variables), the CDNA checkpoint into a DNA graph (shapes)
+    G.reset_default_graph()
+    optim.set_data_parallel(1)
+    sess = G.Session(device=DEV)
+    T.Trainer(sess, True, 'bce', 'adam', True, batch_size=8)
+    sess.run(G.global_variables_initializer())
+    Saver().save(sess, str(tmp_path / 'dna'))
+    with pytest.raises(ValueError):
+        Saver().restore(sess, path)
+    sess.close()
+    sess, tr, _ = _trainer(8)
+    with pytest.raises(ValueError):
+        Saver().restore(sess, str(tmp_path / 'dna'))
+    sess.close()
+
+
+def test_cli_train_then_evaluate(tmp_path):
+    out, ev = tmp_path / 'run', tmp_path / 'eval'
+    T.main(['synthetic', str(out), '--adv', 'True', '--cdna', '--batch_size', '8', '--pretrain_iter', '0', '--train_iter', '3'])
+    E.main([str(out / 'models'), 'synthetic', str(ev), '--cdna', '--num_sequences', '16'])
+    got = json.load(open(ev / 'metrics.json'))
+    assert got['model'] == 'cdna' and got['num_masks'] == 10 and got['ksize'] == 5 and got['sequences'] == 16
+    assert all(np.isfinite(got[k]).all() for k in ('ssim', 'psnr', 'identity_ssim', 'identity_psnr'))
+    assert os.path.isfile(os.path.join(str(out), 'logs', 'test.jsonl'))
+
+
+def test_library_exports_the_cdna_table():
+    lib = _lib.get()
+    assert all(hasattr(lib, n[4:]) for n in _lib.CDNA_SIGNATURES)
