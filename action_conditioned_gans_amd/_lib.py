@@ -172,6 +172,14 @@ CDNA_SIGNATURES = {
                                + [c_float, _P, c_size_t, _P]),
 }
 
+# include/acgan_rollout.h: the image gradient of the DNA tail and the gradient of a tiled action vector that training through
+# the generator's own rollouts needs (train.Trainer rollout_steps > 1); an addition under ABI version 8 bound as a table of its
+# own like CDNA_SIGNATURES (the C oracle does not implement it: ops.DnaImageGradOp / ActionGradOp raise a RuntimeError there)
+ROLLOUT_SIGNATURES = {
+    'acg_dna_bwd_image': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
+    'acg_action_grad': (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -238,7 +246,7 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES))
+        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES))
     return _LIB
 
 

@@ -813,13 +813,12 @@ class DnaOp(G.Op):
         return lambda s: fn(*args, s)
 
     def grad(self, gouts, needs, ctx):
-        if needs[1]:
-            raise NotImplementedError('dna_gather: gradient w.r.t. the image is not part of the hot path '
-                                      '(the image is a network input, train.py:53-54)')
+        # needs[1]: the image is a frame the generator predicted (a rollout step >= 1, train.Trainer rollout_steps): its gradient
+        # is the DNA tail's image adjoint (DnaImageGradOp).  The one-step graphs feed the image and never ask for it.
         dst, acc = (None, 0.0)
         if self.has_bias and needs[2] and ctx.wants(self.inputs[2]):
             dst, acc = ctx.slot(self.inputs[2])
-        if not needs[0] and dst is None:
+        if not needs[0] and not needs[1] and dst is None:
             return [None] * len(self.inputs)
         # dout = (gradient of the frame losses) + (the frame channels of d(discriminator input)): when that sum is an AddOp over
         # a SliceOp of the pitched gradient, the kernel reads the window itself (acg_dna_bwd dout2) and the slice and add
@@ -831,10 +830,14 @@ class DnaOp(G.Op):
                 if isinstance(t.op, SliceOp) and t is t.op.outputs[0] and t.op.c_dst == self.outputs[0].shape[-1] and parts[1 - k].dtype == torch.float32:
                     dout, dout2 = parts[1 - k], (t.op.inputs[0], t.op.c_off)
                     break
-        op = DnaBwdOp(self, dout, dst, acc, self.name + '/bwd', dout2=dout2)
-        if dst is not None:
-            ctx.wrote(self.inputs[2], op)
-        return [op.outputs[0] if needs[0] else None, None] + ([None] if self.has_bias else [])
+        dlogits = None
+        if needs[0] or dst is not None:
+            op = DnaBwdOp(self, dout, dst, acc, self.name + '/bwd', dout2=dout2)
+            if dst is not None:
+                ctx.wrote(self.inputs[2], op)
+            dlogits = op.outputs[0] if needs[0] else None
+        dimage = DnaImageGradOp(self, dout, self.name + '/bwd_image', dout2=dout2).outputs[0] if needs[1] else None
+        return [dlogits, dimage] + ([None] if self.has_bias else [])
 
 
 class DnaBwdOp(G.Op):
@@ -861,6 +864,39 @@ class DnaBwdOp(G.Op):
                 _p(self.dbias.buf) if self.dbias is not None else None,
                 self.accumulate, b, h, w, c, self.fwd.ksize, _code(lg), _p(ws) if ws is not None else None, n)
         fn = rt.lib.dna_bwd
+        return lambda s: fn(*args, s)
+
+
+def _rollout_entry(rt, name):
+    """An entry of include/acgan_rollout.h (_lib.ROLLOUT_SIGNATURES); a library without it (the C oracle) is a clear error."""
+    fn = getattr(rt.lib, name, None)
+    if fn is None:
+        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_rollout.h): training through rollouts runs on the HIP '
+                            'library only' % (getattr(rt.lib, 'path', rt.lib), name))
+    return fn
+
+
+class DnaImageGradOp(G.Op):
+    """acg_dna_bwd_image: the DNA tail's gradient with respect to its image - the exact adjoint of the gather under the forward's
+    softmax(logits + bias) weights.  Reads the same ``dout`` (and ``dout2`` window of d(discriminator input)) as the layer's
+    DnaBwdOp, in a launch of its own."""
+
+    def __init__(self, fwd, dout, name, dout2=None):
+        self.fwd, self.dout2 = fwd, dout2
+        lg, img = fwd.inputs[:2]
+        super().__init__(G.get_default_graph(), name, [lg, dout] + list(fwd.inputs[2:]) + ([dout2[0]] if dout2 is not None else []),
+                         [_new(img.shape, name + ':0')])
+
+    def bind(self, rt):
+        lg, dout = self.inputs[:2]
+        b, h, w, c = self.outputs[0].shape
+        fn = _rollout_entry(rt, 'dna_bwd_image')
+        pb = _p(self.inputs[2].buf) if self.fwd.has_bias else None
+        p2, pitch2, off2, dt2 = None, 0, 0, 0
+        if self.dout2 is not None:
+            t2, off2 = self.dout2
+            p2, pitch2, dt2 = _p(t2.buf), t2.shape[-1], _code(t2)
+        args = (_p(lg.buf), pb, _p(dout.buf), p2, pitch2, off2, dt2, _p(self.outputs[0].buf), 0.0, b, h, w, c, self.fwd.ksize, _code(lg))
         return lambda s: fn(*args, s)
 
 
@@ -1062,19 +1098,39 @@ class ConcatActionsOp(G.Op):
         return lambda s: fn(*args, s)
 
     def grad(self, gouts, needs, ctx):
-        if needs[1]:
-            raise NotImplementedError('concat_actions: actions are inputs, no gradient path')
         x = self.inputs[0]
+        # needs[1]: the action vector carries a predicted state (a rollout step >= 1, train.Trainer rollout_steps): its gradient is
+        # the sum of the tiled channels' gradients (ActionGradOp).  The one-step graphs feed the actions and never ask for it.
+        dact = ActionGradOp(gouts[0], self.c, self.inputs[1], self.name + '/bwd_actions').outputs[0] if needs[1] else None
         if not needs[0]:
-            return [None, None]
+            return [None, dact]
         src = gouts[0].op
-        if DGRAD_CHANNEL_LIMIT and isinstance(src, ConvDgradOp) and gouts[0] is src.outputs[0]:
+        if DGRAD_CHANNEL_LIMIT and not needs[1] and isinstance(src, ConvDgradOp) and gouts[0] is src.outputs[0]:
             src.limit_channels(self.c)      # the action channels are inputs: their gradient columns need not be computed
         if self.in_place:      # d(concat) IS dy of the BatchNorm, read at the concat pitch (a window, not a copy)
             g = gouts[0].view(0, gouts[0].shape, name=self.name + '/bwd:view')
             g.valid_c = self.c
-            return [g, None]
-        return [SliceOp(gouts[0], 0, x.shape[-1], x.shape, self.name + '/bwd', x.dtype).outputs[0], None]
+            return [g, dact]
+        return [SliceOp(gouts[0], 0, x.shape[-1], x.shape, self.name + '/bwd', x.dtype).outputs[0], dact]
+
+
+class ActionGradOp(G.Op):
+    """acg_action_grad: d actions [B, A] of a concatenation whose channels [c_off, c_off + A) tile the action vector over the
+    feature map - row r of the concatenation took action row (r // (h w)) % B - summed per sample in a fixed order."""
+
+    def __init__(self, dcat, c_off, actions, name):
+        if dcat.dtype != torch.float32:
+            raise NotImplementedError('concat_actions: the action gradient is float32 only')
+        b, h, w = dcat.shape[:3]
+        self.c_off, self.div, self.mod = int(c_off), h * w, actions.shape[0]
+        super().__init__(G.get_default_graph(), name, [dcat], [_new(actions.shape, name + ':0')])
+
+    def bind(self, rt):
+        dcat, dact = self.inputs[0], self.outputs[0]
+        pitch = dcat.shape[-1]
+        fn = _rollout_entry(rt, 'action_grad')
+        args = (_p(dcat.buf), dcat.numel // pitch, pitch, self.c_off, dact.shape[-1], self.div, self.mod, _p(dact.buf), 0.0)
+        return lambda s: fn(*args, s)
 
 
 class ConcatChannelsOp(G.Op):
@@ -1449,6 +1505,14 @@ def concat(values, axis=3, name='concat', out=None, pitch=0, act=False):
     if axis not in (3, -1) or len(values) != 2:
         raise ValueError('concat: only two tensors on the channel axis are supported')
     return ConcatChannelsOp(values[0], values[1], _scope_name(name), out=out, pitch=pitch, act=act).outputs[0]
+
+
+def rollout_actions(command, state, name='rollout_actions'):
+    """The action vector of a rollout step >= 1 on the device: [command [B, 5] (fed), state [B, 5] (the state the generator
+    predicted one step earlier)] - one acg_concat_channels_fwd launch; the fed half lands through the feed copy."""
+    if len(command.shape) != 2 or len(state.shape) != 2 or command.shape[0] != state.shape[0]:
+        raise ValueError('rollout_actions: [B, A] command and [B, S] state expected, got %s and %s' % (command.shape, state.shape))
+    return ConcatChannelsOp(command, state, _scope_name(name)).outputs[0]
 
 
 def repeat_batch(x, times, name='repeat_batch'):

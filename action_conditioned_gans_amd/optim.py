@@ -187,7 +187,10 @@ class Optimizer:
         launch._keep = (oa, pl)
         return launch
 
-    def minimize(self, loss, var_list=None):
+    def minimize(self, loss, var_list=None, slots_of=None):
+        """``slots_of``: the StepOp of an earlier ``minimize`` by an optimizer of this kind over the same scope; this update then
+        continues that one's state (moments, step counter) instead of owning slots of its own - a second loss of one training
+        run (train.Trainer's rollout G step continues the one-step G step's optimizer, and checkpoints hold one set of slots)."""
         if not isinstance(loss, O.Scalar):
             raise TypeError('minimize expects a loss built from this package\'s loss functions')
         g = G.get_default_graph()
@@ -216,7 +219,12 @@ class Optimizer:
         deps = list(dict.fromkeys(writers))
         if dp.active:
             deps += self._insert_allreduce(var_list, ctx, flat_grad, offsets, buckets, dp.collectives == 'side')
-        slots = self._make_slots(g, total)
+        if slots_of is not None:
+            if type(slots_of.opt) is not type(self) or slots_of.scope != scope:
+                raise ValueError('minimize: slots_of is a %s update of scope %r' % (type(slots_of.opt).__name__, slots_of.scope))
+            slots = list(slots_of.inputs[2:])
+        else:
+            slots = self._make_slots(g, total)
         step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size)
         step_op.reduce_ops = reduce_ops        # one of them can carry the step counter's increment (_step_inc_launch)
         return step_op

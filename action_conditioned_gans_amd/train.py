@@ -38,7 +38,7 @@ ACTION_DIM, STATE_DIM = 10, 5
 
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
-                 seed=0, batched_d=True, lookahead=True, num_masks=10):
+                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -46,9 +46,15 @@ class Trainer:
         touch them), so this is the reference's arithmetic - one D step, then one G step (train.py:241-263) - with the two
         generator forward passes of an iteration sharing their launches at twice the GEMM height.
         ``arg_transform``: False - the plain generator; True or 'dna' - the DNA generator (the reference's ``--dna``); 'cdna' -
-        the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses."""
+        the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses.
+        ``rollout_steps`` K > 1 (no reference counterpart): also builds the K-step G programs of ``train_g_rollout`` /
+        ``pretrain_g_rollout`` - the generator trained through its own rollout (see there).  DNA or plain generator, float32,
+        one rank; K = 1 builds nothing more."""
         self.sess = sess
         self.model = model_kind(arg_transform)
+        dp = G.get_default_graph().collections.get('data_parallel')
+        self.rollout_steps = check_rollout(rollout_steps, self.model, bf16=G.get_default_graph().act_dtype != torch.float32,
+                                           data_parallel=dp is not None and (dp.active or dp.sync_bn))
         self.num_masks = num_masks
         self.batch_size, self.img_size, self.ksize = batch_size, img_size, ksize
         self.arg_adv, self.arg_loss, self.arg_opt, self.arg_transform = arg_adv, arg_loss, arg_opt, arg_transform
@@ -175,6 +181,8 @@ class Trainer:
         self._zero_state = np.zeros((B, STATE_DIM), np.float32)
         self._announced = None          # (images, actions) of the G step a look-ahead D step has prepared
         self._skip_d = self._skip_g = None
+        if self.rollout_steps > 1:
+            self._build_rollout(build_g, make)
         if self.lookahead:
             # what the pair pass replaces.  D step: the whole batch-B generator and the launch that puts its frame into D's input.
             # G step: the generator up to and including the frame (an alias of the pair's first half) and, where the DNA kernel
@@ -185,6 +193,83 @@ class Trainer:
                 self._skip_g, self._g_extra = frozenset(trunk + [d_in_gen.op]), [self._stash_copy]
             else:                                   # plain generator: its concat launch puts the (aliased) frame into D(fake)'s input as usual
                 self._skip_g, self._g_extra = frozenset(trunk), []
+
+    def _build_rollout(self, build_g, make):
+        """K generator instances chained through their own predictions and K D(fake) instances, on the existing variables.
+        Step j: x_{t+j+1}, s_{t+j+1} = G(in_j, act_j) with in_0 the fed frame and in_j the frame of step j-1; act_0 is fed, act_j
+        is [command_j (fed), the state of step j-1] (the plain generator has no state head: act_j is fed whole, as test_sequence
+        does).  Each step's loss is the one-step G loss on its own step - L1 / GDL against frame t+j+1, the state norm against
+        s_{t+j+1}, the adversarial term on D(concat(in_j, x_{t+j+1}), act_j) - and BatchNorm takes the statistics of each instance.
+        The G loss is the mean of the K step losses, the pretraining loss the mean of their l2 parts; both updates continue the
+        one-step optimizers' state (optim minimize slots_of)."""
+        K, B, S = self.rollout_steps, self.batch_size, self.img_size
+        graph = G.get_default_graph()
+        dna = self.model == 'dna'
+        self.roll_img_ph = G.placeholder((B, S, S, 3), name='rollout/frame0')
+        self.roll_img_ph.padded = self._roll_img_pad = G.placeholder((B, S, S, 3), name='rollout/frame0_conv', channel_pitch=O.cpad(3), act=True)
+        self.roll_next_ph = [G.placeholder((B, S, S, 3), name='rollout/next_frame%d' % j) for j in range(K)]
+        self.roll_state_ph = [G.placeholder((B, STATE_DIM), name='rollout/next_state%d' % j) for j in range(K)]
+        # fed action input of each step: the whole vector at step 0 (and every step of the plain generator), the command half else
+        self.roll_action_ph = [G.placeholder((B, ACTION_DIM if (j == 0 or not dna) else 5), name='rollout/action%d' % j) for j in range(K)]
+        img, act = self.roll_img_ph, self.roll_action_ph[0]
+        self.rollout_frames, self.rollout_states, self.rollout_losses, l2_losses = [], [], [], []
+        for j in range(K):
+            frame, state = build_g(img, act, B, True)
+            d_out = M.build_discriminator(O.concat([img, frame], axis=3, name='rollout/d_in%d' % j, pitch=8, act=True), act, reuse=True)
+            l1, gdl = O.frame_losses(frame, self.roll_next_ph[j])
+            l2 = l1 / B
+            if dna:
+                with graph.side_branch():
+                    state_loss = O.l2_norm(state, self.roll_state_ph[j], name='rollout/g_state_loss%d' % j)
+                l2 = l2 * L2_WEIGHT + state_loss / B
+            loss = l2 + O.build_g_adv_loss(d_out, self.arg_loss) + gdl if self.arg_adv else l2
+            self.rollout_frames.append(frame)
+            self.rollout_states.append(state)
+            self.rollout_losses.append(loss)
+            l2_losses.append(l2)
+            if j + 1 < K:
+                img = frame
+                act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
+        total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
+        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op)
+        self.g_rollout_pretrain_opt_op = make('g_pretrain_opt_rollout').minimize(l2_total / K, var_list=self.g_vars,
+                                                                                slots_of=self.g_pretrain_opt_op)
+
+    def _rollout_feed(self, frames, actions, states):
+        """frames [B, K+1, H, W, 3] (t .. t+K), actions [B, K, 10] (a_t .. a_{t+K-1}, state half read at step 0 only by the DNA
+        generator), states [B, K, 5] (s_{t+1} .. s_{t+K}) -> the feed of the K-step programs."""
+        K = self.rollout_steps
+        if frames.shape[1] != K + 1 or actions.shape[1] != K or states.shape[1] != K:
+            raise ValueError('rollout of %d steps: frames [B, %d, ...], actions [B, %d, 10] and states [B, %d, 5] expected, got %s, %s, %s'
+                             % (K, K + 1, K, K, tuple(frames.shape), tuple(actions.shape), tuple(states.shape)))
+        f0 = frames[:, 0]
+        fd = {self.roll_img_ph: f0, self._roll_img_pad: f0}
+        for j in range(K):
+            fd[self.roll_next_ph[j]] = frames[:, j + 1]
+            fd[self.roll_state_ph[j]] = states[:, j]
+            a = actions[:, j]
+            fd[self.roll_action_ph[j]] = a if self.roll_action_ph[j].shape[1] == ACTION_DIM else a[:, :5]
+        return fd
+
+    def train_g_rollout(self, frames, actions, states, device_fetch=False):
+        """One G step through the generator's own K-step rollout (K = ``rollout_steps``): the mean of the K step losses, every
+        gradient flowing through the fed-back frames and states (_build_rollout).  frames [B, K+1, H, W, 3], actions [B, K, 10],
+        states [B, K, 5] (_rollout_feed).  -> the frames of the last step, as train_g returns its frames.  K = 1: train_g."""
+        if self.rollout_steps == 1:
+            return self.train_g(frames[:, 0], frames[:, 1], actions[:, 0], states[:, 0], device_fetch=device_fetch)
+        self._announced = None
+        res = self.sess.run([self.g_rollout_opt_op, self.rollout_frames[-1]], self._rollout_feed(frames, actions, states),
+                            device_fetch=device_fetch)
+        return res[1]
+
+    def pretrain_g_rollout(self, frames, actions, states):
+        """pretrain_g through the K-step rollout: the mean of the step l2 losses.  -> the G loss of the last step, as pretrain_g
+        returns its G loss.  K = 1: pretrain_g."""
+        if self.rollout_steps == 1:
+            return self.pretrain_g(frames[:, 0], frames[:, 1], actions[:, 0], states[:, 0])
+        self._announced = None
+        _, g_res = self.sess.run([self.g_rollout_pretrain_opt_op, self.rollout_losses[-1]], self._rollout_feed(frames, actions, states))
+        return float(g_res[0])
 
     # ---- steps: one sess.run each (train.py:114-155)
     def _feed(self, input_images, next_frame, actions, state=None):
@@ -359,6 +444,22 @@ def model_kind(arg_transform):
     return 'dna' if arg_transform else 'plain'
 
 
+def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
+    """ValueError for a ``rollout_steps`` the K-step trainer does not take (with the generator ``model``, a bf16 graph, data
+    parallelism / synchronised BatchNorm); -> K."""
+    k = int(rollout_steps)
+    if k < 1:
+        raise ValueError('rollout_steps must be >= 1, got %d' % k)
+    if k > 1:
+        if model == 'cdna':
+            raise ValueError('rollout_steps > 1: the CDNA composite has no image gradient (train the DNA or the plain generator)')
+        if bf16:
+            raise ValueError('rollout_steps > 1 is float32 only (dtype bf16)')
+        if data_parallel:
+            raise ValueError('rollout_steps > 1 runs on one rank (no data parallelism, sync_bn or exact_global_batch)')
+    return k
+
+
 def _join(first, second):
     """[first ; second] along the batch axis, numpy arrays or (device) torch tensors."""
     if torch.is_tensor(first):
@@ -427,6 +528,21 @@ def select_pairs(rng_randint, boolean_mask, batch_size):
     return start_mask, np.roll(start_mask, 1, axis=1)
 
 
+def select_windows(rng_randint, boolean_mask, batch_size, steps):
+    """The (t, t+1, ..., t+steps) selection of a K-step rollout (K = ``steps``): t = randint(0, T-K) per sample, one draw of the
+    same size from the same generator as select_pairs.  -> [steps + 1] one-hot masks [B, T] (frame t + i); for K = 1 exactly
+    select_pairs' two masks."""
+    start_mask = boolean_mask[rng_randint(0, len(boolean_mask) - steps + 1, size=batch_size)]
+    return [start_mask] + [np.roll(start_mask, i, axis=1) for i in range(1, steps + 1)]
+
+
+def window_batch(masks, inp, nxt, acts, states):
+    """The K-step inputs of train_g_rollout from one batch and its select_windows masks: frames [B, K+1, ...] (frame t from
+    ``inp``, the rest from ``nxt``), actions a_t .. a_{t+K-1} [B, K, 10], target states s_{t+1} .. s_{t+K} [B, K, 5]."""
+    frames = np.stack([inp[masks[0]]] + [nxt[m] for m in masks[1:]], axis=1)
+    return frames, np.stack([acts[m] for m in masks[:-1]], axis=1), np.stack([states[m] for m in masks[1:]], axis=1)
+
+
 class _PairSelections:
     """The frame-pair selections of the coming iterations, drawn AHEAD of the loop in the reference's order (train.py:231-232
     per pretraining iteration; 249-250 per D step, then 258-259 once for the G step on the last D batch), from a private copy
@@ -435,7 +551,10 @@ class _PairSelections:
     step will read (``data.announce``: 2-4 of a record's 7 JPEGs instead of all of them); a source without ``announce``
     (SyntheticPush) just gets its selections from here."""
 
-    def __init__(self, boolean_mask, batch_size, d_per_g, pretrain_iter, train_iter, data, ahead=8):
+    def __init__(self, boolean_mask, batch_size, d_per_g, pretrain_iter, train_iter, data, ahead=8, rollout_steps=1):
+        """``rollout_steps`` K > 1: the G steps and pretraining steps select K-step windows (select_windows) instead of pairs; the
+        D steps keep their pairs.  Drawn in the same order from the same generator."""
+        self.rollout_steps = int(rollout_steps)
         self.rng = np.random.RandomState()
         self.rng.set_state(np.random.get_state())
         self.mask, self.batch_size, self.d_per_g = boolean_mask, batch_size, d_per_g
@@ -446,8 +565,21 @@ class _PairSelections:
     def _draw(self):
         i = self.drawn
         n = 1 if i < self.pretrain_iter else self.d_per_g + 1
-        sels = [select_pairs(self.rng.randint, self.mask, self.batch_size) for _ in range(n)]
-        if self.announce is not None:
+        if self.rollout_steps > 1:
+            sels = [select_pairs(self.rng.randint, self.mask, self.batch_size) for _ in range(n - 1)]
+            sels.append(tuple(select_windows(self.rng.randint, self.mask, self.batch_size, self.rollout_steps)))
+        else:
+            sels = [select_pairs(self.rng.randint, self.mask, self.batch_size) for _ in range(n)]
+        if self.announce is not None and self.rollout_steps > 1:
+            if i < self.pretrain_iter:
+                self.announce(np.logical_or.reduce(sels[0]))
+            else:
+                for j in range(self.d_per_g):
+                    need = sels[j][0] | sels[j][1]
+                    if j == self.d_per_g - 1:                       # the G step's window is on the last D batch
+                        need = need | np.logical_or.reduce(sels[-1])
+                    self.announce(need)
+        elif self.announce is not None:
             if i < self.pretrain_iter:
                 self.announce(sels[0][0] | sels[0][1])
             else:
@@ -476,7 +608,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
-          num_masks=10):
+          num_masks=10, rollout_steps=1):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -492,9 +624,16 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     'dct' (opt-in, approximate: the reduction inside libjpeg's inverse DCT, push_data.decode_frame).  ``data_cache_gb``: keep up to
     that many GiB of decoded frames in host memory - a record that comes round again in a later epoch is not decoded again (same
     bits; 0 = off, as the reference).  ``synthetic_pool``: SyntheticPush(pool=...).  ``arg_transform`` / ``num_masks``: the
-    generator, as Trainer takes them ('cdna': the CDNA generator with ``num_masks`` kernels of ``ksize``)."""
+    generator, as Trainer takes them ('cdna': the CDNA generator with ``num_masks`` kernels of ``ksize``).  ``rollout_steps`` K > 1:
+    every G step (and pretraining step) trains through the generator's own K-step rollout on a window t .. t+K
+    (Trainer.train_g_rollout); the D steps are unchanged and the loop takes the plain call path (no look-ahead pass)."""
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
+    if int(rollout_steps) > 1:
+        check_rollout(rollout_steps, model_kind(arg_transform), bf16=dtype == 'bf16',
+                      data_parallel=world_size > 1 or sync_bn or exact_global_batch)
+        if int(rollout_steps) > seq_len - 1:
+            raise ValueError('rollout_steps %d needs sequences of more than %d frames (seq_len %d)' % (rollout_steps, rollout_steps, seq_len))
     np.random.seed(7)                                           # train.py:14
     synthetic = input_path in (None, '', 'synthetic')
     if synthetic:
@@ -514,7 +653,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     try:
         trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
-                              select_frames=data_frames == 'selected', num_masks=num_masks)
+                              select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps))
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -529,8 +668,12 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10):
-    trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks)
+                num_masks=10, rollout_steps=1):
+    if rollout_steps > 1:               # (the K-step G step takes the plain call path: no pair instance to build)
+        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks,
+                          lookahead=False, rollout_steps=rollout_steps)
+    else:
+        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks)
     sess.run(G.global_variables_initializer())
     saver = Saver()                                                           # train.py:215
     if resume:
@@ -546,41 +689,48 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
     D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
     log_file = os.path.join(log_dir, 'train.jsonl') if log_dir else None
     t0 = time.time()
-    selections = _PairSelections(boolean_mask, batch_size, D_per_G, pretrain_iter, train_iter, data if select_frames else None)
+    selections = _PairSelections(boolean_mask, batch_size, D_per_G, pretrain_iter, train_iter, data if select_frames else None,
+                                 rollout_steps=rollout_steps)
     for i in range(train_iter):
         sels = selections.next()
         if i < pretrain_iter:
             inp, nxt, acts, states = data.get_batch()
-            sm, em = sels[0]
-            trainer.pretrain_g(inp[sm], nxt[em], acts[sm], states[em])
+            if rollout_steps > 1:
+                trainer.pretrain_g_rollout(*window_batch(sels[0], inp, nxt, acts, states))
+            else:
+                sm, em = sels[0]
+                trainer.pretrain_g(inp[sm], nxt[em], acts[sm], states[em])
             if not quiet:
                 print('pre-train iter: ' + str(i))
             continue
-        # The iteration's sub-steps, drawn up front in the reference's order (train.py:241-259: per D step a fresh batch and a
-        # fresh frame-pair selection, then a NEW selection on the last batch for the G step; the steps themselves draw nothing;
-        # the selections come from _PairSelections, which drew them some iterations ago in that same order),
-        # so that a step can announce its successor's inputs to Trainer.train_d (look-ahead generator pass): D1 runs the
-        # generator for D1 and D2, D2 runs none, ... the last pair pass covers the G step.  Logging iterations keep the plain path
-        # for their last D step (its summaries read that step's own generated frames).
-        subs = []
-        for j in range(D_per_G):
-            inp, nxt, acts, states = data.get_batch()
-            sm, em = sels[j]
-            subs.append((inp[sm], nxt[em], acts[sm]))
-        smg, emg = sels[-1]
-        g_in, g_act = inp[smg], acts[smg]
-        summ, carried = None, False
-        for j, (x_d, y_d, a_d) in enumerate(subs):
-            last = j == D_per_G - 1
-            summarize = (i % log_every == 0) and last
-            follow = None
-            if not carried and not summarize:                    # this step runs the pair pass for itself and its successor
-                follow = (g_in, g_act) if last else ((subs[j + 1][0], subs[j + 1][2]) if not ((i % log_every == 0) and j + 1 == D_per_G - 1) else None)
-            summ = trainer.train_d(x_d, y_d, a_d, summarize=summarize, next_d=follow)
-            carried = follow is not None and not carried
-        # (the generated frames stay on the device: the reference fetches them every step only to dump samples at i % 100 == 0,
-        # train.py:130,269-273, which this loop does not do - no D2H copy, no synchronisation per iteration)
-        trainer.train_g(g_in, nxt[emg], g_act, states[emg], device_fetch=True)
+        if rollout_steps > 1:
+            summ = _rollout_iteration(trainer, data, sels, i, D_per_G, log_every)
+        else:
+            # The iteration's sub-steps, drawn up front in the reference's order (train.py:241-259: per D step a fresh batch and a
+            # fresh frame-pair selection, then a NEW selection on the last batch for the G step; the steps themselves draw nothing;
+            # the selections come from _PairSelections, which drew them some iterations ago in that same order),
+            # so that a step can announce its successor's inputs to Trainer.train_d (look-ahead generator pass): D1 runs the
+            # generator for D1 and D2, D2 runs none, ... the last pair pass covers the G step.  Logging iterations keep the plain path
+            # for their last D step (its summaries read that step's own generated frames).
+            subs = []
+            for j in range(D_per_G):
+                inp, nxt, acts, states = data.get_batch()
+                sm, em = sels[j]
+                subs.append((inp[sm], nxt[em], acts[sm]))
+            smg, emg = sels[-1]
+            g_in, g_act = inp[smg], acts[smg]
+            summ, carried = None, False
+            for j, (x_d, y_d, a_d) in enumerate(subs):
+                last = j == D_per_G - 1
+                summarize = (i % log_every == 0) and last
+                follow = None
+                if not carried and not summarize:                    # this step runs the pair pass for itself and its successor
+                    follow = (g_in, g_act) if last else ((subs[j + 1][0], subs[j + 1][2]) if not ((i % log_every == 0) and j + 1 == D_per_G - 1) else None)
+                summ = trainer.train_d(x_d, y_d, a_d, summarize=summarize, next_d=follow)
+                carried = follow is not None and not carried
+            # (the generated frames stay on the device: the reference fetches them every step only to dump samples at i % 100 == 0,
+            # train.py:130,269-273, which this loop does not do - no D2H copy, no synchronisation per iteration)
+            trainer.train_g(g_in, nxt[emg], g_act, states[emg], device_fetch=True)
         if i % log_every == 0:
             # the fetches above synchronised anyway: look at the device-side flags of the one-launch BatchNorm kernels HERE, on
             # every rank, so that a step that ran on wrong statistics fails now - before anything of it is logged or
@@ -590,7 +740,7 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             if not quiet:
                 print('Iteration {:d}'.format(i))
             if log_file and summ:
-                _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0))
+                _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0, rollout_steps=rollout_steps))
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
         if eval_every and i % eval_every == 0 and rank == 0:
@@ -608,6 +758,19 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
         eval_data.close()
     saver.wait()                     # the last checkpoints are on disk when train() returns
     return trainer
+
+
+def _rollout_iteration(trainer, data, sels, i, D_per_G, log_every):
+    """One iteration after pretraining with rollout_steps > 1 -> the summaries of its last D step (or None).  The D steps take
+    their pair selections on fresh batches as the one-step loop does, on its plain call path; the G step trains through the
+    K-step rollout on the window its selection draws on the last D batch (train.py:258-259's order)."""
+    summ = None
+    for j in range(D_per_G):
+        inp, nxt, acts, states = data.get_batch()
+        sm, em = sels[j]
+        summ = trainer.train_d(inp[sm], nxt[em], acts[sm], summarize=(i % log_every == 0) and j == D_per_G - 1)
+    trainer.train_g_rollout(*window_batch(sels[-1], inp, nxt, acts, states), device_fetch=True)
+    return summ
 
 
 def _flag(v):
@@ -643,6 +806,27 @@ def check_model_args(parser, args):
     return args.dna
 
 
+def check_rollout_args(parser, args):
+    """parser.error for a --rollout_steps the K-step trainer does not take (before anything is created)."""
+    k = args.rollout_steps
+    if k < 1:
+        parser.error('--rollout_steps must be >= 1')
+    if k == 1:
+        return
+    if k > args.seq_len - 1:
+        parser.error('--rollout_steps %d needs sequences of more than %d frames (--seq_len %d)' % (k, k, args.seq_len))
+    if args.cdna:
+        parser.error('--rollout_steps > 1 does not train the CDNA generator (its composite has no image gradient)')
+    if args.dtype == 'bf16':
+        parser.error('--rollout_steps > 1 is float32 only (--dtype bf16)')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        parser.error('--rollout_steps > 1 runs on one rank (WORLD_SIZE %s)' % os.environ['WORLD_SIZE'])
+    if args.sync_bn:
+        parser.error('--rollout_steps > 1 runs on one rank (--sync_bn)')
+    if args.exact_global_batch:
+        parser.error('--rollout_steps > 1 runs on one rank (--exact_global_batch)')
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='action-conditioned video-prediction GAN on MI355X')
     parser.add_argument('input_path', type=str)
@@ -659,6 +843,8 @@ def main(argv=None):
     parser.add_argument('--train_iter', type=int, default=TRAIN_ITER)
     parser.add_argument('--pretrain_iter', type=int, default=PRETRAIN_ITER)
     parser.add_argument('--dtype', type=str, default='f32', choices=['f32', 'bf16'])
+    parser.add_argument('--rollout_steps', type=int, default=1,
+                        help='train the generator through its own K-step rollouts (frames and states fed back; 1 = one-step pairs)')
     # data parallel (one process per GPU under torch.distributed.run; no reference counterpart - SURVEY 8(e))
     parser.add_argument('--sync_bn', nargs='?', const=True, default=False, type=_flag,
                         help='BatchNorm statistics of the GLOBAL batch (one small all-reduce per BatchNorm layer and direction)')
@@ -683,6 +869,7 @@ def main(argv=None):
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
     transform = check_model_args(parser, args)
+    check_rollout_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
     log_dir = os.path.join(args.output_path, 'logs')
     os.makedirs(args.output_path)
@@ -700,7 +887,7 @@ def main(argv=None):
                     n_critic=args.n_critic, device='cuda:%d' % local_rank, world_size=world_size, rank=rank, dtype=args.dtype,
                     sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
-                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks)
+                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 
