@@ -180,6 +180,15 @@ ROLLOUT_SIGNATURES = {
     'acg_action_grad': (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
 }
 
+# include/acgan_bn_infer.h: BatchNorm with stored statistics - the apply pass on its own and the calibration pass that pools
+# the moments of the batches it is shown; an addition under ABI version 8 bound as a table of its own like ROLLOUT_SIGNATURES
+# (the C oracle does not implement it: ops.BnInferOp / BnCollectOp raise a RuntimeError there)
+BN_INFER_SIGNATURES = {
+    'acg_bn_act_infer': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_int32, _P]),
+    'acg_bn_collect_workspace_bytes': (c_size_t, [c_int64, c_int32]),
+    'acg_bn_collect': (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -246,7 +255,7 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES))
+        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES, **BN_INFER_SIGNATURES))
     return _LIB
 
 

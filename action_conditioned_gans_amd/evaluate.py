@@ -74,6 +74,53 @@ def _pad(x, batch_size):
     return np.concatenate([x, np.repeat(x[-1:], batch_size - x.shape[0], axis=0)], axis=0)
 
 
+def _calibration_pairs(input_path, actions_path, pair_batch, img_size, seq_len, num_batches):
+    """-> generator of at most ``num_batches`` full batches (frames [pair_batch, S, S, 3], actions [pair_batch, 10]) of one-step
+    pairs (frame t, action t), t = 0 .. T-2 of every sequence, in the order of the source."""
+    frames_q, acts_q, have, done = [], [], 0, 0
+    # (the synthetic source has no end: it is asked for exactly the sequences the batches need)
+    n_seq = -(-num_batches * pair_batch // max(seq_len - 1, 1)) if input_path == 'synthetic' else None
+    for frames, acts in _batches(input_path, actions_path, pair_batch, img_size, seq_len, n_seq):
+        if frames.shape[2:4] != (img_size, img_size):
+            raise ValueError('frames of %s x %s, the model is built for --img_size %d' % (frames.shape[2], frames.shape[3], img_size))
+        t = frames.shape[1] - 1
+        frames_q.append(frames[:, :t].reshape((-1,) + frames.shape[2:]))
+        acts_q.append(acts[:, :t].reshape(-1, acts.shape[2]))
+        have += frames_q[-1].shape[0]
+        while have >= pair_batch and done < num_batches:
+            f, a = np.concatenate(frames_q), np.concatenate(acts_q)
+            yield np.ascontiguousarray(f[:pair_batch]), np.ascontiguousarray(a[:pair_batch])
+            frames_q, acts_q, have, done = [f[pair_batch:]], [a[pair_batch:]], have - pair_batch, done + 1
+        if done >= num_batches:
+            return
+
+
+def calibrate(ckpt, save_prefix, input_path, actions_path, transform, ksize, img_size, dtype, pair_batch, num_batches, seq_len, device,
+              num_masks):
+    """Restore ``ckpt`` into a generator built at batch ``pair_batch``, pool its BatchNorm statistics over ``num_batches`` batches
+    of one-step pairs of ``input_path`` (Trainer.calibrate_bn) and save everything as ``save_prefix``.npz.  -> pairs pooled."""
+    from . import graph as G
+    from .saver import Saver
+    from .train import Trainer
+    G.reset_default_graph()
+    sess = G.Session(device=device, dtype=dtype)
+    try:
+        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=pair_batch, img_size=img_size, ksize=ksize, lookahead=False,
+                          num_masks=num_masks, bn_inference=True)
+        sess.run(G.global_variables_initializer())
+        Saver().restore(sess, ckpt)
+        trainer.reset_bn_statistics()
+        rows = 0
+        for frames, acts in _calibration_pairs(input_path, actions_path, pair_batch, img_size, seq_len, num_batches):
+            rows = trainer.calibrate_bn(frames, acts)
+        if rows == 0:
+            raise ValueError('%s holds fewer than one batch of %d one-step pairs to calibrate on' % (input_path, pair_batch))
+        Saver().save(sess, save_prefix)
+        return rows
+    finally:
+        sess.close()
+
+
 def set_psnr(sqerr, valid, count_per_frame):
     """PSNR of a set by the reference's formula: ``sqerr`` [N, steps] sums of squared errors per frame, ``valid`` [N] bool (False:
     a padding row) -> [steps] 10 log10(1 / (sum over valid rows / (rows * count_per_frame)))."""
@@ -83,13 +130,20 @@ def set_psnr(sqerr, valid, count_per_frame):
 
 
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
-             seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10):
+             seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
+             calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
     ``dna`` / ``cdna`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
-    with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  -> the metrics dict."""
+    with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  ``bn_stats`` 'batch', 'stored' or 'calibrate' and the
+    ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
+    -> the metrics dict."""
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
+    if bn_stats not in ('batch', 'stored', 'calibrate'):
+        raise ValueError("bn_stats must be 'batch', 'stored' or 'calibrate', got %r" % (bn_stats,))
+    if bn_stats == 'calibrate' and (calibrate_batch_size < 1 or calibrate_batches < 1):
+        raise ValueError('calibrate_batch_size and calibrate_batches must be >= 1')
     transform = 'cdna' if cdna else dna
     from . import graph as G
     from .metrics import SSIM_DEFINITION
@@ -101,13 +155,27 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     if ckpt is None:
         raise FileNotFoundError('no checkpoint under %s' % model_path)
     os.makedirs(output_path, exist_ok=True)
+    restore_from = ckpt
+    if bn_stats == 'calibrate':
+        if calibrate_input is None:
+            calibrate_input, calibrate_actions = input_path, actions_path
+        restore_from = os.path.join(output_path, 'calibrated')
+        calibrate(ckpt, restore_from, calibrate_input, calibrate_actions, transform, ksize, img_size, dtype, calibrate_batch_size,
+                  calibrate_batches, seq_len, device, num_masks)
+    stored = bn_stats != 'batch'
+    extra = {'bn_inference': True} if stored else {}      # ('batch' builds exactly the graph it always built)
+    bn = 'stored' if stored else 'batch'
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
     try:
         trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False,
-                          num_masks=num_masks)
+                          num_masks=num_masks, **extra)
         sess.run(G.global_variables_initializer())
-        Saver().restore(sess, ckpt)
+        Saver().restore(sess, restore_from)
+        calibration_rows = trainer.bn_calibration_rows() if stored else None
+        if stored and calibration_rows < 1:
+            raise ValueError('--bn_stats stored: checkpoint %s holds no calibrated BatchNorm statistics (run --bn_stats calibrate first)'
+                             % os.path.abspath(ckpt))
         keys = ('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
         acc = {k: [] for k in keys}
         valid, kept_frames, kept_pred, dumped = [], [], [], []
@@ -119,7 +187,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             steps, hw = frames.shape[1] - 1, frames.shape[2:]
             want = dump or len(kept_pred) < samples
             t0 = time.perf_counter()
-            m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want)
+            m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want, **({'bn': bn} if stored else {}))
             rollout_s += time.perf_counter() - t0
             for k in keys:
                 acc[k].append(m[k])
@@ -153,6 +221,9 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             'identity_psnr': [float(v) for v in set_psnr(acc['identity_sqerr'], valid, count)],
             'frames_per_s': float(valid.size * steps / rollout_s),
         }
+        if stored:
+            result['bn_statistics'] = bn_stats
+            result['calibration_rows'] = int(calibration_rows)
         with open(os.path.join(output_path, 'metrics.json'), 'w') as f:
             json.dump(result, f, indent=1)
         if dump:
@@ -163,6 +234,27 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         return result
     finally:
         sess.close()
+
+
+def check_bn_args(parser, args):
+    """parser.error for --bn_stats / --calibrate_* flags that do not go together (before anything is created); fills the defaults."""
+    given = [n for n in ('calibrate_batch_size', 'calibrate_batches', 'calibrate_input', 'calibrate_actions') if getattr(args, n) is not None]
+    if given and args.bn_stats != 'calibrate':
+        parser.error('--%s goes with --bn_stats calibrate (got --bn_stats %s)' % (given[0], args.bn_stats))
+    if args.calibrate_batch_size is None:
+        args.calibrate_batch_size = 32
+    if args.calibrate_batches is None:
+        args.calibrate_batches = 16
+    if args.calibrate_batch_size < 1 or args.calibrate_batches < 1:
+        parser.error('--calibrate_batch_size and --calibrate_batches must be >= 1')
+    if args.calibrate_actions is not None and args.calibrate_input is None:
+        parser.error('--calibrate_actions goes with --calibrate_input')
+    ci = args.calibrate_input
+    if ci is not None and ci != 'synthetic' and not os.path.isdir(ci):
+        if args.calibrate_actions is None:
+            parser.error('a --calibrate_input frames .npy needs --calibrate_actions ACTIONS.npy')
+        if not os.path.exists(ci) or not os.path.exists(args.calibrate_actions):
+            parser.error('--calibrate_input / --calibrate_actions: no such file')
 
 
 def main(argv=None):
@@ -183,8 +275,16 @@ def main(argv=None):
     parser.add_argument('--gif', action='store_true')
     parser.add_argument('--dump', action='store_true', help='save the predictions as predictions.npy')
     parser.add_argument('--device', type=str, default='cuda:0')
+    parser.add_argument('--bn_stats', type=str, default='batch', choices=['batch', 'stored', 'calibrate'],
+                        help="BatchNorm statistics of the generator: of each batch (as in training), stored in the checkpoint, or "
+                             "calibrated first (writes OUTPUT/calibrated.npz) and then stored")
+    parser.add_argument('--calibrate_batch_size', type=int, default=None, help='pairs per calibration batch (default 32)')
+    parser.add_argument('--calibrate_batches', type=int, default=None, help='calibration batches (default 16)')
+    parser.add_argument('--calibrate_input', type=str, default=None, help='source of the calibration pairs (default: INPUT)')
+    parser.add_argument('--calibrate_actions', type=str, default=None, help='actions .npy of a --calibrate_input frames .npy')
     args = parser.parse_args(argv)
     check_model_args(parser, args)
+    check_bn_args(parser, args)
     if args.batch_size < 1:
         parser.error('--batch_size must be >= 1')
     if args.num_sequences is not None and args.num_sequences < 1:
@@ -206,7 +306,8 @@ def main(argv=None):
     return evaluate(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, ksize=args.ksize,
                     img_size=args.img_size, dtype=args.dtype, batch_size=args.batch_size, seq_len=args.seq_len,
                     num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
-                    cdna=args.cdna, num_masks=args.num_masks)
+                    cdna=args.cdna, num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
+                    calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions)
 
 
 if __name__ == '__main__':

@@ -78,7 +78,7 @@ def build_generator_transform(images, actions, batch_size=None, reuse=False, col
             sk = state.shape[1]           # 4 at 64x64: the reference's 4x4 VALID head (models.py:44-51)
             state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
                              scope='sconv5')
-            state = O.squeeze(state)
+            state = O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
 
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
         logits = O.deconv2d(net, ksize * ksize, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
@@ -125,7 +125,7 @@ def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_ch
             sk = state.shape[1]
             state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
                              scope='sconv5')
-            state = O.squeeze(state)
+            state = O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
         logits = O.deconv2d(net, num_masks + 1, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
         frame = O.cdna_composite(logits, images, params, num_masks, ksize)

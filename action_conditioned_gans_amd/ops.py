@@ -654,6 +654,78 @@ class BnApplyMomentsOp(G.Op):
         return [op.outputs[0] if needs[0] else None, None, None]     # the moments' dependence on x is inside dx
 
 
+# ---- BatchNorm with stored statistics (include/acgan_bn_infer.h): batch-independent prediction ------------------------
+def _bn_infer_entry(rt, name):
+    """An entry of include/acgan_bn_infer.h (_lib.BN_INFER_SIGNATURES); a library without it (the C oracle) is a clear error."""
+    fn = getattr(rt.lib, name, None)
+    if fn is None:
+        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_bn_infer.h): BatchNorm with stored statistics runs on '
+                            'the HIP library only' % (getattr(rt.lib, 'path', rt.lib), name))
+    return fn
+
+
+def bn_statistics_state(name, c):
+    """The stored statistics of the BatchNorm scope ``name`` (``g/conv1/BatchNorm``): graph STATE, not variables - slim's
+    ``moving_mean`` (0) and ``moving_variance`` (1), float32 [c], plus ``calibration_rows``, the int64 count of the rows pooled
+    into them, on the device.  Created once per graph and shared by every instance that names the scope; listed in
+    ``graph.collections['bn_statistics']`` (scope -> (mean, variance, rows))."""
+    g = G.get_default_graph()
+    table = g.collections.setdefault('bn_statistics', {})
+    if name not in table:
+        table[name] = (g.new_state((c,), 0.0, name + '/moving_mean'), g.new_state((c,), 1.0, name + '/moving_variance'),
+                       g.new_state((1,), 0, name + '/calibration_rows', dtype=torch.int64))
+    if table[name][0].shape != (c,):
+        raise ValueError('batch_norm: the statistics of %s hold %d channels, this instance has %d' % (name, table[name][0].shape[0], c))
+    return table[name]
+
+
+class BnInferOp(G.Op):
+    """y = act((x - moving_mean) * rsqrt(moving_variance + eps) + beta): the apply pass alone (acg_bn_act_infer).  A row's result
+    depends on no other row.  Storage types and pitches as BnActOp; no gradient: a prediction-only instance."""
+
+    def __init__(self, x, beta, mean, variance, act, leak, eps, name):
+        self.xp = x.shape[-1]
+        c = x.valid_c or self.xp
+        self.act, self.leak, self.eps = act, float(leak), float(eps)
+        self.rows, self.c = x.numel // self.xp, c
+        if act is None and half_mode():
+            y = _new(x.shape[:-1] + (c,), name + ':0')
+        else:
+            y = _new(x.shape, name + ':0', x.dtype)
+            y.valid_c = x.valid_c
+        self.yp = y.shape[-1]
+        super().__init__(G.get_default_graph(), name, [x, beta, mean, variance], [y])
+
+    def bind(self, rt):
+        fn = _bn_infer_entry(rt, 'bn_act_infer')
+        x, beta, mean, variance = self.inputs
+        y = self.outputs[0]
+        args = (_p(x.buf), _p(beta.buf), _p(mean.buf), _p(variance.buf), _p(y.buf), self.rows, self.c, self.xp, self.yp, self.eps,
+                _ACT_CODE[self.act], self.leak, _code2(x, y))
+        return lambda s: fn(*args, s)
+
+
+class BnCollectOp(G.Op):
+    """Calibration: pools the moments of the rows of ``x`` into the layer's stored statistics (acg_bn_collect: the Chan update of
+    (rows, mean, variance) on the device).  Runs behind ``after``, the layer's BnActOp - where that op sums the split-K slabs of
+    its producer, it is also the one that writes x."""
+
+    def __init__(self, x, mean, variance, count, after, name):
+        self.xp = x.shape[-1]
+        self.rows, self.c = x.numel // self.xp, x.valid_c or self.xp
+        self.extras = [mean, variance, count]
+        super().__init__(G.get_default_graph(), name, [x], [], control_inputs=[after])
+
+    def bind(self, rt):
+        fn = _bn_infer_entry(rt, 'bn_collect')
+        ws, n = rt.workspace(_bn_infer_entry(rt, 'bn_collect_workspace_bytes')(self.rows, self.c))
+        self._keep = ws
+        x = self.inputs[0]
+        mean, variance, count = self.extras
+        args = (_p(x.buf), _p(count.buf), _p(mean.buf), _p(variance.buf), self.rows, self.c, self.xp, _code(x), _p(ws), n)
+        return lambda s: fn(*args, s)
+
+
 def _bn_bwd_code(x, dy, dx):
     """dtype of a BatchNorm backward call: ACG_DTYPE2(x, dy), or the float32-head code (x, dy float32; dx bf16)."""
     if x.dtype == torch.float32 and dx.dtype == torch.bfloat16:
@@ -1055,7 +1127,7 @@ class ConcatActionsOp(G.Op):
         # writes its result straight into the concatenated tensor (its y pitch becomes this tensor's pitch), this op only
         # adds the tiled action channels, and backward hands the gradient of the concatenated tensor to the BatchNorm
         # backward as it is (dy at this pitch) - no copy of the feature map in either direction.
-        self.in_place = isinstance(x.op, BnActOp) and x is x.op.outputs[0] and x.view_of is None and x.dtype == y.dtype
+        self.in_place = isinstance(x.op, (BnActOp, BnInferOp)) and x is x.op.outputs[0] and x.view_of is None and x.dtype == y.dtype
         g = G.get_default_graph()
         self.fed_inputs = []
         if self.in_place:
@@ -1311,17 +1383,21 @@ def _act_of(fn):
 
 @add_arg_scope
 def batch_norm(inputs, decay=0.999, center=True, scale=False, epsilon=0.001, activation_fn=None, is_training=True,
-               reuse=None, scope=None, groups=1):
+               reuse=None, scope=None, groups=1, collect_statistics=False):
     """slim.batch_norm as the reference uses it: batch moments over (B,H,W), beta only.
 
     ``groups`` > 1 normalises equal contiguous chunks of the batch independently (several logical
     batches sharing one launch).  The moving averages of slim exist only as never-updated, never-read
-    variables in the reference (UPDATE_OPS is never run), so they are not materialised.
+    variables in the reference (UPDATE_OPS is never run), so a training graph does not materialise them.
+
+    Stored statistics (no reference counterpart; both switches arrive through ``arg_scope([batch_norm], ...)`` as in slim):
+    ``is_training=False`` normalises with the layer's ``moving_mean`` / ``moving_variance`` (bn_statistics_state) instead of
+    the batch's moments - a row's result then depends on no other row; ``collect_statistics=True`` is the calibration instance:
+    today's batch-statistics op, plus an op that pools the moments of its input rows into that state
+    (``graph.collections['bn_collect']``; it runs when fetched).  Both take ``groups`` == 1 and no synchronised BatchNorm.
     """
     if scale or not center:
         raise ValueError('batch_norm: only center=True, scale=False (the reference configuration) is implemented')
-    if not is_training:
-        raise ValueError('batch_norm: the reference never leaves training mode (moving averages are never updated)')
     act = _act_of(activation_fn)
     c = inputs.valid_c or inputs.shape[-1]
     with variable_scope(scope or 'BatchNorm', reuse=reuse):
@@ -1329,6 +1405,21 @@ def batch_norm(inputs, decay=0.999, center=True, scale=False, epsilon=0.001, act
         name = _scope_name()
     fused = act if act is not None else (None, 0.0)
     dp = G.get_default_graph().collections.get('data_parallel')
+    if not is_training or collect_statistics:
+        if not is_training and collect_statistics:
+            raise ValueError('batch_norm: statistics are collected by an instance that runs on batch statistics (is_training=True)')
+        if groups != 1:
+            raise ValueError('batch_norm: stored statistics take groups == 1, got %d' % groups)
+        if dp is not None and getattr(dp, 'sync_bn', False) and dp.active:
+            raise ValueError('batch_norm: stored statistics do not combine with synchronised BatchNorm')
+        mean, variance, count = bn_statistics_state(name, c)
+        if not is_training:
+            out = BnInferOp(inputs, beta, mean, variance, fused[0], fused[1], epsilon, name + '/infer').outputs[0]
+            return out if act is not None else activation_fn(out)
+        out = BnActOp(inputs, beta, fused[0], fused[1], epsilon, groups, name).outputs[0]
+        G.get_default_graph().collections.setdefault('bn_collect', []).append(
+            BnCollectOp(inputs, mean, variance, count, out.op, name + '/collect'))
+        return out if act is not None else activation_fn(out)
     if dp is not None and getattr(dp, 'sync_bn', False) and dp.active:
         # statistics of the global batch: moments -> all-reduce (host) -> apply (SURVEY 8(e) caveat 1)
         mom = BnMomentsOp(inputs, groups, name + '/moments').outputs[0]
@@ -1523,8 +1614,14 @@ def repeat_batch(x, times, name='repeat_batch'):
     return ConcatChannelsOp(flat, flat, _scope_name(name)).outputs[0].reshape((x.shape[0] * 2,) + x.shape[1:])
 
 
-def squeeze(x, name=None):
-    """tf.squeeze (models.py:74): drop size-1 dimensions (a storage alias, no kernel)."""
+def squeeze(x, name=None, axis=None):
+    """tf.squeeze (models.py:74): drop size-1 dimensions (a storage alias, no kernel) - all of them, or those named by ``axis``
+    (a batch of one keeps its batch dimension that way)."""
+    if axis is not None:
+        axis = tuple(a % len(x.shape) for a in ((axis,) if isinstance(axis, int) else axis))
+        if any(x.shape[a] != 1 for a in axis):
+            raise ValueError('squeeze: dimension(s) %s of %s are not 1' % (axis, x.shape))
+        return x.reshape(tuple(s for i, s in enumerate(x.shape) if i not in axis) or (1,), name=name)
     return x.reshape(tuple(s for s in x.shape if s != 1) or (1,), name=name)
 
 

@@ -38,7 +38,7 @@ ACTION_DIM, STATE_DIM = 10, 5
 
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
-                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1):
+                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -49,7 +49,11 @@ class Trainer:
         the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses.
         ``rollout_steps`` K > 1 (no reference counterpart): also builds the K-step G programs of ``train_g_rollout`` /
         ``pretrain_g_rollout`` - the generator trained through its own rollout (see there).  DNA or plain generator, float32,
-        one rank; K = 1 builds nothing more."""
+        one rank; K = 1 builds nothing more.
+        ``bn_inference`` (no reference counterpart; False builds nothing more): also builds a calibration instance and a
+        stored-statistics instance of the generator on the same variables (_build_bn_inference) - ``calibrate_bn`` pools the
+        BatchNorm moments of the batches it is shown, and ``test`` / ``test_sequence`` / ``rollout_metrics`` with ``bn='stored'``
+        predict with them: a row's prediction then depends on no other row of its batch."""
         self.sess = sess
         self.model = model_kind(arg_transform)
         dp = G.get_default_graph().collections.get('data_parallel')
@@ -193,6 +197,81 @@ class Trainer:
                 self._skip_g, self._g_extra = frozenset(trunk + [d_in_gen.op]), [self._stash_copy]
             else:                                   # plain generator: its concat launch puts the (aliased) frame into D(fake)'s input as usual
                 self._skip_g, self._g_extra = frozenset(trunk), []
+        self.bn_inference = bool(bn_inference)
+        if self.bn_inference:
+            self._build_bn_inference(build_g)
+
+    def _build_bn_inference(self, build_g):
+        """Two more generator instances on the existing variables and placeholders (the modes arrive through the arg scope of
+        ops.batch_norm, as slim's ``is_training`` does).  Calibration: the generator as it runs today, batch statistics in every
+        layer, each BatchNorm layer also pooling the moments of its input rows into its stored statistics
+        (``g/<layer>/BatchNorm/moving_mean`` / ``moving_variance`` / ``calibration_rows``: graph state, in no variable list and no
+        optimizer).  Stored: every BatchNorm layer applies those statistics."""
+        graph = G.get_default_graph()
+        dp = graph.collections.get('data_parallel')
+        if dp is not None and (dp.active or dp.sync_bn):
+            raise ValueError('bn_inference runs on one rank (no data parallelism, sync_bn or exact_global_batch)')
+        B = self.batch_size
+        n_before = len(graph.collections.get('bn_collect', []))
+        with O.arg_scope([O.batch_norm], collect_statistics=True):
+            build_g(self.img_ph, self.action_ph, B, True)
+        self._bn_collect_ops = list(graph.collections['bn_collect'][n_before:])
+        with O.arg_scope([O.batch_norm], is_training=False):
+            self.g_out_stored, self.g_state_stored = build_g(self.img_ph, self.action_ph, B, True)
+        self._stored_psnr = O.build_psnr(self.next_frame_ph, self.g_out_stored)
+        # scope -> (mean, variance, rows) of this generator's layers, in layer order
+        self._bn_state = {op.name[:-len('/collect')]: tuple(op.extras) for op in self._bn_collect_ops}
+        first = self._bn_collect_ops[0]
+        self._bn_rows_per_sample = first.rows // B          # layer rows (B * h * w positions) of the first layer per batch row
+        self._bn_calibrated = False
+
+    def _require_bn_inference(self):
+        if not self.bn_inference:
+            raise RuntimeError("this Trainer was built without bn_inference=True: it has no stored BatchNorm statistics")
+
+    def bn_calibration_rows(self):
+        """Batch rows (frame / action pairs) pooled into the stored statistics so far; reads the device-side count."""
+        self._require_bn_inference()
+        count = self._bn_collect_ops[0].extras[2]
+        return int(self.sess._materialize(count).item()) // self._bn_rows_per_sample
+
+    def _require_calibrated(self):
+        self._require_bn_inference()
+        if not self._bn_calibrated:
+            if self.bn_calibration_rows() < 1:       # (statistics restored from a checkpoint count as well)
+                raise RuntimeError("bn='stored': the BatchNorm statistics are uncalibrated (0 rows): run calibrate_bn, or restore a "
+                                   "checkpoint that holds them")
+            self._bn_calibrated = True
+
+    def reset_bn_statistics(self):
+        """Back to slim's initial values (mean 0, variance 1) and a count of 0: the next calibrate_bn starts afresh."""
+        self._require_bn_inference()
+        for state in self._bn_state.values():
+            for t in state:
+                self.sess._materialize(t).fill_(t.init)
+        self._bn_calibrated = False
+
+    def calibrate_bn(self, images, actions):
+        """Merge one batch (frames [B, H, W, 3], actions [B, 10]) into the stored statistics: the generator runs on batch
+        statistics as ``test`` does and every BatchNorm layer pools its input rows (ops.BnCollectOp).  -> batch rows seen so far."""
+        self._require_bn_inference()
+        self._announced = None
+        self.sess.run(self._bn_collect_ops, {self.img_ph: images, self._img_pad: images, self.action_ph: actions})
+        self._bn_calibrated = False                  # (re-read from the device by the next stored-mode call)
+        return self.bn_calibration_rows()
+
+    def bn_statistics(self):
+        """-> {state name: numpy array}: every layer's ``moving_mean`` / ``moving_variance`` [C] float32 and ``calibration_rows``
+        [1] int64 (layer rows: batch rows times the layer's h * w)."""
+        self._require_bn_inference()
+        return {t.name: self.sess._materialize(t).detach().cpu().numpy().copy() for state in self._bn_state.values() for t in state}
+
+    def _check_bn_mode(self, bn):
+        if bn not in ('batch', 'stored'):
+            raise ValueError("bn must be 'batch' or 'stored', got %r" % (bn,))
+        if bn == 'stored':
+            self._require_calibrated()
+        return bn == 'stored'
 
     def _build_rollout(self, build_g, make):
         """K generator instances chained through their own predictions and K D(fake) instances, on the existing variables.
@@ -337,15 +416,22 @@ class Trainer:
         self.sess.run([self.d_opt_op, self.clip_d], fd)
         return None
 
-    def test(self, input_images, next_frame, actions):
+    def test(self, input_images, next_frame, actions, bn='batch'):
+        """``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
+        summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames)."""
         self._announced = None
+        if self._check_bn_mode(bn):
+            has_state = self.g_state_stored is not None
+            fd = {self.img_ph: input_images, self._img_pad: input_images, self.next_frame_ph: next_frame, self.action_ph: actions}
+            res = self.sess.run([self.g_out_stored] + ([self.g_state_stored] if has_state else []) + [[self._stored_psnr]], fd)
+            return res[0], (res[1] if has_state else None), {'g_psnr': float(np.asarray(res[-1][0]).reshape(-1)[0])}
         tensors = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else []) + [self.merged_summaries]
         res = self.sess.run(tensors, self._feed(input_images, next_frame, actions))
         gen_next_frames, summ = res[0], res[-1]
         gen_next_state = res[1] if self.g_state_out is not None else None      # defect D4
         return gen_next_frames, gen_next_state, self._named(summ)
 
-    def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None):
+    def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None, bn='batch'):
         """Recursive rollout: feed each prediction (and predicted state) back in.
         ``device_loop`` (default: on for a GPU session): from the second step on the prediction and the predicted state stay on the
         device between steps - the program of those steps fetches nothing but the two, so it carries no loss ops either - and
@@ -357,14 +443,16 @@ class Trainer:
         ``(predicted [B, steps, H, W, 3], summaries of step 0)``.
         ``literal=True``: the reference's method of this name exactly as written (train.py:157-176) - SIX steps, step j
         reads ``test_actions[:, 2 j, :5]`` and ``test_next_frame[:, 2 j]`` (the sequences must hold >= 11 frames),
-        and the second return value is ``current_frame[1:7]``, samples 1..6 of the last prediction."""
+        and the second return value is ``current_frame[1:7]``, samples 1..6 of the last prediction.
+        ``bn``: 'batch' (default: every step normalises with the statistics of its batch) or 'stored' (see ``test``)."""
+        self._check_bn_mode(bn)
         if literal:
             predicted = []
             current_frame = input_images[:, 0]
             current_state = test_actions[:, 0, 5:]
             for j in range(0, 6):
                 acs = np.concatenate((test_actions[:, j * 2, :5], current_state), axis=1).astype(np.float32)
-                out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs)
+                out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs, bn=bn)
                 predicted.append(out)
                 current_frame = out
                 current_state = st if st is not None else test_actions[:, j * 2, 5:]      # plain generator: no state head (D4)
@@ -373,28 +461,30 @@ class Trainer:
         if device_loop is None:
             device_loop = self.sess.rt.is_cuda
         if device_loop and steps >= 1:
-            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps)
+            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps, bn=bn)
             return predicted.cpu().numpy(), summ0
         predicted, summ0 = [], None
         current_frame = input_images[:, 0]
         current_state = test_actions[:, 0, 5:]
         for j in range(steps):
             acs = np.concatenate((test_actions[:, j, :5], current_state), axis=1).astype(np.float32)
-            out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs)
+            out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs, bn=bn)
             summ0 = summ0 or summ
             predicted.append(out)
             current_frame = out
             current_state = st if st is not None else test_actions[:, j + 1, 5:]
         return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), summ0
 
-    def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps):
+    def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps, bn='batch'):
         """The device loop of ``test_sequence``: -> (predicted [B, steps, H, W, 3] float32 on the device, summaries of step 0)."""
-        out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32))
+        out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32), bn=bn)
         acts = self.sess.upload(np.asarray(test_actions[:, :steps + 1], np.float32))          # [B, steps + 1, 10], once
         frame = self.sess.upload(out)
         state = self.sess.upload(st) if st is not None else acts[:, 1, 5:]
         frames = [frame]
         fetches = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else [])
+        if bn == 'stored':
+            fetches = [self.g_out_stored] + ([self.g_state_stored] if self.g_state_stored is not None else [])
         for j in range(1, steps):
             acs = torch.cat([acts[:, j, :5], state], dim=1).contiguous()
             fd = self._feed(frame, test_next_frame[:, j + 1], acs)      # (next_frame is not read by this program: checked, not uploaded)
@@ -405,21 +495,23 @@ class Trainer:
             frames.append(frame)
         return torch.stack(frames, dim=1), summ0
 
-    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False):
+    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False, bn='batch'):
         """Quality of the recursive rollout, scored on the GPU (metrics.frame_metrics; no reference counterpart - the curves of
         its report).  Rollout as ``test_sequence``'s default on the device loop: ``steps`` (default T-1) steps,
         step j commanded by ``actions[:, j]`` with the generator's own predicted state (defect D7) and scored against
         ``images[:, j + 1]``.  The predictions stay on the device; all B * steps frames are scored in one launch.  ``identity``:
         also score the identity baseline - ``images[:, 0]`` carried forward - against the same targets.
         -> dict of numpy arrays [B, steps]: ``ssim``, ``sqerr`` (sum of squared errors of the frame), and ``identity_ssim``,
-        ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames)."""
+        ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames).
+        ``bn``: 'batch' or 'stored', as ``test`` takes it."""
         from . import metrics
+        self._check_bn_mode(bn)
         if not self.sess.rt.is_cuda:
             raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
         steps = steps if steps is not None else images.shape[1] - 1
         if steps < 1 or steps + 1 > images.shape[1]:
             raise ValueError('rollout_metrics: %d steps need %d frames per sequence, got %d' % (steps, steps + 1, images.shape[1]))
-        predicted, _ = self._rollout_on_device(images, images, actions, steps)
+        predicted, _ = self._rollout_on_device(images, images, actions, steps, bn=bn)
         seq = self.sess.upload(np.asarray(images[:, :steps + 1], np.float32))                # [B, steps + 1, H, W, 3], once
         truth = seq[:, 1:]
         ssim, sqerr = metrics.frame_metrics(predicted, truth)

@@ -2,6 +2,8 @@
 // reach on MI355X at the tensor sizes of a batch-32 step (4 - 67 MB), launched the way the step launches them (N launches
 // captured in a HIP graph)?  Variants of thread mapping, block size, loads in flight and grid size; prints us and GB/s.
 //   hipcc -O3 --offload-arch=gfx950 -o stream_probe tools/micro/stream_probe.hip && ./stream_probe
+// `./stream_probe ew ROWS CHANNELS [ROWS CHANNELS ...]`: the flat elementwise pass alone (one read, one write) on fp32 tensors of
+// the given sizes, one line each - the yardstick tools/bench_bn_infer.py puts beside acg_bn_act_infer (ROWS * CHANNELS % 4 == 0).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -110,7 +112,34 @@ struct Timer {
   }
 };
 
-int main() {
+// one line per [rows x channels] fp32 tensor: the best of the flat elementwise variants, without and with per-channel parameters
+static int ew_only(int argc, char** argv) {
+  Timer T;
+  float *m, *r, *b;
+  CK(hipMalloc(&m, 1 << 20)); CK(hipMalloc(&r, 1 << 20)); CK(hipMalloc(&b, 1 << 20));
+  CK(hipMemset(m, 0, 1 << 20)); CK(hipMemset(r, 0, 1 << 20)); CK(hipMemset(b, 0, 1 << 20));
+  for (int a = 2; a + 1 < argc; a += 2) {
+    const long long R = atoll(argv[a]);
+    const int C = atoi(argv[a + 1]);
+    const long long n = R * C, n4 = n / 4;
+    if (R <= 0 || C <= 0 || C > (1 << 18) || n % 4 || (C % 4 && (256 * 4) % C)) { printf("ew %lld %d skipped\n", R, C); continue; }
+    float *x, *y;
+    CK(hipMalloc(&x, n * 4)); CK(hipMalloc(&y, n * 4));
+    CK(hipMemset(x, 0x3c, n * 4));
+    float best[2] = {1e30f, 1e30f};
+#define EW_ONE(U, PARAMS) { const int grid = (int)((n4 + 256LL * U - 1) / (256LL * U)); \
+    float us = T.us([&](hipStream_t s) { hipLaunchKernelGGL((ew_flat<256, U, PARAMS>), dim3(grid), dim3(256), 0, s, (const float4*)x, (float4*)y, m, r, b, n4, C); }); \
+    if (us < best[PARAMS]) best[PARAMS] = us; }
+    EW_ONE(1, false) EW_ONE(2, false) EW_ONE(4, false) EW_ONE(8, false)
+    if (C % 4 == 0 && (256 * 4) % C == 0) { EW_ONE(1, true) EW_ONE(2, true) EW_ONE(4, true) EW_ONE(8, true) }
+    printf("ew %lld %d stream_us %.3f params_us %.3f\n", R, C, best[0], best[1] < 1e29f ? best[1] : -1.f);
+    CK(hipFree(x)); CK(hipFree(y));
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && argv[1][0] == 'e') return ew_only(argc, argv);
   Timer T;
   const long long Rs[] = {8192, 32768, 131072};
   const int C = 128;
