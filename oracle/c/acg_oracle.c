@@ -712,26 +712,32 @@ int32_t acg_frame_loss(const void* gv, const void* tv, float* out2, void* dgv, i
   if (out2) { out2[0] = (float)l1; out2[1] = (float)gdl; }      /* out2 == NULL: the gradient alone */
   return ACG_OK;
 }
+/* the one-block heads of the HIP library take 1..65536 elements (acgan_hip.h): the same contract here */
+#define HEAD_N(n, who) do { if ((n) <= 0 || (n) > 65536) return fail(ACG_ERR_INVALID_ARG, who ": n outside 1..65536"); } while (0)
 int32_t acg_l2norm_loss(const float* p, const float* g, float* out, float* dp, int64_t n, float scale, acg_stream_t s) {
-  (void)s; double ss = 0;
+  (void)s; HEAD_N(n, "l2norm_loss");
+  double ss = 0;
   for (int64_t i = 0; i < n; i++) { double e = (double)p[i] - g[i]; ss += e * e; }
   double nrm = sqrt(ss); out[0] = (float)nrm;
   if (dp) for (int64_t i = 0; i < n; i++) dp[i] = nrm > 0 ? (float)(scale * ((double)p[i] - g[i]) / nrm) : 0.f;
   return ACG_OK;
 }
 int32_t acg_sumsq_diff(const float* p, const float* g, float* out, int64_t n, acg_stream_t s) {
-  (void)s; double ss = 0;
+  (void)s; HEAD_N(n, "sumsq_diff");
+  double ss = 0;
   for (int64_t i = 0; i < n; i++) { double e = (double)p[i] - g[i]; ss += e * e; }
   out[0] = (float)ss;
   return ACG_OK;
 }
 int32_t acg_l2norm_loss_global(const float* p, const float* g, const float* gss, float* out, float* dp, int64_t n, float scale, acg_stream_t s) {
-  (void)s; double nrm = sqrt((double)gss[0]); out[0] = (float)nrm;
+  (void)s; HEAD_N(n, "l2norm_loss_global");
+  double nrm = sqrt((double)gss[0]); out[0] = (float)nrm;
   if (dp) for (int64_t i = 0; i < n; i++) dp[i] = nrm > 0 ? (float)(scale * ((double)p[i] - g[i]) / nrm) : 0.f;
   return ACG_OK;
 }
 int32_t acg_sigmoid_ce_loss(const float* x, float label, float* out, float* dx, int64_t n, float scale, acg_stream_t s) {
-  (void)s; double sum = 0;
+  (void)s; HEAD_N(n, "sigmoid_ce_loss");
+  double sum = 0;
   for (int64_t i = 0; i < n; i++) { double v = x[i];
     sum += (v > 0 ? v : 0) - v * label + log1p(exp(-fabs(v)));
     if (dx) dx[i] = (float)(scale * (1.0 / (1.0 + exp(-v)) - label) / (double)n); }
@@ -739,7 +745,8 @@ int32_t acg_sigmoid_ce_loss(const float* x, float label, float* out, float* dx, 
   return ACG_OK;
 }
 int32_t acg_mean_loss(const float* x, float* out, float* dx, int64_t n, float scale, acg_stream_t s) {
-  (void)s; double sum = 0;
+  (void)s; HEAD_N(n, "mean_loss");
+  double sum = 0;
   for (int64_t i = 0; i < n; i++) { sum += x[i]; if (dx) dx[i] = (float)(scale / (double)n); }
   out[0] = (float)(sum / (double)n);
   return ACG_OK;

@@ -566,14 +566,16 @@ class Abi:
                               L.dtype2(L.code(x.dtype), L.code(y.dtype)), self.stream())
         return y
 
-    def bias_act_bwd(self, y, dy, act, leak=0.2, want_dx=True, x_pitch=None, x_dtype=None):
+    def bias_act_bwd(self, y, dy, act, leak=0.2, want_dx=True, x_pitch=None, x_dtype=None, dbias=None, accumulate=0.0):
+        """``dbias`` with ``accumulate``: dbias = accumulate * dbias + the column sums (in place)."""
         c = y.shape[-1]
         rows = y.numel() // c
         xp = x_pitch or c
         dx = torch.zeros(*y.shape[:-1], xp, dtype=x_dtype or y.dtype, device=self.device) if want_dx else None
-        dbias = self.empty(c)
+        if dbias is None:
+            dbias = self.empty(c)
         ws, n = self.ws(self.lib.bias_workspace_bytes(rows, c))
-        self.lib.bias_act_bwd(_p(y), _p(dy), _p(dx), _p(dbias), 0.0, rows, c, xp, c, ACT[act], leak,
+        self.lib.bias_act_bwd(_p(y), _p(dy), _p(dx), _p(dbias), accumulate, rows, c, xp, c, ACT[act], leak,
                               L.dtype2(L.code(x_dtype or y.dtype), L.code(y.dtype)), _p(ws), n, self.stream())
         return dx, dbias
 
@@ -617,18 +619,27 @@ class Abi:
         return (dl, dbias) if want_dbias else dl
 
     # ---- plumbing ops
-    def concat_actions(self, x, actions, pitch=0):
-        b, h, w, c = x.shape
+    def concat_actions(self, x, actions, pitch=0, y=None, c=None):
+        """``y`` [B,h,w,pitch]: the destination as the caller prepared it (else zeros).  ``x`` None: the features are already in
+        ``y`` (``c`` of them per row) and only the actions are tiled in."""
+        if x is None:
+            b, h, w, _ = y.shape
+        else:
+            b, h, w, c = x.shape
         a = actions.shape[1]
-        y = torch.zeros(b, h, w, pitch or (c + a), dtype=x.dtype, device=self.device)
-        self.lib.concat_actions_fwd(_p(x), _p(actions), _p(y), b, h * w, c, a, pitch, L.code(x.dtype), self.stream())
+        if y is None:
+            y = torch.zeros(b, h, w, pitch or (c + a), dtype=x.dtype, device=self.device)
+        self.lib.concat_actions_fwd(_p(x), _p(actions), _p(y), b, h * w, c, a, pitch, L.code(y.dtype), self.stream())
         return y
 
-    def concat_channels(self, a, b, pitch=0, y_dtype=None):
-        ca, cb = a.shape[-1], (b.shape[-1] if b is not None else 0)
-        y = torch.zeros(*a.shape[:-1], pitch or (ca + cb), dtype=y_dtype or a.dtype, device=self.device)
-        self.lib.concat_channels_fwd(_p(a), _p(b), _p(y), a.numel() // ca, ca, cb, pitch, L.dtype2(L.code(a.dtype), L.code(y.dtype)),
-                                     self.stream())
+    def concat_channels(self, a, b, pitch=0, y_dtype=None, y=None, ca=None):
+        """``y``: the destination as the caller prepared it (else zeros).  ``a`` None: channels [0, ca) of ``y`` stay."""
+        first = a if a is not None else b
+        ca, cb = (a.shape[-1] if a is not None else ca), (b.shape[-1] if b is not None else 0)
+        if y is None:
+            y = torch.zeros(*first.shape[:-1], pitch or (ca + cb), dtype=y_dtype or first.dtype, device=self.device)
+        self.lib.concat_channels_fwd(_p(a), _p(b), _p(y), first.numel() // first.shape[-1], ca, cb, pitch,
+                                     L.dtype2(L.code(first.dtype), L.code(y.dtype)), self.stream())
         return y
 
     def slice_channels(self, src, off, cdst, dst=None, accumulate=0.0, dst_dtype=None):
@@ -640,15 +651,18 @@ class Abi:
         return dst
 
     def copy_many(self, pairs):
-        """pairs: [(src [rows, cols] dense, dst [rows, pitch])]; copies every src into the first cols channels of dst."""
+        """pairs: [(src [rows, cols] dense, dst [rows, pitch])]; copies every src into the first cols channels of dst.  An entry
+        (src, dst, src_div, src_mod) tiles: destination row r reads source row (r / src_div) % src_mod (src_mod 0: no wrap)."""
         cl = L.CopyList()
-        for i, (src, dst) in enumerate(pairs):
+        for i, (src, dst, *tiling) in enumerate(pairs):
             cl.src[i], cl.dst[i] = src.data_ptr(), dst.data_ptr()
-            cl.rows[i], cl.cols[i], cl.dst_pitch[i], cl.dst_dtype[i] = src.shape[0], src.shape[1], dst.shape[1], L.code(dst.dtype)
+            cl.rows[i], cl.cols[i], cl.dst_pitch[i], cl.dst_dtype[i] = dst.shape[0], src.shape[1], dst.shape[1], L.code(dst.dtype)
+            cl.src_div[i], cl.src_mod[i] = tiling if tiling else (0, 0)
         self.lib.copy_many(ctypes.byref(cl), len(pairs), L.ACG_F32, self.stream())
 
-    def add(self, a, b):
-        y = torch.empty_like(a)
+    def add(self, a, b, y=None):
+        if y is None:
+            y = torch.empty_like(a)
         self.lib.add(_p(a), _p(b), _p(y), a.numel(), L.code(a.dtype), self.stream())
         return y
 
@@ -662,18 +676,28 @@ class Abi:
                             self.stream())
         return out, dgen
 
-    def l2norm_loss(self, pred, gt, scale):
-        out, d = self.empty(1), torch.empty_like(pred)
+    def l2norm_loss(self, pred, gt, scale, want_grad=True):
+        out, d = self.empty(1), (torch.empty_like(pred) if want_grad else None)
         self.lib.l2norm_loss(_p(pred), _p(gt), _p(out), _p(d), pred.numel(), scale, self.stream())
         return out, d
 
-    def sigmoid_ce_loss(self, logits, label, scale):
-        out, d = self.empty(1), torch.empty_like(logits)
+    def sumsq_diff(self, pred, gt):
+        out = self.empty(1)
+        self.lib.sumsq_diff(_p(pred), _p(gt), _p(out), pred.numel(), self.stream())
+        return out
+
+    def l2norm_loss_global(self, pred, gt, global_sumsq, scale, want_grad=True):
+        out, d = self.empty(1), (torch.empty_like(pred) if want_grad else None)
+        self.lib.l2norm_loss_global(_p(pred), _p(gt), _p(global_sumsq), _p(out), _p(d), pred.numel(), scale, self.stream())
+        return out, d
+
+    def sigmoid_ce_loss(self, logits, label, scale, want_grad=True):
+        out, d = self.empty(1), (torch.empty_like(logits) if want_grad else None)
         self.lib.sigmoid_ce_loss(_p(logits), label, _p(out), _p(d), logits.numel(), scale, self.stream())
         return out, d
 
-    def mean_loss(self, x, scale):
-        out, d = self.empty(1), torch.empty_like(x)
+    def mean_loss(self, x, scale, want_grad=True):
+        out, d = self.empty(1), (torch.empty_like(x) if want_grad else None)
         self.lib.mean_loss(_p(x), _p(out), _p(d), x.numel(), scale, self.stream())
         return out, d
 

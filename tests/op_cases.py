@@ -1371,3 +1371,460 @@ def case_repeatable_launches(abi, reps=60):
         abi.no_timeout(wsf); abi.no_timeout(wsb)
         # the epoch word counts the launches: proof that the one-launch kernels (not the two-launch path) ran
         assert int(wsb[0:4].view(torch.int32)[0]) == reps and int(wsf[0:4].view(torch.int32)[0]) == reps, 'the one-launch kernels did not run'
+
+
+# ---- the loss, optimizer and plumbing kernels at every path ------------------------------------------------------------------
+# The cases above run loss.hip, optim.hip, elementwise.hip and the bias kernels of bn.hip at one or two tiny shapes that all take
+# the same branch.  The cases below reach the grid-stride loops, the scalar tails, the unaligned branches and the entry points no
+# per-op test called.  Each asserts its own premise by arithmetic on the kernel constant it mirrors, so that a later edit of a
+# shape cannot fall back under a threshold unnoticed.  References: float64 torch on the CPU.  bfloat16 sub-cases run on the HIP
+# library only (the C oracle stores float32).
+SENTINEL = -7.0          # exact in bfloat16; no seeded input below takes this value
+
+
+def dyadic(shape, grid, seed):
+    """Values k / grid, k in [-grid, grid]: differences, signs and sums of a few million of them are exact in float32."""
+    return torch.randint(-grid, grid + 1, shape, generator=_rng(seed)).float() / grid
+
+
+def _guarded(t, lead, dev):
+    """``t`` (1-D) copied into a fresh buffer behind ``lead`` elements, with a sentinel in front of it and one behind:
+    -> (buffer, view).  lead = 1: the view starts one element past a 16-byte boundary; lead = 8: on one."""
+    n = t.numel()
+    buf = torch.full((lead + n + 1,), SENTINEL, dtype=t.dtype, device=dev)
+    buf[lead:lead + n] = t.to(dev)
+    view = buf[lead:lead + n]
+    assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == (lead * t.element_size()) % 16, 'test premise: alignment of the view'
+    return buf, view
+
+
+def _guards_intact(buf, lead, what):
+    n = buf.numel() - lead - 1
+    assert float(buf[lead - 1]) == SENTINEL and float(buf[lead + n]) == SENTINEL, what + ': an element next to the view was written'
+    if lead > 1:
+        assert bool((buf[:lead] == SENTINEL).all()), what + ': elements in front of the view were written'
+
+
+# (shape, strides): the shapes the C oracle was checked on (C == 3 and runtime-C templates, power-of-two and division index paths,
+# H = 1 / W = 1 borders), and the two smallest that take frame_loss_k's grid-stride loop (power of two / division)
+FRAME_EXACT_SHAPES = [(2, 64, 64, 3), (1, 5, 7, 3), (3, 2, 2, 1), (2, 16, 32, 4), (1, 12, 16, 2), (2, 1, 9, 3), (2, 9, 1, 3), (1, 1, 1, 4)]
+FRAME_STRIDED = {(9, 256, 256, 1): True, (1, 600, 900, 1): False}      # shape -> power-of-two extents
+FRAME_EXACT_CASES = [(s, g) for s in FRAME_EXACT_SHAPES for g in (64, 4)] + [(s, 4) for s in FRAME_STRIDED]
+
+
+def case_frame_loss_exact(abi, shp, grid):
+    """acg_frame_loss on inputs k / grid with w_l1 = 0.25, w_gdl = 1: every difference, sign and weighted sum is exact in float32
+    and ties (g == t, |tdx| == |gdx|: tf.abs has gradient 0 at 0) are frequent, so the gradient must equal the float64 autograd
+    gradient BIT FOR BIT - no mismatch cap - and, the totals staying below 2^24 grid units, both values the float64 sums."""
+    dev = abi.device
+    b, h, w, c = shp
+    if shp in FRAME_STRIDED:
+        # loss.hip kMaxBlocks (2048) x 256 threads, one pixel per thread: beyond it the grid-stride loop runs
+        assert b * h * w > 2048 * 256, 'test premise: the shape takes the grid-stride loop'
+        assert ((w & (w - 1)) == 0 and (h & (h - 1)) == 0) == FRAME_STRIDED[shp], 'test premise: shift / division index path'
+    gen, gt = dyadic(shp, grid, 1500), dyadic(shp, grid, 1501)
+    w1, w2 = 0.25, 1.0
+    gd, td = gen.double().requires_grad_(True), gt.double()
+    l1 = (gd - td).abs().sum()
+    g = T.gdl(gd, td)
+    dref, = torch.autograd.grad(w1 * l1 + w2 * g, [gd])
+    if gen.numel() >= 1000:
+        dx = lambda t: (t[:, :, 1:] - t[:, :, :-1]).abs()      # noqa: E731
+        assert bool((gen == gt).any()) and (w < 2 or bool((dx(gen) == dx(gt)).any())), 'test premise: the inputs hold exact ties'
+    want = [float(l1.detach()), float(g.detach())]
+    assert max(want) * grid < 2 ** 24, 'test premise: the totals in grid units are exact float32 integers'
+    out, dgen = abi.frame_loss(gen.to(dev), gt.to(dev), w1, w2)
+    bad = int((dgen.double().cpu() != dref).sum())
+    print('frame_loss exact %s grid %d: %d mismatching gradient elements; values %s vs %s' % (shp, grid, bad, out.tolist(), want))
+    assert bad == 0, 'frame_loss %s grid 1/%d: %d of %d gradient elements differ from float64' % (shp, grid, bad, dgen.numel())
+    assert torch.equal(out.double().cpu(), torch.stack([l1, g]).detach()), 'frame_loss %s grid 1/%d values %s, float64 %s' % (shp, grid, out.tolist(), want)
+    _, dgen2 = abi.frame_loss(gen.to(dev), gt.to(dev), w1, w2, want_values=False)
+    assert torch.equal(dgen2.cpu(), dgen.cpu()), 'frame_loss gradient-only mode %s' % (shp,)
+
+
+HEAD_SIZES = [1025, 4099, 65536]
+
+
+def case_loss_heads(abi, tol, n):
+    """The one-block heads (l2norm, sigmoid_ce, mean) beyond one element per thread, up to the largest n they take: value and
+    gradient against float64, and the value-only call (gradient pointer NULL) gives the same value."""
+    dev = abi.device
+    assert 1024 < n <= 65536, 'test premise: more elements than the 1024 threads of the one block (loss.hip), within the limit'
+    pred, tgt = randn((n,), 1510), randn((n,), 1511)
+    pd = pred.double().requires_grad_(True)
+    n2 = torch.sqrt(((pd - tgt.double()) ** 2).sum())
+    dref, = torch.autograd.grad(n2 / 32, [pd])
+    out, d = abi.l2norm_loss(pred.to(dev), tgt.to(dev), 1.0 / 32)
+    close(out, n2.detach().reshape(1), tol, 'l2norm value n=%d' % n)
+    close(d, dref, tol * 4, 'l2norm grad n=%d' % n)
+    out0, none = abi.l2norm_loss(pred.to(dev), tgt.to(dev), 1.0 / 32, want_grad=False)
+    assert none is None and torch.equal(out0.cpu(), out.cpu()), 'l2norm value-only call n=%d' % n
+    for label in (0.0, 0.9, 1.0):
+        x = randn((n,), 1512, 3.0)
+        x[0], x[1], x[n - 1], x[n - 2] = 60.0, -60.0, 60.0, -60.0
+        xd = x.double().requires_grad_(True)
+        ce = T.sigmoid_cross_entropy(torch.full_like(xd, label), xd)
+        dref, = torch.autograd.grad(ce, [xd])
+        out, d = abi.sigmoid_ce_loss(x.to(dev), label, 1.0)
+        close(out, ce.detach().reshape(1), tol, 'sigmoid_ce value label=%g n=%d' % (label, n))
+        close(d, dref, tol * 4, 'sigmoid_ce grad label=%g n=%d' % (label, n))
+        out0, none = abi.sigmoid_ce_loss(x.to(dev), label, 1.0, want_grad=False)
+        assert none is None and torch.equal(out0.cpu(), out.cpu()), 'sigmoid_ce value-only call label=%g n=%d' % (label, n)
+    x = randn((n,), 1513) + 0.25
+    out, d = abi.mean_loss(x.to(dev), -1.0)
+    close(out, x.double().mean().reshape(1), tol, 'mean value n=%d' % n)
+    close(d, torch.full_like(x.double(), -1.0 / n), 1e-6, 'mean grad n=%d' % n)
+    out0, none = abi.mean_loss(x.to(dev), -1.0, want_grad=False)
+    assert none is None and torch.equal(out0.cpu(), out.cpu()), 'mean value-only call n=%d' % n
+
+
+def case_loss_heads_reject(abi):
+    """n = 65537 is one more than the one-block heads take: an error, never a launch."""
+    from action_conditioned_gans_amd._lib import AcgError
+    dev = abi.device
+    n = 65536 + 1
+    x, y = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    one = torch.ones(1, device=dev)
+    for what, call in [('l2norm_loss', lambda: abi.l2norm_loss(x, y, 1.0)), ('sigmoid_ce_loss', lambda: abi.sigmoid_ce_loss(x, 1.0, 1.0)),
+                       ('mean_loss', lambda: abi.mean_loss(x, 1.0)), ('sumsq_diff', lambda: abi.sumsq_diff(x, y)),
+                       ('l2norm_loss_global', lambda: abi.l2norm_loss_global(x, y, one, 1.0))]:
+        with pytest.raises(AcgError):
+            call()
+        abi.sync()
+
+
+def case_state_loss_global(abi, tol):
+    """The data-parallel state loss: acg_sumsq_diff (this rank's sum of squares) and acg_l2norm_loss_global (norm from the
+    all-reduced sum) against float64."""
+    dev = abi.device
+    for n in (160, 4099):
+        pred, tgt = randn((n,), 1520), randn((n,), 1521)
+        e = pred.double() - tgt.double()
+        ss = (e * e).sum()
+        scale = 1.0 / 32
+        got = abi.sumsq_diff(pred.to(dev), tgt.to(dev))
+        close(got, ss.reshape(1), tol, 'sumsq_diff n=%d' % n)
+        # the rank's own sum: acg_l2norm_loss
+        out_l, d_l = abi.l2norm_loss(pred.to(dev), tgt.to(dev), scale)
+        out_g, d_g = abi.l2norm_loss_global(pred.to(dev), tgt.to(dev), got, scale)
+        close(out_g, ss.sqrt().reshape(1), tol, 'l2norm_global value (own sum) n=%d' % n)
+        close(d_g, scale * e / ss.sqrt(), tol * 4, 'l2norm_global grad (own sum) n=%d' % n)
+        close(out_g, out_l.double().cpu(), tol, 'l2norm_global vs l2norm value n=%d' % n)
+        close(d_g, d_l.double().cpu(), tol * 4, 'l2norm_global vs l2norm grad n=%d' % n)
+        # three ranks with the same sum
+        gss = (3.0 * ss).float().reshape(1)
+        out_g, d_g = abi.l2norm_loss_global(pred.to(dev), tgt.to(dev), gss.to(dev), scale)
+        nrm = gss.double().sqrt()
+        close(out_g, nrm, tol, 'l2norm_global value (3 x sum) n=%d' % n)
+        close(d_g, scale * e / nrm, tol * 4, 'l2norm_global grad (3 x sum) n=%d' % n)
+        out0, none = abi.l2norm_loss_global(pred.to(dev), tgt.to(dev), gss.to(dev), scale, want_grad=False)
+        assert none is None and torch.equal(out0.cpu(), out_g.cpu()), 'l2norm_global value-only call n=%d' % n
+        out_g, d_g = abi.l2norm_loss_global(pred.to(dev), tgt.to(dev), torch.zeros(1, device=dev), scale)
+        assert out_g.item() == 0 and bool((d_g == 0).all()), 'l2norm_global at a zero global sum must give zero gradient, not NaN'
+
+
+def case_psnr_strided(abi, tol):
+    n = 600001
+    assert n > 2048 * 256 and n % 2 == 1, 'test premise: beyond loss.hip kMaxBlocks x 256 threads (grid-stride), odd'
+    a, b = uniform((n,), 1530), uniform((n,), 1531)
+    close(abi.psnr(a.to(abi.device), b.to(abi.device)), T.psnr(a.double(), b.double()).reshape(1), tol, 'psnr n=%d' % n)
+
+
+# ---- optimizers
+_f32 = lambda v: float(np.float32(v))      # noqa: E731  TF holds its hyper-parameters as float32 constants
+
+
+def _adam_ref(p, m, v, g, t, gs, clip, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """One TF Adam step in float64 (the recurrence of case_optimizers): pow of the float32-rounded betas in float64."""
+    lr, b1, b2, eps = _f32(lr), _f32(b1), _f32(b2), _f32(eps)
+    gd = g.double() * gs
+    lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+    m = b1 * m + (1 - b1) * gd
+    v = b2 * v + (1 - b2) * gd * gd
+    p = p - lr_t * m / (v.sqrt() + eps)
+    if clip:
+        p = p.clamp(_f32(clip[0]), _f32(clip[1]))
+    return p, m, v
+
+
+def _rms_ref(p, ms, g, gs, clip, lr=5e-5, decay=0.9, eps=1e-10):
+    """One TF RMSProp step in float64 (the recurrence of case_optimizers)."""
+    gd = g.double() * gs
+    ms = _f32(decay) * ms + (1 - _f32(decay)) * gd * gd
+    p = p - _f32(lr) * gd / torch.sqrt(ms + _f32(eps))
+    if clip:
+        p = p.clamp(_f32(clip[0]), _f32(clip[1]))
+    return p, ms
+
+
+OPT_STRIDED_N = 4 * 256 * 4096 + 1024 + 3
+OPT_SIZES = [1, 3, 4, 1027, OPT_STRIDED_N]
+CLIP = (-0.01, 0.01)
+
+
+def case_optimizers_sizes(abi, tol, n):
+    """Adam and RMSProp, 3 steps with clip and grad_scale 0.5: n below one float4 (scalar tail only), exactly one, a ragged
+    few, and the smallest buffers whose float4 count exceeds the grid (optim.hip grid_for: 4096 blocks x 256 threads, one
+    float4 each), where the second float4 loop and the scalar tail both run - D's flat buffer does in every bench step."""
+    dev = abi.device
+    if n > 4096:
+        assert n // 4 > 4096 * 256 and n % 4 == 3, 'test premise: more float4 than threads in the capped grid, and a scalar tail'
+    p0 = randn((n,), 1540, 0.02)
+    grads = [randn((n,), 1541 + i, 0.1) for i in range(3)]
+    p, m, v = p0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
+    pg, mg, vg = p0.clone().to(dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    step = torch.zeros(1, dtype=torch.int32, device=dev)
+    for t, g in enumerate(grads, 1):
+        p, m, v = _adam_ref(p, m, v, g, t, 0.5, CLIP)
+        abi.adam_step(pg, g.to(dev), mg, vg, step, gs=0.5, clip=CLIP)
+    assert step.item() == 3
+    close(pg, p, tol, 'adam param n=%d' % n); close(mg, m, tol, 'adam m n=%d' % n); close(vg, v, tol, 'adam v n=%d' % n)
+    del pg, mg, vg, m, v
+    p, ms = p0.double(), torch.ones(n, dtype=torch.float64)
+    pg, msg = p0.clone().to(dev), torch.ones(n, device=dev)
+    for g in grads:
+        p, ms = _rms_ref(p, ms, g, 0.5, CLIP)
+        abi.rmsprop_step(pg, g.to(dev), msg, gs=0.5, clip=CLIP)
+    close(pg, p, tol, 'rmsprop param n=%d' % n); close(msg, ms, tol, 'rmsprop ms n=%d' % n)
+
+
+def case_optimizers_unaligned(abi, tol):
+    """adam_k / rmsprop_k on views that do not start on a 16-byte boundary (`al == false`: everything through the scalar loop):
+    all of p, g and the slots one element past a boundary, then g alone.  The element in front of every view and the one behind
+    it hold a sentinel that must survive."""
+    dev = abi.device
+    n = 10007
+    p0, g0 = randn((n,), 1550, 0.02), randn((n,), 1551, 0.1)
+    m0, v0 = randn((n,), 1552, 0.01), randn((n,), 1553, 0.01).abs()
+    for leads in ({'p': 1, 'g': 1, 'm': 1, 'v': 1}, {'p': 8, 'g': 1, 'm': 8, 'v': 8}):
+        tag = 'unaligned %s' % ('p, g, slots' if leads['p'] == 1 else 'g only')
+        bufs = {k: _guarded(t, leads[k], dev) for k, t in (('p', p0), ('g', g0), ('m', m0), ('v', v0))}
+        assert any(bufs[k][1].data_ptr() % 16 for k in bufs), 'test premise: a view off the 16-byte boundary'
+        step = torch.zeros(1, dtype=torch.int32, device=dev)
+        abi.adam_step(bufs['p'][1], bufs['g'][1], bufs['m'][1], bufs['v'][1], step, gs=0.5, clip=CLIP)
+        abi.sync()
+        p, m, v = _adam_ref(p0.double(), m0.double(), v0.double(), g0, 1, 0.5, CLIP)
+        close(bufs['p'][1], p, tol, 'adam param ' + tag); close(bufs['m'][1], m, tol, 'adam m ' + tag); close(bufs['v'][1], v, tol, 'adam v ' + tag)
+        assert torch.equal(bufs['g'][1].cpu(), g0), 'adam changed its gradient ' + tag
+        for k in bufs:
+            _guards_intact(bufs[k][0], leads[k], 'adam %s %s' % (k, tag))
+        bufs = {k: _guarded(t, leads[k], dev) for k, t in (('p', p0), ('g', g0), ('m', v0 + 1.0))}
+        abi.rmsprop_step(bufs['p'][1], bufs['g'][1], bufs['m'][1], gs=0.5, clip=CLIP)
+        abi.sync()
+        p, ms = _rms_ref(p0.double(), (v0 + 1.0).double(), g0, 0.5, CLIP)
+        close(bufs['p'][1], p, tol, 'rmsprop param ' + tag); close(bufs['m'][1], ms, tol, 'rmsprop ms ' + tag)
+        for k in bufs:
+            _guards_intact(bufs[k][0], leads[k], 'rmsprop %s %s' % (k, tag))
+
+
+def case_adam_late_steps(abi, tol):
+    """Adam far into training: the device step counter preset so that the steps taken are t = 1000 and t = 200,000 (1 - b^t from
+    double-precision pow of the float32-rounded betas, as the kernel and TensorFlow take it)."""
+    dev = abi.device
+    n = 1027
+    p0, g0 = randn((n,), 1560, 0.02), randn((n,), 1561, 0.1)
+    m0, v0 = randn((n,), 1562, 0.01), randn((n,), 1563, 0.01).abs()
+    for t in (1000, 200000):
+        pg, mg, vg = p0.clone().to(dev), m0.clone().to(dev), v0.clone().to(dev)
+        step = torch.full((1,), t - 1, dtype=torch.int32, device=dev)
+        abi.adam_step(pg, g0.to(dev), mg, vg, step)
+        assert step.item() == t
+        p, m, v = _adam_ref(p0.double(), m0.double(), v0.double(), g0, t, 1.0, None)
+        assert float((p - p0.double()).abs().max()) > 0
+        close(pg, p, tol, 'adam param t=%d' % t); close(mg, m, tol, 'adam m t=%d' % t); close(vg, v, tol, 'adam v t=%d' % t)
+        close(pg.double().cpu() - p0.double(), p - p0.double(), tol * 4, 'adam update t=%d' % t)
+
+
+def case_clip_strided(abi):
+    """acg_clip at 2048 x 256 + 257 elements, and beyond its own grid cap (optim.hip grid_for: 4096 blocks x 256 threads, one
+    element each), where clip_k's grid-stride loop runs."""
+    for n, strided in ((2048 * 256 + 257, False), (4096 * 256 + 257, True)):
+        assert (n > 4096 * 256) == strided and n % 4 == 1, 'test premise: the second size exceeds the capped grid'
+        q = randn((n,), 1570, 0.05).to(abi.device)
+        ref = q.double().cpu().clamp(_f32(-0.01), _f32(0.01))
+        abi.clip(q, -0.01, 0.01)
+        close(q, ref, 1e-7, 'clip n=%d' % n)
+        assert torch.equal(q.cpu(), ref.float()), 'clip n=%d' % n
+
+
+# ---- plumbing: copies, so torch.equal; every destination starts at SENTINEL, pad channels and neighbours must keep it
+ELEMENTWISE_GRID = 2048 * 256      # elementwise.hip grid_for: at most 2048 blocks x 256 threads, one element each
+
+# (The 64-bit index branches of concat_k / slice_k need 2^31 elements - 8 GB in float32 - which no test of a few seconds can
+# hold, let alone check against a CPU reference; they stay unreached.)
+
+
+def _types(abi):
+    return [torch.float32, torch.bfloat16] if abi.device.type == 'cuda' else [torch.float32]
+
+
+def case_concat_actions_paths(abi):
+    """acg_concat_actions_fwd beyond the grid (stride loop), with the features already in y (x == NULL: tile_actions_k) and at
+    the degenerate sizes hw = 1, c = 1, a = 1; float32 dense and bfloat16 at the pitch round8(c + a)."""
+    dev = abi.device
+    for (b, h, w, c, a, strided_x, strided_null) in [(5, 32, 32, 96, 10, True, False), (3, 1, 1, 4, 1, False, False), (2, 7, 1, 1, 10, False, False),
+                                                      (6, 96, 96, 2, 10, True, True)]:
+        assert (b * h * w * (c + a) > ELEMENTWISE_GRID) == strided_x, 'test premise: concat_k stride loop'
+        assert (b * h * w * a > ELEMENTWISE_GRID) == strided_null, 'test premise: tile_actions_k stride loop'
+        x, act = randn((b, h, w, c), 1600), randn((b, a), 1601)
+        for dt in _types(abi):
+            r = r16 if dt == torch.bfloat16 else (lambda t: t)
+            pitch = (c + a + 7) // 8 * 8 if dt == torch.bfloat16 else c + a            # (96 + 10 channels: 112)
+            ref = torch.full((b, h, w, pitch), SENTINEL)
+            ref[..., :c] = r(x)
+            ref[..., c:c + a] = r(act).reshape(b, 1, 1, a).expand(b, h, w, a)
+            tag = 'concat_actions %s %s' % ((b, h, w, c, a), dt)
+            y = torch.full((b, h, w, pitch), SENTINEL, dtype=dt, device=dev)
+            abi.concat_actions(x.to(dev).to(dt), act.to(dev), pitch=0 if pitch == c + a else pitch, y=y)
+            assert torch.equal(y.float().cpu(), ref), tag
+            # x == NULL: the features were written in place by their producer and stay; only the actions are tiled in
+            y = torch.full((b, h, w, pitch), SENTINEL, dtype=dt, device=dev)
+            y[..., :c] = x.to(dev).to(dt)
+            abi.concat_actions(None, act.to(dev), pitch=0 if pitch == c + a else pitch, y=y, c=c)
+            assert torch.equal(y.float().cpu(), ref), tag + ' (x NULL)'
+
+
+def case_concat_slice_strided(abi, tol):
+    """acg_concat_channels_fwd and acg_slice_channels at 70,000 rows of 8 channels (beyond the grid: the stride loop)."""
+    dev = abi.device
+    rows, ca, cb, pitch = 70000, 3, 5, 8
+    assert rows * (ca + cb) > ELEMENTWISE_GRID, 'test premise: concat_k / slice_k stride loop'
+    a, b = randn((rows, ca), 1610), randn((rows, cb), 1611)
+    for dt in _types(abi):
+        r = r16 if dt == torch.bfloat16 else (lambda t: t)
+        tag = 'concat_channels f32 -> %s' % dt
+        y = abi.concat_channels(a.to(dev), b.to(dev), pitch=pitch, y=torch.full((rows, pitch), SENTINEL, dtype=dt, device=dev))
+        assert torch.equal(y.float().cpu(), r(torch.cat([a, b], dim=1))), tag
+        # a == NULL: channels [0, ca) keep what was there
+        y = abi.concat_channels(None, b.to(dev), pitch=pitch, y=torch.full((rows, pitch), SENTINEL, dtype=dt, device=dev), ca=ca)
+        assert torch.equal(y.float().cpu(), torch.cat([torch.full((rows, ca), SENTINEL), r(b)], dim=1)), tag + ' (a NULL)'
+        # cb == 0: re-pitching; the pad channels keep what was there
+        y = abi.concat_channels(a.to(dev), None, pitch=pitch, y=torch.full((rows, pitch), SENTINEL, dtype=dt, device=dev))
+        assert torch.equal(y.float().cpu(), torch.cat([r(a), torch.full((rows, pitch - ca), SENTINEL)], dim=1)), tag + ' (cb 0)'
+    # 8 channels from offset 5: of a pitch of 12 that range does not exist (5 + 8 > 12) and the call must say so; the slices run
+    # from the two nearest layouts that hold it - the same offset in a pitch of 16, and the same pitch from offset 4
+    from action_conditioned_gans_amd._lib import AcgError
+    cd, lead = 8, 8
+    assert rows * cd > ELEMENTWISE_GRID
+    with pytest.raises(AcgError):
+        abi.slice_channels(torch.zeros(rows, 12, device=dev), 5, cd)
+    for cs, off in ((16, 5), (12, 4)):
+        tag = 'slice_channels %d of %d from %d' % (cd, cs, off)
+        src = randn((rows, cs), 1612)
+        want = src[:, off:off + cd].contiguous()
+        buf, view = _guarded(torch.full((rows * cd,), SENTINEL), lead, dev)
+        abi.slice_channels(src.to(dev), off, cd, dst=view.view(rows, cd))
+        assert torch.equal(view.cpu().view(rows, cd), want), tag
+        _guards_intact(buf, lead, tag)
+        d0 = randn((rows, cd), 1613)
+        buf, view = _guarded(d0.reshape(-1), lead, dev)
+        abi.slice_channels(src.to(dev), off, cd, dst=view.view(rows, cd), accumulate=0.5)
+        close(view.view(rows, cd), 0.5 * d0.double() + want.double(), 1e-6, tag + ' accumulate 0.5')
+        _guards_intact(buf, lead, tag + ' accumulate')
+        if abi.device.type == 'cuda':
+            buf, view = _guarded(torch.full((rows * cd,), SENTINEL), lead, dev)
+            abi.slice_channels(src.to(dev).to(torch.bfloat16), off, cd, dst=view.view(rows, cd))
+            assert torch.equal(view.cpu().view(rows, cd), r16(want)), tag + ' bf16 -> f32'
+            _guards_intact(buf, lead, tag + ' bf16 -> f32')
+
+
+def case_add_paths(abi):
+    """acg_add: the scalar tail (n % 4 != 0), the unaligned branch (views one element past a boundary) and, in float32, more
+    groups of four than the grid has threads.  bfloat16: the float32 sum rounded once."""
+    dev = abi.device
+    big = 4 * ELEMENTWISE_GRID + 1027
+    assert big // 4 > ELEMENTWISE_GRID and big % 4 == 3 and 841 % 4 == 1
+    for dt in _types(abi):
+        r = r16 if dt == torch.bfloat16 else (lambda t: t)
+        for n, lead in [(841, 8), (841, 1)] + ([(big, 8)] if dt == torch.float32 else []):
+            u, v = r(randn((n,), 1620)), r(randn((n,), 1621))
+            tag = 'add %s n=%d %s' % (dt, n, 'aligned' if lead == 8 else 'unaligned')
+            (ub, uv), (vb, vv) = _guarded(u.to(dt), lead, dev), _guarded(v.to(dt), lead, dev)
+            yb, yv = _guarded(torch.full((n,), SENTINEL, dtype=dt), lead, dev)
+            assert (uv.data_ptr() % (4 * uv.element_size()) != 0) == (lead == 1), 'test premise: alignment to four elements'
+            abi.add(uv, vv, y=yv)
+            assert torch.equal(yv.float().cpu(), r(u + v)), tag
+            for bf, what in ((ub, 'a'), (vb, 'b'), (yb, 'y')):
+                _guards_intact(bf, lead, tag + ' ' + what)
+            assert torch.equal(uv.float().cpu(), u) and torch.equal(vv.float().cpu(), v), tag + ': an input changed'
+
+
+def case_copy_many_paths(abi):
+    """acg_copy_many in one launch: the thread-per-row path (cols <= 4 at a wider pitch) over more rows than the grid has
+    threads, float32 and bfloat16; a wider bfloat16 segment; a dense ragged segment from an unaligned source; and the tiled
+    branch (src_div / src_mod: the action vector over a feature map, shared by both halves of a joined batch) for both
+    destination types and without wrap."""
+    dev = abi.device
+    half = abi.device.type == 'cuda'
+    g = _rng(1630)
+    # (source rows, cols, destination rows, pitch, destination dtype, src_div, src_mod, source offset in elements)
+    specs = [(5000, 3, 5000, 8, torch.float32, 0, 0, 0),
+             (5000, 3, 5000, 8, torch.bfloat16, 0, 0, 0),
+             (3000, 6, 3000, 8, torch.bfloat16, 0, 0, 0),
+             (2051, 5, 2051, 5, torch.float32, 0, 0, 1),
+             (4, 10, 512, 12, torch.float32, 64, 4, 0),
+             (4, 10, 512, 12, torch.bfloat16, 64, 4, 0),
+             (8, 10, 512, 12, torch.float32, 64, 0, 0)]
+    if not half:
+        specs = [s for s in specs if s[4] == torch.float32]
+
+    def build(spec):
+        srows, cols, drows, pitch, dt, div, mod, soff = spec
+        flat = torch.randn(soff + srows * cols, generator=g).to(dev)
+        src = flat[soff:].view(srows, cols)
+        assert src.data_ptr() % 16 == (4 * soff) % 16
+        lead = 8
+        buf, view = _guarded(torch.full((drows * pitch,), SENTINEL, dtype=dt), lead, dev)
+        r = r16 if dt == torch.bfloat16 else (lambda t: t)
+        ref = torch.full((drows, pitch), SENTINEL)
+        idx = torch.arange(drows) // max(div, 1)
+        if mod:
+            idx = idx % mod
+        ref[:, :cols] = r(src.cpu())[idx]
+        return (src, view.view(drows, pitch), div, mod), buf, ref
+
+    def check(entries, which):
+        for i, (pair, buf, ref) in enumerate(entries):
+            assert torch.equal(pair[1].float().cpu(), ref), 'copy_many %s segment %d %s' % (which, i, specs[i])
+            _guards_intact(buf, 8, 'copy_many %s segment %d' % (which, i))
+
+    entries = [build(s) for s in specs]
+    abi.copy_many([e[0] for e in entries])
+    abi.sync()
+    check(entries, 'all')
+    # the 5000-row segment as the largest of its launch: the grid is sized from it (grid_for(rows * cols / 4 + 1) blocks of 256
+    # threads), and the thread-per-row loop has to stride
+    rows, cols = specs[0][0], specs[0][1]
+    threads = 256 * min(2048, (rows * cols // 4 + 1 + 255) // 256)
+    assert cols <= 4 and specs[0][3] != cols and rows > threads, 'test premise: more rows than threads on the thread-per-row path'
+    entries = [build(specs[0])] + ([build(specs[1])] if half else [])
+    abi.copy_many([e[0] for e in entries])
+    abi.sync()
+    check(entries, 'rows')
+
+
+def case_bias_paths(abi, tol):
+    """acg_bias_act_bwd accumulating into a seeded dbias; acg_bias_act_fwd / _bwd beyond 256 channels (a second ColMap chunk in
+    bn.hip) and with a channel count that leaves threads of the block idle (25: 250 of 256 lanes)."""
+    dev = abi.device
+    acts = {'tanh': torch.tanh, 'relu': T.relu, 'lrelu': T.lrelu, None: lambda t: t}
+    for lead, c, act, acc in [((2, 64, 64), 3, 'tanh', 0.5), ((2, 5, 3), 7, 'lrelu', 0.5), ((4, 3, 3), 300, 'lrelu', 0.0), ((4, 3, 3), 300, None, 0.5),
+                              ((700, 1, 1), 25, 'tanh', 0.0), ((700, 1, 1), 25, 'relu', 0.5)]:
+        if c == 300:
+            assert c > 256, 'test premise: more channels than one ColMap chunk (bn.hip col_map: Cb = 256)'
+        x = randn(lead + (c,), 1640)
+        bias = randn((c,), 1641, 0.5)
+        xd, bd = x.double().requires_grad_(True), bias.double().requires_grad_(True)
+        y_ref = acts[act](xd + bd)
+        dy = randn(tuple(y_ref.shape), 1642)
+        dx_ref, db_ref = torch.autograd.grad(y_ref, [xd, bd], dy.double())
+        tag = 'bias %s x %d %s acc %g' % (lead, c, act, acc)
+        y = abi.bias_act_fwd(x.to(dev), bias.to(dev), act)
+        close(y, y_ref, tol, tag + ' fwd')
+        db0 = randn((c,), 1643, float(db_ref.abs().mean()))
+        dx, db = abi.bias_act_bwd(y, dy.to(dev), act, want_dx=True, dbias=db0.clone().to(dev), accumulate=acc)
+        close(dx, dx_ref, tol * 4, tag + ' dx')
+        close(db, acc * db0.double() + db_ref, tol * 4, tag + ' dbias')
+        if act is None:
+            _, db2 = abi.bias_act_bwd(y, dy.to(dev), act, want_dx=False, dbias=db0.clone().to(dev), accumulate=acc)
+            close(db2, acc * db0.double() + db_ref, tol * 4, tag + ' dbias (dx NULL)')

@@ -384,6 +384,67 @@ def test_optimizers(hip_abi):
     C.case_optimizers(hip_abi, TOL)
 
 
+# ---- loss.hip, optim.hip, elementwise.hip and the bias kernels of bn.hip beyond the one branch the cases above take: grid-stride
+# loops, scalar tails, unaligned views, the tiled / x == NULL / accumulate variants (op_cases.py states each premise)
+@pytest.mark.parametrize('shape,grid', C.FRAME_EXACT_CASES, ids=str)
+def test_frame_loss_exact(hip_abi, shape, grid):
+    C.case_frame_loss_exact(hip_abi, shape, grid)
+
+
+@pytest.mark.parametrize('n', C.HEAD_SIZES)
+def test_loss_heads_sizes(hip_abi, n):
+    C.case_loss_heads(hip_abi, TOL, n)
+
+
+def test_loss_heads_reject_more_than_65536(hip_abi):
+    C.case_loss_heads_reject(hip_abi)
+
+
+def test_state_loss_global(hip_abi):
+    C.case_state_loss_global(hip_abi, TOL)
+
+
+def test_psnr_strided(hip_abi):
+    C.case_psnr_strided(hip_abi, TOL)
+
+
+@pytest.mark.parametrize('n', C.OPT_SIZES)
+def test_optimizers_sizes(hip_abi, n):
+    C.case_optimizers_sizes(hip_abi, TOL, n)
+
+
+def test_optimizers_unaligned(hip_abi):
+    C.case_optimizers_unaligned(hip_abi, TOL)
+
+
+def test_adam_late_steps(hip_abi):
+    C.case_adam_late_steps(hip_abi, TOL)
+
+
+def test_clip_strided(hip_abi):
+    C.case_clip_strided(hip_abi)
+
+
+def test_concat_actions_paths(hip_abi):
+    C.case_concat_actions_paths(hip_abi)
+
+
+def test_concat_slice_strided(hip_abi):
+    C.case_concat_slice_strided(hip_abi, TOL)
+
+
+def test_add_paths(hip_abi):
+    C.case_add_paths(hip_abi)
+
+
+def test_copy_many_paths(hip_abi):
+    C.case_copy_many_paths(hip_abi)
+
+
+def test_bias_paths(hip_abi):
+    C.case_bias_paths(hip_abi, TOL)
+
+
 def test_error_reporting(hip_abi):
     """Bad arguments come back as a non-zero code + message, never a launch."""
     import torch

@@ -100,6 +100,67 @@ def test_optimizers(oracle_abi):
     C.case_optimizers(oracle_abi, TOL)
 
 
+# ---- the loss, optimizer, plumbing and bias entries at every path the HIP kernels have (the same cases as tests/test_gpu_ops.py:
+# here they prove that the float64 references and the C restatement agree before any kernel is asked)
+@pytest.mark.parametrize('shape,grid', C.FRAME_EXACT_CASES, ids=str)
+def test_frame_loss_exact(oracle_abi, shape, grid):
+    C.case_frame_loss_exact(oracle_abi, shape, grid)
+
+
+@pytest.mark.parametrize('n', C.HEAD_SIZES)
+def test_loss_heads_sizes(oracle_abi, n):
+    C.case_loss_heads(oracle_abi, TOL, n)
+
+
+def test_loss_heads_reject_more_than_65536(oracle_abi):
+    C.case_loss_heads_reject(oracle_abi)
+
+
+def test_state_loss_global(oracle_abi):
+    C.case_state_loss_global(oracle_abi, TOL)
+
+
+def test_psnr_strided(oracle_abi):
+    C.case_psnr_strided(oracle_abi, TOL)
+
+
+@pytest.mark.parametrize('n', C.OPT_SIZES)
+def test_optimizers_sizes(oracle_abi, n):
+    C.case_optimizers_sizes(oracle_abi, TOL, n)
+
+
+def test_optimizers_unaligned(oracle_abi):
+    C.case_optimizers_unaligned(oracle_abi, TOL)
+
+
+def test_adam_late_steps(oracle_abi):
+    C.case_adam_late_steps(oracle_abi, TOL)
+
+
+def test_clip_strided(oracle_abi):
+    C.case_clip_strided(oracle_abi)
+
+
+def test_concat_actions_paths(oracle_abi):
+    C.case_concat_actions_paths(oracle_abi)
+
+
+def test_concat_slice_strided(oracle_abi):
+    C.case_concat_slice_strided(oracle_abi, TOL)
+
+
+def test_add_paths(oracle_abi):
+    C.case_add_paths(oracle_abi)
+
+
+def test_copy_many_paths(oracle_abi):
+    C.case_copy_many_paths(oracle_abi)
+
+
+def test_bias_paths(oracle_abi):
+    C.case_bias_paths(oracle_abi, TOL)
+
+
 # ---- pinning the restatement itself: hand-computed values and the published TF-1.0 index algebra --------
 def test_same_padding_known_answers():
     """TF 'SAME': out = ceil(in / s), pad_total = max((out-1) s + k - in, 0), pad_before = pad_total // 2 (A.1)."""
