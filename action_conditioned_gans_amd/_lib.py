@@ -189,6 +189,18 @@ BN_INFER_SIGNATURES = {
     'acg_bn_collect': (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
 }
 
+# include/acgan_ema.h: the exponential moving average of a scope's weights - the stand-alone update, the optimizer steps that
+# carry it in their own launch, and the in-place exchange of two flat buffers; an addition under ABI version 8 bound as a table
+# of its own like BN_INFER_SIGNATURES (the C oracle does not implement it: optim.StepOp raises a RuntimeError there)
+EMA_SIGNATURES = {
+    'acg_ema_update': (c_int32, [_P, _P, c_int64, c_float, _P, _P, _P]),
+    'acg_adam_step_ema': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float,
+                                    c_int32, c_float, c_float, _P, c_float, _P, _P, _P]),
+    'acg_rmsprop_step_ema': (c_int32, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float,
+                                       c_float, _P, c_float, _P, _P, _P]),
+    'acg_swap_f32': (c_int32, [_P, _P, c_int64, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -255,7 +267,8 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES, **BN_INFER_SIGNATURES))
+        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES, **BN_INFER_SIGNATURES,
+                                              **EMA_SIGNATURES))
     return _LIB
 
 

@@ -6,7 +6,9 @@
 
 #include <algorithm>
 
+#include "../../include/acgan_ema.h"
 #include "common.h"
+#include "ema_common.h"
 
 namespace {
 
@@ -100,6 +102,103 @@ __global__ __launch_bounds__(256) void rmsprop_k(float* __restrict__ p, const fl
   }
   for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
     rms1(p[i], g[i], ms[i], lr, decay, eps, gs, use_clip, lo, hi);
+}
+
+// ---- the optimizer update carrying the weight average's (include/acgan_ema.h) ------------------------------------------------
+// adam_k / rmsprop_k with the shadow element updated from the new parameter while it is still in a register: one launch instead
+// of two, and the average costs a read and a write of the shadow instead of those plus a second read of the parameters.  The
+// same adam1 / rms1 / ema1 as the kernels they replace: parameters and slots as adam_k / rmsprop_k leave them, the shadow as
+// ema_update_k behind them does.  The prologue thread derives both the learning rate and the average's coefficient.
+__global__ __launch_bounds__(256) void adam_ema_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, const int* __restrict__ step, long long n, float lr,
+                                                  float b1, float b2, float eps, float gs, int use_clip, float lo, float hi,
+                                                  float* __restrict__ sh, float ema_decay, long long* num_updates, unsigned* done) {
+  __shared__ float s_lr_t;
+  __shared__ acg_ema::Coef s_c;
+  const long long stride = (long long)gridDim.x * 256;
+  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                    reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(sh)) & 15) == 0;
+  const long long n4 = al ? n / 4 : 0;
+  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool have = i0 < n4;
+  float4 pp, mm, vv, gg, ss;
+  if (have) {
+    pp = reinterpret_cast<float4*>(p)[i0]; mm = reinterpret_cast<float4*>(m)[i0]; vv = reinterpret_cast<float4*>(v)[i0];
+    gg = reinterpret_cast<const float4*>(g)[i0]; ss = reinterpret_cast<float4*>(sh)[i0];
+  }
+  long long k = 0;
+  if (threadIdx.x == 0) {
+    const int t = *step;
+    s_lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
+    s_c = acg_ema::coef(num_updates, ema_decay, &k);
+  }
+  __syncthreads();
+  const float lr_t = s_lr_t, omd = s_c.omd;
+  const int seed = s_c.seed;
+  auto four = [&](long long i) {
+    adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
+    adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
+    adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
+    adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
+    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
+    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
+    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(m)[i] = mm; reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(sh)[i] = ss;
+  };
+  if (have) four(i0);
+  for (long long i = i0 + stride; i < n4; i += stride) {
+    pp = reinterpret_cast<float4*>(p)[i]; mm = reinterpret_cast<float4*>(m)[i]; vv = reinterpret_cast<float4*>(v)[i];
+    gg = reinterpret_cast<const float4*>(g)[i]; ss = reinterpret_cast<float4*>(sh)[i];
+    four(i);
+  }
+  for (long long i = n4 * 4 + i0; i < n; i += stride) {
+    adam1(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps, gs, use_clip, lo, hi);
+    sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
+  }
+  if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
+}
+
+__global__ __launch_bounds__(256) void rmsprop_ema_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms,
+                                                     long long n, float lr, float decay, float eps, float gs, int use_clip,
+                                                     float lo, float hi, float* __restrict__ sh, float ema_decay,
+                                                     long long* num_updates, unsigned* done) {
+  __shared__ acg_ema::Coef s_c;
+  const long long stride = (long long)gridDim.x * 256;
+  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(ms) |
+                    reinterpret_cast<uintptr_t>(sh)) & 15) == 0;
+  const long long n4 = al ? n / 4 : 0;
+  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool have = i0 < n4;
+  float4 pp, qq, gg, ss;
+  if (have) {
+    pp = reinterpret_cast<float4*>(p)[i0]; qq = reinterpret_cast<float4*>(ms)[i0];
+    gg = reinterpret_cast<const float4*>(g)[i0]; ss = reinterpret_cast<float4*>(sh)[i0];
+  }
+  long long k = 0;
+  if (threadIdx.x == 0) s_c = acg_ema::coef(num_updates, ema_decay, &k);
+  __syncthreads();
+  const float omd = s_c.omd;
+  const int seed = s_c.seed;
+  auto four = [&](long long i) {
+    rms1(pp.x, gg.x, qq.x, lr, decay, eps, gs, use_clip, lo, hi);
+    rms1(pp.y, gg.y, qq.y, lr, decay, eps, gs, use_clip, lo, hi);
+    rms1(pp.z, gg.z, qq.z, lr, decay, eps, gs, use_clip, lo, hi);
+    rms1(pp.w, gg.w, qq.w, lr, decay, eps, gs, use_clip, lo, hi);
+    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
+    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
+    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(ms)[i] = qq; reinterpret_cast<float4*>(sh)[i] = ss;
+  };
+  if (have) four(i0);
+  for (long long i = i0 + stride; i < n4; i += stride) {
+    pp = reinterpret_cast<float4*>(p)[i]; qq = reinterpret_cast<float4*>(ms)[i];
+    gg = reinterpret_cast<const float4*>(g)[i]; ss = reinterpret_cast<float4*>(sh)[i];
+    four(i);
+  }
+  for (long long i = n4 * 4 + i0; i < n; i += stride) {
+    rms1(p[i], g[i], ms[i], lr, decay, eps, gs, use_clip, lo, hi);
+    sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
+  }
+  if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
 }
 
 __global__ __launch_bounds__(256) void clip_k(float* __restrict__ p, long long n, float lo, float hi) {
@@ -241,6 +340,36 @@ int32_t acg_rmsprop_step(float* param, const float* grad, float* ms, int64_t n, 
   ACG_LAUNCH(rmsprop_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, ms,
                      (long long)n, lr, decay, eps, grad_scale, use_clip, clip_lo, clip_hi);
   return acg::check_launch("rmsprop_step");
+}
+
+#define ACG_EMA_REQUIRE(who)                                                                                                          \
+  do {                                                                                                                                \
+    ACG_REQUIRE(shadow && num_updates && state, ACG_ERR_INVALID_ARG, who ": null shadow / counter / state word");                        \
+    ACG_REQUIRE(ema_decay > 0.f && ema_decay < 1.f, ACG_ERR_INVALID_ARG, who ": decay %g is not in (0, 1)", (double)ema_decay);       \
+    ACG_REQUIRE((reinterpret_cast<uintptr_t>(num_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(state) & 3) == 0,                 \
+                ACG_ERR_INVALID_ARG, who ": the counter must be 8-byte and the state word 4-byte aligned");                           \
+  } while (0)
+
+int32_t acg_adam_step_ema(float* param, const float* grad, float* m, float* v, const int32_t* step_dev, int64_t n, float lr,
+                          float beta1, float beta2, float eps, float grad_scale, int32_t use_clip, float clip_lo, float clip_hi,
+                          float* shadow, float ema_decay, int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
+  ACG_REQUIRE(n > 0 && param && grad && m && v && step_dev, ACG_ERR_INVALID_ARG, "adam_step_ema: bad argument");
+  ACG_EMA_REQUIRE("adam_step_ema");
+  ACG_LAUNCH(adam_ema_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, m, v, step_dev,
+                     (long long)n, lr, beta1, beta2, eps, grad_scale, use_clip, clip_lo, clip_hi, shadow, ema_decay,
+                     reinterpret_cast<long long*>(num_updates), reinterpret_cast<unsigned*>(state));
+  return acg::check_launch("adam_step_ema");
+}
+
+int32_t acg_rmsprop_step_ema(float* param, const float* grad, float* ms, int64_t n, float lr, float decay, float eps,
+                             float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, float* shadow, float ema_decay,
+                             int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
+  ACG_REQUIRE(n > 0 && param && grad && ms, ACG_ERR_INVALID_ARG, "rmsprop_step_ema: bad argument");
+  ACG_EMA_REQUIRE("rmsprop_step_ema");
+  ACG_LAUNCH(rmsprop_ema_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, ms,
+                     (long long)n, lr, decay, eps, grad_scale, use_clip, clip_lo, clip_hi, shadow, ema_decay,
+                     reinterpret_cast<long long*>(num_updates), reinterpret_cast<unsigned*>(state));
+  return acg::check_launch("rmsprop_step_ema");
 }
 
 int32_t acg_clip(float* param, int64_t n, float lo, float hi, acg_stream_t stream) {

@@ -12,6 +12,11 @@ repeating its last sequence and the padded rows enter no sum.
 OUTPUT/metrics.json: the checkpoint, sequences, steps, the SSIM definition, per step the mean SSIM over sequences and the PSNR
 of the whole set by the reference's formula (10 log10(1 / MSE), MSE over all sequences' frames of that step - for a single
 batch the train loop's ``rollout_psnr``), the same two curves for the identity baseline, and the rollout rate in frames/s.
+
+``--weights ema``: predict with the moving average of the generator weights that a run trained with ``--g_ema`` keeps in its
+checkpoints (``state:g/ema/shadow``): after the restore the average is COPIED into the variables (with ``--bn_stats calibrate``
+before calibrating, so that OUTPUT/calibrated.npz restores to the same weights again); metrics.json then also holds ``weights``
+and ``ema_updates``.  ``raw`` (default): the weights as trained.
 """
 import argparse
 import json
@@ -21,6 +26,7 @@ import time
 import numpy as np
 
 ACTION_DIM = 10
+EMA_BUILD_DECAY = 0.999      # evaluation only reads the average: the decay its graph is built with is never applied
 
 
 def load_frames(path):
@@ -95,10 +101,21 @@ def _calibration_pairs(input_path, actions_path, pair_batch, img_size, seq_len, 
             return
 
 
+def _use_ema_weights(trainer, ckpt):
+    """--weights ema, after the restore: the averaged weights into the variables; -> the average's update count."""
+    updates = trainer.ema_updates()
+    if updates < 1:
+        raise ValueError('--weights ema: checkpoint %s holds no generator weight average (no state:g/ema/shadow, or 0 updates): '
+                         'train with --g_ema' % os.path.abspath(ckpt))
+    trainer.load_ema_weights()
+    return updates
+
+
 def calibrate(ckpt, save_prefix, input_path, actions_path, transform, ksize, img_size, dtype, pair_batch, num_batches, seq_len, device,
-              num_masks):
+              num_masks, weights='raw'):
     """Restore ``ckpt`` into a generator built at batch ``pair_batch``, pool its BatchNorm statistics over ``num_batches`` batches
-    of one-step pairs of ``input_path`` (Trainer.calibrate_bn) and save everything as ``save_prefix``.npz.  -> pairs pooled."""
+    of one-step pairs of ``input_path`` (Trainer.calibrate_bn) and save everything as ``save_prefix``.npz.  -> pairs pooled.
+    ``weights='ema'``: calibrate (and save) the averaged weights (_use_ema_weights)."""
     from . import graph as G
     from .saver import Saver
     from .train import Trainer
@@ -106,9 +123,11 @@ def calibrate(ckpt, save_prefix, input_path, actions_path, transform, ksize, img
     sess = G.Session(device=device, dtype=dtype)
     try:
         trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=pair_batch, img_size=img_size, ksize=ksize, lookahead=False,
-                          num_masks=num_masks, bn_inference=True)
+                          num_masks=num_masks, bn_inference=True, **({'ema_decay': EMA_BUILD_DECAY} if weights == 'ema' else {}))
         sess.run(G.global_variables_initializer())
         Saver().restore(sess, ckpt)
+        if weights == 'ema':
+            _use_ema_weights(trainer, ckpt)
         trainer.reset_bn_statistics()
         rows = 0
         for frames, acts in _calibration_pairs(input_path, actions_path, pair_batch, img_size, seq_len, num_batches):
@@ -131,17 +150,20 @@ def set_psnr(sqerr, valid, count_per_frame):
 
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
              seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
-             calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None):
+             calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw'):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
     ``dna`` / ``cdna`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
     with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  ``bn_stats`` 'batch', 'stored' or 'calibrate' and the
     ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
+    ``weights``: 'raw' or 'ema' (module docstring); 'ema' on a checkpoint without an average is a ValueError.
     -> the metrics dict."""
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
     if bn_stats not in ('batch', 'stored', 'calibrate'):
         raise ValueError("bn_stats must be 'batch', 'stored' or 'calibrate', got %r" % (bn_stats,))
+    if weights not in ('raw', 'ema'):
+        raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
     if bn_stats == 'calibrate' and (calibrate_batch_size < 1 or calibrate_batches < 1):
         raise ValueError('calibrate_batch_size and calibrate_batches must be >= 1')
     transform = 'cdna' if cdna else dna
@@ -161,9 +183,11 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             calibrate_input, calibrate_actions = input_path, actions_path
         restore_from = os.path.join(output_path, 'calibrated')
         calibrate(ckpt, restore_from, calibrate_input, calibrate_actions, transform, ksize, img_size, dtype, calibrate_batch_size,
-                  calibrate_batches, seq_len, device, num_masks)
+                  calibrate_batches, seq_len, device, num_masks, **({'weights': weights} if weights == 'ema' else {}))
     stored = bn_stats != 'batch'
     extra = {'bn_inference': True} if stored else {}      # ('batch' builds exactly the graph it always built)
+    if weights == 'ema':
+        extra['ema_decay'] = EMA_BUILD_DECAY
     bn = 'stored' if stored else 'batch'
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
@@ -172,6 +196,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
                           num_masks=num_masks, **extra)
         sess.run(G.global_variables_initializer())
         Saver().restore(sess, restore_from)
+        ema_updates = _use_ema_weights(trainer, ckpt) if weights == 'ema' else None
         calibration_rows = trainer.bn_calibration_rows() if stored else None
         if stored and calibration_rows < 1:
             raise ValueError('--bn_stats stored: checkpoint %s holds no calibrated BatchNorm statistics (run --bn_stats calibrate first)'
@@ -224,6 +249,9 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         if stored:
             result['bn_statistics'] = bn_stats
             result['calibration_rows'] = int(calibration_rows)
+        if weights == 'ema':
+            result['weights'] = weights
+            result['ema_updates'] = int(ema_updates)
         with open(os.path.join(output_path, 'metrics.json'), 'w') as f:
             json.dump(result, f, indent=1)
         if dump:
@@ -282,6 +310,8 @@ def main(argv=None):
     parser.add_argument('--calibrate_batches', type=int, default=None, help='calibration batches (default 16)')
     parser.add_argument('--calibrate_input', type=str, default=None, help='source of the calibration pairs (default: INPUT)')
     parser.add_argument('--calibrate_actions', type=str, default=None, help='actions .npy of a --calibrate_input frames .npy')
+    parser.add_argument('--weights', type=str, default='raw', choices=['raw', 'ema'],
+                        help="the generator weights as trained, or their moving average (a checkpoint of a run trained with --g_ema)")
     args = parser.parse_args(argv)
     check_model_args(parser, args)
     check_bn_args(parser, args)
@@ -307,7 +337,8 @@ def main(argv=None):
                     img_size=args.img_size, dtype=args.dtype, batch_size=args.batch_size, seq_len=args.seq_len,
                     num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
                     cdna=args.cdna, num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
-                    calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions)
+                    calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions,
+                    **({'weights': args.weights} if args.weights != 'raw' else {}))
 
 
 if __name__ == '__main__':

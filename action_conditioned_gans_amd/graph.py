@@ -360,6 +360,7 @@ class Runtime:
         self.epilogue_stats = True
         self.epilogue_bias = True
         self.fuse_weight_refresh = True        # bf16: optimizer update + refresh of the bf16 filter copies in one launch (optim.StepOp)
+        self.fuse_ema = True                   # float32: a scope's weight average updated inside its optimizer launch (optim.StepOp)
         # `flags` of the BatchNorm entries (acgan_hip.h): ACG_BN_NO_GRID_EXCHANGE where two BatchNorm launches can overlap (Session
         # sets it with side_branches: two partially resident grid-exchange kernels would starve each other)
         self.bn_flags = 0
@@ -430,7 +431,7 @@ class Session:
 
     def __init__(self, device='cuda:0', graph=None, use_hip_graphs=True, lib=None,
                  world_size=1, rank=0, process_group=None, dtype='f32', pair_bwd=True, comm=None, slab_handoff=True, epilogue_stats=True, side_branches=False,
-                 epilogue_bias=True, fuse_weight_refresh=True, bn_grid_exchange=None):
+                 epilogue_bias=True, fuse_weight_refresh=True, bn_grid_exchange=None, fuse_ema=True):
         self.graph = graph or get_default_graph()
         dev = torch.device(device)
         if lib is None:
@@ -461,6 +462,8 @@ class Session:
         self.rt.epilogue_bias = bool(epilogue_bias)       # bias + activation of a transposed head layer in its epilogue (models.py:20-21)
         # the C-oracle stand-in library (CPU tests) implements float32 only: the fused entry is a bf16-pipeline entry
         self.rt.fuse_weight_refresh = bool(fuse_weight_refresh)
+        # False: the weight average (optim.WeightAverage) in a launch of its own behind the optimizer's (measurement: tools/bench_ema.py)
+        self.rt.fuse_ema = bool(fuse_ema)
         if dev.type == 'cuda':
             torch.cuda.set_device(dev)
         self.use_hip_graphs = use_hip_graphs and dev.type == 'cuda'

@@ -11,7 +11,8 @@ shape (train.py:91-102) and TensorFlow-1.0's update formulas.  ``mi
    compute stream in program order, or on a side HIP stream overlapping the rest of backward
    (``collectives='side'``; see DataParallel) - captured into the step's HIP graph either way; the
    optimizer step runs behind all of them;
-4. appends ONE fused update launch over the flat buffers (+ the weight clip when it is fetched with it).
+4. appends ONE fused update launch over the flat buffers (+ the weight clip when it is fetched with it); with ``ema=`` that
+   launch also updates the scope's weight average (WeightAverage).
 """
 import torch
 
@@ -88,18 +89,98 @@ class AllReduceOp(G.Op):
         return lambda s: comm.all_reduce(view)
 
 
+class WeightAverage:
+    """The exponential moving average of one scope's weights (tf.train.ExponentialMovingAverage(decay, num_updates)): what
+    ``Optimizer.minimize(..., ema=)`` takes.  Every StepOp given the same object updates the same average.
+
+    State - graph state (Graph.new_state), no variable, no part of a flat parameter / gradient buffer, no optimizer slot:
+    ``<scope>/ema/shadow`` float32 [total] with the layout of the scope's flat parameter buffer (float32 master weights in bf16
+    graphs too), ``<scope>/ema/num_updates`` int64 [1] on the device, and one unnamed 32-bit word (the retired-block count of
+    the in-launch counter advance, include/acgan_ema.h - unnamed, so no checkpoint holds it).
+
+    The update runs behind every parameter update, in the same program.  With k = the counter before it and p = the parameter
+    after the optimizer update (and the clip folded into it): k == 0: shadow = p; else d = min(decay, (1 + k) / (10 + k)) in
+    double and shadow -= float32(1 - d) * (shadow - p) in three float32 roundings; then the counter is k + 1.
+    DEVIATION from TensorFlow, which seeds the shadow with the variable's INITIAL value: here the first update copies the
+    updated parameter, so that a counter of 0 - after ``reset``, or after restoring a checkpoint written before the average
+    existed - starts cleanly from the weights as they stand.  The average never feeds back into training.
+
+    The state is created by ``build`` (at the latest when the first StepOp that carries it is compiled), not by the
+    constructor: a caller that builds more graph after ``minimize`` can create it last and leave every other op where it was."""
+
+    def __init__(self, decay, scope, graph=None):
+        d = float(decay)
+        if not 0.0 < d < 1.0 or not 0.0 < _f32(d) < 1.0:
+            raise ValueError('WeightAverage: decay must lie in (0, 1), got %r' % (decay,))
+        self.decay, self.scope, self.graph = _f32(d), scope, graph or G.get_default_graph()
+        self.shadow = self.num_updates = self.done = None
+
+    def build(self):
+        if self.shadow is None:
+            _, total, _ = self.graph.layout(self.scope)
+            self.shadow = self.graph.new_state((total,), 0.0, self.scope + '/ema/shadow')
+            self.num_updates = self.graph.new_state((1,), 0, self.scope + '/ema/num_updates', dtype=torch.int64)
+            self.done = self.graph.new_state((1,), 0, None, dtype=torch.int32)
+        return self
+
+    def tensors(self):
+        self.build()
+        return [self.shadow, self.num_updates, self.done]
+
+    def args(self):
+        """(shadow, decay, counter, state word): the tail of the acg_*_step_ema argument lists."""
+        return (_p(self.shadow.buf), self.decay, _p(self.num_updates.buf), _p(self.done.buf))
+
+
+def _ema_entry(rt, name):
+    """An entry of include/acgan_ema.h (_lib.EMA_SIGNATURES); a library without it (the C oracle) is a clear error."""
+    fn = getattr(rt.lib, name, None)
+    if fn is None:
+        from . import _lib
+        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_ema.h): the weight average runs on the HIP library only'
+                            % (getattr(rt.lib, 'path', rt.lib), name))
+    return fn
+
+
 class StepOp(G.Op):
-    """One fused optimizer launch over the flat buffers of a scope."""
+    """One fused optimizer launch over the flat buffers of a scope.  ``ema`` (a WeightAverage of the scope, or None): the
+    scope's weight average is updated from the new parameters behind the update -
+    float32 graph, Adam / RMSProp: inside the optimizer's launch (acg_adam_step_ema / acg_rmsprop_step_ema);
+    bf16 graph: acg_ema_update behind the update-and-refresh launch(es), which stay as they are;
+    where the fused entry is declined (an optimizer without one, Session(fuse_ema=False)): acg_ema_update behind the plain step."""
     is_optimizer_step = True
     joins_side = True        # reads every gradient of its scope, whichever stream produced it
 
-    def __init__(self, opt, scope, var_names, flat_param, flat_grad, slots, deps, grad_scale):
+    def __init__(self, opt, scope, var_names, flat_param, flat_grad, slots, deps, grad_scale, ema=None):
         super().__init__(flat_param.graph, opt.name + '/update', [flat_param, flat_grad] + slots, [], control_inputs=deps)
         self.opt, self.scope, self.var_names, self.grad_scale = opt, scope, list(var_names), grad_scale
         self.program_clip = None
-        self.extras = [t for t3 in flat_param.graph.weight_copies.get(scope, []) for t in t3[1:]]
+        self.ema = ema
+        self._copies = [t for t3 in flat_param.graph.weight_copies.get(scope, []) for t in t3[1:]]
+
+    @property
+    def extras(self):
+        """What the launch touches besides its inputs (the session materialises it): the bf16 filter copies, the average's state."""
+        return self._copies + (self.ema.tensors() if self.ema is not None else [])
 
     def bind(self, rt):
+        if self.ema is None:
+            return self._bind_update(rt)
+        ema, p = self.ema, self.inputs[0]
+        update = _ema_entry(rt, 'ema_update')
+        if not self.graph.weight_copies.get(self.scope) and getattr(rt, 'fuse_ema', True):
+            fused = self.opt._bind_step_ema(rt, self, self.program_clip, ema)
+            if fused is not None:
+                return fused
+        step = self._bind_update(rt)
+        args = (_p(ema.shadow.buf), _p(p.buf), p.numel, ema.decay, _p(ema.num_updates.buf), _p(ema.done.buf))
+
+        def launch(s):
+            step(s)
+            update(*args, s)
+        return launch
+
+    def _bind_update(self, rt):
         # bf16 pipeline: the conv kernels read bf16 copies of the filters, which follow the update.  Round 4: update and
         # refresh are ONE launch (acg_opt_step_prepare_bf16: the blocks that write a filter's copies update its elements) where
         # every copy of the scope fits one list; else two launches as before
@@ -155,6 +236,11 @@ class Optimizer:
     def _bind_step(self, rt, step_op, clip):
         raise NotImplementedError
 
+    def _bind_step_ema(self, rt, step_op, clip, ema):
+        """_bind_step with the weight average ``ema`` updated in the same launch, or None (declined: StepOp then runs the
+        stand-alone update behind _bind_step)."""
+        return None
+
     def _opt_args(self, rt, op, clip):
         """-> (kind, (lr, beta1 | decay, beta2, eps), slot1, slot2 | None, step counter | None, launch that must precede | None)"""
         raise NotImplementedError
@@ -187,8 +273,9 @@ class Optimizer:
         launch._keep = (oa, pl)
         return launch
 
-    def minimize(self, loss, var_list=None, slots_of=None):
-        """``slots_of``: the StepOp of an earlier ``minimize`` by an optimizer of this kind over the same scope; this update then
+    def minimize(self, loss, var_list=None, slots_of=None, ema=None):
+        """``ema``: a WeightAverage of the variables' scope; the update then also advances it (StepOp).
+        ``slots_of``: the StepOp of an earlier ``minimize`` by an optimizer of this kind over the same scope; this update then
         continues that one's state (moments, step counter) instead of owning slots of its own - a second loss of one training
         run (train.Trainer's rollout G step continues the one-step G step's optimizer, and checkpoints hold one set of slots)."""
         if not isinstance(loss, O.Scalar):
@@ -202,6 +289,8 @@ class Optimizer:
         if len(scopes) != 1:
             raise ValueError('minimize: var_list must come from one top-level scope, got %s' % sorted(scopes))
         scope = scopes.pop()
+        if ema is not None and (ema.scope != scope or ema.graph is not g):
+            raise ValueError('minimize: ema averages scope %r, the variables are of scope %r' % (ema.scope, scope))
         offsets, total, flat_param = g.layout(scope)
         flat_grad = g.new_state((total,), 0.0, self.name + '/flat_grad')
         heads = {}
@@ -225,7 +314,7 @@ class Optimizer:
             slots = list(slots_of.inputs[2:])
         else:
             slots = self._make_slots(g, total)
-        step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size)
+        step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size, ema=ema)
         step_op.reduce_ops = reduce_ops        # one of them can carry the step counter's increment (_step_inc_launch)
         return step_op
 
@@ -316,6 +405,19 @@ class AdamOptimizer(Optimizer):
             adam(*args, s)
         return launch
 
+    def _bind_step_ema(self, rt, op, clip, ema):
+        p, g, m, v, step = op.inputs
+        lo, hi = clip if clip else (0.0, 0.0)
+        adam, before = _ema_entry(rt, 'adam_step_ema'), self._step_inc_launch(rt, op, step)
+        args = (_p(p.buf), _p(g.buf), _p(m.buf), _p(v.buf), _p(step.buf), p.numel, self.lr, self.b1, self.b2, self.eps,
+                op.grad_scale, 1 if clip else 0, lo, hi) + ema.args()
+
+        def launch(s):
+            if before is not None:
+                before(s)
+            adam(*args, s)
+        return launch
+
     def _opt_args(self, rt, op, clip):
         p, g, m, v, step = op.inputs
         return 0, (self.lr, self.b1, self.b2, self.eps), m, v, step, self._step_inc_launch(rt, op, step)
@@ -339,6 +441,14 @@ class RMSPropOptimizer(Optimizer):
         args = (_p(p.buf), _p(g.buf), _p(ms.buf), p.numel, self.lr, self.decay, self.eps, op.grad_scale,
                 1 if clip else 0, lo, hi)
         fn = rt.lib.rmsprop_step
+        return lambda s: fn(*args, s)
+
+    def _bind_step_ema(self, rt, op, clip, ema):
+        p, g, ms = op.inputs
+        lo, hi = clip if clip else (0.0, 0.0)
+        args = (_p(p.buf), _p(g.buf), _p(ms.buf), p.numel, self.lr, self.decay, self.eps, op.grad_scale,
+                1 if clip else 0, lo, hi) + ema.args()
+        fn = _ema_entry(rt, 'rmsprop_step_ema')
         return lambda s: fn(*args, s)
 
     def _opt_args(self, rt, op, clip):

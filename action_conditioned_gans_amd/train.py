@@ -12,6 +12,7 @@ optional in ``test``; D6 update -> clip; D7 eval uses its own states; D8 boolean
 ``--adv`` and ``--adv True|False``; D9 ksize is a parameter (default 5).
 """
 import argparse
+import contextlib
 import json
 import os
 import time
@@ -38,7 +39,7 @@ ACTION_DIM, STATE_DIM = 10, 5
 
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
-                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False):
+                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -53,7 +54,15 @@ class Trainer:
         ``bn_inference`` (no reference counterpart; False builds nothing more): also builds a calibration instance and a
         stored-statistics instance of the generator on the same variables (_build_bn_inference) - ``calibrate_bn`` pools the
         BatchNorm moments of the batches it is shown, and ``test`` / ``test_sequence`` / ``rollout_metrics`` with ``bn='stored'``
-        predict with them: a row's prediction then depends on no other row of its batch."""
+        predict with them: a row's prediction then depends on no other row of its batch.
+        ``ema_decay`` (no reference counterpart; 0 builds nothing more; else 0 < ema_decay < 1): every G parameter update -
+        ``pretrain_g``, ``train_g`` and the two rollout steps - also advances ONE exponential moving average of the generator's
+        weights (optim.WeightAverage: TF-1.0's ExponentialMovingAverage with its num_updates warm-up, seeded by the first
+        update), inside the same program.  The average never feeds back into training: parameters, slots and frames are those of
+        the run without it.  ``ema_weights()`` predicts with it; ``test`` / ``test_sequence`` / ``rollout_metrics`` take
+        ``weights='ema'``.  Only the generator is averaged.  Rank-local and elementwise: allowed with every generator, with
+        rollout_steps > 1, in bf16 graphs (the average is of the float32 master weights) and with more than one rank."""
+        ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.sess = sess
         self.model = model_kind(arg_transform)
         dp = G.get_default_graph().collections.get('data_parallel')
@@ -173,8 +182,10 @@ class Trainer:
             make = lambda name: optim.AdamOptimizer(ADAM_LR, name=name)
         else:
             raise ValueError('unexpected opt argument')
-        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars)
-        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars)
+        self.ema = optim.WeightAverage(ema_decay, 'g') if ema_decay else None      # shared by every G update of this Trainer
+        self._ema_swapped = False
+        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema)
+        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema)
         self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars)
 
         # the seven tf.summary scalars of ops.py:48-49 / train.py:104-111, names kept
@@ -200,6 +211,77 @@ class Trainer:
         self.bn_inference = bool(bn_inference)
         if self.bn_inference:
             self._build_bn_inference(build_g)
+        if self.ema is not None:
+            self.ema.build()        # last: every op of the graph keeps the place it has without the average
+
+    # ---- the generator's weight average (ema_decay > 0)
+    def _require_ema(self):
+        if self.ema is None:
+            raise RuntimeError('this Trainer was built without ema_decay: it keeps no average of the generator weights')
+
+    def ema_updates(self):
+        """Updates the average has seen (0: the shadow holds nothing yet); reads the device-side counter."""
+        self._require_ema()
+        return int(self.sess._materialize(self.ema.num_updates).item())
+
+    def ema_statistics(self):
+        """-> {variable name: numpy array}: the averaged value of every generator variable (the shadow buffer by ``layout``)."""
+        self._require_ema()
+        offsets = self.ema.graph.layout('g')[0]
+        shadow = self.sess._materialize(self.ema.shadow).detach().cpu().numpy()
+        return {v.name: shadow[offsets[v.name]:offsets[v.name] + v.numel].reshape(v.shape).copy() for v in self.g_vars}
+
+    def reset_ema(self):
+        """Counter back to 0: the next G update seeds the shadow with the weights it leaves."""
+        self._require_ema()
+        self.sess._materialize(self.ema.num_updates).zero_()
+
+    def _ema_buffers(self):
+        self._require_ema()
+        if self.ema_updates() < 1:
+            raise RuntimeError('the weight average has seen 0 updates: there are no averaged weights to predict with')
+        flat = self.ema.graph.layout('g')[2]
+        return self.sess._materialize(flat), self.sess._materialize(self.ema.shadow)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the generator's variables hold the averaged weights and the shadow holds the raw ones: ONE launch
+        exchanges the two flat buffers (programs are captured with their pointers, so the data moves), and a bf16 session
+        refreshes its filter copies before its next program.  On exit they are exchanged back, bit for bit.  Predict inside;
+        a G update inside would train the average and average the training weights.  Raises when the Trainer keeps no average
+        or it has seen no update."""
+        flat, shadow = self._ema_buffers()
+        if self._ema_swapped:
+            raise RuntimeError('ema_weights() is already entered')
+        swap = optim._ema_entry(self.sess.rt, 'swap_f32')
+        args = (optim._p(flat), optim._p(shadow), flat.numel())
+
+        def exchange():
+            swap(*args, self.sess.rt.stream_ptr())
+            self.sess._weights_dirty = True
+            self._announced = None           # (a prepared generator pass was computed with the other weights)
+        exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            exchange()
+            self._ema_swapped = False
+
+    def load_ema_weights(self):
+        """COPY the averaged weights into the generator's variables (the shadow keeps them too): what a session that only
+        predicts wants - a checkpoint saved afterwards restores to the same weights whichever of the two it reads."""
+        flat, shadow = self._ema_buffers()
+        flat.copy_(shadow)
+        self.sess._weights_dirty = True
+        self._announced = None
+
+    def _check_weights(self, weights):
+        if weights not in ('raw', 'ema'):
+            raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
+        if weights == 'ema':
+            self._require_ema()
+        return weights == 'ema'
 
     def _build_bn_inference(self, build_g):
         """Two more generator instances on the existing variables and placeholders (the modes arrive through the arg scope of
@@ -310,9 +392,9 @@ class Trainer:
                 img = frame
                 act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
         total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
-        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op)
+        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op, ema=self.ema)
         self.g_rollout_pretrain_opt_op = make('g_pretrain_opt_rollout').minimize(l2_total / K, var_list=self.g_vars,
-                                                                                slots_of=self.g_pretrain_opt_op)
+                                                                                slots_of=self.g_pretrain_opt_op, ema=self.ema)
 
     def _rollout_feed(self, frames, actions, states):
         """frames [B, K+1, H, W, 3] (t .. t+K), actions [B, K, 10] (a_t .. a_{t+K-1}, state half read at step 0 only by the DNA
@@ -416,9 +498,13 @@ class Trainer:
         self.sess.run([self.d_opt_op, self.clip_d], fd)
         return None
 
-    def test(self, input_images, next_frame, actions, bn='batch'):
+    def test(self, input_images, next_frame, actions, bn='batch', weights='raw'):
         """``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
-        summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames)."""
+        summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames).
+        ``weights='ema'`` (a Trainer built with ``ema_decay``): the same call inside ``ema_weights()``."""
+        if self._check_weights(weights):
+            with self.ema_weights():
+                return self.test(input_images, next_frame, actions, bn=bn)
         self._announced = None
         if self._check_bn_mode(bn):
             has_state = self.g_state_stored is not None
@@ -431,7 +517,8 @@ class Trainer:
         gen_next_state = res[1] if self.g_state_out is not None else None      # defect D4
         return gen_next_frames, gen_next_state, self._named(summ)
 
-    def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None, bn='batch'):
+    def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None, bn='batch',
+                      weights='raw'):
         """Recursive rollout: feed each prediction (and predicted state) back in.
         ``device_loop`` (default: on for a GPU session): from the second step on the prediction and the predicted state stay on the
         device between steps - the program of those steps fetches nothing but the two, so it carries no loss ops either - and
@@ -444,7 +531,12 @@ class Trainer:
         ``literal=True``: the reference's method of this name exactly as written (train.py:157-176) - SIX steps, step j
         reads ``test_actions[:, 2 j, :5]`` and ``test_next_frame[:, 2 j]`` (the sequences must hold >= 11 frames),
         and the second return value is ``current_frame[1:7]``, samples 1..6 of the last prediction.
-        ``bn``: 'batch' (default: every step normalises with the statistics of its batch) or 'stored' (see ``test``)."""
+        ``bn``: 'batch' (default: every step normalises with the statistics of its batch) or 'stored' (see ``test``).
+        ``weights``: 'raw' or 'ema' (see ``test``)."""
+        if self._check_weights(weights):
+            with self.ema_weights():
+                return self.test_sequence(input_images, test_next_frame, test_actions, steps=steps, literal=literal,
+                                          device_loop=device_loop, bn=bn)
         self._check_bn_mode(bn)
         if literal:
             predicted = []
@@ -495,7 +587,7 @@ class Trainer:
             frames.append(frame)
         return torch.stack(frames, dim=1), summ0
 
-    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False, bn='batch'):
+    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False, bn='batch', weights='raw'):
         """Quality of the recursive rollout, scored on the GPU (metrics.frame_metrics; no reference counterpart - the curves of
         its report).  Rollout as ``test_sequence``'s default on the device loop: ``steps`` (default T-1) steps,
         step j commanded by ``actions[:, j]`` with the generator's own predicted state (defect D7) and scored against
@@ -503,8 +595,11 @@ class Trainer:
         also score the identity baseline - ``images[:, 0]`` carried forward - against the same targets.
         -> dict of numpy arrays [B, steps]: ``ssim``, ``sqerr`` (sum of squared errors of the frame), and ``identity_ssim``,
         ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames).
-        ``bn``: 'batch' or 'stored', as ``test`` takes it."""
+        ``bn``: 'batch' or 'stored', ``weights``: 'raw' or 'ema', as ``test`` takes them."""
         from . import metrics
+        if self._check_weights(weights):
+            with self.ema_weights():
+                return self.rollout_metrics(images, actions, steps=steps, identity=identity, return_frames=return_frames, bn=bn)
         self._check_bn_mode(bn)
         if not self.sess.rt.is_cuda:
             raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
@@ -534,6 +629,17 @@ def model_kind(arg_transform):
             return arg_transform
         raise ValueError("unexpected transform argument %r (False, True / 'dna' or 'cdna')" % arg_transform)
     return 'dna' if arg_transform else 'plain'
+
+
+def check_ema_decay(ema_decay):
+    """ValueError for an ``ema_decay`` that is neither 0 (no average) nor inside (0, 1); -> the decay as a float."""
+    try:
+        d = float(ema_decay)
+    except (TypeError, ValueError):
+        raise ValueError('ema_decay must be 0 (off) or a number in (0, 1), got %r' % (ema_decay,))
+    if isinstance(ema_decay, bool) or not 0.0 <= d < 1.0 or (d > 0.0 and not 0.0 < float(np.float32(d)) < 1.0):
+        raise ValueError('ema_decay must be 0 (off) or lie in (0, 1), got %r' % (ema_decay,))
+    return d
 
 
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
@@ -700,7 +806,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
-          num_masks=10, rollout_steps=1):
+          num_masks=10, rollout_steps=1, ema_decay=0.0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -718,7 +824,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     bits; 0 = off, as the reference).  ``synthetic_pool``: SyntheticPush(pool=...).  ``arg_transform`` / ``num_masks``: the
     generator, as Trainer takes them ('cdna': the CDNA generator with ``num_masks`` kernels of ``ksize``).  ``rollout_steps`` K > 1:
     every G step (and pretraining step) trains through the generator's own K-step rollout on a window t .. t+K
-    (Trainer.train_g_rollout); the D steps are unchanged and the loop takes the plain call path (no look-ahead pass)."""
+    (Trainer.train_g_rollout); the D steps are unchanged and the loop takes the plain call path (no look-ahead pass).
+    ``ema_decay`` > 0: the Trainer keeps the moving average of the generator's weights (Trainer ``ema_decay``); checkpoints hold
+    it, ``train.jsonl`` records ``g_ema``, and the evaluation block also scores the rollout of the averaged weights
+    (``rollout_psnr_ema`` / ``rollout_ssim_ema`` in ``test.jsonl``).  Training itself is unchanged."""
+    ema_decay = check_ema_decay(ema_decay)
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
     if int(rollout_steps) > 1:
@@ -745,7 +855,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     try:
         trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
-                              select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps))
+                              select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
+                              ema_decay=ema_decay)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -760,12 +871,13 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10, rollout_steps=1):
+                num_masks=10, rollout_steps=1, ema_decay=0.0):
+    ema = {'ema_decay': ema_decay} if ema_decay else {}
     if rollout_steps > 1:               # (the K-step G step takes the plain call path: no pair instance to build)
         trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks,
-                          lookahead=False, rollout_steps=rollout_steps)
+                          lookahead=False, rollout_steps=rollout_steps, **ema)
     else:
-        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks)
+        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks, **ema)
     sess.run(G.global_variables_initializer())
     saver = Saver()                                                           # train.py:215
     if resume:
@@ -832,7 +944,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             if not quiet:
                 print('Iteration {:d}'.format(i))
             if log_file and summ:
-                _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0, rollout_steps=rollout_steps))
+                _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0, rollout_steps=rollout_steps,
+                                          **({'g_ema': ema_decay} if ema_decay else {})))
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
         if eval_every and i % eval_every == 0 and rank == 0:
@@ -845,7 +958,14 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 # SSIM per step (mean over the batch) by the GPU kernel (metrics.frame_metrics) on the same predictions
                 ssim, _ = frame_metrics(sess.upload(predicted), sess.upload(np.asarray(t_img[:, 1:predicted.shape[1] + 1], np.float32)))
                 ssim = [float(v) for v in ssim.mean(dim=0, dtype=torch.float64).cpu().numpy()]
-                _log_jsonl(os.path.join(log_dir, 'test.jsonl'), dict(e_summ or {}, iteration=i, rollout_psnr=psnr, rollout_ssim=ssim))
+                record = dict(e_summ or {}, iteration=i, rollout_psnr=psnr, rollout_ssim=ssim)
+                if ema_decay and trainer.ema_updates() > 0:      # the same sequences through the averaged weights, scored the same way
+                    pred_e, _ = trainer.test_sequence(t_img, t_img, t_acts, weights='ema')
+                    record['rollout_psnr_ema'] = [float(10.0 * np.log10(1.0 / max(np.mean((pred_e[:, j] - t_img[:, j + 1]) ** 2), 1e-30)))
+                                                  for j in range(pred_e.shape[1])]
+                    ssim_e, _ = frame_metrics(sess.upload(pred_e), sess.upload(np.asarray(t_img[:, 1:pred_e.shape[1] + 1], np.float32)))
+                    record['rollout_ssim_ema'] = [float(v) for v in ssim_e.mean(dim=0, dtype=torch.float64).cpu().numpy()]
+                _log_jsonl(os.path.join(log_dir, 'test.jsonl'), record)
     if hasattr(eval_data, 'close'):
         eval_data.close()
     saver.wait()                     # the last checkpoints are on disk when train() returns
@@ -957,9 +1077,16 @@ def main(argv=None):
                              '0 = decode every time as the reference; the 64x64 push training set is ~17 GiB decoded)')
     parser.add_argument('--data_decode', type=str, default='exact', choices=['exact', 'dct'],
                         help="'dct': approximate 8x reduction inside libjpeg's inverse DCT (3x cheaper; within 2-3 levels of 255)")
+    parser.add_argument('--g_ema', type=float, default=0.0, metavar='DECAY',
+                        help='keep an exponential moving average of the generator weights with this decay (0 < DECAY < 1; 0 = off): '
+                             'checkpoints hold it, the evaluation block also scores it, evaluate --weights ema predicts with it')
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
+    try:
+        check_ema_decay(args.g_ema)
+    except ValueError:
+        parser.error('--g_ema must be 0 (off) or lie in (0, 1), got %r' % args.g_ema)
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
@@ -979,7 +1106,7 @@ def main(argv=None):
                     n_critic=args.n_critic, device='cuda:%d' % local_rank, world_size=world_size, rank=rank, dtype=args.dtype,
                     sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
-                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps)
+                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

@@ -4,6 +4,8 @@
 //   hipcc -O3 --offload-arch=gfx950 -o stream_probe tools/micro/stream_probe.hip && ./stream_probe
 // `./stream_probe ew ROWS CHANNELS [ROWS CHANNELS ...]`: the flat elementwise pass alone (one read, one write) on fp32 tensors of
 // the given sizes, one line each - the yardstick tools/bench_bn_infer.py puts beside acg_bn_act_infer (ROWS * CHANNELS % 4 == 0).
+// `./stream_probe tri N [N ...]`: a flat three-pass stream (two reads, one write: y -= c * (y - x)) over N floats, one line each -
+// the yardstick tools/bench_ema.py puts beside acg_ema_update (N % 4 == 0).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -31,6 +33,23 @@ __global__ __launch_bounds__(NT) void ew_flat(const float4* __restrict__ x, floa
       float4 t = v[u];
       t.x = fmaxf((t.x - mm.x) * rr.x + bb.x, 0.f); t.y = fmaxf((t.y - mm.y) * rr.y + bb.y, 0.f);
       t.z = fmaxf((t.z - mm.z) * rr.z + bb.z, 0.f); t.w = fmaxf((t.w - mm.w) * rr.w + bb.w, 0.f);
+      y[base + (long long)u * NT] = t;
+    }
+  }
+}
+
+// three passes: thread t of block b owns float4 number (b * U + u) * NT + t of x (read) and y (read and written)
+template <int NT, int U>
+__global__ __launch_bounds__(NT) void tri_flat(const float4* __restrict__ x, float4* __restrict__ y, float c, long long n4) {
+  const long long base = (long long)blockIdx.x * U * NT + threadIdx.x;
+  float4 a[U], v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) { const long long i = min(base + (long long)u * NT, n4 - 1); a[u] = x[i]; v[u] = y[i]; }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (base + (long long)u * NT < n4) {
+      float4 t = v[u];
+      t.x -= c * (t.x - a[u].x); t.y -= c * (t.y - a[u].y); t.z -= c * (t.z - a[u].z); t.w -= c * (t.w - a[u].w);
       y[base + (long long)u * NT] = t;
     }
   }
@@ -138,8 +157,29 @@ static int ew_only(int argc, char** argv) {
   return 0;
 }
 
+// one line per flat fp32 buffer of N floats: the best of the three-pass variants
+static int tri_only(int argc, char** argv) {
+  Timer T;
+  for (int a = 2; a < argc; ++a) {
+    const long long n = atoll(argv[a]), n4 = n / 4;
+    if (n <= 0 || n % 4) { printf("tri %lld skipped\n", n); continue; }
+    float *x, *y;
+    CK(hipMalloc(&x, n * 4)); CK(hipMalloc(&y, n * 4));
+    CK(hipMemset(x, 0x3c, n * 4)); CK(hipMemset(y, 0x3c, n * 4));
+    float best = 1e30f;
+#define TRI_ONE(U) { const int grid = (int)((n4 + 256LL * U - 1) / (256LL * U)); \
+    float us = T.us([&](hipStream_t s) { hipLaunchKernelGGL((tri_flat<256, U>), dim3(grid), dim3(256), 0, s, (const float4*)x, (float4*)y, 0.001f, n4); }); \
+    if (us < best) best = us; }
+    TRI_ONE(1) TRI_ONE(2) TRI_ONE(4) TRI_ONE(8)
+    printf("tri %lld stream_us %.3f\n", n, best);
+    CK(hipFree(x)); CK(hipFree(y));
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && argv[1][0] == 'e') return ew_only(argc, argv);
+  if (argc > 1 && argv[1][0] == 't') return tri_only(argc, argv);
   Timer T;
   const long long Rs[] = {8192, 32768, 131072};
   const int C = 128;
