@@ -201,6 +201,15 @@ EMA_SIGNATURES = {
     'acg_swap_f32': (c_int32, [_P, _P, c_int64, _P]),
 }
 
+# include/acgan_ssim_loss.h: SSIM as a training loss - sum_n (1 - SSIM_n) and its gradient with respect to the prediction; an
+# addition under ABI version 8 bound as a table of its own like EMA_SIGNATURES (the C oracle does not implement it:
+# ops.SsimLossOp raises a RuntimeError there)
+SSIM_LOSS_SIGNATURES = {
+    'acg_ssim_loss_workspace_bytes': (c_size_t, [c_int32] * 4),
+    'acg_ssim_loss': (c_int32, [_P, _P, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                _P, c_size_t, _P]),
+}
+
 
 COPY_MAX = 8
 REDUCE_MAX = 32
@@ -268,7 +277,7 @@ def get():
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
         _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES, **BN_INFER_SIGNATURES,
-                                              **EMA_SIGNATURES))
+                                              **EMA_SIGNATURES, **SSIM_LOSS_SIGNATURES))
     return _LIB
 
 

@@ -1657,7 +1657,12 @@ class Scalar:
     def tensor(self):
         if self._tensor is None:
             if len(self.terms) > 4:
-                raise ValueError('a loss may combine at most 4 heads')
+                # acg_scalar_combine takes 4 terms: the first 4, then the partial result (weight 1) plus the next 3, and so on
+                op, rest = CombineOp(self.terms[:4]), self.terms[4:]
+                while rest:
+                    op, rest = CombineOp([(op, 0, 1.0)] + rest[:3]), rest[3:]
+                self._tensor = op.outputs[0]
+                return self._tensor
             self._tensor = CombineOp(self.terms).outputs[0]
         return self._tensor
 
@@ -1721,6 +1726,57 @@ class FrameLossOp(LossHead):
         if needs[1]:                       # both terms are symmetric: differentiate w.r.t. the other argument
             a, b = b, a
         op = FrameLossOp(a, b, (weights.get(0, 0.0), weights.get(1, 0.0)), self.name + '/grad')
+        return [(a, op.dgen)]
+
+
+def _ssim_entry(rt, name):
+    """An entry of include/acgan_ssim_loss.h (_lib.SSIM_LOSS_SIGNATURES); a library without it (the C oracle) is a clear error."""
+    fn = getattr(rt.lib, name, None)
+    if fn is None:
+        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_ssim_loss.h): the SSIM loss runs on the HIP library only'
+                            % (getattr(rt.lib, 'path', rt.lib), name))
+    return fn
+
+
+SSIM_DATA_RANGE, SSIM_K1, SSIM_K2 = 2.0, 0.01, 0.03      # frames in [-1, 1]; include/acgan_metrics.h
+
+
+class SsimLossOp(LossHead):
+    """out0 = sum_b (1 - SSIM(gen_b, gt_b)), SSIM as include/acgan_metrics.h defines it (acg_ssim_loss).  The head itself runs
+    the value-only call; its gradient op (``grad_weight`` given) the gradient-only call - two launches, no reduction."""
+
+    def __init__(self, gen, gt, grad_weight=None, name='ssim_loss'):
+        if gen.shape != gt.shape:
+            raise ValueError('ssim loss: shapes differ %s vs %s' % (gen.shape, gt.shape))
+        if len(gen.shape) != 4 or min(gen.shape[1:3]) < 11 or not 1 <= gen.shape[3] <= 4:
+            raise ValueError('ssim loss: [n, h, w, c] frames with h, w >= 11 and c in 1..4 expected, got %s' % (gen.shape,))
+        for t in (gen, gt):
+            if t.dtype != torch.float32 or t.valid_c is not None:
+                raise ValueError('ssim loss: %r is not a dense float32 tensor' % (t,))
+        self.grad_weight = grad_weight
+        self.dgen = _new(gen.shape, name + '/dgen') if grad_weight is not None else None
+        super().__init__(G.get_default_graph(), name, [gen, gt],
+                         [_new((1,), name + ':0')] + ([self.dgen] if self.dgen is not None else []))
+
+    def bind(self, rt):
+        gen, gt = self.inputs
+        b, h, w, c = gen.shape
+        fn, size = _ssim_entry(rt, 'ssim_loss'), _ssim_entry(rt, 'ssim_loss_workspace_bytes')
+        ws, n = rt.workspace(size(b, h, w, c))
+        self._keep = ws
+        # the gradient op's own value output is read by nobody (FrameLossOp.bind): gradient only
+        pout = None if self.dgen is not None else _p(self.outputs[0].buf)
+        args = (_p(gen.buf), _p(gt.buf), pout, _p(self.dgen.buf) if self.dgen is not None else None, float(self.grad_weight or 0.0),
+                b, h, w, c, SSIM_DATA_RANGE, SSIM_K1, SSIM_K2, _p(ws), n)
+        return lambda s: fn(*args, s)
+
+    def seed(self, weights, needs):
+        a, b = self.inputs
+        if needs[0] and needs[1]:
+            raise NotImplementedError('ssim loss: gradient w.r.t. both arguments')
+        if needs[1]:                       # SSIM is symmetric: differentiate w.r.t. the other argument
+            a, b = b, a
+        op = SsimLossOp(a, b, weights.get(0, 0.0), self.name + '/grad')
         return [(a, op.dgen)]
 
 
@@ -1929,6 +1985,17 @@ def frame_losses(g_out, next_frames):
     dp = G.get_default_graph().collections.get('data_parallel')
     gdl_w = float(dp.world_size) if (dp is not None and getattr(dp, 'exact_global_batch', False) and dp.active) else 1.0
     return Scalar([(head, 0, 1.0)]), Scalar([(head, 1, gdl_w)])
+
+
+def ssim_loss(g_out, next_frames):
+    """-> sum_b (1 - SSIM(g_out_b, next_frames_b)) (SsimLossOp), one head per pair of tensors like frame_losses.  A per-frame
+    mean: divided by the local batch it needs no correction under data parallelism, whatever ``exact_global_batch`` says."""
+    cache = G.get_default_graph().collections.setdefault('ssim_loss_heads', {})
+    key = frozenset((g_out.root().id, next_frames.root().id))
+    head = cache.get(key)
+    if head is None:
+        head = cache[key] = SsimLossOp(g_out, next_frames)
+    return Scalar([(head, 0, 1.0)])
 
 
 def build_gdl(g_out, next_frames, alpha=1):

@@ -39,7 +39,8 @@ ACTION_DIM, STATE_DIM = 10, 5
 
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
-                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0):
+                 seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
+                 ssim_weight=0.0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -61,8 +62,17 @@ class Trainer:
         update), inside the same program.  The average never feeds back into training: parameters, slots and frames are those of
         the run without it.  ``ema_weights()`` predicts with it; ``test`` / ``test_sequence`` / ``rollout_metrics`` take
         ``weights='ema'``.  Only the generator is averaged.  Rank-local and elementwise: allowed with every generator, with
-        rollout_steps > 1, in bf16 graphs (the average is of the float32 master weights) and with more than one rank."""
+        rollout_steps > 1, in bf16 graphs (the average is of the float32 master weights) and with more than one rank.
+        ``ssim_weight`` W (no reference counterpart; 0 builds nothing more; else finite and > 0): adds W / B * sum_b (1 -
+        SSIM(frame_b, next_frame_b)) to ``g_l2_loss`` - after the L2_WEIGHT scaling, not scaled by it - and so to the pretraining
+        loss, the G loss and every step of the two rollout losses (ops.ssim_loss: the SSIM the evaluation reports, the gradient by
+        acg_ssim_loss on the float32 frame).  The summary ``g_ssim_loss`` is the unweighted sum_b (1 - SSIM_b) / B.  L1 here is a
+        sum over the 12 288 values of a frame, so a useful W is in the tens to hundreds.  Every generator, bf16 graphs (the frame
+        is float32 there too), the look-ahead path, rollout_steps > 1, ema_decay and bn_inference take it; no variable and no state
+        is added.  A per-frame mean over the local batch: averaging the ranks' gradients gives the global-batch value, nothing is
+        needed for exact_global_batch - allowed with more than one rank, not verified there."""
         ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
+        self.ssim_weight = check_ssim_weight(ssim_weight)
         self.sess = sess
         self.model = model_kind(arg_transform)
         dp = G.get_default_graph().collections.get('data_parallel')
@@ -158,8 +168,13 @@ class Trainer:
             with G.get_default_graph().side_branch():      # the state head's loss belongs to its side chain (models.py)
                 state_loss = O.l2_norm(self.g_state_out, self.next_state, name='g_state_loss')
             g_l2_loss = g_l2_loss * L2_WEIGHT + state_loss / B
-        self.g_l2_loss = g_l2_loss
         self.summaries = {}
+        self.g_ssim_loss = None
+        if self.ssim_weight:
+            self.g_ssim_loss = O.ssim_loss(self.g_out, self.next_frame_ph) / B
+            g_l2_loss = g_l2_loss + self.g_ssim_loss * self.ssim_weight
+            self.summaries['g_ssim_loss'] = self.g_ssim_loss
+        self.g_l2_loss = g_l2_loss
         if arg_adv:
             self.g_adv_loss = O.build_g_adv_loss(self.d_out_gen, arg_loss)
             self.g_loss = g_l2_loss + self.g_adv_loss + gdl
@@ -383,6 +398,8 @@ class Trainer:
                 with graph.side_branch():
                     state_loss = O.l2_norm(state, self.roll_state_ph[j], name='rollout/g_state_loss%d' % j)
                 l2 = l2 * L2_WEIGHT + state_loss / B
+            if self.ssim_weight:
+                l2 = l2 + O.ssim_loss(frame, self.roll_next_ph[j]) * (self.ssim_weight / B)
             loss = l2 + O.build_g_adv_loss(d_out, self.arg_loss) + gdl if self.arg_adv else l2
             self.rollout_frames.append(frame)
             self.rollout_states.append(state)
@@ -642,6 +659,17 @@ def check_ema_decay(ema_decay):
     return d
 
 
+def check_ssim_weight(ssim_weight):
+    """ValueError for an ``ssim_weight`` that is not a finite number >= 0; -> the weight as a float (0: no SSIM term)."""
+    try:
+        w = float(ssim_weight)
+    except (TypeError, ValueError):
+        raise ValueError('ssim_weight must be a finite number >= 0, got %r' % (ssim_weight,))
+    if isinstance(ssim_weight, bool) or not 0.0 <= w <= float(np.finfo(np.float32).max):      # (finite in float32; nan fails too)
+        raise ValueError('ssim_weight must be finite and >= 0, got %r' % (ssim_weight,))
+    return w
+
+
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
     """ValueError for a ``rollout_steps`` the K-step trainer does not take (with the generator ``model``, a bf16 graph, data
     parallelism / synchronised BatchNorm); -> K."""
@@ -806,7 +834,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
-          num_masks=10, rollout_steps=1, ema_decay=0.0):
+          num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -827,8 +855,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     (Trainer.train_g_rollout); the D steps are unchanged and the loop takes the plain call path (no look-ahead pass).
     ``ema_decay`` > 0: the Trainer keeps the moving average of the generator's weights (Trainer ``ema_decay``); checkpoints hold
     it, ``train.jsonl`` records ``g_ema``, and the evaluation block also scores the rollout of the averaged weights
-    (``rollout_psnr_ema`` / ``rollout_ssim_ema`` in ``test.jsonl``).  Training itself is unchanged."""
+    (``rollout_psnr_ema`` / ``rollout_ssim_ema`` in ``test.jsonl``).  Training itself is unchanged.
+    ``ssim_weight`` W > 0: the generator's losses carry W / B * sum_b (1 - SSIM_b) (Trainer ``ssim_weight``); ``train.jsonl``
+    records ``ssim_weight`` and the summary ``g_ssim_loss``.  Checkpoints and the evaluation block are unchanged."""
     ema_decay = check_ema_decay(ema_decay)
+    ssim_weight = check_ssim_weight(ssim_weight)
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
     if int(rollout_steps) > 1:
@@ -856,7 +887,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
         trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
                               select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
-                              ema_decay=ema_decay)
+                              ema_decay=ema_decay, ssim_weight=ssim_weight)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -871,8 +902,10 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10, rollout_steps=1, ema_decay=0.0):
+                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0):
     ema = {'ema_decay': ema_decay} if ema_decay else {}
+    if ssim_weight:
+        ema['ssim_weight'] = ssim_weight
     if rollout_steps > 1:               # (the K-step G step takes the plain call path: no pair instance to build)
         trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks,
                           lookahead=False, rollout_steps=rollout_steps, **ema)
@@ -945,7 +978,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 print('Iteration {:d}'.format(i))
             if log_file and summ:
                 _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0, rollout_steps=rollout_steps,
-                                          **({'g_ema': ema_decay} if ema_decay else {})))
+                                          **({'g_ema': ema_decay} if ema_decay else {}),
+                                          **({'ssim_weight': ssim_weight} if ssim_weight else {})))
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
         if eval_every and i % eval_every == 0 and rank == 0:
@@ -1080,9 +1114,17 @@ def main(argv=None):
     parser.add_argument('--g_ema', type=float, default=0.0, metavar='DECAY',
                         help='keep an exponential moving average of the generator weights with this decay (0 < DECAY < 1; 0 = off): '
                              'checkpoints hold it, the evaluation block also scores it, evaluate --weights ema predicts with it')
+    parser.add_argument('--ssim_weight', type=float, default=0.0, metavar='W',
+                        help='add W / B * sum_b (1 - SSIM_b) of the generated frame against the next frame to the generator\'s '
+                             'reconstruction loss (0 = off; the L1 term is a SUM over the 12 288 values of a frame, so a useful W is in '
+                             'the tens to hundreds)')
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
+    try:
+        check_ssim_weight(args.ssim_weight)
+    except ValueError:
+        parser.error('--ssim_weight must be finite and >= 0, got %r' % args.ssim_weight)
     try:
         check_ema_decay(args.g_ema)
     except ValueError:
@@ -1106,7 +1148,8 @@ def main(argv=None):
                     n_critic=args.n_critic, device='cuda:%d' % local_rank, world_size=world_size, rank=rank, dtype=args.dtype,
                     sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
-                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema)
+                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema,
+                    ssim_weight=args.ssim_weight)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 
