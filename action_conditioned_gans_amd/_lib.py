@@ -3,7 +3,12 @@
 There is no fallback: if the HIP library has not been built (``python -c "import
 __graft_entry__ as g; g.build()"`` or ``make -C action_conditioned_gans_amd/csrc``) every
 operator raises ``RuntimeError``.  Nothing here knows about the CPU oracle.
+
+``SIGNATURES`` is the core table (include/acgan_hip.h): every library must export all of it.  ``EXTENSIONS`` holds the additions
+that live in a header of their own; a ``Library`` binds each group its shared object exports, ``get()`` requires all of them,
+and ops look such an entry up with ``entry(lib, name)``.
 """
+import collections
 import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
@@ -64,150 +69,149 @@ _D = ctypes.POINTER(ConvDesc)
 _conv = [_P, _P, _P, _D, c_int32, _P, c_size_t, _P]
 _wgrad = [_P, _P, _P, c_float, _D, c_int32, _P, c_size_t, _P]
 
+# The restype of an entry point whose int32 is an error code: bound as c_int32 and wrapped so that a non-zero result raises
+# AcgError with acg_last_error().  A plain c_int32 restype is a value (a count, a layout, a yes/no) and is returned as it is.
+STATUS = type('STATUS', (), {})
+
 # name -> (restype, argtypes); mirrors include/acgan_hip.h one to one.
 SIGNATURES = {
     'acg_version': (c_int32, []),
     'acg_build_info': (c_char_p, []),
     'acg_last_error': (c_char_p, []),
-    'acg_conv_desc_init': (c_int32, [_D] + [c_int32] * 9),
+    'acg_conv_desc_init': (STATUS, [_D] + [c_int32] * 9),
     'acg_conv2d_workspace_bytes': (c_size_t, [_D, c_int32, c_int32]),
-    'acg_conv2d_fwd': (c_int32, _conv),
-    'acg_conv2d_dgrad': (c_int32, _conv),
-    'acg_conv2d_wgrad': (c_int32, _wgrad),
+    'acg_conv2d_fwd': (STATUS, _conv),
+    'acg_conv2d_dgrad': (STATUS, _conv),
+    'acg_conv2d_wgrad': (STATUS, _wgrad),
     'acg_conv2d_splits': (c_int32, [_D, c_int32, c_int32]),
     'acg_conv2d_tile': (c_int32, [_D, c_int32, c_int32, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]),
-    'acg_conv2d_wgrad_slabs': (c_int32, [_P, _P, _D, c_int32, _P, c_size_t, _P]),
-    'acg_deconv2d_wgrad_slabs': (c_int32, [_P, _P, _D, c_int32, _P, c_size_t, _P]),
+    'acg_conv2d_wgrad_slabs': (STATUS, [_P, _P, _D, c_int32, _P, c_size_t, _P]),
+    'acg_deconv2d_wgrad_slabs': (STATUS, [_P, _P, _D, c_int32, _P, c_size_t, _P]),
     'acg_conv2d_stats_blocks': (c_int32, [_D, c_int32, c_int32, c_int32]),
     'acg_conv2d_stats_layout': (c_int32, [_D, c_int32, c_int32, c_int32, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]),
-    'acg_conv2d_fwd_stats': (c_int32, [_P, _P, _P, _D, c_int32, _P, c_size_t, _P, c_int32, _P]),
-    'acg_deconv2d_fwd_stats': (c_int32, [_P, _P, _P, _D, c_int32, _P, c_size_t, _P, c_int32, _P]),
+    'acg_conv2d_fwd_stats': (STATUS, [_P, _P, _P, _D, c_int32, _P, c_size_t, _P, c_int32, _P]),
+    'acg_deconv2d_fwd_stats': (STATUS, [_P, _P, _P, _D, c_int32, _P, c_size_t, _P, c_int32, _P]),
     'acg_deconv2d_fwd_bias_act_ok': (c_int32, [_D, c_int32]),
-    'acg_deconv2d_fwd_bias_act': (c_int32, [_P, _P, _P, _P, _D, c_int32, c_float, c_int32, _P]),
+    'acg_deconv2d_fwd_bias_act': (STATUS, [_P, _P, _P, _P, _D, c_int32, c_float, c_int32, _P]),
     'acg_conv2d_slab_layouts': (c_int32, [_D, c_int32, c_int32]),
-    'acg_conv2d_fwd_slabs': (c_int32, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_conv2d_dgrad_slabs': (c_int32, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_deconv2d_fwd_slabs': (c_int32, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_deconv2d_dgrad_slabs': (c_int32, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_conv2d_bwd_pair': (c_int32, [_P, _P, _P, _P, _P, c_float, _D, c_int32, _P, c_size_t, _P, c_size_t, c_int32, _P]),
-    'acg_deconv2d_bwd_pair': (c_int32, [_P, _P, _P, _P, _P, c_float, _D, c_int32, _P, c_size_t, _P, c_size_t, c_int32, _P]),
-    'acg_splitk_reduce_many': (c_int32, [ctypes.POINTER(ReduceList), c_int32, _P]),
-    'acg_weights_prepare_bf16': (c_int32, [ctypes.POINTER(PrepList), c_int32, _P]),
-    'acg_deconv2d_fwd': (c_int32, _conv),
-    'acg_deconv2d_dgrad': (c_int32, _conv),
-    'acg_deconv2d_wgrad': (c_int32, _wgrad),
+    'acg_conv2d_fwd_slabs': (STATUS, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_conv2d_dgrad_slabs': (STATUS, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_deconv2d_fwd_slabs': (STATUS, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_deconv2d_dgrad_slabs': (STATUS, [_P, _P, _D, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_conv2d_bwd_pair': (STATUS, [_P, _P, _P, _P, _P, c_float, _D, c_int32, _P, c_size_t, _P, c_size_t, c_int32, _P]),
+    'acg_deconv2d_bwd_pair': (STATUS, [_P, _P, _P, _P, _P, c_float, _D, c_int32, _P, c_size_t, _P, c_size_t, c_int32, _P]),
+    'acg_splitk_reduce_many': (STATUS, [ctypes.POINTER(ReduceList), c_int32, _P]),
+    'acg_weights_prepare_bf16': (STATUS, [ctypes.POINTER(PrepList), c_int32, _P]),
+    'acg_deconv2d_fwd': (STATUS, _conv),
+    'acg_deconv2d_dgrad': (STATUS, _conv),
+    'acg_deconv2d_wgrad': (STATUS, _wgrad),
     'acg_bn_workspace_bytes': (c_size_t, [c_int64, c_int32, c_int32]),
-    'acg_bn_moments': (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_bn_act_fwd_moments': (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
+    'acg_bn_moments': (STATUS, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_bn_act_fwd_moments': (STATUS, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
+                                        c_int32, _P]),
+    'acg_bn_bwd_sums': (STATUS, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P,
+                                 c_size_t, _P]),
+    'acg_bn_act_bwd_sums': (STATUS, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                     c_int32, c_float, c_int32, _P]),
+    'acg_bn_exchange_selftest': (STATUS, [_P, c_size_t, _P, c_int32, c_int32, c_int32, ctypes.c_uint32, _P]),
+    'acg_bn_act_fwd': (STATUS, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
+                                c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_bn_act_bwd': (STATUS, [_P, _P, _P, _P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                c_float, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_bn_act_fwd_partials': (STATUS, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
                                          c_int32, _P]),
-    'acg_bn_bwd_sums': (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P,
-                                  c_size_t, _P]),
-    'acg_bn_act_bwd_sums': (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32,
-                                      c_int32, c_float, c_int32, _P]),
-    'acg_bn_exchange_selftest': (c_int32, [_P, c_size_t, _P, c_int32, c_int32, c_int32, ctypes.c_uint32, _P]),
-    'acg_bn_act_fwd': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
-                                 c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_bn_act_bwd': (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                 c_float, c_int32, c_int32, _P, c_size_t, _P]),
-    'acg_bn_act_fwd_partials': (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
-                                          c_int32, _P]),
     'acg_bn_slabs_layout': (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
-    'acg_bn_act_fwd_slabs': (c_int32, [_P, c_int32, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
-                                       c_int32, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_bn_act_fwd_slabs': (STATUS, [_P, c_int32, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, c_float,
+                                      c_int32, c_int32, c_int32, _P, c_size_t, _P]),
     'acg_bn_bwd_slabs_ok': (c_int32, [c_int64, c_int32]),
-    'acg_bn_act_bwd_slabs': (c_int32, [_P, _P, c_int32, _P, _P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                       c_float, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
+    'acg_bn_act_bwd_slabs': (STATUS, [_P, _P, c_int32, _P, _P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_float, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
     'acg_bias_workspace_bytes': (c_size_t, [c_int64, c_int32]),
-    'acg_bias_act_fwd': (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P]),
-    'acg_bias_act_bwd': (c_int32, [_P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32,
-                                   _P, c_size_t, _P]),
+    'acg_bias_act_fwd': (STATUS, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32, _P]),
+    'acg_bias_act_bwd': (STATUS, [_P, _P, _P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_int32,
+                                  _P, c_size_t, _P]),
     'acg_dna_workspace_bytes': (c_size_t, [c_int32] * 4),
-    'acg_dna_fwd': (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    'acg_dna_bwd': (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P,
-                              c_size_t, _P]),
+    'acg_dna_fwd': (STATUS, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    'acg_dna_bwd': (STATUS, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P,
+                             c_size_t, _P]),
     'acg_cdna_workspace_bytes': (c_size_t, [c_int32] * 6),
-    'acg_cdna_fwd': (c_int32, [_P, _P, _P, _P] + [c_int32] * 6 + [c_float, c_int32, _P]),
-    'acg_cdna_bwd': (c_int32, [_P, _P, _P, _P, _P, _P] + [c_int32] * 6 + [c_float, c_int32, _P, c_size_t, _P]),
-    'acg_concat_actions_fwd': (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    'acg_concat_channels_fwd': (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
-    'acg_slice_channels': (c_int32, [_P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
-    'acg_copy_many': (c_int32, [ctypes.POINTER(CopyList), c_int32, c_int32, _P]),
-    'acg_stream_edge_create': (c_int32, [ctypes.POINTER(c_void_p)]),
-    'acg_stream_edge_destroy': (c_int32, [_P]),
-    'acg_stream_edge': (c_int32, [_P, _P, _P]),
-    'acg_add': (c_int32, [_P, _P, _P, c_int64, c_int32, _P]),
+    'acg_cdna_fwd': (STATUS, [_P, _P, _P, _P] + [c_int32] * 6 + [c_float, c_int32, _P]),
+    'acg_cdna_bwd': (STATUS, [_P, _P, _P, _P, _P, _P] + [c_int32] * 6 + [c_float, c_int32, _P, c_size_t, _P]),
+    'acg_concat_actions_fwd': (STATUS, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    'acg_concat_channels_fwd': (STATUS, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+    'acg_slice_channels': (STATUS, [_P, _P, c_float, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
+    'acg_copy_many': (STATUS, [ctypes.POINTER(CopyList), c_int32, c_int32, _P]),
+    'acg_stream_edge_create': (STATUS, [ctypes.POINTER(c_void_p)]),
+    'acg_stream_edge_destroy': (STATUS, [_P]),
+    'acg_stream_edge': (STATUS, [_P, _P, _P]),
+    'acg_add': (STATUS, [_P, _P, _P, c_int64, c_int32, _P]),
     'acg_frame_loss_workspace_bytes': (c_size_t, [c_int64]),
-    'acg_frame_loss': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_int32,
-                                 _P, c_size_t, _P]),
-    'acg_l2norm_loss': (c_int32, [_P, _P, _P, _P, c_int64, c_float, _P]),
-    'acg_sumsq_diff': (c_int32, [_P, _P, _P, c_int64, _P]),
-    'acg_l2norm_loss_global': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_float, _P]),
-    'acg_sigmoid_ce_loss': (c_int32, [_P, c_float, _P, _P, c_int64, c_float, _P]),
-    'acg_mean_loss': (c_int32, [_P, _P, _P, c_int64, c_float, _P]),
-    'acg_psnr': (c_int32, [_P, _P, _P, c_int64, c_int32, _P, c_size_t, _P]),
-    'acg_scalar_combine': (c_int32, [_P, _P, c_float, _P, c_float, _P, c_float, _P, c_float, _P]),
-    'acg_opt_step_prepare_bf16': (c_int32, [_P, _P, _P, _P, _P, c_int64, ctypes.POINTER(OptArgs), ctypes.POINTER(PrepList), c_int32, _P]),
-    'acg_adam_step': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float,
-                                c_int32, c_float, c_float, _P]),
-    'acg_rmsprop_step': (c_int32, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float,
-                                   c_float, _P]),
-    'acg_clip': (c_int32, [_P, c_int64, c_float, c_float, _P]),
-    'acg_step_inc': (c_int32, [_P, _P]),
-}
-
-# include/acgan_metrics.h: an addition under ABI version 8, bound as a table of its own - the C oracle (oracle/cbind) does not
-# implement it and is never asked for it; the HIP library must export it (get() / load_tuning() pass it as `extra`)
-METRICS_SIGNATURES = {
-    'acg_frame_metrics_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32]),
-    'acg_frame_metrics': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
-                                    _P, c_size_t, _P]),
-}
-
-# include/acgan_cdna.h: the CDNA generator's fused transform-and-composite, an addition under ABI version 8 bound as a table of
-# its own like METRICS_SIGNATURES (the C oracle does not implement it: ops.CdnaCompositeOp raises a RuntimeError there)
-CDNA_SIGNATURES = {
-    'acg_cdna_composite_workspace_bytes': (c_size_t, [c_int32] * 6),
-    'acg_cdna_composite_fwd': (c_int32, [_P, _P, _P, _P, c_int32, _P, _P] + [c_int32] * 6 + [c_float, _P]),
-    'acg_cdna_composite_bwd': (c_int32, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 6
-                               + [c_float, _P, c_size_t, _P]),
-}
-
-# include/acgan_rollout.h: the image gradient of the DNA tail and the gradient of a tiled action vector that training through
-# the generator's own rollouts needs (train.Trainer rollout_steps > 1); an addition under ABI version 8 bound as a table of its
-# own like CDNA_SIGNATURES (the C oracle does not implement it: ops.DnaImageGradOp / ActionGradOp raise a RuntimeError there)
-ROLLOUT_SIGNATURES = {
-    'acg_dna_bwd_image': (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
-    'acg_action_grad': (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
-}
-
-# include/acgan_bn_infer.h: BatchNorm with stored statistics - the apply pass on its own and the calibration pass that pools
-# the moments of the batches it is shown; an addition under ABI version 8 bound as a table of its own like ROLLOUT_SIGNATURES
-# (the C oracle does not implement it: ops.BnInferOp / BnCollectOp raise a RuntimeError there)
-BN_INFER_SIGNATURES = {
-    'acg_bn_act_infer': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_int32, _P]),
-    'acg_bn_collect_workspace_bytes': (c_size_t, [c_int64, c_int32]),
-    'acg_bn_collect': (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
-}
-
-# include/acgan_ema.h: the exponential moving average of a scope's weights - the stand-alone update, the optimizer steps that
-# carry it in their own launch, and the in-place exchange of two flat buffers; an addition under ABI version 8 bound as a table
-# of its own like BN_INFER_SIGNATURES (the C oracle does not implement it: optim.StepOp raises a RuntimeError there)
-EMA_SIGNATURES = {
-    'acg_ema_update': (c_int32, [_P, _P, c_int64, c_float, _P, _P, _P]),
-    'acg_adam_step_ema': (c_int32, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float,
-                                    c_int32, c_float, c_float, _P, c_float, _P, _P, _P]),
-    'acg_rmsprop_step_ema': (c_int32, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float,
-                                       c_float, _P, c_float, _P, _P, _P]),
-    'acg_swap_f32': (c_int32, [_P, _P, c_int64, _P]),
-}
-
-# include/acgan_ssim_loss.h: SSIM as a training loss - sum_n (1 - SSIM_n) and its gradient with respect to the prediction; an
-# addition under ABI version 8 bound as a table of its own like EMA_SIGNATURES (the C oracle does not implement it:
-# ops.SsimLossOp raises a RuntimeError there)
-SSIM_LOSS_SIGNATURES = {
-    'acg_ssim_loss_workspace_bytes': (c_size_t, [c_int32] * 4),
-    'acg_ssim_loss': (c_int32, [_P, _P, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+    'acg_frame_loss': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_int32,
                                 _P, c_size_t, _P]),
+    'acg_l2norm_loss': (STATUS, [_P, _P, _P, _P, c_int64, c_float, _P]),
+    'acg_sumsq_diff': (STATUS, [_P, _P, _P, c_int64, _P]),
+    'acg_l2norm_loss_global': (STATUS, [_P, _P, _P, _P, _P, c_int64, c_float, _P]),
+    'acg_sigmoid_ce_loss': (STATUS, [_P, c_float, _P, _P, c_int64, c_float, _P]),
+    'acg_mean_loss': (STATUS, [_P, _P, _P, c_int64, c_float, _P]),
+    'acg_psnr': (STATUS, [_P, _P, _P, c_int64, c_int32, _P, c_size_t, _P]),
+    'acg_scalar_combine': (STATUS, [_P, _P, c_float, _P, c_float, _P, c_float, _P, c_float, _P]),
+    'acg_opt_step_prepare_bf16': (STATUS, [_P, _P, _P, _P, _P, c_int64, ctypes.POINTER(OptArgs), ctypes.POINTER(PrepList), c_int32, _P]),
+    'acg_adam_step': (STATUS, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float,
+                               c_int32, c_float, c_float, _P]),
+    'acg_rmsprop_step': (STATUS, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float,
+                                  c_float, _P]),
+    'acg_clip': (STATUS, [_P, c_int64, c_float, c_float, _P]),
+    'acg_step_inc': (STATUS, [_P, _P]),
+}
+
+Extension = collections.namedtuple('Extension', 'header what signatures')
+
+# Additions under ABI version 8, one header each.  The C oracle (oracle/cbind) implements none of them and is never asked for
+# one: a Library binds the groups its shared object exports, and entry() names the header when an op asks a library for an
+# entry it does not have.  ``what`` closes that message.
+EXTENSIONS = {
+    # per-frame SSIM and squared error for the evaluation (metrics.frame_metrics)
+    'metrics': Extension('include/acgan_metrics.h', 'SSIM runs on the GPU only, there is no host fallback', {
+        'acg_frame_metrics_workspace_bytes': (c_size_t, [c_int32, c_int32, c_int32]),
+        'acg_frame_metrics': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                       _P, c_size_t, _P]),
+    }),
+    # the CDNA generator's fused transform-and-composite (ops.CdnaCompositeOp)
+    'cdna': Extension('include/acgan_cdna.h', 'the CDNA generator runs on the HIP library only', {
+        'acg_cdna_composite_workspace_bytes': (c_size_t, [c_int32] * 6),
+        'acg_cdna_composite_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P] + [c_int32] * 6 + [c_float, _P]),
+        'acg_cdna_composite_bwd': (STATUS, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 6
+                                   + [c_float, _P, c_size_t, _P]),
+    }),
+    # the image gradient of the DNA tail and the gradient of a tiled action vector, which training through the generator's own
+    # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp)
+    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts runs on the HIP library only', {
+        'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
+        'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
+    }),
+    # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
+    # it is shown (ops.BnInferOp / BnCollectOp)
+    'bn_infer': Extension('include/acgan_bn_infer.h', 'BatchNorm with stored statistics runs on the HIP library only', {
+        'acg_bn_act_infer': (STATUS, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_float, c_int32, c_float, c_int32, _P]),
+        'acg_bn_collect_workspace_bytes': (c_size_t, [c_int64, c_int32]),
+        'acg_bn_collect': (STATUS, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
+    }),
+    # the exponential moving average of a scope's weights: the stand-alone update, the optimizer steps that carry it in their own
+    # launch, and the in-place exchange of two flat buffers (optim.StepOp, train.Trainer.ema_weights)
+    'ema': Extension('include/acgan_ema.h', 'the weight average runs on the HIP library only', {
+        'acg_ema_update': (STATUS, [_P, _P, c_int64, c_float, _P, _P, _P]),
+        'acg_adam_step_ema': (STATUS, [_P, _P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_float,
+                                       c_int32, c_float, c_float, _P, c_float, _P, _P, _P]),
+        'acg_rmsprop_step_ema': (STATUS, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float,
+                                          c_float, _P, c_float, _P, _P, _P]),
+        'acg_swap_f32': (STATUS, [_P, _P, c_int64, _P]),
+    }),
+    # SSIM as a training loss: sum_n (1 - SSIM_n) and its gradient with respect to the prediction (ops.SsimLossOp)
+    'ssim_loss': Extension('include/acgan_ssim_loss.h', 'the SSIM loss runs on the HIP library only', {
+        'acg_ssim_loss_workspace_bytes': (c_size_t, [c_int32] * 4),
+        'acg_ssim_loss': (STATUS, [_P, _P, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
+                                   _P, c_size_t, _P]),
+    }),
 }
 
 
@@ -228,7 +232,6 @@ def code(torch_dtype):
     if torch_dtype == torch.bfloat16:
         return ACG_BF16
     raise TypeError('no storage code for %s' % torch_dtype)
-VALUE_RETURNING = ('acg_version', 'acg_conv2d_splits', 'acg_conv2d_tile', 'acg_bn_bwd_slabs_ok', 'acg_bn_slabs_layout', 'acg_conv2d_slab_layouts', 'acg_conv2d_stats_blocks', 'acg_conv2d_stats_layout', 'acg_deconv2d_fwd_bias_act_ok')     # int32 results that are not status codes
 
 
 class AcgError(RuntimeError):
@@ -236,19 +239,29 @@ class AcgError(RuntimeError):
 
 
 class Library:
-    """A loaded C-ABI library; every int-returning entry point is checked and raises AcgError."""
+    """A loaded C-ABI library: the core table, ``extra``, and every extension the shared object exports (``extensions``, a
+    frozenset of EXTENSIONS keys; ``require`` names the ones it must).  Every STATUS entry point is checked and raises AcgError."""
 
-    def __init__(self, path, extra=None):
+    def __init__(self, path, extra=None, require=()):
         self.path = path
         self._cdll = ctypes.CDLL(path)
         sigs = dict(SIGNATURES, **(extra or {}))
         missing = [n for n in sigs if not hasattr(self._cdll, n)]
+        bound = []
+        for key, ext in EXTENSIONS.items():
+            absent = [n for n in ext.signatures if not hasattr(self._cdll, n)]
+            if key in require or len(absent) < len(ext.signatures):      # asked for, or partly there: a half-built library
+                missing += absent
+            if not absent:
+                sigs.update(ext.signatures)
+                bound.append(key)
         if missing:
             raise AcgError('%s does not export %s' % (path, ', '.join(missing)))
+        self.extensions = frozenset(bound)
         for name, (res, args) in sigs.items():
             fn = getattr(self._cdll, name)
-            fn.restype, fn.argtypes = res, args
-            if res is c_int32 and name not in VALUE_RETURNING:
+            fn.restype, fn.argtypes = (c_int32 if res is STATUS else res), args
+            if res is STATUS:
                 fn = self._checked(name, fn)
             setattr(self, name[4:], fn)
         if self.version() != ABI_VERSION:
@@ -265,6 +278,19 @@ class Library:
         return call
 
 
+def entry(lib, name):
+    """``lib.<name>``, the bound entry point acg_<name> of an extension header.  ``lib`` is a Library or any stand-in for one; one
+    that lacks the entry (the C oracle) is a clear error naming the header."""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        path = getattr(lib, 'path', lib)
+        for ext in EXTENSIONS.values():
+            if 'acg_' + name in ext.signatures:
+                raise AcgError('%s does not implement acg_%s (%s): %s' % (path, name, ext.header, ext.what))
+        raise AcgError('%s does not export acg_%s' % (path, name))
+    return fn
+
+
 _LIB = None
 
 
@@ -276,8 +302,7 @@ def get():
             raise RuntimeError(
                 '%s not found: the HIP kernels are not built and there is no fallback path. '
                 'Run `python -c "import __graft_entry__ as g; g.build()"` first.' % LIB_PATH)
-        _LIB = Library(LIB_PATH, extra=dict(METRICS_SIGNATURES, **CDNA_SIGNATURES, **ROLLOUT_SIGNATURES, **BN_INFER_SIGNATURES,
-                                              **EMA_SIGNATURES, **SSIM_LOSS_SIGNATURES))
+        _LIB = Library(LIB_PATH, require=tuple(EXTENSIONS))
     return _LIB
 
 
@@ -289,9 +314,9 @@ def load_tuning():
     and the ACG_* environment knobs, installed as the process's library.  The package itself never loads it."""
     global _LIB
     if not os.path.exists(TUNING_LIB_PATH):
-        # not shipped to the GPU box (.gpurunignore) and never built from inside a library loader: a hidden 16-way hipcc
-        # build at call time would also run under whatever preload (rocprofv3) the calling tool was started with
+        # never built from inside a library loader: a hidden 16-way hipcc build at call time would also run under whatever
+        # preload (rocprofv3) the calling tool was started with
         raise RuntimeError('%s not found: build it first, before any profiler or GPU process starts: '
                            '`make -s -j16 -C %s tuning`' % (TUNING_LIB_PATH, os.path.dirname(LIB_PATH)))
-    _LIB = Library(TUNING_LIB_PATH, extra=dict(METRICS_SIGNATURES, acg_debug_conv_plan=(c_int32, [c_int32, c_int32])))
+    _LIB = Library(TUNING_LIB_PATH, extra={'acg_debug_conv_plan': (STATUS, [c_int32, c_int32])})
     return _LIB

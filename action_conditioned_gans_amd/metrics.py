@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 
+DATA_RANGE = 2.0          # the project's frames lie in [-1, 1]
 K1, K2 = 0.01, 0.03
 SSIM_DEFINITION = ('tf.image.ssim: 11x11 Gaussian window (sigma 1.5, sum 1), VALID positions, population moments, '
                    'C1=(0.01 L)^2, C2=(0.03 L)^2, L=data_range; mean over positions, then channels')
@@ -29,16 +30,14 @@ def _stream_handle(stream, device):
     return ctypes.c_void_p(int(stream))
 
 
-def frame_metrics(pred, truth, data_range=2.0, stream=None, channels=None, lib=None):
+def frame_metrics(pred, truth, data_range=DATA_RANGE, stream=None, channels=None, lib=None):
     """Per-frame (SSIM, sum of squared errors) of device tensors ``pred`` / ``truth`` ``[..., H, W, C]`` (float32 or bfloat16,
     each on its own) -> two float32 device tensors of the leading shape.  ``channels``: the channels to score when the last
     axis is a wider channel pitch (the zero-padded pitch-4 copies of the frames); default all of them.  ``stream``: the
     stream to run on (a ``torch.cuda.Stream``, a raw ``hipStream_t`` or the session's ``rt.stream_ptr()``); default the
     current torch stream.  One partial pass and one per-frame sum, no float atomics: bit-identical across launches."""
     lib = lib or _lib.get()
-    if not hasattr(lib, 'frame_metrics'):
-        raise _lib.AcgError('%s does not implement acg_frame_metrics (include/acgan_metrics.h): SSIM runs on the GPU only, '
-                            'there is no host fallback' % getattr(lib, 'path', lib))
+    run, size = _lib.entry(lib, 'frame_metrics'), _lib.entry(lib, 'frame_metrics_workspace_bytes')
     if not (torch.is_tensor(pred) and torch.is_tensor(truth)):
         raise TypeError('frame_metrics takes device tensors')
     if pred.shape != truth.shape or pred.dim() < 3:
@@ -54,11 +53,11 @@ def frame_metrics(pred, truth, data_range=2.0, stream=None, channels=None, lib=N
     sqerr = torch.empty(n, dtype=torch.float32, device=pred.device)
     if n == 0:
         return ssim.view(lead), sqerr.view(lead)
-    ws_bytes = lib.frame_metrics_workspace_bytes(n, h, w)
+    ws_bytes = size(n, h, w)
     ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=pred.device)
-    lib.frame_metrics(ctypes.c_void_p(pred.data_ptr()), ctypes.c_void_p(truth.data_ptr()), ctypes.c_void_p(ssim.data_ptr()),
-                      ctypes.c_void_p(sqerr.data_ptr()), n, h, w, c, pitch, dtype, float(data_range), K1, K2,
-                      ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_handle(stream, pred.device))
+    run(ctypes.c_void_p(pred.data_ptr()), ctypes.c_void_p(truth.data_ptr()), ctypes.c_void_p(ssim.data_ptr()),
+        ctypes.c_void_p(sqerr.data_ptr()), n, h, w, c, pitch, dtype, float(data_range), K1, K2,
+        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream_handle(stream, pred.device))
     return ssim.view(lead), sqerr.view(lead)
 
 

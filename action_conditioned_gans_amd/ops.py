@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from . import graph as G
+from . import metrics
 from ._lib import ACG_F32, CONV_DGRAD, CONV_FWD, CONV_WGRAD, SLABS_QUADS, ConvDesc
 
 DNA_KERN_SIZE = 5          # ops.py:12
@@ -655,15 +656,6 @@ class BnApplyMomentsOp(G.Op):
 
 
 # ---- BatchNorm with stored statistics (include/acgan_bn_infer.h): batch-independent prediction ------------------------
-def _bn_infer_entry(rt, name):
-    """An entry of include/acgan_bn_infer.h (_lib.BN_INFER_SIGNATURES); a library without it (the C oracle) is a clear error."""
-    fn = getattr(rt.lib, name, None)
-    if fn is None:
-        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_bn_infer.h): BatchNorm with stored statistics runs on '
-                            'the HIP library only' % (getattr(rt.lib, 'path', rt.lib), name))
-    return fn
-
-
 def bn_statistics_state(name, c):
     """The stored statistics of the BatchNorm scope ``name`` (``g/conv1/BatchNorm``): graph STATE, not variables - slim's
     ``moving_mean`` (0) and ``moving_variance`` (1), float32 [c], plus ``calibration_rows``, the int64 count of the rows pooled
@@ -697,7 +689,7 @@ class BnInferOp(G.Op):
         super().__init__(G.get_default_graph(), name, [x, beta, mean, variance], [y])
 
     def bind(self, rt):
-        fn = _bn_infer_entry(rt, 'bn_act_infer')
+        fn = _lib.entry(rt.lib, 'bn_act_infer')
         x, beta, mean, variance = self.inputs
         y = self.outputs[0]
         args = (_p(x.buf), _p(beta.buf), _p(mean.buf), _p(variance.buf), _p(y.buf), self.rows, self.c, self.xp, self.yp, self.eps,
@@ -717,8 +709,8 @@ class BnCollectOp(G.Op):
         super().__init__(G.get_default_graph(), name, [x], [], control_inputs=[after])
 
     def bind(self, rt):
-        fn = _bn_infer_entry(rt, 'bn_collect')
-        ws, n = rt.workspace(_bn_infer_entry(rt, 'bn_collect_workspace_bytes')(self.rows, self.c))
+        fn = _lib.entry(rt.lib, 'bn_collect')
+        ws, n = rt.workspace(_lib.entry(rt.lib, 'bn_collect_workspace_bytes')(self.rows, self.c))
         self._keep = ws
         x = self.inputs[0]
         mean, variance, count = self.extras
@@ -939,15 +931,6 @@ class DnaBwdOp(G.Op):
         return lambda s: fn(*args, s)
 
 
-def _rollout_entry(rt, name):
-    """An entry of include/acgan_rollout.h (_lib.ROLLOUT_SIGNATURES); a library without it (the C oracle) is a clear error."""
-    fn = getattr(rt.lib, name, None)
-    if fn is None:
-        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_rollout.h): training through rollouts runs on the HIP '
-                            'library only' % (getattr(rt.lib, 'path', rt.lib), name))
-    return fn
-
-
 class DnaImageGradOp(G.Op):
     """acg_dna_bwd_image: the DNA tail's gradient with respect to its image - the exact adjoint of the gather under the forward's
     softmax(logits + bias) weights.  Reads the same ``dout`` (and ``dout2`` window of d(discriminator input)) as the layer's
@@ -962,7 +945,7 @@ class DnaImageGradOp(G.Op):
     def bind(self, rt):
         lg, dout = self.inputs[:2]
         b, h, w, c = self.outputs[0].shape
-        fn = _rollout_entry(rt, 'dna_bwd_image')
+        fn = _lib.entry(rt.lib, 'dna_bwd_image')
         pb = _p(self.inputs[2].buf) if self.fwd.has_bias else None
         p2, pitch2, off2, dt2 = None, 0, 0, 0
         if self.dout2 is not None:
@@ -1032,15 +1015,6 @@ class CdnaBwdOp(G.Op):
         return launch
 
 
-def _cdna_entry(rt, name):
-    """An entry of include/acgan_cdna.h (_lib.CDNA_SIGNATURES); a library without it (the C oracle) is a clear error."""
-    fn = getattr(rt.lib, name, None)
-    if fn is None:
-        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_cdna.h): the CDNA generator runs on the HIP library only'
-                            % (getattr(rt.lib, 'path', rt.lib), name))
-    return fn
-
-
 class CdnaCompositeOp(G.Op):
     """The CDNA generator's output stage in one kernel (acg_cdna_composite_fwd): normalise the per-sample kernels ``params``,
     transform the image with each (cdna_transformation's M pieces, kept in registers) and composite s_0 * image +
@@ -1059,7 +1033,7 @@ class CdnaCompositeOp(G.Op):
     def bind(self, rt):
         lg, img, par = self.inputs[:3]
         b, h, w, c = img.shape
-        fn = _cdna_entry(rt, 'cdna_composite_fwd')
+        fn = _lib.entry(rt.lib, 'cdna_composite_fwd')
         pb = _p(self.inputs[3].buf) if self.has_bias else None
         args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), _p(self.kern_norm.buf), b, h, w, c,
                 self.masks, self.ksize, self.relu_shift)
@@ -1095,8 +1069,8 @@ class CdnaCompositeBwdOp(G.Op):
         lg, img, par, kn, dout = self.inputs[:5]
         f = self.fwd
         b, h, w, c = img.shape
-        fn = _cdna_entry(rt, 'cdna_composite_bwd')
-        ws, n = rt.workspace(_cdna_entry(rt, 'cdna_composite_workspace_bytes')(b, h, w, c, f.masks, f.ksize))
+        fn = _lib.entry(rt.lib, 'cdna_composite_bwd')
+        ws, n = rt.workspace(_lib.entry(rt.lib, 'cdna_composite_workspace_bytes')(b, h, w, c, f.masks, f.ksize))
         self._keep = ws
         pb = _p(self.inputs[5].buf) if f.has_bias else None
         args = (_p(par.buf), _p(kn.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf), _p(self.outputs[0].buf),
@@ -1200,7 +1174,7 @@ class ActionGradOp(G.Op):
     def bind(self, rt):
         dcat, dact = self.inputs[0], self.outputs[0]
         pitch = dcat.shape[-1]
-        fn = _rollout_entry(rt, 'action_grad')
+        fn = _lib.entry(rt.lib, 'action_grad')
         args = (_p(dcat.buf), dcat.numel // pitch, pitch, self.c_off, dact.shape[-1], self.div, self.mod, _p(dact.buf), 0.0)
         return lambda s: fn(*args, s)
 
@@ -1729,16 +1703,7 @@ class FrameLossOp(LossHead):
         return [(a, op.dgen)]
 
 
-def _ssim_entry(rt, name):
-    """An entry of include/acgan_ssim_loss.h (_lib.SSIM_LOSS_SIGNATURES); a library without it (the C oracle) is a clear error."""
-    fn = getattr(rt.lib, name, None)
-    if fn is None:
-        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_ssim_loss.h): the SSIM loss runs on the HIP library only'
-                            % (getattr(rt.lib, 'path', rt.lib), name))
-    return fn
-
-
-SSIM_DATA_RANGE, SSIM_K1, SSIM_K2 = 2.0, 0.01, 0.03      # frames in [-1, 1]; include/acgan_metrics.h
+SSIM_DATA_RANGE, SSIM_K1, SSIM_K2 = metrics.DATA_RANGE, metrics.K1, metrics.K2      # the SSIM the evaluation reports
 
 
 class SsimLossOp(LossHead):
@@ -1761,7 +1726,7 @@ class SsimLossOp(LossHead):
     def bind(self, rt):
         gen, gt = self.inputs
         b, h, w, c = gen.shape
-        fn, size = _ssim_entry(rt, 'ssim_loss'), _ssim_entry(rt, 'ssim_loss_workspace_bytes')
+        fn, size = _lib.entry(rt.lib, 'ssim_loss'), _lib.entry(rt.lib, 'ssim_loss_workspace_bytes')
         ws, n = rt.workspace(size(b, h, w, c))
         self._keep = ws
         # the gradient op's own value output is read by nobody (FrameLossOp.bind): gradient only

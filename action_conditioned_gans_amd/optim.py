@@ -16,6 +16,7 @@ shape (train.py:91-102) and TensorFlow-1.0's update formulas.  ``mi
 """
 import torch
 
+from . import _lib
 from . import graph as G
 from . import ops as O
 
@@ -132,16 +133,6 @@ class WeightAverage:
         return (_p(self.shadow.buf), self.decay, _p(self.num_updates.buf), _p(self.done.buf))
 
 
-def _ema_entry(rt, name):
-    """An entry of include/acgan_ema.h (_lib.EMA_SIGNATURES); a library without it (the C oracle) is a clear error."""
-    fn = getattr(rt.lib, name, None)
-    if fn is None:
-        from . import _lib
-        raise _lib.AcgError('%s does not implement acg_%s (include/acgan_ema.h): the weight average runs on the HIP library only'
-                            % (getattr(rt.lib, 'path', rt.lib), name))
-    return fn
-
-
 class StepOp(G.Op):
     """One fused optimizer launch over the flat buffers of a scope.  ``ema`` (a WeightAverage of the scope, or None): the
     scope's weight average is updated from the new parameters behind the update -
@@ -167,7 +158,7 @@ class StepOp(G.Op):
         if self.ema is None:
             return self._bind_update(rt)
         ema, p = self.ema, self.inputs[0]
-        update = _ema_entry(rt, 'ema_update')
+        update = _lib.entry(rt.lib, 'ema_update')
         if not self.graph.weight_copies.get(self.scope) and getattr(rt, 'fuse_ema', True):
             fused = self.opt._bind_step_ema(rt, self, self.program_clip, ema)
             if fused is not None:
@@ -249,7 +240,6 @@ class Optimizer:
         """One launch for the update of the scope and the refresh of its bf16 filter copies, or None (no copies: a float32
         graph; more filters than one list holds)."""
         import ctypes
-        from . import _lib
         entries = op.graph.weight_copies.get(op.scope) or []
         if not entries or len(entries) > _lib.PREP_MAX:
             return None
@@ -408,7 +398,7 @@ class AdamOptimizer(Optimizer):
     def _bind_step_ema(self, rt, op, clip, ema):
         p, g, m, v, step = op.inputs
         lo, hi = clip if clip else (0.0, 0.0)
-        adam, before = _ema_entry(rt, 'adam_step_ema'), self._step_inc_launch(rt, op, step)
+        adam, before = _lib.entry(rt.lib, 'adam_step_ema'), self._step_inc_launch(rt, op, step)
         args = (_p(p.buf), _p(g.buf), _p(m.buf), _p(v.buf), _p(step.buf), p.numel, self.lr, self.b1, self.b2, self.eps,
                 op.grad_scale, 1 if clip else 0, lo, hi) + ema.args()
 
@@ -448,7 +438,7 @@ class RMSPropOptimizer(Optimizer):
         lo, hi = clip if clip else (0.0, 0.0)
         args = (_p(p.buf), _p(g.buf), _p(ms.buf), p.numel, self.lr, self.decay, self.eps, op.grad_scale,
                 1 if clip else 0, lo, hi) + ema.args()
-        fn = _ema_entry(rt, 'rmsprop_step_ema')
+        fn = _lib.entry(rt.lib, 'rmsprop_step_ema')
         return lambda s: fn(*args, s)
 
     def _opt_args(self, rt, op, clip):

@@ -20,6 +20,7 @@ import time
 import numpy as np
 import torch
 
+from . import _lib
 from . import graph as G
 from . import models as M
 from . import ops as O
@@ -268,7 +269,7 @@ class Trainer:
         flat, shadow = self._ema_buffers()
         if self._ema_swapped:
             raise RuntimeError('ema_weights() is already entered')
-        swap = optim._ema_entry(self.sess.rt, 'swap_f32')
+        swap = _lib.entry(self.sess.rt.lib, 'swap_f32')
         args = (optim._p(flat), optim._p(shadow), flat.numel())
 
         def exchange():

@@ -509,4 +509,4 @@ def test_cli_calibrated_predictions_do_not_move_with_the_batch_size(tmp_path):
 
 def test_library_exports_the_bn_infer_table():
     lib = _lib.get()
-    assert all(hasattr(lib, n[4:]) for n in _lib.BN_INFER_SIGNATURES)
+    assert all(hasattr(lib, n[4:]) for n in _lib.EXTENSIONS['bn_infer'].signatures)

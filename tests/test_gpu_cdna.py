@@ -295,4 +295,4 @@ def test_cli_train_then_evaluate(tmp_path):
 
 def test_library_exports_the_cdna_table():
     lib = _lib.get()
-    assert all(hasattr(lib, n[4:]) for n in _lib.CDNA_SIGNATURES)
+    assert all(hasattr(lib, n[4:]) for n in _lib.EXTENSIONS['cdna'].signatures)

@@ -225,8 +225,8 @@ def test_arguments_are_checked():
 def test_library_exports_the_ema_table():
     lib = _lib.get()
     cdll = ctypes.CDLL(_lib.LIB_PATH)
-    assert set(_lib.EMA_SIGNATURES) == {'acg_ema_update', 'acg_adam_step_ema', 'acg_rmsprop_step_ema', 'acg_swap_f32'}
-    for name in _lib.EMA_SIGNATURES:
+    assert set(_lib.EXTENSIONS['ema'].signatures) == {'acg_ema_update', 'acg_adam_step_ema', 'acg_rmsprop_step_ema', 'acg_swap_f32'}
+    for name in _lib.EXTENSIONS['ema'].signatures:
         assert hasattr(cdll, name) and callable(getattr(lib, name[4:]))
     assert lib.version() == _lib.ABI_VERSION == 8
 

@@ -220,4 +220,4 @@ def test_cli_train_with_rollouts_then_evaluate(tmp_path):
 
 def test_library_exports_the_rollout_table():
     lib = _lib.get()
-    assert all(hasattr(lib, n[4:]) for n in _lib.ROLLOUT_SIGNATURES)
+    assert all(hasattr(lib, n[4:]) for n in _lib.EXTENSIONS['rollout'].signatures)

@@ -146,7 +146,7 @@ def test_invalid_arguments_are_errors():
 
 def test_library_exports_the_table():
     lib = _lib.get()
-    assert all(hasattr(lib, n[4:]) for n in _lib.SSIM_LOSS_SIGNATURES)
+    assert all(hasattr(lib, n[4:]) for n in _lib.EXTENSIONS['ssim_loss'].signatures)
 
 
 # ---- through the runtime ---------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 optimizer sequencing, scopes).  The kernels come from the C oracle through the SAME C ABI - injected
 here, by the test, as a stand-in device library; the product itself has no such path."""
 import ctypes
+import os
 
 import numpy as np
 import pytest
@@ -16,6 +17,9 @@ from action_conditioned_gans_amd import models as M
 from action_conditioned_gans_amd import ops as O
 from action_conditioned_gans_amd import optim
 from action_conditioned_gans_amd import train as T
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def cpu_session(**kw):
@@ -326,23 +330,77 @@ def test_side_chain_flags_and_hoisting():
     assert [o for o in out if o.side_stream] == [o for o in ops if o.side_stream]      # its own order is kept
 
 
+def _declared(header):
+    """The acg_*( names a header declares, comments stripped (they mention entry points of other headers)."""
+    import re
+    text = open(os.path.join(ROOT, header)).read()
+    text = re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+    tuning = ' '.join(re.findall(r'#ifdef ACG_TUNING(.*?)#endif', text, flags=re.S))
+    text = re.sub(r'#ifdef ACG_TUNING.*?#endif', '', text, flags=re.S)         # tuning builds only: not part of the shipped ABI
+    names = lambda t: set(re.findall(r'\b(acg_[a-z0-9_]+)\s*\(', t))
+    return names(text), names(tuning)
+
+
 def test_c_abi_exports_every_declared_symbol():
-    """include/acgan_hip.h <-> both libraries: every declared entry point is exported (no compute here)."""
-    import re, os, ctypes
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, 'include', 'acgan_hip.h')).read()
-    tuning = re.findall(r'#ifdef ACG_TUNING(.*?)#endif', header, flags=re.S)
-    header = re.sub(r'#ifdef ACG_TUNING.*?#endif', '', header, flags=re.S)     # tuning builds only: not part of the shipped ABI
-    declared = set(re.findall(r'\b(acg_[a-z0-9_]+)\s*\(', header))
-    declared -= {'acg_conv_desc', 'acg_stream_t', 'acg_edge_t'}
-    assert declared == set(_lib.SIGNATURES), sorted(declared ^ set(_lib.SIGNATURES))
+    """include/*.h <-> the binding's tables <-> the libraries: every header's declared entry points are its table, and
+    libacgan_hip.so exports every one of them (no compute here)."""
     hip = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert hasattr(hip, name), 'libacgan_hip.so lacks ' + name
-    for name in set(re.findall(r'\b(acg_[a-z0-9_]+)\s*\(', ' '.join(tuning))):
-        assert not hasattr(hip, name), 'the shipped library exports the tuning hook ' + name
+    tables = {'include/acgan_hip.h': _lib.SIGNATURES}
+    tables.update((ext.header, ext.signatures) for ext in _lib.EXTENSIONS.values())
+    assert sorted(tables) == sorted('include/' + f for f in os.listdir(os.path.join(ROOT, 'include')))
+    for header, table in tables.items():
+        declared, tuning = _declared(header)
+        if header == 'include/acgan_hip.h':
+            declared -= {'acg_conv_desc', 'acg_stream_t', 'acg_edge_t'}
+        assert declared == set(table), (header, sorted(declared ^ set(table)))
+        for name in declared:
+            assert hasattr(hip, name), 'libacgan_hip.so lacks %s (%s)' % (name, header)
+        for name in tuning:
+            assert not hasattr(hip, name), 'the shipped library exports the tuning hook ' + name
     assert _lib.get().version() == _lib.ABI_VERSION
     assert cbind.load().version() == _lib.ABI_VERSION
+
+
+def test_extension_tables_are_disjoint_and_values_are_marked():
+    """One owner per entry point, and the int32 results that are values - everything else int32 is a checked STATUS."""
+    tables = [_lib.SIGNATURES] + [ext.signatures for ext in _lib.EXTENSIONS.values()]
+    assert list(_lib.EXTENSIONS) == ['metrics', 'cdna', 'rollout', 'bn_infer', 'ema', 'ssim_loss']
+    names = [n for t in tables for n in t]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    values = {n for t in tables for n, (res, _) in t.items() if res is ctypes.c_int32}
+    assert values == {'acg_version', 'acg_conv2d_splits', 'acg_conv2d_tile', 'acg_bn_bwd_slabs_ok', 'acg_bn_slabs_layout',
+                      'acg_conv2d_slab_layouts', 'acg_conv2d_stats_blocks', 'acg_conv2d_stats_layout', 'acg_deconv2d_fwd_bias_act_ok'}
+    lib = _lib.get()
+    for n in values:                                # bound as the ctypes function itself, not behind the status check
+        assert getattr(lib, n[4:]).restype is ctypes.c_int32, n
+
+
+def test_library_binds_the_extensions_it_exports():
+    """The product library has every extension, required (get()) or not (a bare Library(path): bench.py --lib, tools --lib); the
+    C oracle has none, says so by header when asked for an entry, and cannot be loaded where one is required."""
+    every = frozenset(_lib.EXTENSIONS)
+    lib = _lib.get()
+    assert lib.extensions == every
+    assert _lib.Library(_lib.LIB_PATH).extensions == every
+    public = {k for k, v in vars(lib).items() if not k.startswith('_') and callable(v)}
+    assert public == {n[4:] for t in [_lib.SIGNATURES] + [e.signatures for e in _lib.EXTENSIONS.values()] for n in t}
+    assert _lib.entry(lib, 'ema_update') is lib.ema_update
+    oracle = cbind.load()
+    assert oracle.extensions == frozenset()
+    with pytest.raises(_lib.AcgError) as err:
+        _lib.entry(oracle, 'ema_update')
+    for part in ('acg_ema_update', 'include/acgan_ema.h', cbind.SO_PATH):
+        assert part in str(err.value), (part, str(err.value))
+    with pytest.raises(_lib.AcgError, match='acg_swap_f32'):
+        _lib.Library(cbind.SO_PATH, require=('ema',))
+
+
+def test_library_refuses_a_partly_exported_extension(monkeypatch):
+    """Some but not all symbols of a group: a half-built library, refused at load with the missing names (nobody required it)."""
+    ema = _lib.EXTENSIONS['ema']
+    monkeypatch.setitem(_lib.EXTENSIONS, 'ema', ema._replace(signatures=dict(ema.signatures, acg_ema_not_built=(_lib.STATUS, []))))
+    with pytest.raises(_lib.AcgError, match='does not export acg_ema_not_built$'):
+        _lib.Library(_lib.LIB_PATH)
 
 
 def test_cdna_transformation_layer_and_gradients():
