@@ -14,6 +14,32 @@ def _p(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def bn_path(ws, launches=1):
+    """Which kernel family of bn.hip used the BatchNorm workspace ``ws`` (zero before, ``launches`` calls since) - read from what
+    acgan_hip.h documents about it, not from the kernels: -> ('resident', None) the whole workspace is still zero;
+    ('two_launch', None) word 0 is zero and partial sums lie behind the 16 state bytes; ('grid', slots) the epoch (uint32 word 0)
+    advanced by one per launch - ``slots`` counts the 512-byte exchange slots behind the state that hold anything: the number of
+    blocks of a grid with more than one row block per (group, 32-channel chunk), each of which publishes 64 tagged granules."""
+    w = ws.detach().cpu()
+    epoch = int(w[0:4].view(torch.int32)[0])
+    body = w[16:]
+    if epoch == 0:
+        assert not bool(w[4:16].any()), 'BatchNorm workspace: state words set although the epoch is zero'
+        return ('two_launch' if bool(body.any()) else 'resident'), None
+    assert epoch == launches, 'BatchNorm workspace: the epoch advanced by %d in %d launch(es) of a grid kernel' % (epoch, launches)
+    n = body.numel() // 512
+    slots = int(body[:n * 512].view(n, 512).any(dim=1).sum())
+    return 'grid', slots
+
+
+def bn_grid_rows(slots, rows_per_group, c, groups):
+    """Rows per block (128, 512 or 1024) of a grid kernel that published ``slots`` slots; None when no candidate (or more than
+    one) explains the count."""
+    per = (c + 31) // 32 * groups
+    fit = [r for r in (128, 512, 1024) if -(-rows_per_group // r) * per == slots]
+    return fit[0] if len(fit) == 1 else None
+
+
 class Abi:
     def __init__(self, lib, device, conv_dtype=L.ACG_F32):
         self.lib, self.device, self.conv_dtype = lib, torch.device(device), conv_dtype
@@ -351,36 +377,51 @@ class Abi:
         return wsd, wsw
 
     # ---- bn / bias
-    def bn_act_fwd(self, x, beta, act, groups=1, eps=1e-3, leak=0.2, y_dtype=None, c=None):
+    def _bn_ws(self, ws, rows, c, groups):
+        """The caller's workspace (a view out of `ws` / `bn_ws`) or a fresh zeroed one -> (view, bytes)."""
+        if ws is None:
+            return self.ws(self.lib.bn_workspace_bytes(rows, c, groups))
+        return ws, ws.numel()
+
+    def bn_act_fwd(self, x, beta, act, groups=1, eps=1e-3, leak=0.2, y_dtype=None, c=None, y=None, ws=None, want_ws=False):
         """Storage types follow the tensors: x float32 or bfloat16, y like x unless ``y_dtype`` says otherwise.
-        ``c`` < x.shape[-1]: x rows carry pad channels (pitch x.shape[-1]); y is then dense [.., c]."""
+        ``c`` < x.shape[-1]: x rows carry pad channels (pitch x.shape[-1]); y is then dense [.., c] - or ``y`` as the caller
+        prepared it (pitch y.shape[-1]).  ``ws``: the BatchNorm workspace to use (else a fresh one); ``want_ws``: hand it back
+        as a fourth result (``bn_path`` reads which kernel family ran out of it)."""
         xp = x.shape[-1]
         c = c or xp
         rows = x.numel() // xp
-        y = torch.zeros(*x.shape[:-1], c, dtype=y_dtype or x.dtype, device=self.device)
+        if y is None:
+            y = torch.zeros(*x.shape[:-1], c, dtype=y_dtype or x.dtype, device=self.device)
         mean, rstd = self.empty(groups * c), self.empty(groups * c)
-        ws, n = self.ws(self.lib.bn_workspace_bytes(rows, c, groups))
-        self.lib.bn_act_fwd(_p(x), _p(beta), _p(y), _p(mean), _p(rstd), rows, c, xp, c, groups, eps, ACT[act], leak,
+        ws, n = self._bn_ws(ws, rows, c, groups)
+        self.lib.bn_act_fwd(_p(x), _p(beta), _p(y), _p(mean), _p(rstd), rows, c, xp, y.shape[-1], groups, eps, ACT[act], leak,
                             L.dtype2(L.code(x.dtype), L.code(y.dtype)), self.bn_flags, _p(ws), n, self.stream())
         self.no_timeout(ws)
-        return y, mean, rstd
+        return (y, mean, rstd, ws) if want_ws else (y, mean, rstd)
 
-    def bn_act_bwd(self, x, dy, beta, mean, rstd, act, groups=1, leak=0.2, dbeta=None, accumulate=0.0, dx_dtype=None):
-        """``dx_dtype`` bfloat16 with float32 x / dy: ACG_DTYPE2(ACG_F32, ACG_BF16), the float32 head of a bf16 network."""
-        xp, c = x.shape[-1], dy.shape[-1]
+    def bn_act_bwd(self, x, dy, beta, mean, rstd, act, groups=1, leak=0.2, dbeta=None, accumulate=0.0, dx_dtype=None, c=None, dx=None,
+                   ws=None, want_ws=False):
+        """``dx_dtype`` bfloat16 with float32 x / dy: ACG_DTYPE2(ACG_F32, ACG_BF16), the float32 head of a bf16 network.
+        ``c`` < dy.shape[-1]: dy rows carry pad channels too (pitch dy.shape[-1]).  ``dx``: as the caller prepared it (shaped
+        like x).  ``dbeta`` with ``accumulate``: dbeta = accumulate * dbeta + the sums (in place).  ``ws`` / ``want_ws``: as
+        in bn_act_fwd (a third result)."""
+        xp = x.shape[-1]
+        c = c or dy.shape[-1]
         rows = x.numel() // xp
-        dx = torch.zeros_like(x, dtype=dx_dtype or x.dtype)
+        if dx is None:
+            dx = torch.zeros_like(x, dtype=dx_dtype or x.dtype)
         if dbeta is None:
             dbeta = self.empty(c)
-        ws, n = self.ws(self.lib.bn_workspace_bytes(rows, c, groups))
+        ws, n = self._bn_ws(ws, rows, c, groups)
         dt = L.dtype2(L.code(x.dtype), L.code(dy.dtype))
         if dx.dtype != x.dtype:
             assert x.dtype == torch.float32 and dy.dtype == torch.float32 and dx.dtype == torch.bfloat16
             dt = L.dtype2(L.ACG_F32, L.ACG_BF16)
-        self.lib.bn_act_bwd(_p(x), _p(dy), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dbeta), accumulate, rows, c, xp, c,
+        self.lib.bn_act_bwd(_p(x), _p(dy), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dbeta), accumulate, rows, c, xp, dy.shape[-1],
                             groups, ACT[act], leak, dt, self.bn_flags, _p(ws), n, self.stream())
         self.no_timeout(ws)
-        return dx, dbeta
+        return (dx, dbeta, ws) if want_ws else (dx, dbeta)
 
     # ---- BatchNorm statistics out of the producing convolution's epilogue
     def conv_bn_fused(self, x, w, beta, stride, padding, act, groups=1, transposed=False, eps=1e-3, leak=0.2):
@@ -433,9 +474,10 @@ class Abi:
             d.in_pitch = d.out_pitch = 0
         return d, which, c, oshape
 
-    def conv_bn_handoff(self, x, w, beta, stride, padding, act, groups=1, transposed=False, layout=None, eps=1e-3, leak=0.2):
+    def conv_bn_handoff(self, x, w, beta, stride, padding, act, groups=1, transposed=False, layout=None, eps=1e-3, leak=0.2, want_ws=False):
         """acg_(de)conv2d_fwd_slabs + acg_bn_act_fwd_slabs -> (conv output as written back, y, mean, rstd, layout), float32;
-        None when the planner does not split this layer.  ``layout`` None: what acg_bn_slabs_layout asks for."""
+        None when the planner does not split this layer.  ``layout`` None: what acg_bn_slabs_layout asks for.  ``want_ws``: the
+        BatchNorm workspace as a sixth result (``bn_path``)."""
         d, which, c, oshape = self._layer_desc(x.shape, w.shape, stride, padding, transposed)
         splits = self.lib.conv2d_splits(ctypes.byref(d), which, self.conv_dtype)
         if splits < 2:
@@ -461,14 +503,16 @@ class Abi:
         self.lib.bn_act_fwd_slabs(_p(ws), splits, _p(conv), _p(beta), _p(y), _p(mean), _p(rstd), rows, c, cp, cp, groups, eps, ACT[act], leak,
                                   self.conv_dtype, layout, self.bn_flags, _p(bws), bn, self.stream())
         self.no_timeout(bws)
-        return conv[..., :c].float(), y[..., :c].float(), mean, rstd, layout
+        res = (conv[..., :c].float(), y[..., :c].float(), mean, rstd, layout)
+        return res + (bws,) if want_ws else res
 
     def dgrad_bn_bwd_handoff(self, xb, beta, mean, rstd, act, dy2, w2, stride, padding, groups=1, transposed=False, pair_x=None, layout=None,
-                             leak=0.2):
+                             leak=0.2, dbeta=None, accumulate=0.0, want_ws=False):
         """BatchNorm backward fed by the split input gradient of the NEXT layer (filter ``w2``, output gradient ``dy2``; its
         input is the BatchNorm's output, shaped like ``xb``): acg_(de)conv2d_dgrad_slabs - or, with ``pair_x`` (that layer's
         input), acg_(de)conv2d_bwd_pair with flag 2 - then acg_bn_act_bwd_slabs.  -> (dx, dbeta, layout) float32, or None
-        when that input gradient is not split or the BatchNorm cannot take slabs."""
+        when that input gradient is not split or the BatchNorm cannot take slabs.  ``dbeta`` with ``accumulate``: dbeta =
+        accumulate * dbeta + the sums (in place).  ``want_ws``: the BatchNorm workspace as a fourth result (``bn_path``)."""
         if transposed:
             d = self._adj(xb.shape, tuple(w2.shape), stride)
             which = L.CONV_FWD
@@ -506,12 +550,14 @@ class Abi:
                2 | (4 if layout == L.SLABS_QUADS else 0), self.stream())
         x16 = self.to16(xb) if self.half else xb
         dx = torch.zeros(*xb.shape[:-1], cp, dtype=tdt, device=self.device)
-        dbeta = self.empty(c)
+        if dbeta is None:
+            dbeta = self.empty(c)
         bws, bn = self.ws(self.lib.bn_workspace_bytes(rows, c, groups))
-        self.lib.bn_act_bwd_slabs(_p(x16), _p(ws), splits, _p(beta), _p(mean), _p(rstd), _p(dx), _p(dbeta), 0.0, rows, c, cp, cp, groups,
+        self.lib.bn_act_bwd_slabs(_p(x16), _p(ws), splits, _p(beta), _p(mean), _p(rstd), _p(dx), _p(dbeta), accumulate, rows, c, cp, cp, groups,
                                   ACT[act], leak, self.conv_dtype, layout, self.bn_flags, _p(bws), bn, self.stream())
         self.no_timeout(bws)
-        return dx[..., :c].float(), dbeta, layout
+        res = (dx[..., :c].float(), dbeta, layout)
+        return res + (bws,) if want_ws else res
 
     # ---- synchronised BatchNorm entries (statistics supplied by the caller)
     def bn_moments(self, x, groups=1, c=None):
@@ -545,16 +591,20 @@ class Abi:
                              L.dtype2(L.code(x.dtype), L.code(dy.dtype)), _p(ws), n, self.stream())
         return sums
 
-    def bn_act_bwd_sums(self, x, dy, beta, mean, rstd, sums, local_sums, total_rows, act, groups=1, leak=0.2, c=None, dx_dtype=None):
+    def bn_act_bwd_sums(self, x, dy, beta, mean, rstd, sums, local_sums, total_rows, act, groups=1, leak=0.2, c=None, dx_dtype=None, dbeta=None,
+                        accumulate=0.0):
+        """``dbeta`` with ``accumulate``: dbeta = accumulate * dbeta + the local sums (in place)."""
         xp = x.shape[-1]
         c = c or xp
         rows = x.numel() // xp
-        dx, dbeta = torch.zeros_like(x, dtype=dx_dtype or x.dtype), self.empty(c)
+        dx = torch.zeros_like(x, dtype=dx_dtype or x.dtype)
+        if dbeta is None:
+            dbeta = self.empty(c)
         dt = L.dtype2(L.code(x.dtype), L.code(dy.dtype))
         if dx.dtype != x.dtype:
             dt = L.dtype2(L.ACG_F32, L.ACG_BF16)
         self.lib.bn_act_bwd_sums(_p(x), _p(dy), _p(beta), _p(mean), _p(rstd), _p(sums), _p(local_sums), total_rows, _p(dx),
-                                 _p(dbeta), 0.0, rows, c, xp, dy.shape[-1], groups, ACT[act], leak, dt, self.stream())
+                                 _p(dbeta), accumulate, rows, c, xp, dy.shape[-1], groups, ACT[act], leak, dt, self.stream())
         return dx, dbeta
 
     def bias_act_fwd(self, x, bias, act, leak=0.2, c=None, y_dtype=None):
@@ -607,14 +657,17 @@ class Abi:
                          L.code(out2.dtype) if out2 is not None else 0, b, h, w, c, k, L.code(logits.dtype), self.stream())
         return out
 
-    def dna_bwd(self, logits, img, dout, k, bias=None, want_dbias=False, dout2=None, dout2_off=0):
-        """``dout2`` [B,H,W,pitch]: its channels [dout2_off, dout2_off + C) are added to dout."""
+    def dna_bwd(self, logits, img, dout, k, bias=None, want_dbias=False, dout2=None, dout2_off=0, dbias=None, accumulate=0.0):
+        """``dout2`` [B,H,W,pitch]: its channels [dout2_off, dout2_off + C) are added to dout.  ``dbias`` with ``accumulate``:
+        dbias = accumulate * dbias + the tap sums (in place; implies want_dbias)."""
         b, h, w, c = img.shape
         dl = torch.zeros_like(logits)
-        dbias = self.empty(k * k) if want_dbias else None
+        want_dbias = want_dbias or dbias is not None
+        if want_dbias and dbias is None:
+            dbias = self.empty(k * k)
         ws, n = self.ws(self.lib.dna_workspace_bytes(b, h, w, k))
         self.lib.dna_bwd(_p(logits), _p(bias), _p(img), _p(dout), _p(dout2), dout2.shape[-1] if dout2 is not None else 0, dout2_off,
-                         L.code(dout2.dtype) if dout2 is not None else 0, _p(dl), _p(dbias), 0.0, b, h, w, c, k, L.code(logits.dtype),
+                         L.code(dout2.dtype) if dout2 is not None else 0, _p(dl), _p(dbias), accumulate, b, h, w, c, k, L.code(logits.dtype),
                          _p(ws), n, self.stream())
         return (dl, dbias) if want_dbias else dl
 

@@ -720,7 +720,9 @@ DNA_SHAPES = [(2, 64, 64, 3, 5), (1, 16, 16, 3, 6), (1, 24, 20, 3, 11), (2, 7, 5
 
 def case_sync_bn_entries(abi, shape, act, groups, tol):
     """The four synchronised-BatchNorm entries on ONE rank (global = local) must reproduce acg_bn_act_fwd / _bwd, and
-    with doubled total_rows and sums of two identical halves they must give the two-rank answer for identical shards."""
+    with doubled total_rows and sums of two identical halves they must give the two-rank answer for identical shards.  The forward
+    pair is also held to float64 (acg_bn_moments: mean and biased variance; acg_bn_act_fwd_moments: y, mean, rstd), and
+    acg_bn_act_bwd_sums accumulates dbeta with 0 (into NaN: not read), 1 and 0.5 - dx bit-identical across the three."""
     g = torch.Generator().manual_seed(9)
     dev = abi.device
     x = (torch.randn(*shape, generator=g) * 2 + 0.5).to(dev)
@@ -732,10 +734,23 @@ def case_sync_bn_entries(abi, shape, act, groups, tol):
     y, mean, rstd = abi.bn_act_fwd_moments(x, beta, mom, act, groups=groups)
     tag = 'sync_bn%s %s g%d' % (shape, act, groups)
     close(mean, mean_ref, tol, tag + ' mean'); close(rstd, rstd_ref, tol * 4, tag + ' rstd'); close(y, y_ref, tol * 4, tag + ' y')
+    x64 = x.double().cpu()
+    xg64 = x64.reshape(groups, -1, shape[-1])
+    m64, v64 = xg64.mean(1), xg64.var(1, unbiased=False)
+    mom64 = torch.stack([m64, v64], dim=1).reshape(-1)                 # [group][{mean, var}][channel], as acg_bn_moments lays it out
+    close(mom, mom64, tol, tag + ' moments vs float64')
+    close(mean, m64.reshape(-1), tol, tag + ' mean vs float64'); close(rstd, (1.0 / torch.sqrt(v64 + 1e-3)).reshape(-1), tol, tag + ' rstd vs float64')
+    close(y, _bn_ref(x64, beta.double().cpu(), act, groups), tol, tag + ' y vs float64')
     sums = abi.bn_bwd_sums(x, dy, beta, mean_ref, rstd_ref, act, groups=groups)
     rows_per_group = x.numel() // shape[-1] // groups
     dx, dbeta = abi.bn_act_bwd_sums(x, dy, beta, mean_ref, rstd_ref, sums, sums, rows_per_group, act, groups=groups)
     close(dx, dx_ref, tol * 8, tag + ' dx'); close(dbeta, dbeta_ref, tol * 8, tag + ' dbeta')
+    prev = randn((shape[-1],), 91, max(float(dbeta_ref.abs().mean()), 1e-3))
+    for acc in (0.0, 1.0, 0.5):
+        start = (torch.full_like(prev, float('nan')) if acc == 0 else prev.clone()).to(dev)
+        dxa, dba = abi.bn_act_bwd_sums(x, dy, beta, mean_ref, rstd_ref, sums, sums, rows_per_group, act, groups=groups, dbeta=start, accumulate=acc)
+        assert torch.equal(dxa, dx), tag + ' accumulate %g: dx differs from the plain run' % acc
+        close(dba, (acc * prev.double() if acc else 0.0) + dbeta_ref.double().cpu(), tol * 8, tag + ' dbeta accumulate %g' % acc)
     # two ranks holding the SAME shard: global sums double, total rows double -> dx unchanged, dbeta still the local sum
     dx2, dbeta2 = abi.bn_act_bwd_sums(x, dy, beta, mean_ref, rstd_ref, sums * 2, sums, 2 * rows_per_group, act, groups=groups)
     close(dx2, dx_ref, tol * 8, tag + ' dx (two identical ranks)'); close(dbeta2, dbeta_ref, tol * 8, tag + ' dbeta (two identical ranks)')
@@ -770,6 +785,12 @@ def case_sync_bn_entries_bf16(abi, tol):
         dx, dbeta = abi.bn_act_bwd_sums(x, dy, beta, mean_ref, rstd_ref, sums, sums, rows_per_group, act, groups=groups, c=c)
         assert dx.dtype == torch.bfloat16 and (dx[..., c:] == 0).all()
         close(dx[..., :c].float(), dx64, 8e-3, tag + ' dx'); close(dbeta, db64, 2e-4, tag + ' dbeta')
+        prev = randn((c,), 92, max(float(db64.abs().mean()), 1e-3))
+        for acc in (0.0, 1.0, 0.5):                 # dbeta accumulated: 0 into NaN (not read), 1 and 0.5 into a seeded vector
+            start = (torch.full_like(prev, float('nan')) if acc == 0 else prev.clone()).to(dev)
+            dxa, dba = abi.bn_act_bwd_sums(x, dy, beta, mean_ref, rstd_ref, sums, sums, rows_per_group, act, groups=groups, c=c, dbeta=start, accumulate=acc)
+            assert torch.equal(dxa, dx), tag + ' accumulate %g: dx differs from the plain run' % acc
+            close(dba, (acc * prev.double() if acc else 0.0) + db64, 2e-4, tag + ' dbeta accumulate %g' % acc)
     # the float32 head (d/conv6): x float32 at a pitch of 8, y / dy dense float32, dx bf16
     for lead, c, groups in [((8, 2, 2), 1, 2), ((6, 3, 3), 5, 1)]:
         x32 = torch.zeros(*lead, 8, device=dev)

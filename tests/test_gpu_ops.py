@@ -252,7 +252,7 @@ def test_deconv_small_maps_walk_live_taps_only(hip_abi, shape):
 
 
 @pytest.mark.parametrize('shape', C.BN_SHAPES + [((32, 32, 32), 128, 1, 'relu'), ((64, 4, 4), 512, 2, 'lrelu'),
-                                            # register-resident kernels (<= 4096 rows per group): exact fit, one row past it, ragged rows, 3 groups
+                                            # register-resident kernels (<= 2048 rows per group; the whole path matrix: test_gpu_bn_paths.py): exact fit, one row past it, ragged rows, 3 groups
                                             ((4, 32, 32), 16, 1, 'relu'), ((1, 17, 241), 8, 1, 'lrelu'), ((3, 9, 19), 12, 3, None),
                                             ((2, 45, 45), 4, 2, 'relu'), ((2, 30, 30), 3, 1, 'lrelu')], ids=str)
 def test_bn(hip_abi, shape):

@@ -3,6 +3,7 @@ must agree on every op of the hot path.  This is what stands in for reference go
 (parity unpinned: the reference has none)."""
 import pytest
 
+import bn_cases as B
 import op_cases as C
 
 TOL = 2e-6   # the C oracle stores float32; the torch side is float64
@@ -162,6 +163,27 @@ def test_bias_paths(oracle_abi):
 
 
 # ---- pinning the restatement itself: hand-computed values and the published TF-1.0 index algebra --------
+# the BatchNorm path matrix of the GPU suite (tests/bn_cases.py), float32 rows of moderate size: the oracle has one path, so what
+# this proves is the cases themselves - references, kink-free inputs, premises and bars - without a GPU
+@pytest.mark.parametrize('name', B.ORACLE_CASES)
+def test_bn_path_cases(oracle_abi, name):
+    B.case_bn_path(oracle_abi, name, 'f32')
+
+
+@pytest.mark.parametrize('name', [n for n, st in B.PAD_CASES if st == 'f32'])
+def test_bn_pad_channel_cases(oracle_abi, name):
+    B.case_bn_pads(oracle_abi, name, 'f32', check_path=False)
+
+
+def test_bias_accumulate(oracle_abi):
+    B.case_bias_accumulate(oracle_abi, TOL)
+
+
+@pytest.mark.parametrize('shape', B.DNA_ACC_SHAPES, ids=str)
+def test_dna_dbias_accumulate(oracle_abi, shape):
+    B.case_dna_accumulate(oracle_abi, shape, TOL, False)
+
+
 def test_same_padding_known_answers():
     """TF 'SAME': out = ceil(in / s), pad_total = max((out-1) s + k - in, 0), pad_before = pad_total // 2 (A.1)."""
     from oracle import tf_ops as T
