@@ -52,6 +52,11 @@ class PrepList(ctypes.Structure):
                 ('b', c_int32 * 32)]
 
 
+class NormSegments(ctypes.Structure):
+    """struct acg_norm_segments (ACG_NORM_SEGMENTS_MAX = 64 windows of a flat gradient buffer; include/acgan_rollout.h)."""
+    _fields_ = [('count', c_int32), ('offset', c_int64 * 64), ('length', c_int64 * 64)]
+
+
 class OptArgs(ctypes.Structure):
     """struct acg_opt_args (acg_opt_step_prepare_bf16)."""
     _fields_ = [('kind', c_int32), ('lr', c_float), ('beta1_or_decay', c_float), ('beta2', c_float), ('eps', c_float),
@@ -184,10 +189,13 @@ EXTENSIONS = {
                                    + [c_float, _P, c_size_t, _P]),
     }),
     # the image gradient of the DNA tail and the gradient of a tiled action vector, which training through the generator's own
-    # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp)
+    # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp), and the global-norm clip of a flat
+    # gradient buffer that bounds them (optim.ClipNormOp)
     'rollout': Extension('include/acgan_rollout.h', 'training through rollouts runs on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
+        'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
+        'acg_grad_clip_norm': (STATUS, [_P, c_int64, ctypes.POINTER(NormSegments), c_float, c_float, _P, _P, c_size_t, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)
@@ -218,6 +226,7 @@ EXTENSIONS = {
 COPY_MAX = 8
 REDUCE_MAX = 32
 PREP_MAX = 32
+NORM_SEGMENTS_MAX = 64
 
 
 def dtype2(first, second):

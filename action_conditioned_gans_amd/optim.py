@@ -12,8 +12,11 @@ shape (train.py:91-102) and TensorFlow-1.0's update formulas.  ``mi
    (``collectives='side'``; see DataParallel) - captured into the step's HIP graph either way; the
    optimizer step runs behind all of them;
 4. appends ONE fused update launch over the flat buffers (+ the weight clip when it is fetched with it); with ``ema=`` that
-   launch also updates the scope's weight average (WeightAverage).
+   launch also updates the scope's weight average (WeightAverage); with ``clip_norm=`` one ClipNormOp in front of it measures
+   the gradient's global norm and scales the flat gradient buffer to a bound (GradNorm).
 """
+import math
+
 import torch
 
 from . import _lib
@@ -131,6 +134,77 @@ class WeightAverage:
     def args(self):
         """(shadow, decay, counter, state word): the tail of the acg_*_step_ema argument lists."""
         return (_p(self.shadow.buf), self.decay, _p(self.num_updates.buf), _p(self.done.buf))
+
+
+class GradNorm:
+    """The global norm of one scope's gradient and the bound it is clipped to (tf.clip_by_global_norm): what
+    ``Optimizer.minimize(..., clip_norm=)`` takes.  ``max_norm`` > 0, or ``math.inf`` to measure only.  Every StepOp of the scope
+    given the same object gets a ClipNormOp that writes the same statistics, so they hold the last update of the scope that ran.
+
+    State - graph state, no variable, no optimizer slot: ONE unnamed float32 [2 + V] (V = the scope's variables in layout
+    order): the norm of the averaged gradient, the scale it was multiplied by (1: it fitted, or it was not finite), and each
+    variable's norm before scaling (include/acgan_rollout.h acg_grad_clip_norm ``stats``).  Unnamed, so no checkpoint holds it.
+    Created by ``build`` (at the latest when the first ClipNormOp is compiled), like WeightAverage's, so that a caller can create
+    it last and leave every other state where it was."""
+
+    def __init__(self, max_norm, scope, graph=None):
+        try:
+            m = float(max_norm)
+        except (TypeError, ValueError):
+            raise ValueError('GradNorm: max_norm must be a number > 0 (math.inf: measure only), got %r' % (max_norm,))
+        if isinstance(max_norm, bool) or not m > 0.0 or (math.isfinite(m) and not 0.0 < _f32(m) < math.inf):
+            raise ValueError('GradNorm: max_norm must be > 0 (math.inf: measure only), got %r' % (max_norm,))
+        self.max_norm, self.scope, self.graph = _f32(m), scope, graph or G.get_default_graph()
+        self.stats = None
+        self.names = None           # the scope's variables in layout order: stats[2 + i] belongs to names[i]
+
+    def segments(self):
+        """-> (names, [(offset, numel)]) of the scope's variables in the flat buffers, layout order."""
+        offsets, _, _ = self.graph.layout(self.scope)
+        names = sorted(offsets, key=offsets.get)
+        if len(names) > _lib.NORM_SEGMENTS_MAX:
+            raise ValueError('GradNorm: scope %r has %d variables, acg_grad_clip_norm takes at most %d segments'
+                             % (self.scope, len(names), _lib.NORM_SEGMENTS_MAX))
+        return names, [(offsets[n], self.graph.variables[n].numel) for n in names]
+
+    def build(self):
+        if self.stats is None:
+            self.names, _ = self.segments()
+            self.stats = self.graph.new_state((2 + len(self.names),), 0.0, None)
+        return self
+
+    def tensors(self):
+        return [self.build().stats]
+
+
+class ClipNormOp(G.Op):
+    """acg_grad_clip_norm over a scope's flat gradient buffer, immediately in front of the StepOp it was made for: measures
+    grad_scale * g per variable and in all, and multiplies g by min(1, max_norm / norm) in place (never with max_norm = inf).
+    Its control inputs are what the StepOp waited for - the gradient writers, the deferred weight-gradient reductions and, under
+    data parallelism, the all-reduces: every rank then scales the same summed gradient by the same factor."""
+    joins_side = True        # reads every gradient of its scope, whichever stream produced it
+
+    def __init__(self, norm, flat_grad, deps, grad_scale, name):
+        super().__init__(flat_grad.graph, name, [flat_grad], [], control_inputs=deps)
+        self.norm, self.grad_scale = norm, grad_scale
+
+    @property
+    def extras(self):
+        return self.norm.tensors()
+
+    def bind(self, rt):
+        import ctypes
+        fn, size = _lib.entry(rt.lib, 'grad_clip_norm'), _lib.entry(rt.lib, 'grad_clip_norm_workspace_bytes')
+        g, norm = self.inputs[0], self.norm.build()
+        _, windows = norm.segments()
+        segs = _lib.NormSegments()
+        segs.count = len(windows)
+        for i, (off, numel) in enumerate(windows):
+            segs.offset[i], segs.length[i] = off, numel
+        ws, n = rt.workspace(size(g.numel, ctypes.byref(segs)))
+        self._keep = (ws, segs)
+        args = (_p(g.buf), g.numel, ctypes.byref(segs), float(self.grad_scale), norm.max_norm, _p(norm.stats.buf), _p(ws), n)
+        return lambda s: fn(*args, s)
 
 
 class StepOp(G.Op):
@@ -263,8 +337,10 @@ class Optimizer:
         launch._keep = (oa, pl)
         return launch
 
-    def minimize(self, loss, var_list=None, slots_of=None, ema=None):
+    def minimize(self, loss, var_list=None, slots_of=None, ema=None, clip_norm=None):
         """``ema``: a WeightAverage of the variables' scope; the update then also advances it (StepOp).
+        ``clip_norm``: a GradNorm of the variables' scope; a ClipNormOp then sits between the gradients and the update
+        (``step_op.clip_norm_op``) and the update waits for it alone.  None: nothing is built.
         ``slots_of``: the StepOp of an earlier ``minimize`` by an optimizer of this kind over the same scope; this update then
         continues that one's state (moments, step counter) instead of owning slots of its own - a second loss of one training
         run (train.Trainer's rollout G step continues the one-step G step's optimizer, and checkpoints hold one set of slots)."""
@@ -281,6 +357,10 @@ class Optimizer:
         scope = scopes.pop()
         if ema is not None and (ema.scope != scope or ema.graph is not g):
             raise ValueError('minimize: ema averages scope %r, the variables are of scope %r' % (ema.scope, scope))
+        if clip_norm is not None:
+            if clip_norm.scope != scope or clip_norm.graph is not g:
+                raise ValueError('minimize: clip_norm measures scope %r, the variables are of scope %r' % (clip_norm.scope, scope))
+            clip_norm.segments()         # (more variables than one segment list holds: ValueError before anything is built)
         offsets, total, flat_param = g.layout(scope)
         flat_grad = g.new_state((total,), 0.0, self.name + '/flat_grad')
         heads = {}
@@ -304,7 +384,12 @@ class Optimizer:
             slots = list(slots_of.inputs[2:])
         else:
             slots = self._make_slots(g, total)
+        clip_op = None
+        if clip_norm is not None:
+            clip_op = ClipNormOp(clip_norm, flat_grad, deps, 1.0 / dp.world_size, self.name + '/clip_norm')
+            deps = [clip_op]
         step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size, ema=ema)
+        step_op.clip_norm_op = clip_op
         step_op.reduce_ops = reduce_ops        # one of them can carry the step counter's increment (_step_inc_launch)
         return step_op
 

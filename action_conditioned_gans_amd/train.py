@@ -14,6 +14,7 @@ optional in ``test``; D6 update -> clip; D7 eval uses its own states; D8 boolean
 import argparse
 import contextlib
 import json
+import math
 import os
 import time
 
@@ -41,7 +42,7 @@ ACTION_DIM, STATE_DIM = 10, 5
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
-                 ssim_weight=0.0):
+                 ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -71,9 +72,21 @@ class Trainer:
         sum over the 12 288 values of a frame, so a useful W is in the tens to hundreds.  Every generator, bf16 graphs (the frame
         is float32 there too), the look-ahead path, rollout_steps > 1, ema_decay and bn_inference take it; no variable and no state
         is added.  A per-frame mean over the local batch: averaging the ranks' gradients gives the global-batch value, nothing is
-        needed for exact_global_batch - allowed with more than one rank, not verified there."""
+        needed for exact_global_batch - allowed with more than one rank, not verified there.
+        ``g_clip_norm`` / ``d_clip_norm`` X (no reference counterpart; 0 builds nothing; else finite and > 0): every update of the
+        generator / the discriminator first clips its averaged gradient to a global norm of X (tf.clip_by_global_norm; one
+        optim.ClipNormOp in front of each StepOp of the scope - ``pretrain_g``, ``train_g`` and the two rollout steps share one
+        optim.GradNorm, ``train_d`` has its own).  ``grad_norms=True`` measures the norms of a scope without a bound as well (its
+        gradient is then never written).  ``grad_norm_stats(scope)`` reads the last update's norm, scale and per-variable norms;
+        they are not among the summaries.  A gradient with a NaN or an infinity in it is passed on unscaled and the norm says so.
+        No variable, no checkpoint key.  Every generator, bf16 graphs (the flat gradient is float32 there), the look-ahead path,
+        rollout_steps > 1, ema_decay, ssim_weight and bn_inference take it; with more than one rank the clip sits behind the
+        all-reduce, so every rank applies the same scale - not verified there.  ``d_clip_norm`` and the D norms need an
+        adversarial trainer; with ``arg_adv=False`` they are ignored as D itself is."""
         ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.ssim_weight = check_ssim_weight(ssim_weight)
+        self.g_clip_norm, self.d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
+        grad_norms = bool(grad_norms)
         self.sess = sess
         self.model = model_kind(arg_transform)
         dp = G.get_default_graph().collections.get('data_parallel')
@@ -200,9 +213,13 @@ class Trainer:
             raise ValueError('unexpected opt argument')
         self.ema = optim.WeightAverage(ema_decay, 'g') if ema_decay else None      # shared by every G update of this Trainer
         self._ema_swapped = False
-        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema)
-        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema)
-        self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars)
+        # scope -> the optim.GradNorm every update of the scope shares (None: neither clipped nor measured)
+        self.grad_norm = {'g': optim.GradNorm(self.g_clip_norm or math.inf, 'g') if self.g_clip_norm or grad_norms else None,
+                          'd': optim.GradNorm(self.d_clip_norm or math.inf, 'd') if arg_adv and (self.d_clip_norm or grad_norms) else None}
+        g_norm, d_norm = self.grad_norm['g'], self.grad_norm['d']
+        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm)
+        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm)
+        self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars, clip_norm=d_norm)
 
         # the seven tf.summary scalars of ops.py:48-49 / train.py:104-111, names kept
         self.summaries.update({'discriminator_loss': self.d_loss, 'g_loss': self.g_loss, 'g_l2_loss': g_l2_loss,
@@ -229,6 +246,24 @@ class Trainer:
             self._build_bn_inference(build_g)
         if self.ema is not None:
             self.ema.build()        # last: every op of the graph keeps the place it has without the average
+        for norm in self.grad_norm.values():
+            if norm is not None:
+                norm.build()        # (the same: after everything else)
+
+    # ---- gradient norms (g_clip_norm / d_clip_norm / grad_norms)
+    def grad_norm_stats(self, scope):
+        """-> {'norm', 'scale', 'per_variable': {variable name: norm}} of the last update of ``scope`` ('g' or 'd') that ran: the
+        global norm of the averaged gradient, the factor it was multiplied by (1: it fitted, or it was not finite, or the scope
+        is measured only) and each variable's norm BEFORE scaling.  All zero before the first update.  One small device-to-host
+        copy (a synchronisation).  Raises when the Trainer keeps no GradNorm for the scope."""
+        if scope not in self.grad_norm:
+            raise ValueError("grad_norm_stats: scope must be 'g' or 'd', got %r" % (scope,))
+        norm = self.grad_norm[scope]
+        if norm is None:
+            raise RuntimeError('this Trainer was built without %s_clip_norm / grad_norms%s: it measures no gradient norm of scope %r'
+                               % (scope, ' (or without arg_adv)' if scope == 'd' else '', scope))
+        vals = [float(v) for v in self.sess._materialize(norm.stats).detach().cpu().numpy()]
+        return {'norm': vals[0], 'scale': vals[1], 'per_variable': dict(zip(norm.names, vals[2:]))}
 
     # ---- the generator's weight average (ema_decay > 0)
     def _require_ema(self):
@@ -410,9 +445,11 @@ class Trainer:
                 img = frame
                 act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
         total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
-        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op, ema=self.ema)
+        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op, ema=self.ema,
+                                                               clip_norm=self.grad_norm['g'])
         self.g_rollout_pretrain_opt_op = make('g_pretrain_opt_rollout').minimize(l2_total / K, var_list=self.g_vars,
-                                                                                slots_of=self.g_pretrain_opt_op, ema=self.ema)
+                                                                                slots_of=self.g_pretrain_opt_op, ema=self.ema,
+                                                                                clip_norm=self.grad_norm['g'])
 
     def _rollout_feed(self, frames, actions, states):
         """frames [B, K+1, H, W, 3] (t .. t+K), actions [B, K, 10] (a_t .. a_{t+K-1}, state half read at step 0 only by the DNA
@@ -671,6 +708,18 @@ def check_ssim_weight(ssim_weight):
     return w
 
 
+def check_clip_norm(value, what='clip_norm'):
+    """ValueError for a ``g_clip_norm`` / ``d_clip_norm`` that is not a finite number >= 0 (or is positive and rounds to 0 in
+    float32); -> the bound as a float (0: no clip)."""
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be a finite number >= 0, got %r' % (what, value))
+    if isinstance(value, bool) or not 0.0 <= x <= float(np.finfo(np.float32).max) or (x > 0.0 and float(np.float32(x)) == 0.0):
+        raise ValueError('%s must be finite and >= 0 (0: off), got %r' % (what, value))
+    return x
+
+
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
     """ValueError for a ``rollout_steps`` the K-step trainer does not take (with the generator ``model``, a bf16 graph, data
     parallelism / synchronised BatchNorm); -> K."""
@@ -825,6 +874,21 @@ class _PairSelections:
         return self.queue.pop(0)
 
 
+def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None):
+    """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
+    the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
+    ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run)."""
+    record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
+                  **({'g_ema': ema_decay} if ema_decay else {}),
+                  **({'ssim_weight': ssim_weight} if ssim_weight else {}))
+    for scope in sorted(grad_stats or {}, reverse=True):             # g, then d
+        record[scope + '_grad_norm'] = grad_stats[scope]['norm']
+        record[scope + '_clip_scale'] = grad_stats[scope]['scale']
+    for scope in sorted(clip_bounds or {}, reverse=True):
+        record[scope + '_clip_norm'] = clip_bounds[scope]
+    return record
+
+
 def _log_jsonl(path, record):
     with open(path, 'a') as f:
         f.write(json.dumps(record) + '\n')
@@ -835,7 +899,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
-          num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0):
+          num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -858,9 +922,14 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     it, ``train.jsonl`` records ``g_ema``, and the evaluation block also scores the rollout of the averaged weights
     (``rollout_psnr_ema`` / ``rollout_ssim_ema`` in ``test.jsonl``).  Training itself is unchanged.
     ``ssim_weight`` W > 0: the generator's losses carry W / B * sum_b (1 - SSIM_b) (Trainer ``ssim_weight``); ``train.jsonl``
-    records ``ssim_weight`` and the summary ``g_ssim_loss``.  Checkpoints and the evaluation block are unchanged."""
+    records ``ssim_weight`` and the summary ``g_ssim_loss``.  Checkpoints and the evaluation block are unchanged.
+    ``g_clip_norm`` / ``d_clip_norm`` X > 0: the G / D updates clip their gradient to a global norm of X; ``grad_norms``: measure
+    the norms of a scope without a bound too (Trainer, same keywords).  With any of them ``train.jsonl`` records
+    ``g_grad_norm`` / ``g_clip_scale`` / ``d_grad_norm`` / ``d_clip_scale`` of the iteration's last updates at every log
+    interval (the scopes that are measured) and the configured bounds once, in its first record.  Checkpoints are unchanged."""
     ema_decay = check_ema_decay(ema_decay)
     ssim_weight = check_ssim_weight(ssim_weight)
+    g_clip_norm, d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
     if int(rollout_steps) > 1:
@@ -888,7 +957,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
         trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
                               select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
-                              ema_decay=ema_decay, ssim_weight=ssim_weight)
+                              ema_decay=ema_decay, ssim_weight=ssim_weight, g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm,
+                              grad_norms=bool(grad_norms))
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -903,10 +973,12 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0):
+                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
     ema = {'ema_decay': ema_decay} if ema_decay else {}
     if ssim_weight:
         ema['ssim_weight'] = ssim_weight
+    if g_clip_norm or d_clip_norm or grad_norms:
+        ema.update(g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm, grad_norms=grad_norms)
     if rollout_steps > 1:               # (the K-step G step takes the plain call path: no pair instance to build)
         trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks,
                           lookahead=False, rollout_steps=rollout_steps, **ema)
@@ -927,6 +999,7 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
     D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
     log_file = os.path.join(log_dir, 'train.jsonl') if log_dir else None
     t0 = time.time()
+    bounds_logged = False
     selections = _PairSelections(boolean_mask, batch_size, D_per_G, pretrain_iter, train_iter, data if select_frames else None,
                                  rollout_steps=rollout_steps)
     for i in range(train_iter):
@@ -978,9 +1051,10 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             if not quiet:
                 print('Iteration {:d}'.format(i))
             if log_file and summ:
-                _log_jsonl(log_file, dict(summ, iteration=i, wall_s=time.time() - t0, rollout_steps=rollout_steps,
-                                          **({'g_ema': ema_decay} if ema_decay else {}),
-                                          **({'ssim_weight': ssim_weight} if ssim_weight else {})))
+                stats = {sc: trainer.grad_norm_stats(sc) for sc, norm in trainer.grad_norm.items() if norm is not None}
+                bounds = None if bounds_logged or not stats else {'g': g_clip_norm, 'd': d_clip_norm}
+                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds))
+                bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
         if eval_every and i % eval_every == 0 and rank == 0:
@@ -1119,6 +1193,13 @@ def main(argv=None):
                         help='add W / B * sum_b (1 - SSIM_b) of the generated frame against the next frame to the generator\'s '
                              'reconstruction loss (0 = off; the L1 term is a SUM over the 12 288 values of a frame, so a useful W is in '
                              'the tens to hundreds)')
+    parser.add_argument('--g_clip_norm', type=float, default=0.0, metavar='X',
+                        help='clip the gradient of every generator update to a global norm of X (tf.clip_by_global_norm; 0 = off)')
+    parser.add_argument('--d_clip_norm', type=float, default=0.0, metavar='X',
+                        help='clip the gradient of every discriminator update to a global norm of X (0 = off; needs --adv)')
+    parser.add_argument('--log_grad_norms', nargs='?', const=True, default=False, type=_flag,
+                        help='record the gradient norms of G and D in train.jsonl (g_grad_norm, d_grad_norm, ..._clip_scale), also '
+                             'where no bound is set')
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
@@ -1130,6 +1211,11 @@ def main(argv=None):
         check_ema_decay(args.g_ema)
     except ValueError:
         parser.error('--g_ema must be 0 (off) or lie in (0, 1), got %r' % args.g_ema)
+    for flag in ('g_clip_norm', 'd_clip_norm'):
+        try:
+            check_clip_norm(getattr(args, flag), flag)
+        except ValueError:
+            parser.error('--%s must be finite and >= 0, got %r' % (flag, getattr(args, flag)))
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
@@ -1150,7 +1236,8 @@ def main(argv=None):
                     sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
                     data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema,
-                    ssim_weight=args.ssim_weight)
+                    ssim_weight=args.ssim_weight, g_clip_norm=args.g_clip_norm, d_clip_norm=args.d_clip_norm,
+                    grad_norms=args.log_grad_norms)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

@@ -8,6 +8,10 @@
  * pointers are borrowed (NHWC, float32), calls are asynchronous on `stream`, return ACG_OK or an ACG_ERR_* code with the
  * message in acg_last_error().  Neither entry uses atomics: the same call gives the same bits.  The Python binding keeps
  * these entries in a table of their own (_lib.ROLLOUT_SIGNATURES): the C oracle does not implement them.
+ *
+ * Back-propagation through K generator passes is the textbook case for exploding gradients, so the header also holds what bounds
+ * them: acg_grad_clip_norm, the global-norm clip (and the norm measurement) of an optimizer's flat gradient buffer, with its
+ * workspace query - same conventions, same table, no atomics either.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -39,6 +43,34 @@ int32_t acg_dna_bwd_image(const void* logits, const float* bias, const float* do
  * One block per q sums in a fixed order (no atomics).  dact is dense [mod, n]. */
 int32_t acg_action_grad(const float* dcat, int64_t rows, int32_t pitch, int32_t c_off, int32_t n, int32_t div, int32_t mod,
                         float* dact, float accumulate, acg_stream_t stream);
+
+/* Clip by global norm (tf.clip_by_global_norm) over the variables' windows of a flat float32 gradient buffer of n elements.
+ * `segs` (read on the host during the call and copied into the kernel arguments: nothing of it is referenced afterwards, a
+ * captured graph replays the call) lists 1..ACG_NORM_SEGMENTS_MAX windows [offset, offset + length) in elements: offsets are
+ * multiples of 4 (16 bytes), lengths >= 1, inside [0, n), pairwise disjoint, in any order; `grad` is 16-byte aligned.
+ *   ss_i   = sum of the squares of segment i, every square and every sum in double, in an order that depends on (n, segs) only:
+ *            per ACG_NORM_CHUNK elements of a segment one partial (a double in `workspace`), the partials of a segment summed in
+ *            a fixed order by one block, the segments in list order;
+ *   norm_i = |pre_scale| * sqrt(ss_i),   norm = |pre_scale| * sqrt(sum_i ss_i);
+ *   scale  = (float)(max_norm / norm) if norm is finite and norm > max_norm, else 1;
+ *   grad[e] *= scale (one float32 multiply) for every element of every segment - only when scale != 1: a gradient that fits,
+ *            a gradient with a NaN or an infinity in it, and max_norm = +inf (measure only) leave the buffer unwritten.  A
+ *            non-finite gradient is passed on as it is and stats[0] says so.
+ *   stats[0] = (float)norm, stats[1] = scale, stats[2 + i] = (float)norm_i          (device, float32 [2 + count]).
+ * Elements between the segments (alignment gaps) are neither read nor written.  max_norm > 0 (+inf allowed), pre_scale finite:
+ * with pre_scale = the optimizer's grad_scale, what the optimizer then sees is clip_by_global_norm of the averaged gradient.
+ * Three launches (two for max_norm = +inf); workspace: acg_grad_clip_norm_workspace_bytes(n, segs) bytes, 8-byte aligned, its
+ * content on entry is irrelevant (0 is returned for an invalid (n, segs); the call itself then reports the error). */
+#define ACG_NORM_SEGMENTS_MAX 64
+#define ACG_NORM_CHUNK 8192
+typedef struct acg_norm_segments {
+  int32_t count;
+  int64_t offset[ACG_NORM_SEGMENTS_MAX];
+  int64_t length[ACG_NORM_SEGMENTS_MAX];
+} acg_norm_segments;
+size_t acg_grad_clip_norm_workspace_bytes(int64_t n, const acg_norm_segments* segs);
+int32_t acg_grad_clip_norm(float* grad, int64_t n, const acg_norm_segments* segs, float pre_scale, float max_norm, float* stats,
+                           void* workspace, size_t workspace_bytes, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
