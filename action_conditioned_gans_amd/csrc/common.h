@@ -81,6 +81,13 @@ __device__ __forceinline__ float act_deriv_out(int act, float y, float leak) {
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Blocks of 256 threads for a streaming kernel over `n` work items (float4s, mostly) with a grid-stride loop: one item per
+// thread up to 4096 blocks (optim.hip, ema.hip).
+static inline int grid_for(int64_t n) {
+  const int64_t b = ceil_div(n, 256);
+  return (int)(b > 4096 ? 4096 : b < 1 ? 1 : b);
+}
+
 // ---- storage types ---------------------------------------------------------------------------------
 // A `dtype` argument names the storage type of a call's activation-class tensors: ACG_F32 / ACG_BF16 for all of
 // them, or ACG_DTYPE2(first, second) where two differ (include/acgan_hip.h).

@@ -9,13 +9,6 @@
 
 namespace {
 
-int grid_for(long long n4) {
-  long long b = acg::ceil_div(n4, 256);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 __global__ __launch_bounds__(256) void ema_update_k(float* __restrict__ shadow, const float* __restrict__ p, long long n,
                                                     float decay, long long* num_updates, unsigned* done) {
   __shared__ acg_ema::Coef s_c;
@@ -27,23 +20,16 @@ __global__ __launch_bounds__(256) void ema_update_k(float* __restrict__ shadow, 
   const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
   const bool have = i0 < n4;
   float4 ss, pp;
-  if (have) { ss = reinterpret_cast<float4*>(shadow)[i0]; pp = reinterpret_cast<const float4*>(p)[i0]; }
+  auto load = [&](long long i) { ss = reinterpret_cast<float4*>(shadow)[i]; pp = reinterpret_cast<const float4*>(p)[i]; };
+  if (have) load(i0);
   long long k = 0;
   if (threadIdx.x == 0) s_c = acg_ema::coef(num_updates, decay, &k);
   __syncthreads();
   const float omd = s_c.omd;
   const int seed = s_c.seed;
-  if (have) {
-    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
-    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
-    reinterpret_cast<float4*>(shadow)[i0] = ss;
-  }
-  for (long long i = i0 + stride; i < n4; i += stride) {
-    ss = reinterpret_cast<float4*>(shadow)[i]; pp = reinterpret_cast<const float4*>(p)[i];
-    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
-    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
-    reinterpret_cast<float4*>(shadow)[i] = ss;
-  }
+  auto update = [&](long long i) { acg_ema::ema4(ss, pp, omd, seed); reinterpret_cast<float4*>(shadow)[i] = ss; };
+  if (have) update(i0);
+  for (long long i = i0 + stride; i < n4; i += stride) { load(i); update(i); }
   for (long long i = n4 * 4 + i0; i < n; i += stride) shadow[i] = acg_ema::ema1(shadow[i], p[i], omd, seed);
   if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
 }
@@ -73,7 +59,7 @@ int32_t acg_ema_update(float* shadow, const float* param, int64_t n, float decay
   ACG_REQUIRE(decay > 0.f && decay < 1.f, ACG_ERR_INVALID_ARG, "ema_update: decay %g is not in (0, 1)", (double)decay);
   ACG_REQUIRE((reinterpret_cast<uintptr_t>(num_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(state) & 3) == 0, ACG_ERR_INVALID_ARG,
               "ema_update: the counter must be 8-byte and the state word 4-byte aligned");
-  ACG_LAUNCH(ema_update_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), shadow, param, (long long)n, decay,
+  ACG_LAUNCH(ema_update_k, dim3(acg::grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), shadow, param, (long long)n, decay,
              reinterpret_cast<long long*>(num_updates), reinterpret_cast<unsigned*>(state));
   return acg::check_launch("ema_update");
 }
@@ -81,7 +67,7 @@ int32_t acg_ema_update(float* shadow, const float* param, int64_t n, float decay
 int32_t acg_swap_f32(float* a, float* b, int64_t n, acg_stream_t stream) {
   ACG_REQUIRE(n > 0 && a && b, ACG_ERR_INVALID_ARG, "swap_f32: null pointer / n <= 0");
   ACG_REQUIRE(a + n <= b || b + n <= a, ACG_ERR_INVALID_ARG, "swap_f32: the buffers overlap");
-  ACG_LAUNCH(swap_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), a, b, (long long)n);
+  ACG_LAUNCH(swap_k, dim3(acg::grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), a, b, (long long)n);
   return acg::check_launch("swap_f32");
 }
 

@@ -29,6 +29,12 @@ __device__ __forceinline__ float ema1(float s, float p, float omd, int seed) {
   return seed ? p : s - prod;
 }
 
+// ema1 over the four elements of a 16-byte access
+__device__ __forceinline__ void ema4(float4& s, const float4& p, float omd, int seed) {
+  s.x = ema1(s.x, p.x, omd, seed); s.y = ema1(s.y, p.y, omd, seed);
+  s.z = ema1(s.z, p.z, omd, seed); s.w = ema1(s.w, p.w, omd, seed);
+}
+
 // Called by the thread that called coef(), behind a block barrier that follows it.  The last block of the grid to get here
 // writes the counter and resets the word; nobody waits on either.  Relaxed is enough: this thread's read of the counter has
 // RETURNED (its value went through shared memory in front of the barrier), so it was performed before this add, and the

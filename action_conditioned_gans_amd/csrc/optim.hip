@@ -12,13 +12,6 @@
 
 namespace {
 
-int grid_for(long long n4) {
-  long long b = acg::ceil_div(n4, 256);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 __device__ __forceinline__ float clipf(float v, int use, float lo, float hi) { return use ? fminf(fmaxf(v, lo), hi) : v; }
 
 // (explicitly rounded operations: the same sequence whichever kernel inlines it - hipcc otherwise contracts multiplies and adds
@@ -31,53 +24,6 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, flo
   p = clipf(__fsub_rn(p, __fdiv_rn(__fmul_rn(lr_t, m), __fadd_rn(sqrtf(v), eps))), use_clip, lo, hi);
 }
 
-__global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                              float* __restrict__ v, const int* __restrict__ step, long long n, float lr,
-                                              float b1, float b2, float eps, float gs, int use_clip, float lo, float hi) {
-  // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)   (SURVEY A.6); fp64 pow keeps the tiny 1-b^t differences exact.  ONE thread per
-  // block evaluates it: two double-precision pow calls are several hundred instructions, more than the whole update of
-  // the one or two float4 a thread owns.
-  __shared__ float s_lr_t;
-  const long long stride = (long long)gridDim.x * 256;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                    reinterpret_cast<uintptr_t>(v)) & 15) == 0;
-  const long long n4 = al ? n / 4 : 0;
-  // Round 5: the first float4 of every thread (the grid is sized so that it is nearly the only one) is loaded BEFORE the
-  // learning-rate prologue: that prologue is a dependent read of the step counter plus ~1 us of double-precision pow on one
-  // thread, during which the whole chip used to wait with nothing in flight (19.4 us for 133 MB in situ, 3.2 TB/s).
-  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool have = i0 < n4;
-  float4 pp, mm, vv, gg;
-  if (have) {
-    pp = reinterpret_cast<float4*>(p)[i0]; mm = reinterpret_cast<float4*>(m)[i0]; vv = reinterpret_cast<float4*>(v)[i0];
-    gg = reinterpret_cast<const float4*>(g)[i0];
-  }
-  if (threadIdx.x == 0) {
-    const int t = *step;
-    s_lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-  }
-  __syncthreads();
-  const float lr_t = s_lr_t;
-  if (have) {
-    adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    reinterpret_cast<float4*>(p)[i0] = pp; reinterpret_cast<float4*>(m)[i0] = mm; reinterpret_cast<float4*>(v)[i0] = vv;
-  }
-  for (long long i = i0 + stride; i < n4; i += stride) {
-    pp = reinterpret_cast<float4*>(p)[i]; mm = reinterpret_cast<float4*>(m)[i]; vv = reinterpret_cast<float4*>(v)[i];
-    gg = reinterpret_cast<const float4*>(g)[i];
-    adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(m)[i] = mm; reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    adam1(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-}
-
 __device__ __forceinline__ void rms1(float& p, float g, float& ms, float lr, float decay, float eps, float gs, int use_clip,
                                      float lo, float hi) {
   g = __fmul_rn(g, gs);
@@ -85,120 +31,129 @@ __device__ __forceinline__ void rms1(float& p, float g, float& ms, float lr, flo
   p = clipf(__fsub_rn(p, __fdiv_rn(__fmul_rn(lr, g), sqrtf(__fadd_rn(ms, eps)))), use_clip, lo, hi);
 }
 
+struct OptScalars {
+  float lr, b1, b2, eps, gs, lo, hi;      // b1: Adam's beta1, RMSProp's decay
+  int use_clip;
+};
+
+// ---- the update rules: what a kernel below is instantiated with -----------------------------------------------------------------
+// kSlots: the slot buffers the rule reads and writes (a one-slot rule never touches s2); kPrologue: `rate` must be derived by
+// one thread of the block before any element is updated; one(): the update of one element, given that rate.
+struct Adam {
+  static constexpr int kSlots = 2;
+  static constexpr bool kPrologue = true;
+  // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)   (SURVEY A.6); fp64 pow keeps the tiny 1-b^t differences exact.  ONE thread per
+  // block evaluates it: a dependent read of the step counter and two double-precision pow calls, several hundred
+  // instructions (~1 us) - more than the whole update of the one or two float4 a thread owns.
+  static __device__ __forceinline__ float rate(const OptScalars& a, const int* step) {
+    const int t = *step;
+    return (float)((double)a.lr * sqrt(1.0 - pow((double)a.b2, (double)t)) / (1.0 - pow((double)a.b1, (double)t)));
+  }
+  static __device__ __forceinline__ void one(float& p, float g, float& m, float& v, float lr_t, const OptScalars& a) {
+    adam1(p, g, m, v, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
+  }
+};
+struct RmsProp {
+  static constexpr int kSlots = 1;
+  static constexpr bool kPrologue = false;
+  static __device__ __forceinline__ float rate(const OptScalars& a, const int*) { return a.lr; }
+  static __device__ __forceinline__ void one(float& p, float g, float& ms, float&, float lr, const OptScalars& a) {
+    rms1(p, g, ms, lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
+  }
+};
+
+template <class R>
+__device__ __forceinline__ void four(float4& p, const float4& g, float4& s1, float4& s2, float rate, const OptScalars& a) {
+  R::one(p.x, g.x, s1.x, s2.x, rate, a);
+  R::one(p.y, g.y, s1.y, s2.y, rate, a);
+  R::one(p.z, g.z, s1.z, s2.z, rate, a);
+  R::one(p.w, g.w, s1.w, s2.w, rate, a);
+}
+
+// ---- the update over flat float32 buffers: the body of adam_k, rmsprop_k and of the two kernels that carry the weight average ----
+// EMA: the shadow element (include/acgan_ema.h) is updated from the new parameter while it is still in a register - one launch
+// instead of two, and the average costs a read and a write of the shadow instead of those plus a second read of the parameters;
+// parameters and slots come out as without it, the shadow as ema_update_k behind the plain kernel leaves it.  The prologue
+// thread then also derives the average's coefficient, and retires the launch's count of it at the end.
+template <class R, bool EMA>
+__device__ __forceinline__ void flat_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                            float* __restrict__ s2, const int* __restrict__ step, long long n, const OptScalars& a,
+                                            float* __restrict__ sh, float ema_decay, long long* num_updates, unsigned* done) {
+  constexpr bool kTwo = R::kSlots == 2, kPrologue = R::kPrologue || EMA;
+  __shared__ float s_rate;
+  __shared__ acg_ema::Coef s_c;
+  const long long stride = (long long)gridDim.x * 256;
+  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(s1) |
+                    (kTwo ? reinterpret_cast<uintptr_t>(s2) : 0) | (EMA ? reinterpret_cast<uintptr_t>(sh) : 0)) & 15) == 0;
+  const long long n4 = al ? n / 4 : 0;
+  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+  float rate = a.lr, omd = 0.f;
+  int seed = 0;
+  long long k = 0;
+  float4 pp, gg, aa, bb, ss;
+  auto load = [&](long long i) {
+    pp = reinterpret_cast<float4*>(p)[i]; aa = reinterpret_cast<float4*>(s1)[i];
+    if constexpr (kTwo) bb = reinterpret_cast<float4*>(s2)[i];
+    gg = reinterpret_cast<const float4*>(g)[i];
+    if constexpr (EMA) ss = reinterpret_cast<float4*>(sh)[i];
+  };
+  auto update = [&](long long i) {
+    four<R>(pp, gg, aa, bb, rate, a);
+    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(s1)[i] = aa;
+    if constexpr (kTwo) reinterpret_cast<float4*>(s2)[i] = bb;
+    if constexpr (EMA) { acg_ema::ema4(ss, pp, omd, seed); reinterpret_cast<float4*>(sh)[i] = ss; }
+  };
+  long long i = i0;
+  if constexpr (kPrologue) {
+    // Round 5: the first float4 of every thread (the grid is sized so that it is nearly the only one) is loaded BEFORE the
+    // prologue, during which the whole chip used to wait with nothing in flight (19.4 us for 133 MB in situ, 3.2 TB/s).
+    // A kernel without a prologue has nothing to hide the load behind and keeps its plain loop.
+    const bool have = i0 < n4;
+    if (have) load(i0);
+    if (threadIdx.x == 0) {
+      if constexpr (R::kPrologue) s_rate = R::rate(a, step);
+      if constexpr (EMA) s_c = acg_ema::coef(num_updates, ema_decay, &k);
+    }
+    __syncthreads();
+    if constexpr (R::kPrologue) rate = s_rate;
+    if constexpr (EMA) { omd = s_c.omd; seed = s_c.seed; }
+    if (have) update(i0);
+    i += stride;
+  }
+  for (; i < n4; i += stride) { load(i); update(i); }
+  for (i = n4 * 4 + i0; i < n; i += stride) {
+    float none;
+    R::one(p[i], g[i], s1[i], kTwo ? s2[i] : none, rate, a);
+    if constexpr (EMA) sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
+  }
+  if constexpr (EMA) if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
+}
+
+// (the kernels keep their names: tools/insitu_times.py, tools/gap_analysis.py and the committed traces find them by name)
+__global__ __launch_bounds__(256) void adam_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, const int* __restrict__ step, long long n, float lr,
+                                              float b1, float b2, float eps, float gs, int use_clip, float lo, float hi) {
+  flat_update<Adam, false>(p, g, m, v, step, n, OptScalars{lr, b1, b2, eps, gs, lo, hi, use_clip}, nullptr, 0.f, nullptr, nullptr);
+}
+
 __global__ __launch_bounds__(256) void rmsprop_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms,
                                                  long long n, float lr, float decay, float eps, float gs, int use_clip,
                                                  float lo, float hi) {
-  const long long stride = (long long)gridDim.x * 256;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(ms)) & 15) == 0;
-  const long long n4 = al ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-    float4 pp = reinterpret_cast<float4*>(p)[i], ss = reinterpret_cast<float4*>(ms)[i];
-    const float4 gg = reinterpret_cast<const float4*>(g)[i];
-    rms1(pp.x, gg.x, ss.x, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.y, gg.y, ss.y, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.z, gg.z, ss.z, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.w, gg.w, ss.w, lr, decay, eps, gs, use_clip, lo, hi);
-    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(ms)[i] = ss;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    rms1(p[i], g[i], ms[i], lr, decay, eps, gs, use_clip, lo, hi);
+  flat_update<RmsProp, false>(p, g, ms, nullptr, nullptr, n, OptScalars{lr, decay, 0.f, eps, gs, lo, hi, use_clip}, nullptr, 0.f, nullptr, nullptr);
 }
 
-// ---- the optimizer update carrying the weight average's (include/acgan_ema.h) ------------------------------------------------
-// adam_k / rmsprop_k with the shadow element updated from the new parameter while it is still in a register: one launch instead
-// of two, and the average costs a read and a write of the shadow instead of those plus a second read of the parameters.  The
-// same adam1 / rms1 / ema1 as the kernels they replace: parameters and slots as adam_k / rmsprop_k leave them, the shadow as
-// ema_update_k behind them does.  The prologue thread derives both the learning rate and the average's coefficient.
 __global__ __launch_bounds__(256) void adam_ema_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, const int* __restrict__ step, long long n, float lr,
                                                   float b1, float b2, float eps, float gs, int use_clip, float lo, float hi,
                                                   float* __restrict__ sh, float ema_decay, long long* num_updates, unsigned* done) {
-  __shared__ float s_lr_t;
-  __shared__ acg_ema::Coef s_c;
-  const long long stride = (long long)gridDim.x * 256;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                    reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(sh)) & 15) == 0;
-  const long long n4 = al ? n / 4 : 0;
-  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool have = i0 < n4;
-  float4 pp, mm, vv, gg, ss;
-  if (have) {
-    pp = reinterpret_cast<float4*>(p)[i0]; mm = reinterpret_cast<float4*>(m)[i0]; vv = reinterpret_cast<float4*>(v)[i0];
-    gg = reinterpret_cast<const float4*>(g)[i0]; ss = reinterpret_cast<float4*>(sh)[i0];
-  }
-  long long k = 0;
-  if (threadIdx.x == 0) {
-    const int t = *step;
-    s_lr_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-    s_c = acg_ema::coef(num_updates, ema_decay, &k);
-  }
-  __syncthreads();
-  const float lr_t = s_lr_t, omd = s_c.omd;
-  const int seed = s_c.seed;
-  auto four = [&](long long i) {
-    adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
-    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
-    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(m)[i] = mm; reinterpret_cast<float4*>(v)[i] = vv;
-    reinterpret_cast<float4*>(sh)[i] = ss;
-  };
-  if (have) four(i0);
-  for (long long i = i0 + stride; i < n4; i += stride) {
-    pp = reinterpret_cast<float4*>(p)[i]; mm = reinterpret_cast<float4*>(m)[i]; vv = reinterpret_cast<float4*>(v)[i];
-    gg = reinterpret_cast<const float4*>(g)[i]; ss = reinterpret_cast<float4*>(sh)[i];
-    four(i);
-  }
-  for (long long i = n4 * 4 + i0; i < n; i += stride) {
-    adam1(p[i], g[i], m[i], v[i], lr_t, b1, b2, eps, gs, use_clip, lo, hi);
-    sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
-  }
-  if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
+  flat_update<Adam, true>(p, g, m, v, step, n, OptScalars{lr, b1, b2, eps, gs, lo, hi, use_clip}, sh, ema_decay, num_updates, done);
 }
 
 __global__ __launch_bounds__(256) void rmsprop_ema_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms,
                                                      long long n, float lr, float decay, float eps, float gs, int use_clip,
                                                      float lo, float hi, float* __restrict__ sh, float ema_decay,
                                                      long long* num_updates, unsigned* done) {
-  __shared__ acg_ema::Coef s_c;
-  const long long stride = (long long)gridDim.x * 256;
-  const bool al = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(ms) |
-                    reinterpret_cast<uintptr_t>(sh)) & 15) == 0;
-  const long long n4 = al ? n / 4 : 0;
-  const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
-  const bool have = i0 < n4;
-  float4 pp, qq, gg, ss;
-  if (have) {
-    pp = reinterpret_cast<float4*>(p)[i0]; qq = reinterpret_cast<float4*>(ms)[i0];
-    gg = reinterpret_cast<const float4*>(g)[i0]; ss = reinterpret_cast<float4*>(sh)[i0];
-  }
-  long long k = 0;
-  if (threadIdx.x == 0) s_c = acg_ema::coef(num_updates, ema_decay, &k);
-  __syncthreads();
-  const float omd = s_c.omd;
-  const int seed = s_c.seed;
-  auto four = [&](long long i) {
-    rms1(pp.x, gg.x, qq.x, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.y, gg.y, qq.y, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.z, gg.z, qq.z, lr, decay, eps, gs, use_clip, lo, hi);
-    rms1(pp.w, gg.w, qq.w, lr, decay, eps, gs, use_clip, lo, hi);
-    ss.x = acg_ema::ema1(ss.x, pp.x, omd, seed); ss.y = acg_ema::ema1(ss.y, pp.y, omd, seed);
-    ss.z = acg_ema::ema1(ss.z, pp.z, omd, seed); ss.w = acg_ema::ema1(ss.w, pp.w, omd, seed);
-    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(ms)[i] = qq; reinterpret_cast<float4*>(sh)[i] = ss;
-  };
-  if (have) four(i0);
-  for (long long i = i0 + stride; i < n4; i += stride) {
-    pp = reinterpret_cast<float4*>(p)[i]; qq = reinterpret_cast<float4*>(ms)[i];
-    gg = reinterpret_cast<const float4*>(g)[i]; ss = reinterpret_cast<float4*>(sh)[i];
-    four(i);
-  }
-  for (long long i = n4 * 4 + i0; i < n; i += stride) {
-    rms1(p[i], g[i], ms[i], lr, decay, eps, gs, use_clip, lo, hi);
-    sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
-  }
-  if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
+  flat_update<RmsProp, true>(p, g, ms, nullptr, nullptr, n, OptScalars{lr, decay, 0.f, eps, gs, lo, hi, use_clip}, sh, ema_decay, num_updates, done);
 }
 
 __global__ __launch_bounds__(256) void clip_k(float* __restrict__ p, long long n, float lo, float hi) {
@@ -215,10 +170,6 @@ __global__ void step_inc_k(int* step) { *step += 1; }
 // Here a block owns one 32 (a) x 32 (b) tile of one tap of one filter: it updates the tile's elements (the same adam1 / rms1
 // as the flat kernels: bit-identical parameters and slots), stores the rm run as it goes and the tr run through an LDS
 // transpose; what lies between the filters in the flat buffer (beta, biases, alignment gaps) goes to one block per gap.
-struct OptScalars {
-  float lr, b1, b2, eps, gs, lo, hi;
-  int use_clip;
-};
 struct OptPrepList {
   long long off[ACG_PREP_MAX];            // element offset of filter e in the flat buffers
   __bf16* rm[ACG_PREP_MAX];
@@ -228,7 +179,7 @@ struct OptPrepList {
   long long gap_lo[ACG_PREP_MAX + 1], gap_len[ACG_PREP_MAX + 1];      // gap j is block first_block[count] + j
 };
 
-template <int KIND>      // 0: Adam, 1: RMSProp
+template <class R>       // Adam / RmsProp
 __global__ __launch_bounds__(256) void opt_prepare_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
                                                      float* __restrict__ s2, const int* __restrict__ step, const OptScalars a,
                                                      const OptPrepList l, int count) {
@@ -237,17 +188,13 @@ __global__ __launch_bounds__(256) void opt_prepare_k(float* __restrict__ p, cons
   float lr_t = a.lr;
   // Adam's bias-corrected learning rate: one thread derives it (a dependent read of the step counter + double-precision pow,
   // ~1-2 us); the block picks it up with `sync_lr()` - in the float4 path AFTER its loads are in flight (round 5)
-  if (KIND == 0 && threadIdx.x == 0) {
-    const int t = *step;
-    s_lr_t = (float)((double)a.lr * sqrt(1.0 - pow((double)a.b2, (double)t)) / (1.0 - pow((double)a.b1, (double)t)));
-  }
-  auto sync_lr = [&]() { if (KIND == 0) { __syncthreads(); lr_t = s_lr_t; } };     // block-uniform call sites only
+  constexpr bool kTwo = R::kSlots == 2;
+  if (R::kPrologue && threadIdx.x == 0) s_lr_t = R::rate(a, step);
+  auto sync_lr = [&]() { if (R::kPrologue) { __syncthreads(); lr_t = s_lr_t; } };     // block-uniform call sites only
   auto upd = [&](long long i) -> float {
-    float pp = p[i], m = s1[i];
-    if (KIND == 0) { float v = s2[i]; adam1(pp, g[i], m, v, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi); s2[i] = v; }
-    else rms1(pp, g[i], m, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-    p[i] = pp; s1[i] = m;
-    return pp;
+    float none;
+    R::one(p[i], g[i], s1[i], kTwo ? s2[i] : none, lr_t, a);
+    return p[i];
   };
   const int blk = (int)blockIdx.x;
   if (blk >= l.first_block[count]) {             // a run between two filters: beta / bias vectors, alignment gaps
@@ -275,22 +222,12 @@ __global__ __launch_bounds__(256) void opt_prepare_k(float* __restrict__ p, cons
     if (have) {
       pp = *reinterpret_cast<float4*>(p + i0); mm = *reinterpret_cast<float4*>(s1 + i0);
       gg = *reinterpret_cast<const float4*>(g + i0);
-      if (KIND == 0) vv = *reinterpret_cast<float4*>(s2 + i0);
+      if (kTwo) vv = *reinterpret_cast<float4*>(s2 + i0);
     }
     sync_lr();
     if (have) {
-      if (KIND == 0) {
-        adam1(pp.x, gg.x, mm.x, vv.x, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        adam1(pp.y, gg.y, mm.y, vv.y, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        adam1(pp.z, gg.z, mm.z, vv.z, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        adam1(pp.w, gg.w, mm.w, vv.w, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        *reinterpret_cast<float4*>(s2 + i0) = vv;
-      } else {
-        rms1(pp.x, gg.x, mm.x, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        rms1(pp.y, gg.y, mm.y, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        rms1(pp.z, gg.z, mm.z, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-        rms1(pp.w, gg.w, mm.w, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
-      }
+      four<R>(pp, gg, mm, vv, lr_t, a);
+      if (kTwo) *reinterpret_cast<float4*>(s2 + i0) = vv;
       *reinterpret_cast<float4*>(p + i0) = pp; *reinterpret_cast<float4*>(s1 + i0) = mm;
       nv[0] = pp.x; nv[1] = pp.y; nv[2] = pp.z; nv[3] = pp.w;
     }
@@ -321,6 +258,40 @@ __global__ __launch_bounds__(256) void opt_prepare_k(float* __restrict__ p, cons
         acg::bf16x4{(__bf16)tile[4 * q][r], (__bf16)tile[4 * q + 1][r], (__bf16)tile[4 * q + 2][r], (__bf16)tile[4 * q + 3][r]};
 }
 
+// The four flat entries: one argument check, one launch.  `e`: the weight average the launch carries, or null.
+struct EmaArgs {
+  float* shadow;
+  float decay;
+  int64_t* num_updates;
+  uint32_t* state;
+};
+
+int32_t flat_step(const char* who, bool adam, float* p, const float* g, float* s1, float* s2, const int32_t* step, int64_t n,
+                  const OptScalars& a, const EmaArgs* e, acg_stream_t stream) {
+  ACG_REQUIRE(n > 0 && p && g && s1 && (!adam || (s2 && step)), ACG_ERR_INVALID_ARG, "%s: bad argument", who);
+  if (e) {
+    ACG_REQUIRE(e->shadow && e->num_updates && e->state, ACG_ERR_INVALID_ARG, "%s: null shadow / counter / state word", who);
+    ACG_REQUIRE(e->decay > 0.f && e->decay < 1.f, ACG_ERR_INVALID_ARG, "%s: decay %g is not in (0, 1)", who, (double)e->decay);
+    ACG_REQUIRE((reinterpret_cast<uintptr_t>(e->num_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(e->state) & 3) == 0,
+                ACG_ERR_INVALID_ARG, "%s: the counter must be 8-byte and the state word 4-byte aligned", who);
+  }
+  const dim3 grid(acg::grid_for(n / 4 + 1)), block(256);
+  hipStream_t st = acg::to_stream(stream);
+  long long* count = e ? reinterpret_cast<long long*>(e->num_updates) : nullptr;
+  unsigned* done = e ? reinterpret_cast<unsigned*>(e->state) : nullptr;
+  if (adam && e)
+    ACG_LAUNCH(adam_ema_k, grid, block, 0, st, p, g, s1, s2, step, (long long)n, a.lr, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi,
+               e->shadow, e->decay, count, done);
+  else if (adam)
+    ACG_LAUNCH(adam_k, grid, block, 0, st, p, g, s1, s2, step, (long long)n, a.lr, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
+  else if (e)
+    ACG_LAUNCH(rmsprop_ema_k, grid, block, 0, st, p, g, s1, (long long)n, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi, e->shadow,
+               e->decay, count, done);
+  else
+    ACG_LAUNCH(rmsprop_k, grid, block, 0, st, p, g, s1, (long long)n, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
+  return acg::check_launch(who);
+}
+
 }  // namespace
 
 extern "C" {
@@ -328,53 +299,35 @@ extern "C" {
 int32_t acg_adam_step(float* param, const float* grad, float* m, float* v, const int32_t* step_dev, int64_t n, float lr,
                       float beta1, float beta2, float eps, float grad_scale, int32_t use_clip, float clip_lo, float clip_hi,
                       acg_stream_t stream) {
-  ACG_REQUIRE(n > 0 && param && grad && m && v && step_dev, ACG_ERR_INVALID_ARG, "adam_step: bad argument");
-  ACG_LAUNCH(adam_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, m, v, step_dev,
-                     (long long)n, lr, beta1, beta2, eps, grad_scale, use_clip, clip_lo, clip_hi);
-  return acg::check_launch("adam_step");
+  return flat_step("adam_step", true, param, grad, m, v, step_dev, n, {lr, beta1, beta2, eps, grad_scale, clip_lo, clip_hi, use_clip},
+                   nullptr, stream);
 }
 
 int32_t acg_rmsprop_step(float* param, const float* grad, float* ms, int64_t n, float lr, float decay, float eps,
                          float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, acg_stream_t stream) {
-  ACG_REQUIRE(n > 0 && param && grad && ms, ACG_ERR_INVALID_ARG, "rmsprop_step: bad argument");
-  ACG_LAUNCH(rmsprop_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, ms,
-                     (long long)n, lr, decay, eps, grad_scale, use_clip, clip_lo, clip_hi);
-  return acg::check_launch("rmsprop_step");
+  return flat_step("rmsprop_step", false, param, grad, ms, nullptr, nullptr, n, {lr, decay, 0.f, eps, grad_scale, clip_lo, clip_hi, use_clip},
+                   nullptr, stream);
 }
-
-#define ACG_EMA_REQUIRE(who)                                                                                                          \
-  do {                                                                                                                                \
-    ACG_REQUIRE(shadow && num_updates && state, ACG_ERR_INVALID_ARG, who ": null shadow / counter / state word");                        \
-    ACG_REQUIRE(ema_decay > 0.f && ema_decay < 1.f, ACG_ERR_INVALID_ARG, who ": decay %g is not in (0, 1)", (double)ema_decay);       \
-    ACG_REQUIRE((reinterpret_cast<uintptr_t>(num_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(state) & 3) == 0,                 \
-                ACG_ERR_INVALID_ARG, who ": the counter must be 8-byte and the state word 4-byte aligned");                           \
-  } while (0)
 
 int32_t acg_adam_step_ema(float* param, const float* grad, float* m, float* v, const int32_t* step_dev, int64_t n, float lr,
                           float beta1, float beta2, float eps, float grad_scale, int32_t use_clip, float clip_lo, float clip_hi,
                           float* shadow, float ema_decay, int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
-  ACG_REQUIRE(n > 0 && param && grad && m && v && step_dev, ACG_ERR_INVALID_ARG, "adam_step_ema: bad argument");
-  ACG_EMA_REQUIRE("adam_step_ema");
-  ACG_LAUNCH(adam_ema_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, m, v, step_dev,
-                     (long long)n, lr, beta1, beta2, eps, grad_scale, use_clip, clip_lo, clip_hi, shadow, ema_decay,
-                     reinterpret_cast<long long*>(num_updates), reinterpret_cast<unsigned*>(state));
-  return acg::check_launch("adam_step_ema");
+  const EmaArgs e{shadow, ema_decay, num_updates, state};
+  return flat_step("adam_step_ema", true, param, grad, m, v, step_dev, n, {lr, beta1, beta2, eps, grad_scale, clip_lo, clip_hi, use_clip},
+                   &e, stream);
 }
 
 int32_t acg_rmsprop_step_ema(float* param, const float* grad, float* ms, int64_t n, float lr, float decay, float eps,
                              float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, float* shadow, float ema_decay,
                              int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
-  ACG_REQUIRE(n > 0 && param && grad && ms, ACG_ERR_INVALID_ARG, "rmsprop_step_ema: bad argument");
-  ACG_EMA_REQUIRE("rmsprop_step_ema");
-  ACG_LAUNCH(rmsprop_ema_k, dim3(grid_for(n / 4 + 1)), dim3(256), 0, acg::to_stream(stream), param, grad, ms,
-                     (long long)n, lr, decay, eps, grad_scale, use_clip, clip_lo, clip_hi, shadow, ema_decay,
-                     reinterpret_cast<long long*>(num_updates), reinterpret_cast<unsigned*>(state));
-  return acg::check_launch("rmsprop_step_ema");
+  const EmaArgs e{shadow, ema_decay, num_updates, state};
+  return flat_step("rmsprop_step_ema", false, param, grad, ms, nullptr, nullptr, n,
+                   {lr, decay, 0.f, eps, grad_scale, clip_lo, clip_hi, use_clip}, &e, stream);
 }
 
 int32_t acg_clip(float* param, int64_t n, float lo, float hi, acg_stream_t stream) {
   ACG_REQUIRE(n > 0 && param, ACG_ERR_INVALID_ARG, "clip: bad argument");
-  ACG_LAUNCH(clip_k, dim3(grid_for(n)), dim3(256), 0, acg::to_stream(stream), param, (long long)n, lo, hi);
+  ACG_LAUNCH(clip_k, dim3(acg::grid_for(n)), dim3(256), 0, acg::to_stream(stream), param, (long long)n, lo, hi);
   return acg::check_launch("clip");
 }
 
@@ -413,8 +366,8 @@ int32_t acg_opt_step_prepare_bf16(float* param, const float* grad, float* slot1,
   l.first_block[count] = (int)blocks;
   const OptScalars a{args->lr, args->beta1_or_decay, args->beta2, args->eps, args->grad_scale, args->clip_lo, args->clip_hi, args->use_clip};
   hipStream_t st = acg::to_stream(stream);
-  if (args->kind == 0) ACG_LAUNCH((opt_prepare_k<0>), dim3((unsigned)(blocks + ngaps)), dim3(256), 0, st, param, grad, slot1, slot2, (const int*)step_dev, a, l, (int)count);
-  else ACG_LAUNCH((opt_prepare_k<1>), dim3((unsigned)(blocks + ngaps)), dim3(256), 0, st, param, grad, slot1, slot2, (const int*)step_dev, a, l, (int)count);
+  if (args->kind == 0) ACG_LAUNCH((opt_prepare_k<Adam>), dim3((unsigned)(blocks + ngaps)), dim3(256), 0, st, param, grad, slot1, slot2, (const int*)step_dev, a, l, (int)count);
+  else ACG_LAUNCH((opt_prepare_k<RmsProp>), dim3((unsigned)(blocks + ngaps)), dim3(256), 0, st, param, grad, slot1, slot2, (const int*)step_dev, a, l, (int)count);
   return acg::check_launch("opt_step_prepare_bf16");
 }
 

@@ -68,6 +68,18 @@ def _dp(graph):
     return graph.collections.get('data_parallel') or DataParallel(1)
 
 
+def _chain(*launches):
+    """The launches that are not None as one launch, in order (a single one: itself)."""
+    live = [f for f in launches if f is not None]
+    if len(live) == 1:
+        return live[0]
+
+    def launch(s):
+        for f in live:
+            f(s)
+    return launch
+
+
 class AllReduceOp(G.Op):
     """Sum-all-reduce of one contiguous gradient bucket, in place: ``ncclAllReduce`` on the stream the launch list
     hands it - the compute stream (collectives='stream') or the session's side stream (collectives='side',
@@ -212,7 +224,7 @@ class StepOp(G.Op):
     scope's weight average is updated from the new parameters behind the update -
     float32 graph, Adam / RMSProp: inside the optimizer's launch (acg_adam_step_ema / acg_rmsprop_step_ema);
     bf16 graph: acg_ema_update behind the update-and-refresh launch(es), which stay as they are;
-    where the fused entry is declined (an optimizer without one, Session(fuse_ema=False)): acg_ema_update behind the plain step."""
+    where the fused entry is declined (Session(fuse_ema=False)): acg_ema_update behind the plain step."""
     is_optimizer_step = True
     joins_side = True        # reads every gradient of its scope, whichever stream produced it
 
@@ -229,38 +241,20 @@ class StepOp(G.Op):
         return self._copies + (self.ema.tensors() if self.ema is not None else [])
 
     def bind(self, rt):
-        if self.ema is None:
-            return self._bind_update(rt)
-        ema, p = self.ema, self.inputs[0]
-        update = _lib.entry(rt.lib, 'ema_update')
-        if not self.graph.weight_copies.get(self.scope) and getattr(rt, 'fuse_ema', True):
-            fused = self.opt._bind_step_ema(rt, self, self.program_clip, ema)
-            if fused is not None:
-                return fused
-        step = self._bind_update(rt)
-        args = (_p(ema.shadow.buf), _p(p.buf), p.numel, ema.decay, _p(ema.num_updates.buf), _p(ema.done.buf))
-
-        def launch(s):
-            step(s)
-            update(*args, s)
-        return launch
-
-    def _bind_update(self, rt):
+        opt, ema, clip, update = self.opt, self.ema, self.program_clip, None
+        if ema is not None:
+            fn, p = _lib.entry(rt.lib, 'ema_update'), self.inputs[0]
+            args = (_p(ema.shadow.buf), _p(p.buf), p.numel, ema.decay, _p(ema.num_updates.buf), _p(ema.done.buf))
+            update = lambda s: fn(*args, s)
+            if not self.graph.weight_copies.get(self.scope) and getattr(rt, 'fuse_ema', True):
+                return opt._bind_flat(rt, self, clip, ema)
         # bf16 pipeline: the conv kernels read bf16 copies of the filters, which follow the update.  Round 4: update and
         # refresh are ONE launch (acg_opt_step_prepare_bf16: the blocks that write a filter's copies update its elements) where
         # every copy of the scope fits one list; else two launches as before
-        fused = self.opt._bind_step_prepared(rt, self, self.program_clip) if rt.fuse_weight_refresh else None
-        if fused is not None:
-            return fused
-        step = self.opt._bind_step(rt, self, self.program_clip)
-        prep = O.prepare_weights_launch(rt, self.graph, self.scope)
-        if prep is None:
-            return step
-
-        def launch(s):
-            step(s)
-            prep(s)
-        return launch
+        step = opt._bind_prepared(rt, self, clip) if rt.fuse_weight_refresh else None
+        if step is None:
+            step = _chain(opt._bind_flat(rt, self, clip), O.prepare_weights_launch(rt, self.graph, self.scope))
+        return _chain(step, update)
 
 
 class ClipOp(G.Op):
@@ -298,42 +292,46 @@ class Optimizer:
     def _make_slots(self, graph, total):
         raise NotImplementedError
 
-    def _bind_step(self, rt, step_op, clip):
+    def _describe(self, op):
+        """What the optimizer is, said once: -> (kind of acg_opt_args, the flat entry's name - ``<entry>_ema`` carries a weight
+        average -, (lr, beta1 | decay, beta2 | None, eps), [slot, ...], step counter | None)."""
         raise NotImplementedError
 
-    def _bind_step_ema(self, rt, step_op, clip, ema):
-        """_bind_step with the weight average ``ema`` updated in the same launch, or None (declined: StepOp then runs the
-        stand-alone update behind _bind_step)."""
+    def _before(self, rt, op, step):
+        """The launch that must precede the update of this program, or None."""
         return None
 
-    def _opt_args(self, rt, op, clip):
-        """-> (kind, (lr, beta1 | decay, beta2, eps), slot1, slot2 | None, step counter | None, launch that must precede | None)"""
-        raise NotImplementedError
+    def _bind_flat(self, rt, op, clip, ema=None):
+        """The flat entry over the scope's buffers; with ``ema`` the one that updates that weight average in the same launch."""
+        _, entry, hyper, slots, step = self._describe(op)
+        p, g = op.inputs[:2]
+        lo, hi = clip if clip else (0.0, 0.0)
+        buffers = [p, g] + slots + ([step] if step is not None else [])
+        args = tuple(_p(t.buf) for t in buffers) + (p.numel,) + tuple(h for h in hyper if h is not None)
+        args += (op.grad_scale, 1 if clip else 0, lo, hi) + (ema.args() if ema is not None else ())
+        fn = _lib.entry(rt.lib, entry + ('_ema' if ema is not None else ''))
+        return _chain(self._before(rt, op, step), lambda s: fn(*args, s))
 
-    def _bind_step_prepared(self, rt, op, clip):
+    def _bind_prepared(self, rt, op, clip):
         """One launch for the update of the scope and the refresh of its bf16 filter copies, or None (no copies: a float32
         graph; more filters than one list holds)."""
         import ctypes
         entries = op.graph.weight_copies.get(op.scope) or []
         if not entries or len(entries) > _lib.PREP_MAX:
             return None
-        kind, fields, s1, s2, step, before = self._opt_args(rt, op, clip)
+        kind, _, hyper, slots, step = self._describe(op)
         pl = _lib.PrepList()
         for i, (w, rm, tr) in enumerate(entries):
             kh, kw, a, b = w.shape
             pl.src[i], pl.rm[i], pl.tr[i] = w.buf.data_ptr(), rm.buf.data_ptr(), tr.buf.data_ptr()
             pl.taps[i], pl.a[i], pl.b[i] = kh * kw, a, b
         lo, hi = clip if clip else (0.0, 0.0)
-        oa = _lib.OptArgs(kind, fields[0], fields[1], fields[2], fields[3], op.grad_scale, 1 if clip else 0, lo, hi)
-        p, g = op.inputs[0], op.inputs[1]
-        args = (_p(p.buf), _p(g.buf), _p(s1.buf), _p(s2.buf) if s2 is not None else None, _p(step.buf) if step is not None else None,
-                p.numel, ctypes.byref(oa), ctypes.byref(pl), len(entries))
+        oa = _lib.OptArgs(kind, *(h or 0.0 for h in hyper), op.grad_scale, 1 if clip else 0, lo, hi)
+        p, g = op.inputs[:2]
+        s1, s2 = (slots + [None])[:2]
+        args = tuple(_p(t.buf) if t is not None else None for t in (p, g, s1, s2, step)) + (p.numel, ctypes.byref(oa), ctypes.byref(pl), len(entries))
         fn = rt.lib.opt_step_prepare_bf16
-
-        def launch(s):
-            if before is not None:
-                before(s)
-            fn(*args, s)
+        launch = _chain(self._before(rt, op, step), lambda s: fn(*args, s))
         launch._keep = (oa, pl)
         return launch
 
@@ -467,35 +465,11 @@ class AdamOptimizer(Optimizer):
         inc, ps = rt.lib.step_inc, _p(step.buf)
         return lambda s: inc(ps, s)
 
-    def _bind_step(self, rt, op, clip):
-        p, g, m, v, step = op.inputs
-        lo, hi = clip if clip else (0.0, 0.0)
-        adam, before = rt.lib.adam_step, self._step_inc_launch(rt, op, step)
-        args = (_p(p.buf), _p(g.buf), _p(m.buf), _p(v.buf), _p(step.buf), p.numel, self.lr, self.b1, self.b2, self.eps,
-                op.grad_scale, 1 if clip else 0, lo, hi)
+    _before = _step_inc_launch
 
-        def launch(s):
-            if before is not None:
-                before(s)
-            adam(*args, s)
-        return launch
-
-    def _bind_step_ema(self, rt, op, clip, ema):
-        p, g, m, v, step = op.inputs
-        lo, hi = clip if clip else (0.0, 0.0)
-        adam, before = _lib.entry(rt.lib, 'adam_step_ema'), self._step_inc_launch(rt, op, step)
-        args = (_p(p.buf), _p(g.buf), _p(m.buf), _p(v.buf), _p(step.buf), p.numel, self.lr, self.b1, self.b2, self.eps,
-                op.grad_scale, 1 if clip else 0, lo, hi) + ema.args()
-
-        def launch(s):
-            if before is not None:
-                before(s)
-            adam(*args, s)
-        return launch
-
-    def _opt_args(self, rt, op, clip):
-        p, g, m, v, step = op.inputs
-        return 0, (self.lr, self.b1, self.b2, self.eps), m, v, step, self._step_inc_launch(rt, op, step)
+    def _describe(self, op):
+        m, v, step = op.inputs[2:]
+        return 0, 'adam_step', (self.lr, self.b1, self.b2, self.eps), [m, v], step
 
 
 class RMSPropOptimizer(Optimizer):
@@ -510,22 +484,5 @@ class RMSPropOptimizer(Optimizer):
     def _make_slots(self, graph, total):
         return [graph.new_state((total,), 1.0, self.name + '/ms')]
 
-    def _bind_step(self, rt, op, clip):
-        p, g, ms = op.inputs
-        lo, hi = clip if clip else (0.0, 0.0)
-        args = (_p(p.buf), _p(g.buf), _p(ms.buf), p.numel, self.lr, self.decay, self.eps, op.grad_scale,
-                1 if clip else 0, lo, hi)
-        fn = rt.lib.rmsprop_step
-        return lambda s: fn(*args, s)
-
-    def _bind_step_ema(self, rt, op, clip, ema):
-        p, g, ms = op.inputs
-        lo, hi = clip if clip else (0.0, 0.0)
-        args = (_p(p.buf), _p(g.buf), _p(ms.buf), p.numel, self.lr, self.decay, self.eps, op.grad_scale,
-                1 if clip else 0, lo, hi) + ema.args()
-        fn = _lib.entry(rt.lib, 'rmsprop_step_ema')
-        return lambda s: fn(*args, s)
-
-    def _opt_args(self, rt, op, clip):
-        p, g, ms = op.inputs
-        return 1, (self.lr, self.decay, 0.0, self.eps), ms, None, None, None
+    def _describe(self, op):
+        return 1, 'rmsprop_step', (self.lr, self.decay, None, self.eps), [op.inputs[2]], None

@@ -25,6 +25,10 @@ pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
 DECAY = float(np.float32(0.999))
+# the launch grid is min(4096, ceil((n / 4 + 1) / 256)) blocks of 256 threads: only past 4 * 4096 * 256 elements does the grid-stride
+# loop of a float4 path run (here for the first blocks, and n % 4 == 3); N_TAIL is for views one float off the 16-byte grid
+N_STRIDE = 4 * 4096 * 256 + 2051
+N_TAIL = 4096 * 256 + 5
 
 
 def _p(t):
@@ -82,10 +86,10 @@ def _check_against_restatement(n, start, inputs, got):
         assert diff == 0, 'n %d, counter %d: %d elements differ from the restatement' % (n, start + j, diff)
 
 
-@pytest.mark.parametrize('n', [1, 3, 4, 5, 255, 257, 4097, 1048579])
+@pytest.mark.parametrize('n', [1, 3, 4, 5, 255, 257, 4097, 1048579, N_STRIDE])
 def test_ema_update_is_the_restatement_bit_for_bit(n):
     lib = _lib.get()
-    for start in (0, 1, 2, 8, 8989, 8991, 10 ** 7):
+    for start in (0, 1, 2, 8, 8989, 8991, 10 ** 7) if n < N_STRIDE else (0, 8989):          # (the coefficient does not depend on n)
         inputs = _ema_inputs(n, start)
         first = _ema_sequence(lib, n, start, inputs)
         _check_against_restatement(n, start, inputs, first)
@@ -93,7 +97,7 @@ def test_ema_update_is_the_restatement_bit_for_bit(n):
         assert all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(first, again)), 'a second sequence gives other bits'
 
 
-@pytest.mark.parametrize('n', [1, 6, 4097])
+@pytest.mark.parametrize('n', [1, 6, 4097, N_TAIL])
 def test_ema_update_on_buffers_off_the_16_byte_grid(n):
     inputs = _ema_inputs(n, 3)
     _check_against_restatement(n, 3, inputs, _ema_sequence(_lib.get(), n, 3, inputs, offset=1))
@@ -135,11 +139,19 @@ def _opt_inputs(n, seed):
     return param, grads
 
 
+def _shifted(t, offset):
+    """``t`` as a view ``offset`` floats into an allocation of its own (offset 1: off the 16-byte grid)."""
+    buf = torch.zeros(t.numel() + offset, dtype=t.dtype, device=DEV)
+    buf[offset:].copy_(t)
+    return buf[offset:]
+
+
 @pytest.mark.parametrize('start', [0, 8989])
-@pytest.mark.parametrize('n', [5, 4097, 1048579])
+@pytest.mark.parametrize('n,offset', [(5, 0), (4097, 0), (1048579, 0), (4097, 1), (N_STRIDE, 0), (N_TAIL, 1)],
+                         ids=['5', '4097', '1048579', '4097_off1', str(N_STRIDE), '%d_off1' % N_TAIL])
 @pytest.mark.parametrize('clip', [False, True])
 @pytest.mark.parametrize('kind', ['adam', 'rmsprop'])
-def test_fused_steps_equal_the_two_launches(kind, clip, n, start):
+def test_fused_steps_equal_the_two_launches(kind, clip, n, offset, start):
     lib = _lib.get()
     lr, b1, b2, eps, gs = (float(np.float32(v)) for v in (1e-3, 0.9, 0.999, 1e-8, 0.5))
     rlr, rdecay, reps = (float(np.float32(v)) for v in (5e-5, 0.9, 1e-10))
@@ -147,10 +159,11 @@ def test_fused_steps_equal_the_two_launches(kind, clip, n, start):
     results = []
     for fused in (False, True):
         param, grads = _opt_inputs(n, n + start)
-        s1 = torch.zeros(n, device=DEV) if kind == 'adam' else torch.ones(n, device=DEV)
-        s2 = torch.zeros(n, device=DEV)
+        param, grads = _shifted(param, offset), [_shifted(g, offset) for g in grads]
+        s1 = _shifted(torch.zeros(n, device=DEV) if kind == 'adam' else torch.ones(n, device=DEV), offset)
+        s2 = _shifted(torch.zeros(n, device=DEV), offset)
         step = torch.zeros(1, dtype=torch.int32, device=DEV)
-        shadow = _dev(R.kernel_values(np.random.default_rng(n), n))
+        shadow = _shifted(_dev(R.kernel_values(np.random.default_rng(n), n)), offset)
         count, word = _ema_state(start)
         for t, g in enumerate(grads):
             step.fill_(t + 1)
@@ -182,7 +195,7 @@ def test_fused_steps_equal_the_two_launches(kind, clip, n, start):
         assert torch.equal(results[0][3], results[0][0])
 
 
-@pytest.mark.parametrize('n', [1, 3, 5, 255, 257, 4097, 1048579])
+@pytest.mark.parametrize('n', [1, 3, 5, 255, 257, 4097, 1048579, N_STRIDE])
 def test_swap_exchanges_and_two_swaps_restore(n):
     lib = _lib.get()
     rng = np.random.default_rng(n)
