@@ -37,36 +37,8 @@ constexpr int env_int(const char*, int dflt) { return dflt; }
 #endif
 constexpr int kMaxC = 1024;
 
-struct ColMap {
-  int Cb, RPP, cl, rsub, nchunk;
-  bool active;
-};
-__device__ __forceinline__ ColMap col_map(int C) {
-  ColMap m;
-  m.Cb = C < 256 ? C : 256;
-  m.RPP = 256 / m.Cb;
-  m.cl = threadIdx.x % m.Cb;
-  m.rsub = threadIdx.x / m.Cb;
-  m.active = m.rsub < m.RPP;
-  m.nchunk = (C + m.Cb - 1) / m.Cb;
-  return m;
-}
-
-// Reduce two per-thread values over the rsub dimension; result valid where rsub == 0.
-__device__ __forceinline__ void reduce_rsub(const ColMap& m, float& a, float& b, float* sh /* 512 floats */) {
-  __syncthreads();
-  sh[threadIdx.x] = a;
-  sh[256 + threadIdx.x] = b;
-  __syncthreads();
-  if (m.active && m.rsub == 0) {
-    float sa = 0.f, sb = 0.f;
-    for (int r = 0; r < m.RPP; ++r) { sa += sh[r * m.Cb + m.cl]; sb += sh[256 + r * m.Cb + m.cl]; }
-    a = sa; b = sb;
-  }
-}
-
-// ---- vectorised [rows, C] walking ----------------------------------------------------------------------
-// V = 4 floats per lane when C % 4 == 0 (every BatchNorm'd layer of the models except d/conv6), else 1.
+// ---- [rows, C] walking: 256 threads = (256 / Cb) rows x Cb lanes of V channels --------------------------
+// V = 4 floats per lane when C % 4 == 0 (every BatchNorm'd layer of the models except d/conv6), else 1 (also the bias kernels).
 template <int V>
 struct VMap {
   int Cv, Cb, RPP, cl, rsub, nchunk;
@@ -128,6 +100,35 @@ __device__ __forceinline__ void ld_or_sum(T* base, long long off, const Slabs& s
 #pragma unroll
   for (int j = 0; j < V; ++j) v[j] = (float)(T)v[j];
   if (write) stv<V>(base + off, v);
+}
+
+// Sums of d = x - pv and of d^2 over the R rows of a group (pv: the group's first row) -> mean, rstd; the combine in float64
+// (the float64 square root and division were most of the apply kernel's instructions: rsqrtf on the float32 variance)
+template <int V>
+__device__ __forceinline__ void stats_from_shifted(const float (&s1)[V], const float (&s2)[V], const float (&pv)[V], long long R, float eps,
+                                                   float (&mean)[V], float (&rstd)[V]) {
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    const double inv = 1.0 / (double)R, dm = (double)s1[j] * inv;
+    double var = (double)s2[j] * inv - dm * dm;
+    var = var > 0.0 ? var : 0.0;
+    mean[j] = (float)((double)pv[j] + dm);
+    rstd[j] = rsqrtf((float)var + eps);
+  }
+}
+// dbeta[c ...] = acc * dbeta[c ...] + tot (acc == 0: dbeta is not read)
+template <int V>
+__device__ __forceinline__ void store_dbeta(float* __restrict__ dbeta, int c, float acc, const float (&tot)[V]) {
+  float d[V];
+  if (acc != 0.f) {
+    ldv<V>(dbeta + c, d);
+#pragma unroll
+    for (int j = 0; j < V; ++j) d[j] = acc * d[j] + tot[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) d[j] = tot[j];
+  }
+  stv<V>(dbeta + c, d);
 }
 
 // partial layout: part[((g * nblk + b) * 2 + which) * C + c]
@@ -323,14 +324,7 @@ __global__ __launch_bounds__(NT) void bn_apply_fwd(const TX* __restrict__ x, con
     sum_partials<V, CL>(part, g, nblk, C, c, cvalid, rl, s1, s2, sh);
     if (!cvalid) return;
     ldv<V>(xg + c, pv);
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-      const double inv = 1.0 / (double)R, dm = (double)s1[j] * inv;
-      double var = (double)s2[j] * inv - dm * dm;
-      var = var > 0.0 ? var : 0.0;
-      mean[j] = (float)((double)pv[j] + dm);
-      rstd[j] = rsqrtf((float)var + eps);        // (the float64 square root and division were most of this kernel's instructions)
-    }
+    stats_from_shifted<V>(s1, s2, pv, R, eps, mean, rstd);
   } else {
     if (!cvalid) return;
     ldv<V>(save_mean + g * C + c, mean); ldv<V>(save_rstd + g * C + c, rstd);
@@ -466,18 +460,7 @@ __global__ __launch_bounds__(NT) void bn_apply_bwd(const TX* __restrict__ x, con
     }
 #pragma unroll
     for (int j = 0; j < V; ++j) { s1[j] = k1[j]; s2[j] = k2[j]; }
-    if (cvalid && rl == 0) {
-      float d[V];
-      if (dbeta_acc != 0.f) {
-        ldv<V>(dbeta + c, d);
-#pragma unroll
-        for (int j = 0; j < V; ++j) d[j] = dbeta_acc * d[j] + tot[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < V; ++j) d[j] = tot[j];
-      }
-      stv<V>(dbeta + c, d);
-    }
+    if (cvalid && rl == 0) store_dbeta<V>(dbeta, c, dbeta_acc, tot);
   } else {
     sum_partials<V, CL>(part, g, nblk, C, c, cvalid, rl, s1, s2, sh);
   }
@@ -549,7 +532,8 @@ struct FusedExchange {
   unsigned spin_limit = 1u << 22;      // polls before a block gives up (seconds); acg_bn_exchange_selftest lowers it
 
   // the per-thread partials s[0..7] (value index within the lane: {stat 0: 0..3, stat 1: 4..7}) -> this block's 64 sums, published
-  __device__ __forceinline__ void publish(float (&s)[2 * V], long long slot /* granule index of this block's value 0 */) {
+  // folds the row lanes of each wave and leaves the waves' sums in red; thread tid < NV then adds up value tid of the block
+  __device__ __forceinline__ void fold_waves(float (&s)[2 * V]) {
 #pragma unroll
     for (int j = 0; j < 2 * V; ++j) {
 #pragma unroll
@@ -560,10 +544,17 @@ struct FusedExchange {
       for (int j = 0; j < 2 * V; ++j) red[wave][lane * 2 * V + j] = s[j];
     }
     __syncthreads();
-    if (tid < NV) {
-      float v = 0.f;
+  }
+  __device__ __forceinline__ float block_value() const {
+    float v = 0.f;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) v += red[w][tid];
+    for (int w = 0; w < NW; ++w) v += red[w][tid];
+    return v;
+  }
+  __device__ __forceinline__ void publish(float (&s)[2 * V], long long slot /* granule index of this block's value 0 */) {
+    fold_waves(s);
+    if (tid < NV) {
+      const float v = block_value();
       __hip_atomic_store((gran_ptr)(grans + slot + tid), ((unsigned long long)epoch << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -572,22 +563,8 @@ struct FusedExchange {
   // a grid with ONE row block per (group, chunk) has nobody to exchange with: the block's own 64 sums straight into out[NV] (LDS) -
   // no granule store, no polling round trip (round 5: the 2x2 ... 4x4 layers, whose whole tensor is one row block)
   __device__ __forceinline__ void local(float (&s)[2 * V], float* out) {
-#pragma unroll
-    for (int j = 0; j < 2 * V; ++j) {
-#pragma unroll
-      for (int off = CL; off < 64; off <<= 1) s[j] += __shfl_xor(s[j], off, 64);
-    }
-    if (lane < CL) {
-#pragma unroll
-      for (int j = 0; j < 2 * V; ++j) red[wave][lane * 2 * V + j] = s[j];
-    }
-    __syncthreads();
-    if (tid < NV) {
-      float v = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) v += red[w][tid];
-      out[tid] = v;
-    }
+    fold_waves(s);
+    if (tid < NV) out[tid] = block_value();
     __syncthreads();
   }
   // sums over the nrb row blocks whose granules start at `base` ([row block][NV]) -> out[NV] (LDS); every thread of the block calls it
@@ -800,15 +777,10 @@ __global__ __launch_bounds__(NT) void bn_fwd_fused(TX* __restrict__ x, const flo
     ex.gather(base, tot);
   }
   if (cvalid) {
-    float mean[V], rstd[V];
+    float mean[V], rstd[V], s1[V], s2[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-      const double inv = 1.0 / (double)R, dm = (double)tot[cq * 2 * V + j] * inv;
-      double var = (double)tot[cq * 2 * V + V + j] * inv - dm * dm;
-      var = var > 0.0 ? var : 0.0;
-      mean[j] = (float)((double)pv[j] + dm);
-      rstd[j] = rsqrtf((float)var + eps);
-    }
+    for (int j = 0; j < V; ++j) { s1[j] = tot[cq * 2 * V + j]; s2[j] = tot[cq * 2 * V + V + j]; }
+    stats_from_shifted<V>(s1, s2, pv, R, eps, mean, rstd);
     if (rb == 0 && rl == 0) { stv<V>(save_mean + g * C + c, mean); stv<V>(save_rstd + g * C + c, rstd); }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -861,8 +833,12 @@ struct FusedShape { int nt, U; dim3 grid; };
 // the round-4 bound "one block per CU" alone, 131072 x 16 asked for 131 KB of granules in a 66 KB workspace - ADVICE r4).
 constexpr int kMaxFusedBlocks = 512;
 constexpr size_t kFusedExchangeBytes = (size_t)kMaxFusedBlocks * 512;
-FusedShape fused_shape(long long R, int C, int groups, bool no_grid = false, int splits = 0) {
+int device_cus() {
   static const int ncu = [] { int dev = 0, n = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0; (void)hipGetLastError(); return n; }();
+  return ncu;
+}
+// (`ncu`: the CU count of the device - BnCall carries device_cus(); a pure function of its arguments apart from the tuning hooks)
+FusedShape fused_shape(long long R, int C, int groups, bool no_grid, int splits, int ncu) {
   static const int small_rb = env_int("ACG_BN_FUSED_SMALL_ROWBLOCKS", 16);       // tuning hook
   FusedShape f{0, 0, dim3(1, 1, 1)};
   if (ncu <= 0 || no_grid) return f;
@@ -932,15 +908,10 @@ __global__ __launch_bounds__(256) void bn_resident_fwd(TX* __restrict__ x, const
     for (int j = 0; j < V; ++j) { const float d = (v[u][j] - pv[j]) * w; s[j] += d; s[V + j] += d * d; }
   }
   block_sum<2 * V>(s, sh);
-  float mean[V], rstd[V];
+  float mean[V], rstd[V], s1[V], s2[V];
 #pragma unroll
-  for (int j = 0; j < V; ++j) {
-    const double inv = 1.0 / (double)R, dm = (double)s[j] * inv;
-    double var = (double)s[V + j] * inv - dm * dm;
-    var = var > 0.0 ? var : 0.0;
-    mean[j] = (float)((double)pv[j] + dm);
-    rstd[j] = rsqrtf((float)var + eps);        // (the float64 square root and division were most of this kernel's instructions)
-  }
+  for (int j = 0; j < V; ++j) { s1[j] = s[j]; s2[j] = s[V + j]; }
+  stats_from_shifted<V>(s1, s2, pv, R, eps, mean, rstd);
   if (threadIdx.x == 0) { stv<V>(save_mean + g * C + c, mean); stv<V>(save_rstd + g * C + c, rstd); }
 #pragma unroll
   for (int u = 0; u < NR; ++u) {
@@ -1004,26 +975,22 @@ __global__ __launch_bounds__(256) void bn_resident_bwd(const TX* __restrict__ x,
       }
     }
   }
-  if (threadIdx.x == 0) {
-    float d[V];
-    if (dbeta_acc != 0.f) {
-      ldv<V>(dbeta + c, d);
-#pragma unroll
-      for (int j = 0; j < V; ++j) d[j] = dbeta_acc * d[j] + tot[j];
-    } else {
-#pragma unroll
-      for (int j = 0; j < V; ++j) d[j] = tot[j];
-    }
-    stv<V>(dbeta + c, d);
-  }
+  if (threadIdx.x == 0) store_dbeta<V>(dbeta, c, dbeta_acc, tot);
 }
 
 // Rows per thread of the resident kernels, 0 = two-launch path.  `R` = rows a block walks (fwd: one group; bwd: all
 // groups in turn).  A block pulls one cache line per row through its CU's L1, ~2R cycles: measured break-even
 // against the two-launch path is ~2048 rows (profiles/r1/q_non_conv_ops.txt: 512 rows 3.9 vs 7.5 us, 2048 rows 6.1
 // vs 7.7 us, 4096 rows 20.9 vs 9.5 us, 8192 rows 23.5 vs 9.3 us).
+constexpr int kResidentRows = 2048;
+#ifdef ACG_TUNING
+constexpr int kMaxNrFwd = 32, kMaxNrBwd = 16;     // a tuning build can raise the limit: it carries the kernels to go with it
+#else
+constexpr int kMaxNrFwd = 8, kMaxNrBwd = 8;       // pick_nr offers no more: the larger kernels could never run
+static_assert(kResidentRows <= 256 * kMaxNrFwd && kResidentRows <= 256 * kMaxNrBwd, "resident_nr must not return an NR that pick_nr does not offer");
+#endif
 int resident_nr(long long R, int max_nr) {
-  static const int lim = env_int("ACG_BN_RESIDENT_ROWS", 2048);     // tuning hook; 0 disables the resident kernels
+  static const int lim = env_int("ACG_BN_RESIDENT_ROWS", kResidentRows);     // tuning hook; 0 disables the resident kernels
   if (R > lim) return 0;
   for (int nr = 1; nr <= max_nr; nr *= 2)
     if (R <= 256ll * nr) return nr;
@@ -1035,7 +1002,7 @@ int resident_nr(long long R, int max_nr) {
 template <typename TI, typename TO>
 __global__ __launch_bounds__(256) void bias_act_fwd_k(const TI* __restrict__ x, const float* __restrict__ bias,
                                                       TO* __restrict__ y, long long R, int C, int xp, int yp, int act, float leak) {
-  const ColMap m = col_map(C);
+  const VMap<1> m = vmap<1>(C);
   if (!m.active) return;
   for (int ch = 0; ch < m.nchunk; ++ch) {
     const int c = ch * m.Cb + m.cl;
@@ -1052,13 +1019,13 @@ __global__ __launch_bounds__(256) void bias_act_bwd_partial(const TO* __restrict
                                                             TI* __restrict__ dx, float* __restrict__ part,
                                                             long long R, int C, int xp, int yp, int nblk, int act, float leak) {
   __shared__ float sh[512];
-  const ColMap m = col_map(C);
+  const VMap<1> m = vmap<1>(C);
   const int b = blockIdx.x;
   const long long rpb = (R + nblk - 1) / nblk;
   const long long r0 = (long long)b * rpb, r1 = min(R, r0 + rpb);
   for (int ch = 0; ch < m.nchunk; ++ch) {
     const int c = ch * m.Cb + m.cl;
-    float s1 = 0.f, s2 = 0.f;
+    float s1[1] = {0.f}, s2[1] = {0.f};
     if (m.active && c < C) {
       // batches of 4 row passes with all loads in flight; y is not read at all for the identity activation
       for (long long r = r0 + m.rsub; r < r1; r += 4 * m.RPP) {
@@ -1074,13 +1041,13 @@ __global__ __launch_bounds__(256) void bias_act_bwd_partial(const TO* __restrict
           if (r + u * m.RPP < r1) {
             const float gq = g[u] * acg::act_deriv_out(act, yv[u], leak);
             if (dx) acg::stf(dx + (r + u * m.RPP) * xp + c, gq);
-            s1 += gq;
+            s1[0] += gq;
           }
         }
       }
     }
-    reduce_rsub(m, s1, s2, sh);
-    if (part && m.active && m.rsub == 0 && c < C) part[(long long)b * C + c] = s1;
+    reduce_rsub_v<1>(m, s1, s2, sh);
+    if (part && m.active && m.rsub == 0 && c < C) part[(long long)b * C + c] = s1[0];
   }
 }
 
@@ -1195,12 +1162,170 @@ __global__ __launch_bounds__(256) void bn_dbeta_local_k(const float* __restrict_
   dbeta[c] = (acc != 0.f ? acc * dbeta[c] : 0.f) + s;
 }
 
-int check_bn(const char* who, long long rows, int C, int groups) {
+// ---- host side: one prepared call, the path rule, one launch statement per kernel family -----------------------------------
+// What every BatchNorm entry hands to the dispatcher once prepare has checked its arguments (R: rows per group; v4: four channels per lane - C and the pitches % 4 == 0, the entry's pointers 16-byte aligned; ncu: device_cus())
+struct BnCall {
+  long long R; int C, groups, XP, YP, act; float leak, eps;
+  bool v4, no_grid; Slabs sl; float* ws; hipStream_t st; int ncu;
+};
+
+// The checks the entries share - each entry names the ones it has (an entry without a y pitch passes its x pitch twice) - and
+// the call they describe.  v4 still lacks the entry's pointers: c.v4 = c.v4 && aligned16(...).
+enum : unsigned { kCheckAct = 1, kCheckFlags = 2, kCheckWs = 4 };
+int prepare(const char* who, unsigned checks, BnCall& c, int64_t rows, int C, int x_pitch, int y_pitch, int groups, float eps, int act,
+            float leak, int flags, void* ws, size_t wsb, acg_stream_t stream) {
+  c.XP = x_pitch > 0 ? x_pitch : C;
+  c.YP = y_pitch > 0 ? y_pitch : C;
+  ACG_REQUIRE(c.XP >= C && c.YP >= C, ACG_ERR_INVALID_ARG, "%s: pitch smaller than the row", who);
+  if (checks & kCheckFlags) ACG_REQUIRE((flags & ~ACG_BN_NO_GRID_EXCHANGE) == 0, ACG_ERR_INVALID_ARG, "%s: unknown flags 0x%x", who, flags);
   ACG_REQUIRE(rows > 0 && C > 0 && groups > 0, ACG_ERR_INVALID_ARG, "%s: non-positive size", who);
-  ACG_REQUIRE(rows % groups == 0, ACG_ERR_INVALID_ARG, "%s: rows (%lld) not divisible by groups (%d)", who, rows, groups);
+  ACG_REQUIRE(rows % groups == 0, ACG_ERR_INVALID_ARG, "%s: rows (%lld) not divisible by groups (%d)", who, (long long)rows, groups);
   ACG_REQUIRE(C <= kMaxC, ACG_ERR_UNSUPPORTED, "%s: more than %d channels", who, kMaxC);
   ACG_REQUIRE(groups <= 65535, ACG_ERR_UNSUPPORTED, "%s: too many groups", who);
+  if (checks & kCheckAct) ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "%s: activation %d", who, act);
+  if (checks & kCheckWs) ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "%s: workspace too small", who);
+  c.R = rows / groups; c.C = C; c.groups = groups; c.act = act; c.leak = leak; c.eps = eps;
+  c.v4 = C % 4 == 0 && c.XP % 4 == 0 && c.YP % 4 == 0;
+  c.no_grid = (flags & ACG_BN_NO_GRID_EXCHANGE) != 0;
+  c.sl = Slabs{nullptr, 0, 0, 0}; c.ws = (float*)ws; c.st = acg::to_stream(stream); c.ncu = device_cus();
   return ACG_OK;
+}
+template <typename... P>
+bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+// The slabs of the two hand-off entries (`want`: what acg_bn_slabs_layout answers for the tensor; `pitch`: of the summed tensor); c.v4 is final
+int take_slabs(const char* who, BnCall& c, const float* slabs, int splits, int layout, int want, int pitch) {
+  ACG_REQUIRE(layout == ACG_SLABS_ROWS || (layout == ACG_SLABS_QUADS && want == ACG_SLABS_QUADS), ACG_ERR_UNSUPPORTED, "%s: slab layout %d for this tensor (acg_bn_slabs_layout)", who, layout);
+  ACG_REQUIRE(layout == ACG_SLABS_ROWS || c.v4, ACG_ERR_INVALID_ARG, "%s: the quad layout needs 16-byte aligned pointers", who);
+  const long long rows = c.R * c.groups;
+  c.sl = Slabs{slabs, splits, rows * pitch, layout == ACG_SLABS_QUADS ? rows : 0ll};
+  return ACG_OK;
+}
+
+// ---- the path rule ----------------------------------------------------------------------------------------------------------
+// kGrid: bn_fwd_fused / bn_bwd_fused in the shape `f`; kResident: bn_resident_fwd / _bwd with `nr` rows per thread; kTwoLaunch:
+// partial sums, then apply; kNoPath: slabs that no one-launch kernel takes (backward only - acg_bn_slabs_layout answers -1).
+// `c.v4` is final here: alignment and one storage type (the typed functions clear it for the mixed pairs).
+enum BnFamily { kNoPath, kResident, kGrid, kTwoLaunch };
+struct BnPath { BnFamily family; int nr; FusedShape f; };
+bool rows_slabs(const BnCall& c) { return c.sl.p != nullptr && c.sl.qrows == 0; }
+
+// One launch, one read of x, statistics included (bn_fwd_fused) where the grid is resident; small tensors keep the
+// one-block-per-four-channels kernels below `fused_min` rows per group (tuning hook).  Slabs in the rows layout: the grid kernel
+// also where the resident ones would apply - its rows are coalesced, theirs cost a cache line per row and slab.
+BnPath fwd_path(const BnCall& c) {
+  static const int fused_on = env_int("ACG_BN_FUSED_FWD", 1), fused_min = env_int("ACG_BN_FUSED_MIN_ROWS", 1 << 30);
+  const bool rs = rows_slabs(c);
+  const int nr = resident_nr(c.R, 32);
+  if (fused_on && c.v4 && (rs || (!c.sl.p && (nr == 0 || c.R >= fused_min)))) {
+    const FusedShape f = fused_shape(c.R, c.C, c.groups, c.no_grid, rs ? c.sl.splits : 0, c.ncu);
+    if (f.nt) return BnPath{kGrid, 0, f};
+  }
+  return BnPath{nr ? kResident : kTwoLaunch, nr, FusedShape{0, 0, dim3(1, 1, 1)}};
+}
+// Small tensors: ONE block per four channels holds every row of every group in turn (bn_resident_bwd) - unless the grid kernel
+// takes them, from `fused_min` rows per group on (2048 x 128 runs 6.1 us fused, 7.7 resident; below, resident wins:
+// profiles/r4/d_bn_fused_ab.txt) and for slabs in the rows layout.  Then the grid kernel where its grid is resident.
+BnPath bwd_path(const BnCall& c) {
+  static const int fused_on = env_int("ACG_BN_FUSED_BWD", 1), fused_min = env_int("ACG_BN_FUSED_MIN_ROWS", 2048);      // tuning hooks
+  const FusedShape none{0, 0, dim3(1, 1, 1)};
+  const bool rs = rows_slabs(c);
+  const bool prefer_grid = c.v4 && (rs || (!c.sl.p && c.R >= fused_min)) && fused_shape(c.R, c.C, c.groups, c.no_grid, 0, c.ncu).nt != 0;
+  if (!prefer_grid && resident_nr(c.R * c.groups, 16)) return BnPath{kResident, resident_nr(c.R, 16), none};
+  if (fused_on && c.v4 && (!c.sl.p || rs)) {
+    const FusedShape f = fused_shape(c.R, c.C, c.groups, c.no_grid, rs ? c.sl.splits : 0, c.ncu);
+    if (f.nt) return BnPath{kGrid, 0, f};
+  }
+  return BnPath{c.sl.p ? kNoPath : kTwoLaunch, 0, none};
+}
+// The path of a tensor whose slabs do not exist yet, for the two entries that tell a producer what to leave.
+BnFamily slabs_family(long long R, int C, int groups, bool v4, bool no_grid, bool quads, bool backward, int ncu) {
+  static const float probe = 0.f;      // a slab pointer that is only compared with nullptr
+  BnCall c{};
+  c.R = R; c.C = C; c.groups = groups; c.v4 = v4; c.no_grid = no_grid; c.ncu = ncu;
+  c.sl = Slabs{&probe, 0, 0, quads ? R * groups : 0};
+  return (backward ? bwd_path(c) : fwd_path(c)).family;
+}
+// acg_bn_slabs_layout for a checked shape (`vec`: C and the pitches % 4 == 0, one storage type).  The one-launch grid kernels sum
+// slabs laid out like the tensor while they load their rows: coalesced, any tensor whose grid is resident.  Else the
+// register-resident kernels with four channels per block, which read [channels / 4][rows][4] slabs as consecutive 16-byte rows.
+int slabs_layout(long long R, int C, int groups, bool vec, bool no_grid, bool backward, int ncu) {
+  static const int fused_slabs = env_int("ACG_BN_SLABS_FUSED", 1);      // tuning hook
+  const BnFamily fam = slabs_family(R, C, groups, vec, no_grid || !fused_slabs, false, backward, ncu);
+  if (fam == kGrid) return ACG_SLABS_ROWS;
+  if (backward && fam != kResident) return -1;
+  return (fam == kResident && vec) ? ACG_SLABS_QUADS : ACG_SLABS_ROWS;
+}
+
+// ---- run-time choices as template arguments ---------------------------------------------------------------------------------
+// Each helper calls a generic lambda with a std::integral_constant (read back as decltype(v)::value), so a kernel family has ONE
+// launch statement, inside such a lambda.  The tuning hooks stay in the non-template functions around them: one static each.
+template <int N> using Int = std::integral_constant<int, N>;
+// f(Int<N>) for the N of the list that equals n; the last N also takes every other n
+template <int N0, int... Ns, typename F>
+int pick(int n, F&& f) {
+  if constexpr (sizeof...(Ns) == 0) return f(Int<N0>{});
+  else return n == N0 ? f(Int<N0>{}) : pick<Ns...>(n, f);
+}
+template <typename F>
+int pick_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// V: 4 exists for one storage type only (the mixed pairs are the loss-facing layers of a bf16 network: scalar kernels)
+template <typename TX, typename TY, typename F>
+int pick_v(bool v4, F&& f) {
+  if constexpr (std::is_same<TX, TY>::value) { if (v4) return f(Int<4>{}); }
+  return f(Int<1>{});
+}
+// NR of the resident kernels: what resident_nr can return (kMaxNrFwd / kMaxNrBwd)
+template <bool FWD, typename F>
+int pick_nr(int nr, F&& f) {
+#ifdef ACG_TUNING
+  return pick<1, 2, 4, 8, 16, FWD ? kMaxNrFwd : kMaxNrBwd>(nr, f);
+#else
+  return pick<1, 2, 4, FWD ? kMaxNrFwd : kMaxNrBwd>(nr, f);
+#endif
+}
+// CL of the apply kernels (apply_shape): 16 channel lanes are a tuning build's experiment, for V = 4
+template <int V, typename F>
+int pick_cl(int cl, F&& f) {
+#ifdef ACG_TUNING
+  if constexpr (V == 4) { if (cl == 16) return f(Int<16>{}); }
+#endif
+  (void)cl;
+  return f(Int<8>{});
+}
+// (U, NT) of a grid kernel: the four shapes fused_shape hands out
+template <typename F>
+int pick_fused(const FusedShape& s, F&& f) {
+  if (s.nt == 256) return f(Int<4>{}, Int<256>{});
+  return pick<1, 4, 8>(s.U, [&](auto u) { return f(u, Int<1024>{}); });
+}
+// Storage types of the entries that also take ACG_DTYPE2(ACG_F32, ACG_BF16) - a head layer of a bf16 network: x and dy float32,
+// dx bf16 (acgan_hip.h): f(Types<TX, TY, TD>)
+template <typename TX, typename TY, typename TD = TX> struct Types {};
+template <typename F>
+int with_bn_types(int dtype, const char* who, F&& f) {
+  if (dtype == ACG_DTYPE2(ACG_F32, ACG_BF16)) return f(Types<float, float, __bf16>{});
+  ACG_WITH_TYPES(dtype, who, return f(Types<TA, TB>{}));
+}
+
+// ---- the launches -----------------------------------------------------------------------------------------------------------
+template <typename TX>
+int launch_stats_partial(const BnCall& c, TX* x, float* part, int nblk) {
+  return pick<4, 1>(c.v4 ? 4 : 1, [&](auto v) { return pick_bool(c.sl.p != nullptr, [&](auto sl) {
+    ACG_LAUNCH((bn_stats_partial<decltype(v)::value, TX, decltype(sl)::value>), dim3(nblk, c.groups), dim3(256), 0, c.st, x, part, c.R, c.C, nblk, c.XP, c.sl);
+    return acg::check_launch("bn_stats_partial");
+  }); });
+}
+// `deep`: a block walks more than one batch of kU passes - eight passes of loads in flight at once instead of two serial batches
+template <typename TX, typename TY>
+int launch_bwd_partial(const BnCall& c, const TX* x, const TY* dy, const float* beta, const float* save_mean, const float* save_rstd, float* part,
+                       int nblk, bool deep) {
+  return pick_v<TX, TY>(c.v4, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    return pick<(V == 4 ? 8 : kU), kU>(deep ? 8 : kU, [&](auto u) {
+      ACG_LAUNCH((bn_bwd_partial<V, TX, TY, decltype(u)::value>), dim3(nblk, c.groups), dim3(256), 0, c.st, x, dy, beta, save_mean, save_rstd, part, c.R, c.C, nblk, c.act, c.leak, c.XP, c.YP);
+      return acg::check_launch("bn_bwd_partial");
+    });
+  });
 }
 
 // Launch shape of the tiled apply kernels (bn_apply_fwd / bn_apply_bwd): NT threads = CL channel lanes x NT / CL row lanes, a
@@ -1224,195 +1349,140 @@ ApplyShape apply_shape(long long R, int C, int V, int groups, int elem_bytes) {
 }
 
 template <typename TX, typename TY>
-int launch_apply_fwd(bool v4, const TX* x, const float* beta, const float* part, TY* y, float* save_mean, float* save_rstd, long long R,
-                     int C, int groups, int nblk, float eps, int act, float leak, int XP, int YP, int mode, const TileGeom tg, hipStream_t st) {
+int launch_apply_fwd(const BnCall& c, const TX* x, const float* beta, const float* part, TY* y, float* save_mean, float* save_rstd, int nblk, int mode,
+                     const TileGeom tg) {
+  return pick_v<TX, TY>(c.v4, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    const ApplyShape a = apply_shape(c.R, c.C, V, c.groups, (int)sizeof(TX));
+    return pick_cl<V>(a.cl, [&](auto cl) {
+      ACG_LAUNCH((bn_apply_fwd<V, TX, TY, 256, decltype(cl)::value>), a.grid, dim3(256), 0, c.st, x, beta, part, y, save_mean, save_rstd, c.R, c.C, nblk, c.eps, c.act, c.leak, c.XP, c.YP, mode, tg);
+      return acg::check_launch("bn_apply_fwd");
+    });
+  });
+}
+// `gsums` (synchronised BatchNorm): the sums of the global batch, weighted by inv_total; else from `part`, and dbeta with them
+template <typename TX, typename TY, typename TD>
+int launch_apply_bwd(Types<TX, TY, TD>, const BnCall& c, const void* xv, const void* dyv, const float* beta, const float* save_mean, const float* save_rstd,
+                     const float* part, void* dxv, float* dbeta, float dbeta_acc, int nblk, const float* gsums, float inv_total) {
+  const TX* x = (const TX*)xv;
+  const TY* dy = (const TY*)dyv;
+  TD* dx = (TD*)dxv;
+  return pick_v<TX, TY>(c.v4, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    const ApplyShape a = apply_shape(c.R, c.C, V, c.groups, (int)sizeof(TX));
+    return pick_cl<V>(a.cl, [&](auto cl) {
+      ACG_LAUNCH((bn_apply_bwd<V, TX, TY, TD, 256, decltype(cl)::value>), a.grid, dim3(256), 0, c.st, x, dy, beta, save_mean, save_rstd, part, dx, dbeta, dbeta_acc, c.R, c.C, c.groups, nblk, c.act, c.leak, c.XP, c.YP, gsums, inv_total);
+      return acg::check_launch("bn_apply_bwd");
+    });
+  });
+}
+
+int partial_blocks_of(const BnCall& c, bool backward) {
+  static const int fwd_iters = env_int("ACG_BN_STATS_ITERS", 8), bwd_iters = env_int("ACG_BN_BWD_ITERS", 4);        // tuning hooks
+  return vpartial_blocks(c.R, c.C, c.v4 ? 4 : 1, backward ? bwd_iters : fwd_iters);
+}
+
+// One BatchNorm direction for one pair of storage types.  The mixed pair (bf16 x, float32 y: the loss-facing last layer of a
+// bf16 network) exists for the scalar (V = 1) variants only.  The two-launch path keeps its partial sums behind the 16 state
+// bytes the one-launch grid kernels own.
+template <typename TX, typename TY>
+int bn_fwd_typed(BnCall c, const void* xv, const float* beta, void* yv, float* save_mean, float* save_rstd) {
   constexpr bool same = std::is_same<TX, TY>::value;
-  if (!same) v4 = false;
-  const ApplyShape a = apply_shape(R, C, v4 ? 4 : 1, groups, (int)sizeof(TX));
-#define ACG_BN_AF(VV, NN, LL) ACG_LAUNCH((bn_apply_fwd<VV, TX, TY, NN, LL>), a.grid, dim3(NN), 0, st, x, beta, part, y, save_mean, save_rstd, R, C, nblk, eps, act, leak, XP, YP, mode, tg)
+  TX* x = (TX*)const_cast<void*>(xv);
+  TY* y = (TY*)yv;
+  if (!same) c.v4 = false;
+  const BnPath p = fwd_path(c);
+  const bool slabs = c.sl.p != nullptr;
   if constexpr (same) {
-    if (v4) {
-      if (a.cl == 16) ACG_BN_AF(4, 256, 16); else ACG_BN_AF(4, 256, 8);
-    } else {
-      ACG_BN_AF(1, 256, 8);
-    }
-  } else {
-    ACG_BN_AF(1, 256, 8);
+    if (p.family == kGrid) return pick_fused(p.f, [&](auto u, auto nt) { return pick_bool(slabs, [&](auto sl) {
+      constexpr int NT = decltype(nt)::value;
+      ACG_LAUNCH((bn_fwd_fused<4, TX, TY, decltype(u)::value, NT, decltype(sl)::value>), p.f.grid, dim3(NT), 0, c.st, x, beta, y, save_mean, save_rstd, c.R, c.C, c.eps, c.act, c.leak, c.XP, c.YP, (unsigned*)c.ws, c.sl);
+      return acg::check_launch("bn_fwd_fused");
+    }); });
   }
-#undef ACG_BN_AF
-  return acg::check_launch("bn_apply_fwd");
+  if (p.family == kResident) return pick_v<TX, TY>(c.v4, [&](auto v) { return pick_nr<true>(p.nr, [&](auto nr) { return pick_bool(slabs, [&](auto sl) {
+    constexpr int V = decltype(v)::value;
+    ACG_LAUNCH((bn_resident_fwd<V, decltype(nr)::value, TX, TY, decltype(sl)::value>), dim3(c.C / V, c.groups), dim3(256), 0, c.st, x, beta, y, save_mean, save_rstd, (int)c.R, c.C, c.eps, c.act, c.leak, c.XP, c.YP, c.sl);
+    return acg::check_launch("bn_resident_fwd");
+  }); }); });
+  float* const scratch = c.ws + 4;
+  const int nblk = partial_blocks_of(c, false);
+  if (int rc = launch_stats_partial<TX>(c, x, scratch, nblk)) return rc;
+  return launch_apply_fwd<TX, TY>(c, x, beta, scratch, y, save_mean, save_rstd, nblk, (int)kPartShifted, TileGeom{0, 0, 1});
 }
 
 template <typename TX, typename TY, typename TD>
-int launch_apply_bwd(bool v4, const TX* x, const TY* dy, const float* beta, const float* save_mean, const float* save_rstd, const float* part,
-                     TD* dx, float* dbeta, float dbeta_acc, long long R, int C, int groups, int nblk, int act, float leak, int XP, int YP,
-                     const float* gsums, float inv_total, hipStream_t st) {
+int bn_bwd_typed(Types<TX, TY, TD>, BnCall c, const void* xv, const void* dyv, const float* beta, const float* save_mean, const float* save_rstd,
+                 void* dxv, float* dbeta, float dbeta_acc) {
   constexpr bool same = std::is_same<TX, TY>::value;
-  if (!same) v4 = false;
-  const ApplyShape a = apply_shape(R, C, v4 ? 4 : 1, groups, (int)sizeof(TX));
-#define ACG_BN_AB(VV, NN, LL) ACG_LAUNCH((bn_apply_bwd<VV, TX, TY, TD, NN, LL>), a.grid, dim3(NN), 0, st, x, dy, beta, save_mean, save_rstd, part, dx, dbeta, dbeta_acc, R, C, groups, nblk, act, leak, XP, YP, gsums, inv_total)
-  if constexpr (same) {
-    if (v4) {
-      if (a.cl == 16) ACG_BN_AB(4, 256, 16); else ACG_BN_AB(4, 256, 8);
-    } else {
-      ACG_BN_AB(1, 256, 8);
-    }
-  } else {
-    ACG_BN_AB(1, 256, 8);
-  }
-#undef ACG_BN_AB
-  return acg::check_launch("bn_apply_bwd");
-}
-
-bool vec4_ok(int C, const void* a, const void* b, const void* c) {
-  return C % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
-}
-
-// One BatchNorm direction for one pair of storage types.  The mixed pair (bf16 x, float32 y: the loss-facing last
-// layer of a bf16 network) exists for the scalar (V = 1) variants only.
-template <typename TX, typename TY>
-int bn_fwd_typed(const void* x, const float* beta, void* y, float* save_mean, float* save_rstd, long long R, int C, int groups,
-                 float eps, int act, float leak, float* part, bool v4, int XP, int YP, hipStream_t st, const Slabs sl = Slabs{nullptr, 0, 0, 0},
-                 bool no_grid = false) {
-  constexpr bool same = std::is_same<TX, TY>::value;
-  TX* xf = (TX*)const_cast<void*>(x);
-  TY* yf = (TY*)y;
-  if (!same) v4 = false;
-  const int V = v4 ? 4 : 1;
-  float* const scratch = part + 4;       // partial sums of the two-launch path: behind the 16 state bytes the one-launch kernels own
-  // One launch, one read of x, statistics included (bn_fwd_fused) where the grid is resident; small tensors keep the
-  // one-block-per-four-channels kernels below `fused_min` rows per group (tuning hook)
-  static const int fused_on_f = env_int("ACG_BN_FUSED_FWD", 1), fused_min_f = env_int("ACG_BN_FUSED_MIN_ROWS", 1 << 30);
-  if constexpr (same) {
-    // (slabs in the rows layout: the fused kernel also where the resident ones would apply - its rows are coalesced, theirs cost a
-    // cache line per row and slab)
-    const bool rows_slabs = sl.p != nullptr && sl.qrows == 0;
-    const FusedShape f = (fused_on_f && v4 && (rows_slabs || (!sl.p && (resident_nr(R, 32) == 0 || R >= fused_min_f)))) ? fused_shape(R, C, groups, no_grid, rows_slabs ? sl.splits : 0) : FusedShape{0, 0, dim3(1, 1, 1)};
-    if (f.nt) {
-#define ACG_BN_FF(UU, NN) do { if (rows_slabs) ACG_LAUNCH((bn_fwd_fused<4, TX, TY, UU, NN, true>), f.grid, dim3(NN), 0, st, xf, beta, yf, save_mean, save_rstd, R, C, eps, act, leak, XP, YP, (unsigned*)part, sl); \
-      else ACG_LAUNCH((bn_fwd_fused<4, TX, TY, UU, NN, false>), f.grid, dim3(NN), 0, st, xf, beta, yf, save_mean, save_rstd, R, C, eps, act, leak, XP, YP, (unsigned*)part, sl); } while (0)
-      if (f.nt == 256) ACG_BN_FF(4, 256); else if (f.U == 1) ACG_BN_FF(1, 1024); else if (f.U == 4) ACG_BN_FF(4, 1024); else ACG_BN_FF(8, 1024);
-#undef ACG_BN_FF
-      return acg::check_launch("bn_fwd_fused");
-    }
-  }
-  if (const int nr = resident_nr(R, 32)) {
-    const dim3 rg(C / V, groups);
-#define ACG_BN_RES_FWD(VV, NN) do { if (sl.p) ACG_LAUNCH((bn_resident_fwd<VV, NN, TX, TY, true>), rg, dim3(256), 0, st, xf, beta, yf, save_mean, save_rstd, (int)R, C, eps, act, leak, XP, YP, sl); \
-    else ACG_LAUNCH((bn_resident_fwd<VV, NN, TX, TY, false>), rg, dim3(256), 0, st, xf, beta, yf, save_mean, save_rstd, (int)R, C, eps, act, leak, XP, YP, sl); } while (0)
-#define ACG_BN_RES_FWD_V(NN) do { if constexpr (same) { if (v4) ACG_BN_RES_FWD(4, NN); else ACG_BN_RES_FWD(1, NN); } else ACG_BN_RES_FWD(1, NN); } while (0)
-    switch (nr) {
-      case 1: ACG_BN_RES_FWD_V(1); break;
-      case 2: ACG_BN_RES_FWD_V(2); break;
-      case 4: ACG_BN_RES_FWD_V(4); break;
-      case 8: ACG_BN_RES_FWD_V(8); break;
-      case 16: ACG_BN_RES_FWD_V(16); break;
-      default: ACG_BN_RES_FWD_V(32); break;
-    }
-#undef ACG_BN_RES_FWD_V
-#undef ACG_BN_RES_FWD
-    return acg::check_launch("bn_resident_fwd");
-  }
-  static const int stats_iters = env_int("ACG_BN_STATS_ITERS", 8);  // tuning hook
-  const int nblk = vpartial_blocks(R, C, V, stats_iters);
-  if (sl.p) {
-    if (same && v4) ACG_LAUNCH((bn_stats_partial<4, TX, true>), dim3(nblk, groups), dim3(256), 0, st, xf, scratch, R, C, nblk, XP, sl);
-    else ACG_LAUNCH((bn_stats_partial<1, TX, true>), dim3(nblk, groups), dim3(256), 0, st, xf, scratch, R, C, nblk, XP, sl);
-  } else {
-    if (same && v4) ACG_LAUNCH((bn_stats_partial<4, TX, false>), dim3(nblk, groups), dim3(256), 0, st, xf, scratch, R, C, nblk, XP, sl);
-    else ACG_LAUNCH((bn_stats_partial<1, TX, false>), dim3(nblk, groups), dim3(256), 0, st, xf, scratch, R, C, nblk, XP, sl);
-  }
-  if (int rc = acg::check_launch("bn_stats_partial")) return rc;
-  return launch_apply_fwd<TX, TY>(v4, xf, beta, (const float*)scratch, yf, save_mean, save_rstd, R, C, groups, nblk, eps, act, leak, XP, YP, (int)kPartShifted, TileGeom{0, 0, 1}, st);
-}
-
-template <typename TX, typename TY, typename TD = TX>
-int bn_bwd_typed(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd, void* dx,
-                 float* dbeta, float dbeta_acc, long long R, int C, int groups, int act, float leak, float* part, bool v4, int XP, int YP,
-                 hipStream_t st, const Slabs sl = Slabs{nullptr, 0, 0, 0}, bool no_grid = false) {
-  constexpr bool same = std::is_same<TX, TY>::value;
-  const TX* xf = (const TX*)x;
-  const TY* dyf = (const TY*)dy;
-  TD* dxf = (TD*)dx;
-  if (!same) v4 = false;
-  const int V = v4 ? 4 : 1;
-  float* const scratch = part + 4;       // as in bn_fwd_typed
-  // small tensors: ONE block per four channels holds every row (bn_resident_bwd) - unless the fused grid kernel is asked to take
-  // them from `fused_min` rows per group on (tuning hook; measured in profiles/r4/d_bn_fused_ab.txt)
-  static const int fused_min_b = env_int("ACG_BN_FUSED_MIN_ROWS", 2048);      // backward: 2048 x 128 runs 6.1 us fused, 7.7 resident; below, resident wins
-  const bool rows_slabs_b = sl.p != nullptr && sl.qrows == 0;
-  const bool prefer_fused_b = same && v4 && (rows_slabs_b || (!sl.p && R >= fused_min_b)) && fused_shape(R, C, groups, no_grid).nt != 0;
-  if (const int nr = prefer_fused_b ? 0 : (resident_nr(R * groups, 16) ? resident_nr(R, 16) : 0)) {
-    const dim3 rg(C / V);
-#define ACG_BN_RES_BWD(VV, NN) do { if (sl.p) ACG_LAUNCH((bn_resident_bwd<VV, NN, TX, TY, true, TD>), rg, dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, dxf, dbeta, dbeta_acc, (int)R, C, groups, act, leak, XP, YP, sl); \
-    else ACG_LAUNCH((bn_resident_bwd<VV, NN, TX, TY, false, TD>), rg, dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, dxf, dbeta, dbeta_acc, (int)R, C, groups, act, leak, XP, YP, sl); } while (0)
-#define ACG_BN_RES_BWD_V(NN) do { if constexpr (same) { if (v4) ACG_BN_RES_BWD(4, NN); else ACG_BN_RES_BWD(1, NN); } else ACG_BN_RES_BWD(1, NN); } while (0)
-    switch (nr) {
-      case 1: ACG_BN_RES_BWD_V(1); break;
-      case 2: ACG_BN_RES_BWD_V(2); break;
-      case 4: ACG_BN_RES_BWD_V(4); break;
-      case 8: ACG_BN_RES_BWD_V(8); break;
-      default: ACG_BN_RES_BWD_V(16); break;
-    }
-#undef ACG_BN_RES_BWD_V
-#undef ACG_BN_RES_BWD
+  const TX* x = (const TX*)xv;
+  const TY* dy = (const TY*)dyv;
+  TD* dx = (TD*)dxv;
+  if (!same) c.v4 = false;
+  const BnPath p = bwd_path(c);
+  const bool slabs = c.sl.p != nullptr;
+  if (p.family == kResident) return pick_v<TX, TY>(c.v4, [&](auto v) { return pick_nr<false>(p.nr, [&](auto nr) { return pick_bool(slabs, [&](auto sl) {
+    constexpr int V = decltype(v)::value;
+    ACG_LAUNCH((bn_resident_bwd<V, decltype(nr)::value, TX, TY, decltype(sl)::value, TD>), dim3(c.C / V), dim3(256), 0, c.st, x, dy, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc, (int)c.R, c.C, c.groups, c.act, c.leak, c.XP, c.YP, c.sl);
     return acg::check_launch("bn_resident_bwd");
-  }
-  // One launch with the tensor held in registers between the sums and the apply phase (bn_bwd_fused) where the whole grid is
-  // resident at one block of 1024 threads per CU
+  }); }); });
   if constexpr (same) {
-    static const int fused_on = env_int("ACG_BN_FUSED_BWD", 1);     // tuning hook
-    const FusedShape f = (fused_on && v4 && (!sl.p || rows_slabs_b)) ? fused_shape(R, C, groups, no_grid, rows_slabs_b ? sl.splits : 0) : FusedShape{0, 0, dim3(1, 1, 1)};
-    if (f.nt) {
-#define ACG_BN_FB(UU, NN) do { if (rows_slabs_b) ACG_LAUNCH((bn_bwd_fused<4, TX, TY, TD, UU, NN, true>), f.grid, dim3(NN), 0, st, xf, dyf, beta, save_mean, save_rstd, dxf, dbeta, dbeta_acc, R, C, groups, act, leak, XP, YP, (unsigned*)part, sl); \
-      else ACG_LAUNCH((bn_bwd_fused<4, TX, TY, TD, UU, NN, false>), f.grid, dim3(NN), 0, st, xf, dyf, beta, save_mean, save_rstd, dxf, dbeta, dbeta_acc, R, C, groups, act, leak, XP, YP, (unsigned*)part, sl); } while (0)
-      if (f.nt == 256) ACG_BN_FB(4, 256); else if (f.U == 1) ACG_BN_FB(1, 1024); else if (f.U == 4) ACG_BN_FB(4, 1024); else ACG_BN_FB(8, 1024);
-#undef ACG_BN_FB
+    if (p.family == kGrid) return pick_fused(p.f, [&](auto u, auto nt) { return pick_bool(slabs, [&](auto sl) {
+      constexpr int NT = decltype(nt)::value;
+      ACG_LAUNCH((bn_bwd_fused<4, TX, TY, TD, decltype(u)::value, NT, decltype(sl)::value>), p.f.grid, dim3(NT), 0, c.st, x, dy, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc, c.R, c.C, c.groups, c.act, c.leak, c.XP, c.YP, (unsigned*)c.ws, c.sl);
       return acg::check_launch("bn_bwd_fused");
-    }
+    }); });
   }
-  if (sl.p) return acg::fail(ACG_ERR_UNSUPPORTED, "bn_act_bwd_slabs: %lld rows per group fit neither the one-launch grid kernel nor the register-resident kernels (acg_bn_slabs_layout)", R);
-  static const int bwd_iters = env_int("ACG_BN_BWD_ITERS", 4);      // tuning hook
-  const int nblk = vpartial_blocks(R, C, V, bwd_iters);
-  {
-    // passes a block walks: more than one batch of kU -> eight passes of loads in flight at once instead of two serial batches
-    const int Cv = C / V, Cb = Cv < 256 ? Cv : 256, RPP = 256 / Cb;
-    const bool deep = acg::ceil_div(acg::ceil_div(R, nblk), RPP) > kU;
-    if constexpr (same) {
-      if (v4 && deep) ACG_LAUNCH((bn_bwd_partial<4, TX, TY, 8>), dim3(nblk, groups), dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, scratch, R, C, nblk, act, leak, XP, YP);
-      else if (v4) ACG_LAUNCH((bn_bwd_partial<4, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, scratch, R, C, nblk, act, leak, XP, YP);
-      else ACG_LAUNCH((bn_bwd_partial<1, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, scratch, R, C, nblk, act, leak, XP, YP);
-    } else {
-      ACG_LAUNCH((bn_bwd_partial<1, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, xf, dyf, beta, save_mean, save_rstd, scratch, R, C, nblk, act, leak, XP, YP);
-    }
-  }
-  if (int rc = acg::check_launch("bn_bwd_partial")) return rc;
-  return launch_apply_bwd<TX, TY, TD>(v4, xf, dyf, beta, save_mean, save_rstd, (const float*)scratch, dxf, dbeta, dbeta_acc, R, C, groups, nblk, act, leak, XP, YP,
-                                      (const float*)nullptr, 0.f, st);
+  if (p.family == kNoPath)
+    return acg::fail(ACG_ERR_UNSUPPORTED, "bn_act_bwd_slabs: %lld rows per group fit neither the one-launch grid kernel nor the register-resident kernels (acg_bn_slabs_layout)", c.R);
+  float* const scratch = c.ws + 4;
+  const int nblk = partial_blocks_of(c, true), V = c.v4 ? 4 : 1;
+  const int Cv = c.C / V, Cb = Cv < 256 ? Cv : 256, RPP = 256 / Cb;
+  const bool deep = acg::ceil_div(acg::ceil_div(c.R, nblk), RPP) > kU;
+  if (int rc = launch_bwd_partial<TX, TY>(c, x, dy, beta, save_mean, save_rstd, scratch, nblk, deep)) return rc;
+  return launch_apply_bwd(Types<TX, TY, TD>{}, c, x, dy, beta, save_mean, save_rstd, scratch, dx, dbeta, dbeta_acc, nblk, nullptr, 0.f);
 }
 
 // BatchNorm + activation whose statistics arrive as per-tile (sum, M2) partials out of the producing convolution's epilogue
 // (acg_conv2d_fwd_stats / acg_deconv2d_fwd_stats): the apply pass alone - ONE launch, x is read once; above kFinalizeBlocks
-// partial blocks per group a small launch merges them first.
+// partial blocks per group a small launch merges them first (mode kPartDone).  The partials / statistics side is float32
+// whatever the tensors are: V follows the alignment alone there.
 constexpr int kFinalizeBlocks = 512;
-template <typename TX, typename TY>
-int bn_fwd_partials_typed(const void* x, const float* beta, const float* part, int nblk, const TileGeom tg, void* y, float* save_mean,
-                          float* save_rstd, long long R, int C, int groups, float eps, int act, float leak, bool v4, int XP, int YP,
-                          hipStream_t st) {
-  const TX* xf = (const TX*)x;
-  TY* yf = (TY*)y;
-  const bool v4p = v4;                     // the partials / statistics side is float32 whatever the tensors are
-  int mode = kPartTiles;
+int finalize_limit() {
   static const int fin = env_int("ACG_BN_FINALIZE_BLOCKS", kFinalizeBlocks);   // tuning hook
-  if (nblk > fin) {
-    if (v4p) ACG_LAUNCH((bn_partials_finalize<4, 2>), dim3(1, (C + 7) / 8, groups), dim3(1024), 0, st, part, save_mean, save_rstd, R, C, nblk, eps, tg);
-    else ACG_LAUNCH((bn_partials_finalize<1, 8>), dim3(1, (C + 7) / 8, groups), dim3(1024), 0, st, part, save_mean, save_rstd, R, C, nblk, eps, tg);
-    if (int rc = acg::check_launch("bn_partials_finalize")) return rc;
-    mode = kPartDone;
-  }
-  return launch_apply_fwd<TX, TY>(v4, xf, beta, part, yf, save_mean, save_rstd, R, C, groups, nblk, eps, act, leak, XP, YP, mode, tg, st);
+  return fin;
+}
+template <typename TX, typename TY>
+int bn_fwd_partials_typed(const BnCall& c, const void* x, const float* beta, const float* part, int nblk, const TileGeom tg, void* y, float* save_mean,
+                          float* save_rstd) {
+  const bool merged = nblk > finalize_limit();
+  if (merged)
+    if (int rc = pick<4, 1>(c.v4 ? 4 : 1, [&](auto v) {
+          constexpr int V = decltype(v)::value;
+          ACG_LAUNCH((bn_partials_finalize<V, V == 4 ? 2 : 8>), dim3(1, (c.C + 7) / 8, c.groups), dim3(1024), 0, c.st, part, save_mean, save_rstd, c.R, c.C, nblk, c.eps, tg);
+          return acg::check_launch("bn_partials_finalize");
+        })) return rc;
+  return launch_apply_fwd<TX, TY>(c, (const TX*)x, beta, part, (TY*)y, save_mean, save_rstd, nblk, merged ? (int)kPartDone : (int)kPartTiles, tg);
 }
 
+// ---- synchronised BatchNorm (statistics of the global batch supplied by the caller): the partial sums fill the workspace from
+// its first byte
+template <typename TX>
+int bn_moments_typed(const BnCall& c, const void* x, float* moments) {
+  const int nblk = vpartial_blocks(c.R, c.C, c.v4 ? 4 : 1, 8);
+  if (int rc = launch_stats_partial<TX>(c, (TX*)const_cast<void*>(x), c.ws, nblk)) return rc;
+  ACG_LAUNCH((bn_moments_finalize<TX>), dim3((c.groups * c.C + 255) / 256), dim3(256), 0, c.st, (const float*)c.ws, (const TX*)x, moments, c.R, c.C, c.XP, c.groups, nblk);
+  return acg::check_launch("bn_moments_finalize");
+}
+template <typename TX, typename TY, typename TD>
+int bn_bwd_sums_typed(Types<TX, TY, TD>, BnCall c, const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd,
+                      float* sums) {
+  if (!std::is_same<TX, TY>::value) c.v4 = false;
+  const int nblk = vpartial_blocks(c.R, c.C, c.v4 ? 4 : 1, 4);
+  if (int rc = launch_bwd_partial<TX, TY>(c, (const TX*)x, (const TY*)dy, beta, save_mean, save_rstd, c.ws, nblk, false)) return rc;
+  ACG_LAUNCH(bn_sums_finalize, dim3((c.C + 31) / 32, c.groups), dim3(256), 0, c.st, (const float*)c.ws, sums, c.C, c.groups, nblk);
+  return acg::check_launch("bn_sums_finalize");
+}
 }  // namespace
 
 extern "C" {
@@ -1428,80 +1498,57 @@ size_t acg_bn_workspace_bytes(int64_t rows, int32_t channels, int32_t groups) {
 int32_t acg_bn_act_fwd(const void* x, const float* beta, void* y, float* save_mean, float* save_rstd, int64_t rows,
                        int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, float eps, int32_t act, float leak, int32_t dtype,
                        int32_t flags, void* ws, size_t wsb, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_fwd: pitch smaller than the row");
-  if (int rc = check_bn("bn_act_fwd", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && beta && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "bn_act_fwd: null pointer");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_fwd: activation %d", act);
-  ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "bn_act_fwd: workspace too small");
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, y, beta) && vec4_ok(C, save_mean, save_rstd, ws) && XP % 4 == 0 && YP % 4 == 0;
-  ACG_REQUIRE((flags & ~ACG_BN_NO_GRID_EXCHANGE) == 0, ACG_ERR_INVALID_ARG, "bn_act_fwd: unknown flags 0x%x", flags);
-  const bool no_grid = (flags & ACG_BN_NO_GRID_EXCHANGE) != 0;
-  ACG_WITH_TYPES(dtype, "bn_act_fwd", return (bn_fwd_typed<TA, TB>(x, beta, y, save_mean, save_rstd, R, C, groups, eps, act, leak, (float*)ws, v4, XP, YP, acg::to_stream(stream), Slabs{nullptr, 0, 0, 0}, no_grid)));
+  const char* who = "bn_act_fwd";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct | kCheckFlags | kCheckWs, c, rows, C, x_pitch, y_pitch, groups, eps, act, leak, flags, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(x && beta && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  c.v4 = c.v4 && aligned16(x, y, beta, save_mean, save_rstd, ws);
+  ACG_WITH_TYPES(dtype, who, return (bn_fwd_typed<TA, TB>(c, x, beta, y, save_mean, save_rstd)));
 }
 
 int32_t acg_bn_act_fwd_partials(const void* x, const float* beta, const float* partials, int32_t nblk, int32_t block_rows, int32_t run_rows,
                                 void* y, float* save_mean, float* save_rstd, int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch,
                                 int32_t groups, float eps, int32_t act, float leak, int32_t dtype, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_fwd_partials: pitch smaller than the row");
-  if (int rc = check_bn("bn_act_fwd_partials", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && beta && partials && nblk >= 1 && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "bn_act_fwd_partials: null pointer / nblk < 1");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_fwd_partials: activation %d", act);
-  const long long R = rows / groups;
+  const char* who = "bn_act_fwd_partials";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct, c, rows, C, x_pitch, y_pitch, groups, eps, act, leak, 0, nullptr, 0, stream)) return rc;
+  ACG_REQUIRE(x && beta && partials && nblk >= 1 && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "%s: null pointer / nblk < 1", who);
   // the blocks of a group tile `runs` runs of run_rows rows each, block_rows at a time (acg_conv2d_stats_layout)
-  ACG_REQUIRE(block_rows >= 1 && run_rows >= 1, ACG_ERR_INVALID_ARG, "bn_act_fwd_partials: block_rows / run_rows < 1");
+  ACG_REQUIRE(block_rows >= 1 && run_rows >= 1, ACG_ERR_INVALID_ARG, "%s: block_rows / run_rows < 1", who);
   const int bpr = (int)acg::ceil_div(run_rows, block_rows);
-  ACG_REQUIRE(nblk % bpr == 0 && (long long)(nblk / bpr) * run_rows == R, ACG_ERR_INVALID_ARG,
-              "bn_act_fwd_partials: %d blocks of %d rows in runs of %d do not cover %lld rows per group", nblk, block_rows, run_rows, R);
+  ACG_REQUIRE(nblk % bpr == 0 && (long long)(nblk / bpr) * run_rows == c.R, ACG_ERR_INVALID_ARG,
+              "%s: %d blocks of %d rows in runs of %d do not cover %lld rows per group", who, nblk, block_rows, run_rows, c.R);
   const TileGeom tg{block_rows, run_rows, bpr};
-  const bool v4 = vec4_ok(C, x, y, beta) && vec4_ok(C, save_mean, save_rstd, partials) && XP % 4 == 0 && YP % 4 == 0;
-  ACG_WITH_TYPES(dtype, "bn_act_fwd_partials", return (bn_fwd_partials_typed<TA, TB>(x, beta, partials, nblk, tg, y, save_mean, save_rstd, R, C, groups, eps, act, leak, v4, XP, YP, acg::to_stream(stream))));
+  c.v4 = c.v4 && aligned16(x, y, beta, save_mean, save_rstd, partials);
+  ACG_WITH_TYPES(dtype, who, return (bn_fwd_partials_typed<TA, TB>(c, x, beta, partials, nblk, tg, y, save_mean, save_rstd)));
 }
 
 int32_t acg_bn_act_bwd(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd,
                        void* dx, float* dbeta, float dbeta_acc, int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch,
                        int32_t groups, int32_t act, float leak, int32_t dtype, int32_t flags, void* ws, size_t wsb, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_bwd: pitch smaller than the row");
-  ACG_REQUIRE((flags & ~ACG_BN_NO_GRID_EXCHANGE) == 0, ACG_ERR_INVALID_ARG, "bn_act_bwd: unknown flags 0x%x", flags);
-  const bool no_grid = (flags & ACG_BN_NO_GRID_EXCHANGE) != 0;
-  const Slabs none{nullptr, 0, 0, 0};
-  if (int rc = check_bn("bn_act_bwd", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && dx && dbeta, ACG_ERR_INVALID_ARG, "bn_act_bwd: null pointer");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_bwd: activation %d", act);
-  ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "bn_act_bwd: workspace too small");
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, dy, dx) && vec4_ok(C, save_mean, save_rstd, ws) && vec4_ok(C, beta, dbeta, ws) && XP % 4 == 0 && YP % 4 == 0;
-  // ACG_DTYPE2(ACG_F32, ACG_BF16): a head layer of a bf16 network - x and dy float32, dx bf16 (acgan_hip.h)
-  if (dtype == ACG_DTYPE2(ACG_F32, ACG_BF16))
-    return bn_bwd_typed<float, float, __bf16>(x, dy, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc, R, C, groups, act, leak, (float*)ws, v4, XP, YP, acg::to_stream(stream), none, no_grid);
-  ACG_WITH_TYPES(dtype, "bn_act_bwd", return (bn_bwd_typed<TA, TB>(x, dy, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc, R, C, groups, act, leak, (float*)ws, v4, XP, YP, acg::to_stream(stream), none, no_grid)));
+  const char* who = "bn_act_bwd";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct | kCheckFlags | kCheckWs, c, rows, C, x_pitch, y_pitch, groups, 0.f, act, leak, flags, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && dx && dbeta, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  c.v4 = c.v4 && aligned16(x, dy, dx, save_mean, save_rstd, ws, beta, dbeta);
+  return with_bn_types(dtype, who, [&](auto t) { return bn_bwd_typed(t, c, x, dy, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc); });
 }
 
 int32_t acg_bn_act_fwd_slabs(const float* slabs, int32_t splits, void* x, const float* beta, void* y, float* save_mean, float* save_rstd,
                              int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, float eps, int32_t act, float leak,
                              int32_t dtype, int32_t layout, int32_t flags, void* ws, size_t wsb, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_fwd_slabs: pitch smaller than the row");
-  ACG_REQUIRE((flags & ~ACG_BN_NO_GRID_EXCHANGE) == 0, ACG_ERR_INVALID_ARG, "bn_act_fwd_slabs: unknown flags 0x%x", flags);
-  ACG_REQUIRE(layout == ACG_SLABS_ROWS || (layout == ACG_SLABS_QUADS && acg_bn_slabs_layout(rows, C, x_pitch, y_pitch, groups, dtype, 0, flags) == ACG_SLABS_QUADS),
-              ACG_ERR_UNSUPPORTED, "bn_act_fwd_slabs: slab layout %d for this tensor (acg_bn_slabs_layout)", layout);
-  if (int rc = check_bn("bn_act_fwd_slabs", rows, C, groups)) return rc;
-  ACG_REQUIRE(slabs && splits >= 1 && x && beta && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "bn_act_fwd_slabs: null pointer / splits < 1");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_fwd_slabs: activation %d", act);
-  ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "bn_act_fwd_slabs: workspace too small");
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, y, beta) && vec4_ok(C, save_mean, save_rstd, ws) && vec4_ok(C, slabs, slabs, slabs) && XP % 4 == 0 && YP % 4 == 0;
-  ACG_REQUIRE(layout == ACG_SLABS_ROWS || v4, ACG_ERR_INVALID_ARG, "bn_act_fwd_slabs: the quad layout needs 16-byte aligned pointers");
-  const Slabs sl{slabs, splits, (long long)rows * XP, layout == ACG_SLABS_QUADS ? (long long)rows : 0ll};
-  ACG_WITH_TYPES(dtype, "bn_act_fwd_slabs", return (bn_fwd_typed<TA, TB>(x, beta, y, save_mean, save_rstd, R, C, groups, eps, act, leak, (float*)ws, v4, XP, YP, acg::to_stream(stream), sl, (flags & ACG_BN_NO_GRID_EXCHANGE) != 0)));
+  const char* who = "bn_act_fwd_slabs";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct | kCheckFlags | kCheckWs, c, rows, C, x_pitch, y_pitch, groups, eps, act, leak, flags, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(slabs && splits >= 1 && x && beta && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "%s: null pointer / splits < 1", who);
+  c.v4 = c.v4 && aligned16(x, y, beta, save_mean, save_rstd, ws, slabs);
+  if (int rc = take_slabs(who, c, slabs, splits, layout, acg_bn_slabs_layout(rows, C, x_pitch, y_pitch, groups, dtype, 0, flags), c.XP)) return rc;
+  ACG_WITH_TYPES(dtype, who, return (bn_fwd_typed<TA, TB>(c, x, beta, y, save_mean, save_rstd)));
 }
 
 int32_t acg_bn_bwd_slabs_ok(int64_t rows, int32_t groups) {
   if (rows <= 0 || groups <= 0 || rows % groups) return 0;
-  return (resident_nr(rows, 16) && resident_nr(rows / groups, 16)) ? 1 : 0;
+  return slabs_family(rows / groups, 4, groups, false, true, true, true, device_cus()) == kResident ? 1 : 0;
 }
 
 int32_t acg_bn_slabs_layout(int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, int32_t dtype, int32_t backward,
@@ -1509,34 +1556,22 @@ int32_t acg_bn_slabs_layout(int64_t rows, int32_t C, int32_t x_pitch, int32_t y_
   if (rows <= 0 || C <= 0 || groups <= 0 || rows % groups || (flags & ~ACG_BN_NO_GRID_EXCHANGE)) return -1;
   const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
   const bool vec = C % 4 == 0 && XP % 4 == 0 && YP % 4 == 0 && acg::dt_valid(dtype) && acg::dt_first(dtype) == acg::dt_second(dtype);
-  // the one-launch grid kernels (bn_fwd_fused / bn_bwd_fused) sum slabs laid out like the tensor while they load their rows:
-  // coalesced, any tensor whose grid is resident
-  static const int fused_slabs = env_int("ACG_BN_SLABS_FUSED", 1);      // tuning hook
-  if (fused_slabs && vec && fused_shape(rows / groups, C, groups, (flags & ACG_BN_NO_GRID_EXCHANGE) != 0).nt != 0) return ACG_SLABS_ROWS;
-  const bool resident = backward ? acg_bn_bwd_slabs_ok(rows, groups) != 0 : resident_nr(rows / groups, 32) != 0;
-  if (backward && !resident) return -1;
-  // the register-resident kernels with four channels per block read [channels / 4][rows][4] slabs as consecutive 16-byte rows
-  return (resident && vec) ? ACG_SLABS_QUADS : ACG_SLABS_ROWS;
+  return slabs_layout(rows / groups, C, groups, vec, (flags & ACG_BN_NO_GRID_EXCHANGE) != 0, backward != 0, device_cus());
 }
 
 int32_t acg_bn_act_bwd_slabs(const void* x, const float* dy_slabs, int32_t splits, const float* beta, const float* save_mean,
                              const float* save_rstd, void* dx, float* dbeta, float dbeta_acc, int64_t rows, int32_t C, int32_t x_pitch,
                              int32_t y_pitch, int32_t groups, int32_t act, float leak, int32_t dtype, int32_t layout, int32_t flags, void* ws, size_t wsb,
                              acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_bwd_slabs: pitch smaller than the row");
-  ACG_REQUIRE((flags & ~ACG_BN_NO_GRID_EXCHANGE) == 0, ACG_ERR_INVALID_ARG, "bn_act_bwd_slabs: unknown flags 0x%x", flags);
-  ACG_REQUIRE(layout == ACG_SLABS_ROWS || (layout == ACG_SLABS_QUADS && acg_bn_slabs_layout(rows, C, x_pitch, y_pitch, groups, dtype, 1, flags) == ACG_SLABS_QUADS),
-              ACG_ERR_UNSUPPORTED, "bn_act_bwd_slabs: slab layout %d for this tensor (acg_bn_slabs_layout)", layout);
-  if (int rc = check_bn("bn_act_bwd_slabs", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && dy_slabs && splits >= 1 && beta && save_mean && save_rstd && dx && dbeta, ACG_ERR_INVALID_ARG, "bn_act_bwd_slabs: null pointer / splits < 1");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_bwd_slabs: activation %d", act);
-  ACG_REQUIRE(acg_bn_slabs_layout(rows, C, x_pitch, y_pitch, groups, dtype, 1, flags) >= 0, ACG_ERR_UNSUPPORTED, "bn_act_bwd_slabs: tensor too large for the one-launch kernels (acg_bn_slabs_layout)");
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, dy_slabs, dx) && vec4_ok(C, save_mean, save_rstd, beta) && vec4_ok(C, beta, dbeta, dbeta) && XP % 4 == 0 && YP % 4 == 0;
-  ACG_REQUIRE(layout == ACG_SLABS_ROWS || v4, ACG_ERR_INVALID_ARG, "bn_act_bwd_slabs: the quad layout needs 16-byte aligned pointers");
-  const Slabs sl{dy_slabs, splits, (long long)rows * YP, layout == ACG_SLABS_QUADS ? (long long)rows : 0ll};
-  ACG_WITH_TYPES(dtype, "bn_act_bwd_slabs", return (bn_bwd_typed<TA, TB>(x, nullptr, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc, R, C, groups, act, leak, (float*)ws, v4, XP, YP, acg::to_stream(stream), sl, (flags & ACG_BN_NO_GRID_EXCHANGE) != 0)));
+  const char* who = "bn_act_bwd_slabs";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct | kCheckFlags, c, rows, C, x_pitch, y_pitch, groups, 0.f, act, leak, flags, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(x && dy_slabs && splits >= 1 && beta && save_mean && save_rstd && dx && dbeta, ACG_ERR_INVALID_ARG, "%s: null pointer / splits < 1", who);
+  const int want = acg_bn_slabs_layout(rows, C, x_pitch, y_pitch, groups, dtype, 1, flags);
+  ACG_REQUIRE(want >= 0, ACG_ERR_UNSUPPORTED, "%s: tensor too large for the one-launch kernels (acg_bn_slabs_layout)", who);
+  c.v4 = c.v4 && aligned16(x, dy_slabs, dx, save_mean, save_rstd, beta, dbeta);
+  if (int rc = take_slabs(who, c, dy_slabs, splits, layout, want, c.YP)) return rc;
+  ACG_WITH_TYPES(dtype, who, return (bn_bwd_typed(Types<TA, TB>{}, c, x, nullptr, beta, save_mean, save_rstd, dx, dbeta, dbeta_acc)));
 }
 
 int32_t acg_bn_exchange_selftest(void* ws, size_t wsb, float* out, int32_t blocks, int32_t threads, int32_t withhold, uint32_t spin_limit,
@@ -1552,121 +1587,57 @@ int32_t acg_bn_exchange_selftest(void* ws, size_t wsb, float* out, int32_t block
   return acg::check_launch("exchange_selftest_k");
 }
 
-}  // extern "C"
-
 // ---- synchronised BatchNorm entries: any storage-type pair the plain entries take, pitched rows ---------------------------
-namespace {
-template <typename TX>
-int bn_moments_typed(const void* x, float* moments, long long R, int C, int XP, int groups, float* part, bool v4, hipStream_t st) {
-  TX* xf = (TX*)const_cast<void*>(x);
-  const int V = v4 ? 4 : 1, nblk = vpartial_blocks(R, C, V, 8);
-  if (v4) ACG_LAUNCH((bn_stats_partial<4, TX>), dim3(nblk, groups), dim3(256), 0, st, xf, part, R, C, nblk, XP, Slabs{nullptr, 0, 0});
-  else ACG_LAUNCH((bn_stats_partial<1, TX>), dim3(nblk, groups), dim3(256), 0, st, xf, part, R, C, nblk, XP, Slabs{nullptr, 0, 0});
-  if (int rc = acg::check_launch("bn_stats_partial")) return rc;
-  ACG_LAUNCH((bn_moments_finalize<TX>), dim3((groups * C + 255) / 256), dim3(256), 0, st, (const float*)part, (const TX*)x, moments, R, C, XP, groups, nblk);
-  return acg::check_launch("bn_moments_finalize");
-}
-template <typename TX, typename TY>
-int bn_fwd_moments_typed(const void* x, const float* beta, void* y, float* save_mean, float* save_rstd, long long R, int C, int groups,
-                         float eps, int act, float leak, bool v4, int XP, int YP, hipStream_t st) {
-  return launch_apply_fwd<TX, TY>(v4, (const TX*)x, beta, (const float*)nullptr, (TY*)y, save_mean, save_rstd, R, C, groups, 0, eps, act, leak, XP, YP,
-                                  (int)kPartDone, TileGeom{0, 0, 1}, st);
-}
-template <typename TX, typename TY>
-int bn_bwd_sums_typed(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd, float* sums,
-                      long long R, int C, int groups, int act, float leak, float* part, bool v4, int XP, int YP, hipStream_t st) {
-  constexpr bool same = std::is_same<TX, TY>::value;
-  if (!same) v4 = false;
-  const int V = v4 ? 4 : 1, nblk = vpartial_blocks(R, C, V, 4);
-  if constexpr (same) {
-    if (v4) ACG_LAUNCH((bn_bwd_partial<4, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, (const TX*)x, (const TY*)dy, beta, save_mean, save_rstd, part, R, C, nblk, act, leak, XP, YP);
-    else ACG_LAUNCH((bn_bwd_partial<1, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, (const TX*)x, (const TY*)dy, beta, save_mean, save_rstd, part, R, C, nblk, act, leak, XP, YP);
-  } else {
-    ACG_LAUNCH((bn_bwd_partial<1, TX, TY>), dim3(nblk, groups), dim3(256), 0, st, (const TX*)x, (const TY*)dy, beta, save_mean, save_rstd, part, R, C, nblk, act, leak, XP, YP);
-  }
-  if (int rc = acg::check_launch("bn_bwd_partial")) return rc;
-  ACG_LAUNCH(bn_sums_finalize, dim3((C + 31) / 32, groups), dim3(256), 0, st, (const float*)part, sums, C, groups, nblk);
-  return acg::check_launch("bn_sums_finalize");
-}
-template <typename TX, typename TY, typename TD = TX>
-int bn_bwd_apply_sums_typed(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd,
-                            const float* gsums, float inv_total, void* dx, long long R, int C, int groups, int act, float leak, bool v4,
-                            int XP, int YP, hipStream_t st) {
-  return launch_apply_bwd<TX, TY, TD>(v4, (const TX*)x, (const TY*)dy, beta, save_mean, save_rstd, (const float*)nullptr, (TD*)dx, (float*)nullptr, 0.f,
-                                      R, C, groups, 0, act, leak, XP, YP, gsums, inv_total, st);
-}
-}  // namespace
-
-extern "C" {
-
 int32_t acg_bn_moments(const void* x, float* moments, int64_t rows, int32_t C, int32_t x_pitch, int32_t groups, int32_t dtype, void* ws,
                        size_t wsb, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C;
-  ACG_REQUIRE(XP >= C, ACG_ERR_INVALID_ARG, "bn_moments: pitch smaller than the row");
-  if (int rc = check_bn("bn_moments", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && moments, ACG_ERR_INVALID_ARG, "bn_moments: null pointer");
-  ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "bn_moments: workspace too small");
-  ACG_REQUIRE(dtype == ACG_F32 || dtype == ACG_BF16, ACG_ERR_UNSUPPORTED, "bn_moments: dtype %d (the storage type of x)", dtype);
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, x, ws) && XP % 4 == 0;
-  if (dtype == ACG_BF16) return bn_moments_typed<__bf16>(x, moments, R, C, XP, groups, (float*)ws, v4, acg::to_stream(stream));
-  return bn_moments_typed<float>(x, moments, R, C, XP, groups, (float*)ws, v4, acg::to_stream(stream));
+  const char* who = "bn_moments";
+  BnCall c;
+  if (int rc = prepare(who, kCheckWs, c, rows, C, x_pitch, x_pitch, groups, 0.f, ACG_ACT_NONE, 0.f, 0, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(x && moments, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  ACG_REQUIRE(dtype == ACG_F32 || dtype == ACG_BF16, ACG_ERR_UNSUPPORTED, "%s: dtype %d (the storage type of x)", who, dtype);
+  c.v4 = c.v4 && aligned16(x, ws);
+  return dtype == ACG_BF16 ? bn_moments_typed<__bf16>(c, x, moments) : bn_moments_typed<float>(c, x, moments);
 }
 
 int32_t acg_bn_act_fwd_moments(const void* x, const float* beta, const float* moments, void* y, float* save_mean,
                                float* save_rstd, int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, float eps,
                                int32_t act, float leak, int32_t dtype, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_fwd_moments: pitch smaller than the row");
-  if (int rc = check_bn("bn_act_fwd_moments", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && beta && moments && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "bn_act_fwd_moments: null pointer");
-  ACG_REQUIRE(act == ACG_ACT_NONE || act == ACG_ACT_RELU || act == ACG_ACT_LRELU, ACG_ERR_UNSUPPORTED, "bn_act_fwd_moments: activation %d", act);
-  hipStream_t st = acg::to_stream(stream);
-  ACG_LAUNCH(bn_moments_to_stats, dim3((groups * C + 255) / 256), dim3(256), 0, st, moments, save_mean, save_rstd, C, groups, eps);
+  const char* who = "bn_act_fwd_moments";
+  BnCall c;
+  if (int rc = prepare(who, kCheckAct, c, rows, C, x_pitch, y_pitch, groups, eps, act, leak, 0, nullptr, 0, stream)) return rc;
+  ACG_REQUIRE(x && beta && moments && y && save_mean && save_rstd, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  ACG_LAUNCH(bn_moments_to_stats, dim3((groups * C + 255) / 256), dim3(256), 0, c.st, moments, save_mean, save_rstd, C, groups, eps);
   if (int rc = acg::check_launch("bn_moments_to_stats")) return rc;
-  const long long R = rows / groups;
-  const bool v4 = vec4_ok(C, x, y, beta) && vec4_ok(C, save_mean, save_rstd, beta) && XP % 4 == 0 && YP % 4 == 0;
-  ACG_WITH_TYPES(dtype, "bn_act_fwd_moments", return (bn_fwd_moments_typed<TA, TB>(x, beta, y, save_mean, save_rstd, R, C, groups, eps, act, leak, v4, XP, YP, st)));
+  c.v4 = c.v4 && aligned16(x, y, beta, save_mean, save_rstd);
+  ACG_WITH_TYPES(dtype, who, return (launch_apply_fwd<TA, TB>(c, (const TA*)x, beta, (const float*)nullptr, (TB*)y, save_mean, save_rstd, 0, (int)kPartDone,
+                                                              TileGeom{0, 0, 1})));
 }
 
 int32_t acg_bn_bwd_sums(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd,
                         float* sums, int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, int32_t act, float leak,
                         int32_t dtype, void* ws, size_t wsb, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_bwd_sums: pitch smaller than the row");
-  if (int rc = check_bn("bn_bwd_sums", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && sums, ACG_ERR_INVALID_ARG, "bn_bwd_sums: null pointer");
-  ACG_REQUIRE(ws && wsb >= acg_bn_workspace_bytes(rows, C, groups), ACG_ERR_WORKSPACE, "bn_bwd_sums: workspace too small");
-  const long long R = rows / groups;
-  hipStream_t st = acg::to_stream(stream);
-  const bool v4 = vec4_ok(C, x, dy, ws) && vec4_ok(C, save_mean, save_rstd, beta) && XP % 4 == 0 && YP % 4 == 0;
-  if (dtype == ACG_DTYPE2(ACG_F32, ACG_BF16))      // the float32 head of a bf16 network: x and dy float32 (dx, bf16, is not touched here)
-    return bn_bwd_sums_typed<float, float>(x, dy, beta, save_mean, save_rstd, sums, R, C, groups, act, leak, (float*)ws, v4, XP, YP, st);
-  ACG_WITH_TYPES(dtype, "bn_bwd_sums", return (bn_bwd_sums_typed<TA, TB>(x, dy, beta, save_mean, save_rstd, sums, R, C, groups, act, leak, (float*)ws, v4, XP, YP, st)));
+  const char* who = "bn_bwd_sums";
+  BnCall c;
+  if (int rc = prepare(who, kCheckWs, c, rows, C, x_pitch, y_pitch, groups, 0.f, act, leak, 0, ws, wsb, stream)) return rc;
+  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && sums, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  c.v4 = c.v4 && aligned16(x, dy, ws, save_mean, save_rstd, beta);
+  // (the float32 head of a bf16 network: x and dy float32 - dx, bf16, is not touched here)
+  return with_bn_types(dtype, who, [&](auto t) { return bn_bwd_sums_typed(t, c, x, dy, beta, save_mean, save_rstd, sums); });
 }
 
 int32_t acg_bn_act_bwd_sums(const void* x, const void* dy, const float* beta, const float* save_mean, const float* save_rstd,
                             const float* sums, const float* local_sums, int64_t total_rows, void* dx, float* dbeta,
                             float dbeta_acc, int64_t rows, int32_t C, int32_t x_pitch, int32_t y_pitch, int32_t groups, int32_t act,
                             float leak, int32_t dtype, acg_stream_t stream) {
-  const int XP = x_pitch > 0 ? x_pitch : C, YP = y_pitch > 0 ? y_pitch : C;
-  ACG_REQUIRE(XP >= C && YP >= C, ACG_ERR_INVALID_ARG, "bn_act_bwd_sums: pitch smaller than the row");
-  if (int rc = check_bn("bn_act_bwd_sums", rows, C, groups)) return rc;
-  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && sums && local_sums && dx && dbeta, ACG_ERR_INVALID_ARG, "bn_act_bwd_sums: null pointer");
-  ACG_REQUIRE(total_rows >= rows / groups, ACG_ERR_INVALID_ARG, "bn_act_bwd_sums: total_rows smaller than this rank's rows");
-  hipStream_t st = acg::to_stream(stream);
-  const long long R = rows / groups;
+  const char* who = "bn_act_bwd_sums";
+  BnCall c;
+  if (int rc = prepare(who, 0, c, rows, C, x_pitch, y_pitch, groups, 0.f, act, leak, 0, nullptr, 0, stream)) return rc;
+  ACG_REQUIRE(x && dy && beta && save_mean && save_rstd && sums && local_sums && dx && dbeta, ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  ACG_REQUIRE(total_rows >= c.R, ACG_ERR_INVALID_ARG, "%s: total_rows smaller than this rank's rows", who);
   const float inv_total = 1.0f / (float)total_rows;
-  const bool v4 = vec4_ok(C, x, dy, dx) && vec4_ok(C, save_mean, save_rstd, beta) && vec4_ok(C, sums, sums, sums) && XP % 4 == 0 && YP % 4 == 0;
-  int rc;
-  if (dtype == ACG_DTYPE2(ACG_F32, ACG_BF16)) {
-    rc = bn_bwd_apply_sums_typed<float, float, __bf16>(x, dy, beta, save_mean, save_rstd, sums, inv_total, dx, R, C, groups, act, leak, v4, XP, YP, st);
-  } else {
-    rc = ACG_OK;
-    ACG_WITH_TYPES(dtype, "bn_act_bwd_sums", rc = (bn_bwd_apply_sums_typed<TA, TB>(x, dy, beta, save_mean, save_rstd, sums, inv_total, dx, R, C, groups, act, leak, v4, XP, YP, st)));
-  }
-  if (rc) return rc;
-  ACG_LAUNCH(bn_dbeta_local_k, dim3((C + 255) / 256), dim3(256), 0, st, local_sums, dbeta, dbeta_acc, C, groups);
+  c.v4 = c.v4 && aligned16(x, dy, dx, save_mean, save_rstd, beta, sums);
+  if (int rc = with_bn_types(dtype, who, [&](auto t) { return launch_apply_bwd(t, c, x, dy, beta, save_mean, save_rstd, nullptr, dx, nullptr, 0.f, 0, sums, inv_total); })) return rc;
+  ACG_LAUNCH(bn_dbeta_local_k, dim3((C + 255) / 256), dim3(256), 0, c.st, local_sums, dbeta, dbeta_acc, C, groups);
   return acg::check_launch("bn_dbeta_local_k");
 }
 

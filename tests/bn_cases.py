@@ -2,19 +2,21 @@
 also asserts WHICH kernel family ran, and - float32 rows of moderate size - the CPU suite on the C oracle, which proves the
 references, inputs, premises and bars without a GPU).
 
-The host (bn_fwd_typed / bn_bwd_typed) picks a kernel from the rows per group R, the channel count C, `groups`, pointer
-alignment, the storage types and ACG_BN_NO_GRID_EXCHANGE.  Every row of PATH_ROWS states the family it is there for, in
-each direction; the test reads the family back out of the workspace (abi_call.bn_path: what acgan_hip.h documents about it)
-and fails with the name of the path that lost its case when a retune moves the shape - correct the table then from
-fused_shape / resident_nr, and keep a case on every path.
+The host picks a kernel from the rows per group R, the channel count C, `groups`, pointer alignment, the storage types, the
+slabs and ACG_BN_NO_GRID_EXCHANGE: bn.hip states that rule once, in fwd_path / bwd_path (tools/bn_path_sweep.hip prints it as
+a table without a GPU).  Every row of PATH_ROWS and SLAB_ROWS states the family it is there for, in each direction; the test
+reads the family back out of the workspace (abi_call.bn_path: what acgan_hip.h documents about it) and fails with the name
+of the path that lost its case when a retune moves the shape - correct the table then from those two functions, and keep a
+case on every path.  profiles/bn_host/README.md lists, for every launch statement of the dispatcher, the case that reaches
+each of its (V, slabs, storage types) arms.
 
 Inputs keep every pre-activation away from the kink of relu / lrelu (where float32 and float64 legitimately pick different
 derivatives): per channel x = shift + scale * s * u with s = +-1 in antithetic pairs (so the column mean is the shift) and u
 uniform in [0.5, 1.5], |beta| <= 0.25: |x-hat| >= 0.48, |x-hat + beta| >= 0.2, both branches taken.  Each case asserts
 min |pre-activation| > 0.05 on the float64 reference before it looks at the kernel.
 
-Not reachable without a tuning build's environment hooks, and therefore not covered: the `case 16` / `default: 32` arms of
-the resident switches and the CL = 16 apply variants."""
+The resident kernels with more than 8 rows per thread and the apply kernels with 16 channel lanes exist in a tuning build only
+(bn.hip pick_nr / pick_cl): the package's library has nothing here that these tables leave out on purpose."""
 import torch
 
 import op_cases as C
@@ -46,12 +48,13 @@ def path_rows(ncu):
     assert -(-r_1024 // 512) * 2 > cap1 >= -(-r_1024 // 1024) * 2 and -(-r_nofit // 1024) > cap1, 'test premise: sizes derived from the CU count'
     NG = L.BN_NO_GRID_EXCHANGE
     f, h, a = ('f32',), ('f32', 'bf16'), ('f32', 'bf16', 'bf16_f32', 'f32_bf16')
+    hd = h + ('f32_bf16',)      # with the float32 head of a bf16 network (bf16 dx) on the V = 4 kernels of each family
     return [
         # register-resident, V = 4: NR = 1 / 2 / 4 / 8 at the last size of each and the first of the next
         ('res_v4_nr1', 256, 8, 1, 0, None, RES, RES, ACTS, f),
         ('res_v4_nr2_first', 257, 8, 2, 0, None, RES, RES, ACTS, f),
         ('res_v4_nr2', 512, 8, 1, 0, None, RES, RES, ACTS, f),
-        ('res_v4_nr4_first', 513, 8, 3, 0, None, RES, RES, ACTS, h),
+        ('res_v4_nr4_first', 513, 8, 3, 0, None, RES, RES, ACTS, hd),
         # backward: the resident limit counts the rows of ALL groups - 2 x 1024 is the last resident size, 2 x 1025 goes to the
         # 256-thread grid kernel (9 row blocks x 2 groups)
         ('res_v4_nr4_bwd_limit', 1024, 8, 2, 0, None, RES, RES, ACTS, f),
@@ -59,16 +62,16 @@ def path_rows(ncu):
         ('bwd_past_group_limit', 1025, 8, 2, 0, None, RES, grid(128), ACTS, h),
         ('res_v4_nr8_bwd_last', 2047, 8, 1, 0, None, RES, RES, ACTS, f),
         # 2048: the last resident forward; backward prefers the grid kernel from here (16 row blocks of 256 threads x 128 rows)
-        ('res_fwd_last_grid128_bwd', 2048, 8, 1, 0, None, RES, grid(128), ACTS, h),
+        ('res_fwd_last_grid128_bwd', 2048, 8, 1, 0, None, RES, grid(128), ACTS, hd),
         ('res_v1_nr8', 2048, 7, 1, 0, None, RES, RES, ACTS, a),
         ('res_v1_many_channels', 40, 1023, 2, 0, None, RES, RES, ACTS, h),
         # one-launch grid kernels; 40 channels: two chunks, the second ragged
-        ('grid512', 2049, 40, 2, 0, None, grid(512), grid(512), ACTS, h),
+        ('grid512', 2049, 40, 2, 0, None, grid(512), grid(512), ACTS, hd),
         ('grid1024', r_1024, 4, 2, 0, None, grid(1024), grid(1024), ACTS, h),
         # two launches
         ('two_v4_grid_does_not_fit', r_nofit, 4, 1, 0, None, TWO, TWO, ('relu',), h),
         ('two_v4_deep_several_batches', 2049, 1024, 1, NG, None, TWO, TWO, ('lrelu',), h),      # 8 MB
-        ('two_v4_shallow', 2049, 8, 3, NG, None, TWO, TWO, ACTS, h),
+        ('two_v4_shallow', 2049, 8, 3, NG, None, TWO, TWO, ACTS, hd),
         ('two_v1', 2100, 7, 2, 0, None, TWO, TWO, ACTS, a),
         ('two_v1_channel_chunks', 2100, 259, 1, 0, None, TWO, TWO, ACTS, h),
         # V = 1 by alignment alone: C = 8, x (then dbeta) one float into its buffer.  Aligned, 2100 x 8 runs the grid kernel
@@ -206,6 +209,157 @@ def case_bn_path(abi, name, storage, ncu=None):
                 _guards_intact(xbuf, 1, tag + ' x')
     finally:
         abi.bn_flags = 0
+
+
+# ---- slabs handed over by a split-K producer (acg_bn_act_fwd_slabs / acg_bn_act_bwd_slabs), called directly -------------------------
+def slab_rows(ncu):
+    """(name, R, C, groups, splits, flags, layout, forward path, backward path).  Rows layout: the grid kernels wherever their grid
+    is resident - from two slabs on as 1024 threads x one row where 128-row blocks fit (fused_shape), else 256 threads x four
+    rows - and, without V = 4 or a grid, whatever takes the tensor itself; quad layout: the resident kernels.  A backward path
+    of None: acg_bn_slabs_layout answers -1 and acg_bn_act_bwd_slabs refuses (the two-launch kernels take no dy slabs)."""
+    cap1 = min(ncu, 512)
+    r_1024 = 512 * (cap1 // 2) + 1
+    NG, RO, QU = L.BN_NO_GRID_EXCHANGE, L.SLABS_ROWS, L.SLABS_QUADS
+    return [
+        ('rows_grid128_wide', 256, 8, 1, 2, 0, RO, grid(128), grid(128)),
+        ('rows_grid128_one_slab', 257, 8, 2, 1, 0, RO, grid(128), grid(128)),
+        ('rows_grid512', 2049, 40, 2, 2, 0, RO, grid(512), grid(512)),
+        ('rows_grid1024', r_1024, 4, 2, 2, 0, RO, grid(1024), grid(1024)),
+        ('quads_resident', 256, 8, 1, 2, NG, QU, RES, RES),
+        ('quads_resident_nr4', 513, 12, 3, 3, NG, QU, RES, RES),
+        ('rows_v1_resident', 300, 7, 2, 2, 0, RO, RES, RES),
+        ('rows_v4_two', 2049, 8, 1, 2, NG, RO, TWO, None),
+        ('rows_v1_two', 2100, 7, 1, 2, 0, RO, TWO, None),
+    ]
+
+
+# (the mixed pair - bf16 x / dx, float32 y / dy - runs the scalar kernels: on the two rows that are there for them)
+SLAB_CASES = [(r[0], st) for r in slab_rows(NOMINAL_CUS) for st in ('f32', 'bf16') + (('bf16_f32',) if r[0].startswith('rows_v1') else ())]
+
+
+def _slabs_of(t, splits, cp, quads, seed, dev):
+    """float32 [rows, C] -> (`splits` float32 slabs whose sum in slab order is close to t, that sum as float32 [rows, C]).  A slab is
+    [rows][cp] (pad channels NaN: not read) or, ``quads``, [C / 4][rows][4]; slabs lie rows * cp floats apart."""
+    rows, c = t.shape
+    parts = [randn((rows, c), seed + z, 1.0) for z in range(splits - 1)]
+    parts.append(t - sum(parts) if parts else t.clone())
+    total = torch.zeros_like(t)
+    for q in parts:
+        total = total + q                                    # float32, slab order: what the kernels add up
+    buf = torch.full((splits, rows * cp), float('nan'))
+    for z, q in enumerate(parts):
+        if quads:
+            buf[z, :rows * c] = q.reshape(rows, c // 4, 4).permute(1, 0, 2).reshape(-1)
+        else:
+            buf[z].view(rows, cp)[:, :c] = q
+    return buf.to(dev), total
+
+
+def case_bn_slabs(abi, name, storage, ncu):
+    """One row of SLAB_ROWS in the storage layouts of case_bn_path (bf16 at the pitch round8(C), float32 dense); the slabs are float32
+    either way, pitched like the tensor they sum to.  Forward: x
+    written back bit-identical to the slab sum rounded to its storage type, y / mean / rstd against float64 BatchNorm of that x.
+    Backward: dx, dbeta against float64 with dy = the slab sum rounded to the storage type.  The family from the workspace."""
+    from abi_call import ACT, _p
+    _, R, c, groups, splits, flags, layout, fpath, bpath = next(r for r in slab_rows(ncu) if r[0] == name)
+    dev, lib = abi.device, abi.lib
+    rows, half, half_y = R * groups, storage != 'f32', storage == 'bf16'
+    cp = (c + 7) // 8 * 8 if half else c
+    yp = cp if half_y else c
+    tt, ty = (torch.bfloat16 if half else torch.float32), (torch.bfloat16 if half_y else torch.float32)
+    code = L.dtype2(L.code(tt), L.code(ty))
+    quads = layout == L.SLABS_QUADS
+    seed = 7000 + 16 * [r[0] for r in slab_rows(NOMINAL_CUS)].index(name)
+    act = ACTS[seed // 16 % 3]
+    tag = 'bn slabs %s %s %s' % (name, storage, act)
+    for backward in (0, 1):
+        want = -1 if (backward and bpath is None) else layout
+        assert lib.bn_slabs_layout(rows, c, cp, yp, groups, code, backward, flags) == want, tag + ': test premise: acg_bn_slabs_layout'
+    xslabs, x = _slabs_of(kink_free(R, c, groups, seed).float(), splits, cp, quads, seed + 4, dev)
+    dslabs, dy = _slabs_of(randn((rows, c), seed + 2), splits, yp, quads, seed + 8, dev)
+    x, dy = (r16(x) if half else x), (r16(dy) if half_y else dy)
+    beta = (torch.rand(c, generator=_rng(seed + 1), dtype=torch.float64) * 0.5 - 0.25).float()
+    y_ref, mean_ref, rstd_ref, dx_ref, db_ref = reference(x, beta, dy, act, groups, tag)
+    bg = beta.to(dev)
+    # ---- forward
+    xs = torch.zeros(rows, cp, dtype=tt, device=dev)
+    y = torch.zeros(rows, yp, dtype=ty, device=dev)
+    mean, rstd = abi.empty(groups * c), abi.empty(groups * c)
+    ws, n = abi.bn_ws(rows, c, groups)
+    lib.bn_act_fwd_slabs(_p(xslabs), splits, _p(xs), _p(bg), _p(y), _p(mean), _p(rstd), rows, c, cp, yp, groups, 1e-3, ACT[act], 0.2, code, layout, flags,
+                         _p(ws), n, abi.stream())
+    abi.sync()
+    abi.no_timeout(ws)
+    _expect(fpath, ws, R, c, groups, tag + ' forward')
+    assert torch.equal(xs[:, :c].float().cpu(), x), tag + ': x written back is not the slab sum rounded to its storage type'
+    assert bool((xs[:, c:] == 0).all()) and bool((y[:, c:] == 0).all()), tag + ': pad channels were written'
+    close(y[:, :c].float(), y_ref, TOL16 if half_y else TOL, tag + ' y')
+    close(mean, mean_ref, TOL, tag + ' mean'); close(rstd, rstd_ref, TOL, tag + ' rstd')
+    # ---- backward from the float32-rounded reference statistics, accumulating into a seeded dbeta
+    xg = _store(x, cp, tt, dev)
+    mg, rg = mean_ref.float().to(dev), rstd_ref.float().to(dev)
+    prev = randn((c,), seed + 3, max(float(db_ref.abs().mean()), 1e-3))
+    dbeta, dx = prev.clone().to(dev), torch.zeros(rows, cp, dtype=tt, device=dev)
+    ws, n = abi.bn_ws(rows, c, groups)
+    call = lambda: lib.bn_act_bwd_slabs(_p(xg), _p(dslabs), splits, _p(bg), _p(mg), _p(rg), _p(dx), _p(dbeta), 0.5, rows, c, cp, yp, groups, ACT[act], 0.2,
+                                        code, layout, flags, _p(ws), n, abi.stream())
+    if bpath is None:
+        try:
+            call()
+        except L.AcgError as e:
+            assert '(code 4)' in str(e) and 'bn_act_bwd_slabs:' in str(e), tag + ': ' + str(e)
+        else:
+            raise AssertionError(tag + ': acg_bn_act_bwd_slabs took a tensor no one-launch kernel fits')
+        return
+    call()
+    abi.sync()
+    abi.no_timeout(ws)
+    _expect(bpath, ws, R, c, groups, tag + ' backward')
+    large = R >= LARGE_ROWS
+    close(dx[:, :c].float(), dx_ref, TOL16 if half else (TOL if large else 4 * TOL), tag + ' dx')
+    close(dbeta, 0.5 * prev.double() + db_ref, (3e-4 if large else 2e-4) if half else 4 * TOL, tag + ' dbeta')
+    assert bool((dx[:, c:] == 0).all()), tag + ': pad channels of dx were written'
+
+
+# ---- statistics out of a producer's tile partials (acg_bn_act_fwd_partials), called directly -----------------------------------------
+# (name, R, C, groups, block_rows, run_rows): more than 512 partial blocks per group - bn_partials_finalize merges them before the
+# apply pass - with four channels per lane and with one; a ragged last block per run; and few blocks (merged in the apply prologue)
+PARTIAL_ROWS = [
+    ('finalize_v4', 1026, 8, 1, 2, 1026),
+    ('finalize_v1_ragged', 1540, 7, 2, 3, 1540),
+    ('prologue_v4', 96, 8, 2, 16, 48),
+]
+PARTIAL_CASES = [r[0] for r in PARTIAL_ROWS]
+
+
+def case_bn_partials(abi, name):
+    """float32 y, mean, rstd of acg_bn_act_fwd_partials against float64, from per-tile (sum, M2) partials computed in float64."""
+    from abi_call import ACT, _p
+    i, (_, R, c, groups, brows, rrows) = next((i, r) for i, r in enumerate(PARTIAL_ROWS) if r[0] == name)
+    assert R % rrows == 0, 'test premise: whole runs'
+    bpr = -(-rrows // brows)
+    nblk = R // rrows * bpr
+    assert (nblk > 512) == name.startswith('finalize'), 'test premise: %d partial blocks per group (bn.hip kFinalizeBlocks)' % nblk
+    dev, seed, act = abi.device, 8000 + 16 * i, 'lrelu'
+    rows = R * groups
+    x = kink_free(R, c, groups, seed).float()
+    beta = (torch.rand(c, generator=_rng(seed + 1), dtype=torch.float64) * 0.5 - 0.25).float()
+    tag = 'bn partials ' + name
+    y_ref, mean_ref, rstd_ref, _, _ = reference(x, beta, torch.zeros(rows, c), act, groups, tag)
+    part = torch.zeros(groups, nblk, 2, c, dtype=torch.float64)
+    xd = x.double().reshape(groups, R // rrows, rrows, c)
+    for b in range(nblk):
+        t = xd[:, b // bpr, (b % bpr) * brows:min((b % bpr + 1) * brows, rrows)]
+        part[:, b, 0] = t.sum(1)
+        part[:, b, 1] = ((t - t.mean(1, keepdim=True)) ** 2).sum(1)
+    xs, bg, pg = x.to(dev), beta.to(dev), part.float().reshape(-1).to(dev)
+    y = torch.zeros(rows, c, device=dev)
+    mean, rstd = abi.empty(groups * c), abi.empty(groups * c)
+    abi.lib.bn_act_fwd_partials(_p(xs), _p(bg), _p(pg), nblk, brows, rrows, _p(y), _p(mean), _p(rstd), rows, c, c, c, groups, 1e-3, ACT[act], 0.2,
+                                L.dtype2(L.ACG_F32, L.ACG_F32), abi.stream())
+    abi.sync()
+    close(y, y_ref, TOL, tag + ' y')
+    close(mean, mean_ref, TOL, tag + ' mean'); close(rstd, rstd_ref, TOL, tag + ' rstd')
 
 
 # ---- pad channels: "neither read nor written" (acgan_hip.h) --------------------------------------------------------------------

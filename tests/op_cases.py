@@ -1825,14 +1825,14 @@ def case_copy_many_paths(abi):
 
 
 def case_bias_paths(abi, tol):
-    """acg_bias_act_bwd accumulating into a seeded dbias; acg_bias_act_fwd / _bwd beyond 256 channels (a second ColMap chunk in
+    """acg_bias_act_bwd accumulating into a seeded dbias; acg_bias_act_fwd / _bwd beyond 256 channels (a second VMap<1> chunk in
     bn.hip) and with a channel count that leaves threads of the block idle (25: 250 of 256 lanes)."""
     dev = abi.device
     acts = {'tanh': torch.tanh, 'relu': T.relu, 'lrelu': T.lrelu, None: lambda t: t}
     for lead, c, act, acc in [((2, 64, 64), 3, 'tanh', 0.5), ((2, 5, 3), 7, 'lrelu', 0.5), ((4, 3, 3), 300, 'lrelu', 0.0), ((4, 3, 3), 300, None, 0.5),
                               ((700, 1, 1), 25, 'tanh', 0.0), ((700, 1, 1), 25, 'relu', 0.5)]:
         if c == 300:
-            assert c > 256, 'test premise: more channels than one ColMap chunk (bn.hip col_map: Cb = 256)'
+            assert c > 256, 'test premise: more channels than one VMap<1> chunk (bn.hip vmap: Cb = 256)'
         x = randn(lead + (c,), 1640)
         bias = randn((c,), 1641, 0.5)
         xd, bd = x.double().requires_grad_(True), bias.double().requires_grad_(True)

@@ -1,5 +1,6 @@
 """GPU parity: BatchNorm at every kernel path of bn.hip, storage type and accumulate mode against float64, with the kernel family
-that ran asserted from the workspace (tests/bn_cases.py); accumulate on acg_bn_act_bwd_slabs, acg_bias_act_bwd and acg_dna_bwd."""
+that ran asserted from the workspace (tests/bn_cases.py), also behind the slabs and the tile partials of a producer; accumulate on
+acg_bn_act_bwd_slabs, acg_bias_act_bwd and acg_dna_bwd."""
 import pytest
 
 import bn_cases as B
@@ -43,6 +44,16 @@ def test_path_classifier_on_known_launches(hip_abi, ncu):
 @pytest.mark.parametrize('name,storage', B.PATH_CASES, ids=lambda v: str(v))
 def test_bn_path(hip_abi, ncu, name, storage):
     B.case_bn_path(hip_abi, name, storage, ncu=ncu)
+
+
+@pytest.mark.parametrize('name,storage', B.SLAB_CASES, ids=lambda v: str(v))
+def test_bn_slabs(hip_abi, ncu, name, storage):
+    B.case_bn_slabs(hip_abi, name, storage, ncu)
+
+
+@pytest.mark.parametrize('name', B.PARTIAL_CASES)
+def test_bn_tile_partials(hip_abi, name):
+    B.case_bn_partials(hip_abi, name)
 
 
 @pytest.mark.parametrize('name,storage', B.PAD_CASES, ids=lambda v: str(v))

@@ -170,6 +170,11 @@ def test_bn_path_cases(oracle_abi, name):
     B.case_bn_path(oracle_abi, name, 'f32')
 
 
+@pytest.mark.parametrize('name', B.PARTIAL_CASES)
+def test_bn_tile_partials_oracle(oracle_abi, name):
+    B.case_bn_partials(oracle_abi, name)
+
+
 @pytest.mark.parametrize('name', [n for n, st in B.PAD_CASES if st == 'f32'])
 def test_bn_pad_channel_cases(oracle_abi, name):
     B.case_bn_pads(oracle_abi, name, 'f32', check_path=False)

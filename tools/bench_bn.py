@@ -3,12 +3,13 @@
 BASELINE configs 2, 3 and 5, timed the way the step runs them (N launches captured into a HIP graph, replayed between two
 events).  `--rot K` rotates over K sets of tensors, so that with K sets larger than the 256 MB memory-side cache every launch
 finds its operands in HBM (the step itself finds them where the producing conv left them: mostly cache-warm).
-  python tools/bench_bn.py [--dtype bf16] [--set c2|c5] [--rot 1] [--lib alt.so] [--check]
+  python tools/bench_bn.py [--dtype bf16] [--set c2|c5] [--rot 1] [--lib alt.so] [--check] [--host]
 GB/s = algorithmic bytes (fwd: x in + y out; fwd without epilogue statistics: 2 x in + y out; bwd: x, dy in + dx out)."""
 import argparse
 import ctypes
 import os
 import sys
+import time
 
 import torch
 
@@ -49,6 +50,21 @@ def timed(fns, n_graph=20, reps=5):
     return e0.elapsed_time(e1) * 1e3 / (reps * n_graph)
 
 
+def host_us(fn, n=200, rounds=5):
+    """Host microseconds until one uncaptured call returns (argument checks, dispatch, enqueue - the device runs behind): the
+    median of `rounds` runs of `n` calls.  Outside a captured graph this is what the entry's host code costs the caller."""
+    sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out = []
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn(sp)
+        out.append((time.perf_counter() - t0) / n * 1e6)
+    torch.cuda.synchronize()
+    return sorted(out)[rounds // 2]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'])
@@ -57,6 +73,7 @@ def main():
     ap.add_argument('--lib', default=None)
     ap.add_argument('--tile', type=int, default=64, help='rows per conv tile of the synthetic epilogue statistics')
     ap.add_argument('--check', action='store_true', help='compare every result with a float64 torch restatement')
+    ap.add_argument('--host', action='store_true', help='also the host time of an uncaptured call (host_us)')
     args = ap.parse_args()
     lib, dev = (_lib.Library(args.lib) if args.lib else _lib.get()), torch.device('cuda:0')
     half = args.dtype == 'bf16'
@@ -102,6 +119,8 @@ def main():
             label, R, C, G, us[0], by[0] / us[0] / 1e3, us[1], by[1] / us[1] / 1e3, us[2], by[2] / us[2] / 1e3))
         for i in range(3):
             tot[i] += us[i]
+        if args.host:
+            print('    host, uncaptured | %7.2f us         | %7.2f us         | %7.2f us' % tuple(host_us(f(sets[0])) for f in (f_fwd, f_fwdp, f_bwd)))
         if args.check:
             x, dy, beta, y, dx, mean, rstd, dbeta, ws, part, nblk, wsb = sets[0]
             sp = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
