@@ -190,12 +190,14 @@ EXTENSIONS = {
     }),
     # the image gradient of the DNA tail and the gradient of a tiled action vector, which training through the generator's own
     # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp), and the global-norm clip of a flat
-    # gradient buffer that bounds them (optim.ClipNormOp)
-    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts runs on the HIP library only', {
+    # gradient buffer that bounds them (optim.ClipNormOp); the header owns the device-side action vector, so the noise that is
+    # appended to it - drawn on the device, the counter advanced by the kernel (ops.NoiseOp) - is here too
+    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, the gradient clip and the noise input run on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
         'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
         'acg_grad_clip_norm': (STATUS, [_P, c_int64, ctypes.POINTER(NormSegments), c_float, c_float, _P, _P, c_size_t, _P]),
+        'acg_noise_concat': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)
@@ -227,6 +229,8 @@ COPY_MAX = 8
 REDUCE_MAX = 32
 PREP_MAX = 32
 NORM_SEGMENTS_MAX = 64
+NOISE_DIM_MAX = 64            # acgan_rollout.h ACG_NOISE_DIM_MAX / ACG_NOISE_VALUES_MAX
+NOISE_VALUES_MAX = 8192
 
 
 def dtype2(first, second):

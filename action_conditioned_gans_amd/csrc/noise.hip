@@ -1,0 +1,83 @@
+// The generator's noise input (include/acgan_rollout.h, acg_noise_concat): out[b] = [actions[b], scale * z[b]] with z drawn
+// on the device by Philox4x32-10 + Box-Muller from a {seed, counter} pair in device memory that the kernel itself advances - a
+// captured program draws a fresh z at every replay with no host in the loop.
+//
+// One block: at most 8192 normals (2048 Philox blocks, 8 per thread) and 8192 * 64 copied action values - the call is launch-latency
+// bound like the one-block loss heads of loss.hip, and one block needs no handshake for the counter: every thread reads it, a
+// barrier, thread 0 stores counter + 1.  No atomics; the draw is a pure function of (seed, counter, stream_id, element index).
+#include <hip/hip_runtime.h>
+#include "../../include/acgan_rollout.h"
+#include "common.h"
+
+namespace {
+
+constexpr int NTH = 256;
+
+// Philox4x32-10 (Salmon et al., SC'11): counter c[4], key (k0, k1) -> c[4]
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
+// the top 23 bits of x, centred in their cell: exact in float32, inside (0, 1)
+__device__ __forceinline__ float unit(uint32_t x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }
+
+__global__ __launch_bounds__(NTH) void noise_concat_kernel(const float* __restrict__ actions, unsigned long long* __restrict__ state,
+                                                           const float* __restrict__ scale, float* __restrict__ out, int B, int A, int Z,
+                                                           uint32_t stream_id) {
+  const int tid = threadIdx.x, P = A + Z, n = B * Z;
+  const unsigned long long seed = state[0], counter = state[1];
+  const float sc = scale[0];
+  for (int idx = tid; idx < B * A; idx += NTH) {
+    const int b = idx / A;
+    out[b * P + idx - b * A] = actions[idx];
+  }
+  for (int i = tid; i * 4 < n; i += NTH) {
+    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)i, stream_id};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    float z[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float r = sqrtf(-2.f * logf(unit(c[2 * h]))), t = 6.283185307179586f * unit(c[2 * h + 1]);
+      z[2 * h] = r * cosf(t);
+      z[2 * h + 1] = r * sinf(t);
+    }
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+      const int e = i * 4 + l;                 // the tail of the last Philox block is dropped
+      if (e < n) {
+        const int b = e / Z;
+        out[b * P + A + e - b * Z] = sc == 0.f ? 0.f : sc * z[l];
+      }
+    }
+  }
+  __syncthreads();                             // every thread has read the counter
+  if (tid == 0) state[1] = counter + 1;
+}
+
+}  // namespace
+
+extern "C" int32_t acg_noise_concat(const float* actions, uint64_t* state, const float* scale, float* out, int32_t batch,
+                                    int32_t action_dim, int32_t noise_dim, int32_t stream_id, acg_stream_t stream) {
+  ACG_REQUIRE(actions && state && scale && out, ACG_ERR_INVALID_ARG, "noise_concat: null pointer");
+  ACG_REQUIRE(batch >= 1, ACG_ERR_INVALID_ARG, "noise_concat: batch %d", batch);
+  ACG_REQUIRE(action_dim >= 1 && action_dim <= ACG_NOISE_DIM_MAX, ACG_ERR_INVALID_ARG, "noise_concat: action_dim %d outside 1..%d",
+              action_dim, ACG_NOISE_DIM_MAX);
+  ACG_REQUIRE(noise_dim >= 1 && noise_dim <= ACG_NOISE_DIM_MAX, ACG_ERR_INVALID_ARG, "noise_concat: noise_dim %d outside 1..%d",
+              noise_dim, ACG_NOISE_DIM_MAX);
+  ACG_REQUIRE((int64_t)batch * noise_dim <= ACG_NOISE_VALUES_MAX, ACG_ERR_UNSUPPORTED, "noise_concat: %d x %d values, at most %d", batch,
+              noise_dim, ACG_NOISE_VALUES_MAX);
+  ACG_LAUNCH(noise_concat_kernel, dim3(1), dim3(NTH), 0, acg::to_stream(stream), actions, (unsigned long long*)state, scale, out,
+             (int)batch, (int)action_dim, (int)noise_dim, (uint32_t)stream_id);
+  return acg::check_launch("noise_concat");
+}

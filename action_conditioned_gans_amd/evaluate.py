@@ -17,6 +17,14 @@ batch the train loop's ``rollout_psnr``), the same two curves for the identity b
 checkpoints (``state:g/ema/shadow``): after the restore the average is COPIED into the variables (with ``--bn_stats calibrate``
 before calibrating, so that OUTPUT/calibrated.npz restores to the same weights again); metrics.json then also holds ``weights``
 and ``ema_updates``.  ``raw`` (default): the weights as trained.
+
+``--noise_dim Z``: the checkpoint is of a run trained with ``--noise_dim Z`` (it must match: the generator's bottleneck layers
+are Z channels wider).  ``--noise zero`` (default) predicts with z = 0; ``--noise sample`` rolls every sequence out
+``--noise_samples`` N times, every step of every rollout with a fresh z from the stream (``--noise_seed``, 0): ``ssim`` and
+``psnr`` are then the mean over the N samples (of N curves, each computed as above), and ``best_ssim`` / ``best_psnr`` the
+best-of-N protocol of stochastic video prediction - for each sequence and each metric separately the sample whose mean over
+the steps is best, then the same reductions over sequences.  metrics.json also holds ``noise_dim``, ``noise`` and
+``noise_samples``.  Not with ``--bn_stats stored`` / ``calibrate``.
 """
 import argparse
 import json
@@ -150,13 +158,15 @@ def set_psnr(sqerr, valid, count_per_frame):
 
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
              seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
-             calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw'):
+             calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw', noise_dim=0,
+             noise='zero', noise_samples=1, noise_seed=0):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
     ``dna`` / ``cdna`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
     with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  ``bn_stats`` 'batch', 'stored' or 'calibrate' and the
     ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
     ``weights``: 'raw' or 'ema' (module docstring); 'ema' on a checkpoint without an average is a ValueError.
+    ``noise_dim`` / ``noise`` ('zero' or 'sample') / ``noise_samples`` / ``noise_seed``: the module docstring.
     -> the metrics dict."""
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
@@ -166,6 +176,15 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
     if bn_stats == 'calibrate' and (calibrate_batch_size < 1 or calibrate_batches < 1):
         raise ValueError('calibrate_batch_size and calibrate_batches must be >= 1')
+    from .train import check_noise
+    noise_dim = check_noise(noise_dim, noise_seed, 1, bn_stats != 'batch', batch_size)
+    if noise not in ('zero', 'sample'):
+        raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
+    if noise == 'sample' and not noise_dim:
+        raise ValueError("noise 'sample' needs noise_dim > 0")
+    if int(noise_samples) < 1 or (noise == 'zero' and int(noise_samples) != 1):
+        raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' (got %r)" % (noise_samples,))
+    n_draws = int(noise_samples)
     transform = 'cdna' if cdna else dna
     from . import graph as G
     from .metrics import SSIM_DEFINITION
@@ -188,6 +207,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     extra = {'bn_inference': True} if stored else {}      # ('batch' builds exactly the graph it always built)
     if weights == 'ema':
         extra['ema_decay'] = EMA_BUILD_DECAY
+    if noise_dim:
+        extra.update(noise_dim=noise_dim, noise_seed=noise_seed)
     bn = 'stored' if stored else 'batch'
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
@@ -195,7 +216,15 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False,
                           num_masks=num_masks, **extra)
         sess.run(G.global_variables_initializer())
-        Saver().restore(sess, restore_from)
+        try:
+            Saver().restore(sess, restore_from)
+        except ValueError as e:
+            if 'has shape' in str(e):        # the Saver's shape refusal: the bottleneck layers are noise_dim channels wider
+                raise ValueError('%s - the generator is built with --noise_dim %d: does that match the run that wrote the checkpoint?'
+                                 % (e, noise_dim)) from None
+            raise
+        if noise_dim:
+            trainer.set_noise_state(noise_seed)        # the stream of this evaluation, not the training run's
         ema_updates = _use_ema_weights(trainer, ckpt) if weights == 'ema' else None
         calibration_rows = trainer.bn_calibration_rows() if stored else None
         if stored and calibration_rows < 1:
@@ -203,6 +232,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
                              % os.path.abspath(ckpt))
         keys = ('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
         acc = {k: [] for k in keys}
+        draws = {'ssim': [], 'sqerr': []}        # noise 'sample': [n_draws, batch, steps] per batch
         valid, kept_frames, kept_pred, dumped = [], [], [], []
         rollout_s, n_seq, steps, hw = 0.0, 0, None, None
         for frames, acts in _batches(input_path, actions_path, batch_size, img_size, seq_len, num_sequences):
@@ -212,7 +242,13 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             steps, hw = frames.shape[1] - 1, frames.shape[2:]
             want = dump or len(kept_pred) < samples
             t0 = time.perf_counter()
-            m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want, **({'bn': bn} if stored else {}))
+            m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want, **({'bn': bn} if stored else {}),
+                                        **({'noise': noise} if noise_dim else {}))
+            if noise == 'sample':        # the first draw is the one that is kept as a sample video; the others are scored only
+                more = [trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), identity=False, noise=noise)
+                        for _ in range(n_draws - 1)]
+                for k in draws:
+                    draws[k].append(np.stack([m[k]] + [d[k] for d in more]))
             rollout_s += time.perf_counter() - t0
             for k in keys:
                 acc[k].append(m[k])
@@ -244,8 +280,12 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             'psnr': [float(v) for v in set_psnr(acc['sqerr'], valid, count)],
             'identity_ssim': [float(v) for v in acc['identity_ssim'][valid].mean(axis=0, dtype=np.float64)],
             'identity_psnr': [float(v) for v in set_psnr(acc['identity_sqerr'], valid, count)],
-            'frames_per_s': float(valid.size * steps / rollout_s),
+            'frames_per_s': float(valid.size * steps * n_draws / rollout_s),
         }
+        if noise_dim:
+            result.update(noise_dim=noise_dim, noise=noise, noise_samples=n_draws)
+        if noise == 'sample':
+            result.update(best_of_n(np.concatenate(draws['ssim'], axis=1)[:, valid], np.concatenate(draws['sqerr'], axis=1)[:, valid], count))
         if stored:
             result['bn_statistics'] = bn_stats
             result['calibration_rows'] = int(calibration_rows)
@@ -262,6 +302,23 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         return result
     finally:
         sess.close()
+
+
+def best_of_n(ssim, sqerr, count_per_frame):
+    """``ssim`` / ``sqerr`` [N draws, sequences, steps] -> the curves of a sampled evaluation.  ``ssim`` / ``psnr``: the mean over
+    the N draws of the curve of each draw (mean SSIM over sequences; set_psnr).  ``best_ssim`` / ``best_psnr``: for each sequence
+    the draw whose mean over the steps is best - SSIM, and the PSNR of the sequence's own frames, chosen separately - then the
+    same reductions over sequences."""
+    from .metrics import psnr_from_sqerr
+    ssim, sqerr = np.asarray(ssim, np.float64), np.asarray(sqerr, np.float64)
+    every = np.ones(ssim.shape[1], bool)
+    seq = np.arange(ssim.shape[1])
+    frame_psnr = 10.0 * np.log10(count_per_frame / np.maximum(sqerr, 1e-30))
+    pick_s, pick_p = ssim.mean(axis=2).argmax(axis=0), frame_psnr.mean(axis=2).argmax(axis=0)
+    return {'ssim': [float(v) for v in ssim.mean(axis=(0, 1))],
+            'psnr': [float(v) for v in np.mean([psnr_from_sqerr(d.sum(axis=0), d.shape[0] * count_per_frame) for d in sqerr], axis=0)],
+            'best_ssim': [float(v) for v in ssim[pick_s, seq].mean(axis=0)],
+            'best_psnr': [float(v) for v in set_psnr(sqerr[pick_p, seq], every, count_per_frame)]}
 
 
 def check_bn_args(parser, args):
@@ -312,9 +369,23 @@ def main(argv=None):
     parser.add_argument('--calibrate_actions', type=str, default=None, help='actions .npy of a --calibrate_input frames .npy')
     parser.add_argument('--weights', type=str, default='raw', choices=['raw', 'ema'],
                         help="the generator weights as trained, or their moving average (a checkpoint of a run trained with --g_ema)")
+    from .train import add_noise_args, check_noise_args
+    add_noise_args(parser)
+    parser.add_argument('--noise', type=str, default='zero', choices=['zero', 'sample'],
+                        help="predict with z = 0, or roll every sequence out --noise_samples times with fresh noise (needs --noise_dim)")
+    parser.add_argument('--noise_samples', type=int, default=None, metavar='N', help="rollouts per sequence with --noise sample (default 1)")
     args = parser.parse_args(argv)
     check_model_args(parser, args)
     check_bn_args(parser, args)
+    check_noise_args(parser, args)
+    if args.noise_dim > 0 and args.bn_stats != 'batch':
+        parser.error('--noise_dim > 0 predicts with batch statistics (--bn_stats %s)' % args.bn_stats)
+    if args.noise == 'sample' and args.noise_dim < 1:
+        parser.error('--noise sample needs --noise_dim > 0')
+    if args.noise_samples is not None and (args.noise != 'sample' or args.noise_samples < 1):
+        parser.error('--noise_samples N >= 1 goes with --noise sample')
+    if args.noise_samples is None:
+        args.noise_samples = 1
     if args.batch_size < 1:
         parser.error('--batch_size must be >= 1')
     if args.num_sequences is not None and args.num_sequences < 1:
@@ -338,7 +409,9 @@ def main(argv=None):
                     num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
                     cdna=args.cdna, num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
                     calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions,
-                    **({'weights': args.weights} if args.weights != 'raw' else {}))
+                    **({'weights': args.weights} if args.weights != 'raw' else {}),
+                    **({'noise_dim': args.noise_dim, 'noise': args.noise, 'noise_samples': args.noise_samples, 'noise_seed': args.noise_seed}
+                       if args.noise_dim else {}))
 
 
 if __name__ == '__main__':

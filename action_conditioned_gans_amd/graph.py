@@ -34,6 +34,14 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _fill(buf, init):
+    """Write a state slot's initial value (Tensor.init): a constant, or a tuple with one value per element."""
+    if isinstance(init, tuple):
+        buf.copy_(torch.tensor(init, dtype=buf.dtype).reshape(buf.shape))
+    else:
+        buf.fill_(init)
+
+
 class Tensor:
     """A statically shaped float32 (or int32) value in the graph; ``buf`` is bound by the session."""
 
@@ -43,7 +51,7 @@ class Tensor:
         self.name = name
         self.dtype = dtype
         self.op = op                # producing Op (None: placeholder, variable, state slot)
-        self.init = init            # constant fill value for state slots (optimizer slots, counters)
+        self.init = init            # initial value of a state slot: one constant (optimizer slots, counters) or a tuple, one per element
         self.view_of = None         # (base Tensor, element offset): a window into a flat buffer
         self.alias_of = None        # same storage as another tensor, different shape (reshape)
         self.buf = None
@@ -513,10 +521,12 @@ class Session:
             base, off = t.view_of
             t.buf = self._materialize(base).view(-1)[off:off + t.numel].view(t.shape)
         else:
-            if t.init is not None:
+            if t.init is not None and not isinstance(t.init, tuple):
                 t.buf = torch.full(t.shape, t.init, dtype=t.dtype, device=self.rt.device)
             else:
                 t.buf = torch.zeros(t.shape, dtype=t.dtype, device=self.rt.device)
+                if t.init is not None:
+                    _fill(t.buf, t.init)
         return t.buf
 
     def _initialize(self):
@@ -527,8 +537,7 @@ class Session:
             v.buf = None
             self._materialize(v).copy_(v.value)
         for s in g.state:
-            buf = self._materialize(s)
-            buf.fill_(s.init)
+            _fill(self._materialize(s), s.init)
         self._initialized = True
         self._weights_dirty = True
 

@@ -1179,6 +1179,55 @@ class ActionGradOp(G.Op):
         return lambda s: fn(*args, s)
 
 
+NOISE_STATE = 'g/noise/state'
+
+
+def noise_state(seed=0):
+    """The noise state every NoiseOp of the graph shares, created by the first call (``seed`` is read by that call alone):
+    -> (state, scale).  ``state``: ``g/noise/state``, {seed, counter} - uint64 [2] to the kernel, which advances the counter; torch
+    holds the same bits as int64 [2] - initialised to {seed, 0}, named graph state and so a checkpoint key like a BatchNorm
+    layer's statistics.  ``scale``: float32 [1], initialised to 1, unnamed (no checkpoint key): whoever runs the programs writes it
+    between them - 0 switches the noise off, the counter advances all the same."""
+    g = G.get_default_graph()
+    if 'noise' not in g.collections:
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError('noise seed must be in [0, 2^64), got %r' % (seed,))
+        g.collections['noise'] = (g.new_state((2,), (seed - 2 ** 64 if seed >= 2 ** 63 else seed, 0), NOISE_STATE, dtype=torch.int64),
+                                  g.new_state((1,), 1.0, None))
+    return g.collections['noise']
+
+
+class NoiseOp(G.Op):
+    """[actions [B, A], scale * z [B, Z]] -> [B, A + Z] float32 (also in a bf16 graph), z ~ N(0, 1) drawn on the device by
+    acg_noise_concat from the graph's noise state (noise_state): a program that holds this op draws a fresh z every time it runs,
+    replayed from a captured graph or not.  The stream id of the draw is the data-parallel rank.  No gradient to z (an input);
+    the gradient of the action columns is their slice of the output's gradient."""
+
+    def __init__(self, actions, noise_dim, name):
+        if len(actions.shape) != 2 or actions.dtype != torch.float32:
+            raise ValueError('append_noise: actions must be float32 [batch, A], got %s %s' % (actions.dtype, actions.shape))
+        b, a = actions.shape
+        z = int(noise_dim)
+        if not (1 <= z <= _lib.NOISE_DIM_MAX and 1 <= a <= _lib.NOISE_DIM_MAX and b * z <= _lib.NOISE_VALUES_MAX):
+            raise ValueError('append_noise: noise_dim %d on actions %s (1 <= A, Z <= %d and B * Z <= %d)'
+                             % (z, actions.shape, _lib.NOISE_DIM_MAX, _lib.NOISE_VALUES_MAX))
+        self.noise_dim = z
+        self.extras = list(noise_state())
+        super().__init__(G.get_default_graph(), name, [actions], [_new((b, a + z), name + ':0')])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'noise_concat')
+        actions, out = self.inputs[0], self.outputs[0]
+        state, scale = self.extras
+        args = (_p(actions.buf), _p(state.buf), _p(scale.buf), _p(out.buf), actions.shape[0], actions.shape[1], self.noise_dim, int(rt.rank))
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        a = self.inputs[0]
+        return [SliceOp(gouts[0], 0, a.shape[-1], a.shape, self.name + '/bwd').outputs[0] if needs[0] else None]
+
+
 class ConcatChannelsOp(G.Op):
     """a ++ b on the channel axis; ``pitch`` > ca+cb stores the result with zero pad channels (``valid_c`` set);
     ``act``: the result is an activation (the conv-facing discriminator input: bf16 in a bf16 graph)."""
@@ -1578,6 +1627,11 @@ def rollout_actions(command, state, name='rollout_actions'):
     if len(command.shape) != 2 or len(state.shape) != 2 or command.shape[0] != state.shape[0]:
         raise ValueError('rollout_actions: [B, A] command and [B, S] state expected, got %s and %s' % (command.shape, state.shape))
     return ConcatChannelsOp(command, state, _scope_name(name)).outputs[0]
+
+
+def append_noise(actions, noise_dim, name='noise'):
+    """actions [B, A] -> [B, A + noise_dim]: the generator's latent input, appended to its action vector (NoiseOp)."""
+    return NoiseOp(actions, noise_dim, _scope_name(name)).outputs[0]
 
 
 def repeat_batch(x, times, name='repeat_batch'):

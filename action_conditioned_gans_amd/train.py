@@ -42,7 +42,7 @@ ACTION_DIM, STATE_DIM = 10, 5
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
-                 ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
+                 ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -82,7 +82,21 @@ class Trainer:
         No variable, no checkpoint key.  Every generator, bf16 graphs (the flat gradient is float32 there), the look-ahead path,
         rollout_steps > 1, ema_decay, ssim_weight and bn_inference take it; with more than one rank the clip sits behind the
         all-reduce, so every rank applies the same scale - not verified there.  ``d_clip_norm`` and the D norms need an
-        adversarial trainer; with ``arg_adv=False`` they are ignored as D itself is."""
+        adversarial trainer; with ``arg_adv=False`` they are ignored as D itself is.
+        ``noise_dim`` Z (no reference counterpart; 0 builds nothing: ops, variables and state names are those of a Trainer without
+        the argument; else 1 <= Z <= 64): the generator reads [action, z] with z ~ N(0, 1) [B, Z] drawn on the device inside the
+        step's program (ops.append_noise, acg_noise_concat: Philox4x32-10 + Box-Muller from the graph state ``g/noise/state`` =
+        {``noise_seed``, counter}, which the kernel advances - a replayed HIP graph draws fresh values with no host in the loop).
+        ``g/tconv1`` (and ``g/cdna_params`` of the CDNA generator) get Z more input channels, drawn by their own initialiser; the
+        discriminator keeps the 10-dim action.  Every generator pass draws a fresh z: ``pretrain_g``, ``train_g``, the G pass
+        inside ``train_d`` and ``test``; ``last_noise()`` returns the values of the last one.  ``test`` / ``test_sequence`` /
+        ``rollout_metrics`` take ``noise='zero'`` (default: z = 0, a deterministic prediction; the counter advances all the same)
+        or ``'sample'``; the device rollout loop draws per step.  The state is a checkpoint key (a restored run continues its
+        stream), the 0 / 1 factor that switches the noise is not.  bf16 graphs take it (the action vector is float32 there too).
+        More than one rank is allowed - the rank is the stream id of the draw, so ranks draw different z from one seed - but not
+        verified.  Declined here: the look-ahead pair pass is switched off for Z > 0 (as it is for rollout_steps > 1), and
+        Z > 0 with ``rollout_steps`` > 1 or with ``bn_inference`` is a ValueError, as is Z outside 0..64."""
+        self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
         ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.ssim_weight = check_ssim_weight(ssim_weight)
         self.g_clip_norm, self.d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
@@ -111,9 +125,13 @@ class Trainer:
         graph = G.get_default_graph()
         dp = graph.collections.get('data_parallel')
         # (synchronised BatchNorm builds other ops per layer and is a validation mode: it keeps the plain call path)
-        self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn)
+        self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn) and not self.noise_dim
+        self._noise = None            # the [B, 10 + Z] vector the generator reads (noise_dim > 0)
 
         def build_g(images, actions, batch, reuse):
+            if self.noise_dim:
+                O.noise_state(noise_seed)
+                actions = self._noise = O.append_noise(actions, self.noise_dim)
             if self.model == 'cdna':
                 return M.build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse)
             if arg_transform:
@@ -228,6 +246,7 @@ class Trainer:
         self.merged_summaries = [self.summaries[k] for k in self._summary_names]
         self._zero_state = np.zeros((B, STATE_DIM), np.float32)
         self._announced = None          # (images, actions) of the G step a look-ahead D step has prepared
+        self._noise_on = None           # the 0 / 1 factor of the noise as last written (_noise_switch; None: not yet)
         self._skip_d = self._skip_g = None
         if self.rollout_steps > 1:
             self._build_rollout(build_g, make)
@@ -249,6 +268,50 @@ class Trainer:
         for norm in self.grad_norm.values():
             if norm is not None:
                 norm.build()        # (the same: after everything else)
+
+    # ---- the generator's noise input (noise_dim > 0)
+    def _check_noise_mode(self, noise):
+        if noise not in ('zero', 'sample'):
+            raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
+        if noise == 'sample' and not self.noise_dim:
+            raise RuntimeError("noise='sample': this Trainer was built without noise_dim, its generator reads no noise")
+        return noise == 'sample'
+
+    def _set_noise(self, noise):
+        """The predicting calls: the noise as their ``noise`` says."""
+        self._noise_switch(self._check_noise_mode(noise), always=True)
+
+    def _noise_switch(self, on, always=False):
+        """Write the 0 / 1 factor of the noise the next generator pass reads (ops.noise_state: outside the programs, on their
+        stream).  The training steps switch it on and write only when they last wrote something else; a predicting call always
+        writes (the initializer, run again, resets the factor behind this object's back)."""
+        if self.noise_dim and (always or on is not self._noise_on):
+            self.sess._materialize(O.noise_state()[1]).fill_(1.0 if on else 0.0)
+            self._noise_on = on
+
+    def last_noise(self):
+        """-> [B, noise_dim] float32: the z the last generator pass read (zeros after a ``noise='zero'`` pass, and before the
+        first pass).  One small device-to-host copy (a synchronisation)."""
+        if not self.noise_dim:
+            raise RuntimeError('this Trainer was built without noise_dim: its generator reads no noise')
+        return self.sess._materialize(self._noise).detach()[:, ACTION_DIM:].cpu().numpy().copy()
+
+    def noise_state(self):
+        """-> (seed, counter) of ``g/noise/state`` as Python ints in [0, 2^64): the counter is the number of draws so far."""
+        if not self.noise_dim:
+            raise RuntimeError('this Trainer was built without noise_dim: it keeps no noise state')
+        seed, counter = (int(v) % 2 ** 64 for v in self.sess._materialize(O.noise_state()[0]).cpu().numpy())
+        return seed, counter
+
+    def set_noise_state(self, seed, counter=0):
+        """Restart the noise stream at (seed, counter): the draws that follow are those of a fresh Trainer built with that seed
+        after ``counter`` generator passes."""
+        if not self.noise_dim:
+            raise RuntimeError('this Trainer was built without noise_dim: it keeps no noise state')
+        vals = [check_noise_seed(seed), check_noise_seed(counter)]
+        state = self.sess._materialize(O.noise_state()[0])
+        state.copy_(torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64))
+        self._announced = None
 
     # ---- gradient norms (g_clip_norm / d_clip_norm / grad_norms)
     def grad_norm_stats(self, scope):
@@ -494,6 +557,7 @@ class Trainer:
 
     def pretrain_g(self, input_images, next_frame, actions, state):
         self._announced = None
+        self._noise_switch(True)
         _, g_res = self.sess.run([self.g_pretrain_opt_op, self.g_loss], self._feed(input_images, next_frame, actions, state))
         return float(g_res[0])
 
@@ -501,6 +565,7 @@ class Trainer:
         # the generator forward pass of these very inputs was run by the preceding train_d(..., next_g=(input_images, actions)):
         # the program then starts behind it (Session.run skip=)
         prepared, self._announced = self._announced, None
+        self._noise_switch(True)
         if prepared is not None and prepared[0] is input_images and prepared[1] is actions:
             fd = self._feed(input_images, next_frame, actions, state)
             if len(prepared) == 4:      # host arrays the announcing D step already put on the device: no second upload
@@ -520,6 +585,7 @@ class Trainer:
         joined, (frames [2 B, H, W, 3], actions [2 B, 10]) with the FOLLOWING step's samples first - saves the concatenation
         here when the caller keeps its batches that way."""
         prepared, self._announced = self._announced, None
+        self._noise_switch(True)
         fd = self._feed(input_images, next_frame, actions)
         if summarize:
             _, summ, _ = self.sess.run([self.d_opt_op, self.merged_summaries, self.clip_d], fd)
@@ -553,14 +619,16 @@ class Trainer:
         self.sess.run([self.d_opt_op, self.clip_d], fd)
         return None
 
-    def test(self, input_images, next_frame, actions, bn='batch', weights='raw'):
-        """``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
+    def test(self, input_images, next_frame, actions, bn='batch', weights='raw', noise='zero'):
+        """``noise`` (a Trainer built with ``noise_dim``): 'zero' - z = 0 - or 'sample' - a fresh z, see ``last_noise``.
+        ``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
         summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames).
         ``weights='ema'`` (a Trainer built with ``ema_decay``): the same call inside ``ema_weights()``."""
         if self._check_weights(weights):
             with self.ema_weights():
-                return self.test(input_images, next_frame, actions, bn=bn)
+                return self.test(input_images, next_frame, actions, bn=bn, noise=noise)
         self._announced = None
+        self._set_noise(noise)
         if self._check_bn_mode(bn):
             has_state = self.g_state_stored is not None
             fd = {self.img_ph: input_images, self._img_pad: input_images, self.next_frame_ph: next_frame, self.action_ph: actions}
@@ -573,7 +641,7 @@ class Trainer:
         return gen_next_frames, gen_next_state, self._named(summ)
 
     def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None, bn='batch',
-                      weights='raw'):
+                      weights='raw', noise='zero'):
         """Recursive rollout: feed each prediction (and predicted state) back in.
         ``device_loop`` (default: on for a GPU session): from the second step on the prediction and the predicted state stay on the
         device between steps - the program of those steps fetches nothing but the two, so it carries no loss ops either - and
@@ -587,19 +655,20 @@ class Trainer:
         reads ``test_actions[:, 2 j, :5]`` and ``test_next_frame[:, 2 j]`` (the sequences must hold >= 11 frames),
         and the second return value is ``current_frame[1:7]``, samples 1..6 of the last prediction.
         ``bn``: 'batch' (default: every step normalises with the statistics of its batch) or 'stored' (see ``test``).
-        ``weights``: 'raw' or 'ema' (see ``test``)."""
+        ``weights``: 'raw' or 'ema' (see ``test``).  ``noise``: 'zero' or 'sample' (see ``test``): every step draws its own z."""
         if self._check_weights(weights):
             with self.ema_weights():
                 return self.test_sequence(input_images, test_next_frame, test_actions, steps=steps, literal=literal,
-                                          device_loop=device_loop, bn=bn)
+                                          device_loop=device_loop, bn=bn, noise=noise)
         self._check_bn_mode(bn)
+        self._set_noise(noise)
         if literal:
             predicted = []
             current_frame = input_images[:, 0]
             current_state = test_actions[:, 0, 5:]
             for j in range(0, 6):
                 acs = np.concatenate((test_actions[:, j * 2, :5], current_state), axis=1).astype(np.float32)
-                out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs, bn=bn)
+                out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs, bn=bn, noise=noise)
                 predicted.append(out)
                 current_frame = out
                 current_state = st if st is not None else test_actions[:, j * 2, 5:]      # plain generator: no state head (D4)
@@ -608,23 +677,25 @@ class Trainer:
         if device_loop is None:
             device_loop = self.sess.rt.is_cuda
         if device_loop and steps >= 1:
-            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps, bn=bn)
+            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps, bn=bn, noise=noise)
             return predicted.cpu().numpy(), summ0
         predicted, summ0 = [], None
         current_frame = input_images[:, 0]
         current_state = test_actions[:, 0, 5:]
         for j in range(steps):
             acs = np.concatenate((test_actions[:, j, :5], current_state), axis=1).astype(np.float32)
-            out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs, bn=bn)
+            out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs, bn=bn, noise=noise)
             summ0 = summ0 or summ
             predicted.append(out)
             current_frame = out
             current_state = st if st is not None else test_actions[:, j + 1, 5:]
         return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), summ0
 
-    def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps, bn='batch'):
-        """The device loop of ``test_sequence``: -> (predicted [B, steps, H, W, 3] float32 on the device, summaries of step 0)."""
-        out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32), bn=bn)
+    def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps, bn='batch', noise='zero'):
+        """The device loop of ``test_sequence``: -> (predicted [B, steps, H, W, 3] float32 on the device, summaries of step 0).
+        The noise switch ``test`` sets stays as it is for the steps that follow: each of them draws (or zeroes) its own z."""
+        out, st, summ0 = self.test(input_images[:, 0], test_next_frame[:, 1], np.asarray(test_actions[:, 0], np.float32), bn=bn,
+                                   noise=noise)
         acts = self.sess.upload(np.asarray(test_actions[:, :steps + 1], np.float32))          # [B, steps + 1, 10], once
         frame = self.sess.upload(out)
         state = self.sess.upload(st) if st is not None else acts[:, 1, 5:]
@@ -642,7 +713,8 @@ class Trainer:
             frames.append(frame)
         return torch.stack(frames, dim=1), summ0
 
-    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False, bn='batch', weights='raw'):
+    def rollout_metrics(self, images, actions, steps=None, identity=True, return_frames=False, bn='batch', weights='raw',
+                        noise='zero'):
         """Quality of the recursive rollout, scored on the GPU (metrics.frame_metrics; no reference counterpart - the curves of
         its report).  Rollout as ``test_sequence``'s default on the device loop: ``steps`` (default T-1) steps,
         step j commanded by ``actions[:, j]`` with the generator's own predicted state (defect D7) and scored against
@@ -650,18 +722,20 @@ class Trainer:
         also score the identity baseline - ``images[:, 0]`` carried forward - against the same targets.
         -> dict of numpy arrays [B, steps]: ``ssim``, ``sqerr`` (sum of squared errors of the frame), and ``identity_ssim``,
         ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames).
-        ``bn``: 'batch' or 'stored', ``weights``: 'raw' or 'ema', as ``test`` takes them."""
+        ``bn``: 'batch' or 'stored', ``weights``: 'raw' or 'ema', ``noise``: 'zero' or 'sample', as ``test`` takes them."""
         from . import metrics
         if self._check_weights(weights):
             with self.ema_weights():
-                return self.rollout_metrics(images, actions, steps=steps, identity=identity, return_frames=return_frames, bn=bn)
+                return self.rollout_metrics(images, actions, steps=steps, identity=identity, return_frames=return_frames, bn=bn,
+                                            noise=noise)
         self._check_bn_mode(bn)
+        self._check_noise_mode(noise)
         if not self.sess.rt.is_cuda:
             raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
         steps = steps if steps is not None else images.shape[1] - 1
         if steps < 1 or steps + 1 > images.shape[1]:
             raise ValueError('rollout_metrics: %d steps need %d frames per sequence, got %d' % (steps, steps + 1, images.shape[1]))
-        predicted, _ = self._rollout_on_device(images, images, actions, steps, bn=bn)
+        predicted, _ = self._rollout_on_device(images, images, actions, steps, bn=bn, noise=noise)
         seq = self.sess.upload(np.asarray(images[:, :steps + 1], np.float32))                # [B, steps + 1, H, W, 3], once
         truth = seq[:, 1:]
         ssim, sqerr = metrics.frame_metrics(predicted, truth)
@@ -718,6 +792,29 @@ def check_clip_norm(value, what='clip_norm'):
     if isinstance(value, bool) or not 0.0 <= x <= float(np.finfo(np.float32).max) or (x > 0.0 and float(np.float32(x)) == 0.0):
         raise ValueError('%s must be finite and >= 0 (0: off), got %r' % (what, value))
     return x
+
+
+def check_noise_seed(seed):
+    """ValueError for a noise seed (or counter) that is not an integer in [0, 2^64); -> it as an int."""
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError('noise_seed must be an integer in [0, 2^64), got %r' % (seed,))
+    return int(seed)
+
+
+def check_noise(noise_dim, noise_seed=0, rollout_steps=1, bn_inference=False, batch_size=1):
+    """ValueError for a ``noise_dim`` the Trainer does not take (outside 0..64; > 0 together with rollout_steps > 1 or with
+    bn_inference; more than 8192 values per batch) or a bad ``noise_seed``; -> Z."""
+    if isinstance(noise_dim, bool) or not isinstance(noise_dim, (int, np.integer)) or not 0 <= int(noise_dim) <= _lib.NOISE_DIM_MAX:
+        raise ValueError('noise_dim must be an integer in 0..%d (0: no noise input), got %r' % (_lib.NOISE_DIM_MAX, noise_dim))
+    check_noise_seed(noise_seed)
+    z = int(noise_dim)
+    if z and int(rollout_steps) > 1:
+        raise ValueError('noise_dim > 0 does not go with rollout_steps > 1 (the K-step programs read no noise)')
+    if z and bn_inference:
+        raise ValueError('noise_dim > 0 does not go with bn_inference (the calibration and stored-statistics instances read no noise)')
+    if z * int(batch_size) > _lib.NOISE_VALUES_MAX:
+        raise ValueError('noise_dim %d at batch %d: one draw holds at most %d values' % (z, batch_size, _lib.NOISE_VALUES_MAX))
+    return z
 
 
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
@@ -874,13 +971,14 @@ class _PairSelections:
         return self.queue.pop(0)
 
 
-def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None):
+def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0):
     """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
     the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
-    ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run)."""
+    ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0."""
     record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
                   **({'g_ema': ema_decay} if ema_decay else {}),
-                  **({'ssim_weight': ssim_weight} if ssim_weight else {}))
+                  **({'ssim_weight': ssim_weight} if ssim_weight else {}),
+                  **({'noise_dim': noise_dim} if noise_dim else {}))
     for scope in sorted(grad_stats or {}, reverse=True):             # g, then d
         record[scope + '_grad_norm'] = grad_stats[scope]['norm']
         record[scope + '_clip_scale'] = grad_stats[scope]['scale']
@@ -899,7 +997,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           n_critic=None, device='cuda:0', world_size=1, rank=0, process_group=None, log_every=100, quiet=False,
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
-          num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
+          num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
+          noise_dim=0, noise_seed=0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -926,7 +1025,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     ``g_clip_norm`` / ``d_clip_norm`` X > 0: the G / D updates clip their gradient to a global norm of X; ``grad_norms``: measure
     the norms of a scope without a bound too (Trainer, same keywords).  With any of them ``train.jsonl`` records
     ``g_grad_norm`` / ``g_clip_scale`` / ``d_grad_norm`` / ``d_clip_scale`` of the iteration's last updates at every log
-    interval (the scopes that are measured) and the configured bounds once, in its first record.  Checkpoints are unchanged."""
+    interval (the scopes that are measured) and the configured bounds once, in its first record.  Checkpoints are unchanged.
+    ``noise_dim`` Z > 0 / ``noise_seed``: the generator reads Z noise values drawn on the device (Trainer, same keywords); the loop
+    takes the plain call path (no look-ahead pass), checkpoints hold ``g/noise/state``, ``train.jsonl`` records ``noise_dim`` and
+    the evaluation block predicts with z = 0."""
+    noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
     ema_decay = check_ema_decay(ema_decay)
     ssim_weight = check_ssim_weight(ssim_weight)
     g_clip_norm, d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
@@ -958,7 +1061,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
                               select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
                               ema_decay=ema_decay, ssim_weight=ssim_weight, g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm,
-                              grad_norms=bool(grad_norms))
+                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -973,8 +1076,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False):
+                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
+                noise_dim=0, noise_seed=0):
     ema = {'ema_decay': ema_decay} if ema_decay else {}
+    if noise_dim:
+        ema.update(noise_dim=noise_dim, noise_seed=noise_seed)
     if ssim_weight:
         ema['ssim_weight'] = ssim_weight
     if g_clip_norm or d_clip_norm or grad_norms:
@@ -1053,7 +1159,7 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             if log_file and summ:
                 stats = {sc: trainer.grad_norm_stats(sc) for sc, norm in trainer.grad_norm.items() if norm is not None}
                 bounds = None if bounds_logged or not stats else {'g': g_clip_norm, 'd': d_clip_norm}
-                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds))
+                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds, noise_dim))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
@@ -1148,6 +1254,22 @@ def check_rollout_args(parser, args):
         parser.error('--rollout_steps > 1 runs on one rank (--exact_global_batch)')
 
 
+def add_noise_args(parser):
+    """The noise flags shared by this CLI and evaluate's: --noise_dim and --noise_seed."""
+    parser.add_argument('--noise_dim', type=int, default=0, metavar='Z',
+                        help='give the generator Z noise values per sample, drawn on the device inside the step (1..64; 0 = off, the '
+                             'deterministic generator); evaluate takes the same --noise_dim')
+    parser.add_argument('--noise_seed', type=int, default=0, metavar='S', help='seed of the noise stream (0 <= S < 2^64)')
+
+
+def check_noise_args(parser, args):
+    """parser.error for a --noise_dim / --noise_seed the Trainer does not take (before anything is created)."""
+    try:
+        check_noise(args.noise_dim, args.noise_seed, getattr(args, 'rollout_steps', 1), False, args.batch_size)
+    except ValueError as e:
+        parser.error('--noise_dim / --noise_seed: %s' % e)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='action-conditioned video-prediction GAN on MI355X')
     parser.add_argument('input_path', type=str)
@@ -1200,6 +1322,7 @@ def main(argv=None):
     parser.add_argument('--log_grad_norms', nargs='?', const=True, default=False, type=_flag,
                         help='record the gradient norms of G and D in train.jsonl (g_grad_norm, d_grad_norm, ..._clip_scale), also '
                              'where no bound is set')
+    add_noise_args(parser)
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
@@ -1218,6 +1341,7 @@ def main(argv=None):
             parser.error('--%s must be finite and >= 0, got %r' % (flag, getattr(args, flag)))
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
+    check_noise_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
     log_dir = os.path.join(args.output_path, 'logs')
     os.makedirs(args.output_path)
@@ -1237,7 +1361,7 @@ def main(argv=None):
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
                     data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema,
                     ssim_weight=args.ssim_weight, g_clip_norm=args.g_clip_norm, d_clip_norm=args.d_clip_norm,
-                    grad_norms=args.log_grad_norms)
+                    grad_norms=args.log_grad_norms, noise_dim=args.noise_dim, noise_seed=args.noise_seed)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

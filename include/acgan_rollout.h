@@ -12,6 +12,9 @@
  * Back-propagation through K generator passes is the textbook case for exploding gradients, so the header also holds what bounds
  * them: acg_grad_clip_norm, the global-norm clip (and the norm measurement) of an optimizer's flat gradient buffer, with its
  * workspace query - same conventions, same table, no atomics either.
+ *
+ * The action vector on the device is this header's, so the generator's noise input - a latent drawn on the device and appended
+ * to that vector, the last entry below - is declared here as well: same conventions, same table, no atomics.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -71,6 +74,23 @@ typedef struct acg_norm_segments {
 size_t acg_grad_clip_norm_workspace_bytes(int64_t n, const acg_norm_segments* segs);
 int32_t acg_grad_clip_norm(float* grad, int64_t n, const acg_norm_segments* segs, float pre_scale, float max_norm, float* stats,
                            void* workspace, size_t workspace_bytes, acg_stream_t stream);
+
+/* The generator's noise input.  This header owns the device-side action vector, so the latent that is appended to it lives here:
+ *   out[b, :A]    = actions[b, :]                    (bit for bit),
+ *   out[b, A + j] = scale[0] * z[b * Z + j]          (exactly 0 when scale[0] == 0),
+ * actions [B, A], out [B, A + Z] dense float32, scale float32 [1] and state uint64 [2] = {seed, counter} in device memory, all
+ * distinct.  z is a pure function of (seed, counter, stream_id, element index e): Philox4x32-10 on block i = e / 4 with the counter
+ * words (lo32(counter), hi32(counter), i, stream_id) and the key (lo32(seed), hi32(seed)) - multipliers 0xD2511F53 / 0xCD9E8D57,
+ * Weyl constants 0x9E3779B9 / 0xBB67AE85; each output word x gives u = ((x >> 9) + 0.5) * 2^-23 in (0, 1); Box-Muller on the pairs
+ * (u0, u1), (u2, u3): r = sqrt(-2 ln u_even), z = r cos(2 pi u_odd), r sin(2 pi u_odd) in full float32 precision, |z| <= 5.77;
+ * element e is lane e % 4 of block e / 4 and the tail of the last block is dropped.  After the draw the kernel stores
+ * counter + 1 (also when scale[0] == 0): the same call draws fresh values each time it runs, a replayed graph included, with no
+ * host in the loop.  stream_id separates concurrent streams of one seed (the data-parallel rank).  One launch of one block, no
+ * atomics; 1 <= A, Z <= ACG_NOISE_DIM_MAX and B * Z <= ACG_NOISE_VALUES_MAX.  Calls that share a state must be stream-ordered. */
+#define ACG_NOISE_DIM_MAX 64
+#define ACG_NOISE_VALUES_MAX 8192
+int32_t acg_noise_concat(const float* actions, uint64_t* state, const float* scale, float* out, int32_t batch, int32_t action_dim,
+                         int32_t noise_dim, int32_t stream_id, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
