@@ -2,10 +2,9 @@
 //
 // Two launches for the gradient, a third small one when the value is asked for:
 //
-// 1. ssim_maps_k - the structure of metrics.hip's ssim_partial_k: one block = one frame x one strip of <= 64 map columns x
-//    one band of map rows, one wave per channel (lane = map column); the band's input rows go through LDS in chunks of 11, a
-//    lane runs the horizontal 11-tap pass on five quantities and adds the result into a ring of 11 vertical accumulators.  The
-//    position whose window ended at this row is turned into its SSIM value S and into the three maps of the gradient
+// 1. ssim_maps_k - the windowed-moments pass of ssim_window.h (one block = one frame x one strip of <= 64 map columns x one band
+//    of map rows, one wave per channel, lane = map column).  A finished position is turned into its SSIM value S and into the
+//    three maps of the gradient
 //        M0 = U - 2 a' Pq - m' Pr,   M1 = 2 Pq,   M2 = Pr        (a', m': the means of the SHIFTED x and y)
 //    which go to the workspace, planar [n][c][3][h - 10][w - 10] (lanes write consecutive floats).
 // 2. ssim_adjoint_k - G^T, the zero-padded correlation of a map back to the frame, is the same VALID 11 x 11 filter run on the
@@ -28,38 +27,47 @@
 #include "../../include/acgan_ssim_loss.h"
 #include "common.h"
 
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)   // before ssim_window.h: the shared pass takes this file's mode (see there)
+
+#include "ssim_window.h"
 
 namespace {
 
-constexpr int kTaps = 11, kHalo = kTaps - 1;
-constexpr int kStrip = 64;                  // output columns per block (one per lane)
-constexpr int kCols = kStrip + kHalo;       // input columns a strip reads
-constexpr int kLdsCols = kCols + 2;         // (row pitch in LDS)
-constexpr int kMaxC = 4;
+using namespace acg::ssim;
 
-struct Window {
-  float g[kTaps];
+// Blocking of the map (launch 1) and of the frame (launch 2).  A training batch is tens of frames, not the hundreds the metric
+// pass sees: the launch is latency bound until the grid fills the device, so the bands go down to the size of the halo.
+Plan loss_plan(int n, int rows, int cols) { return plan_for(n, rows, cols, 512, kTaps); }
+
+// What ssim_maps_k does with a finished position: S and the three gradient maps.
+template <bool MAPS, bool VALUE>
+struct LossEpilogue {
+  float sx, sy, c1, c2;
+  float* mp;        // the (frame, channel)'s three planes, at (p0, q0 + lane)
+  size_t plane;
+  int out_w;
+  double ssim_sum;
+
+  __device__ __forceinline__ void row(int, const float*, const float*) {}
+  __device__ __forceinline__ void position(int p, const float (&mo)[5]) {
+    const float A = mo[0], B = mo[1], dm = A - B;
+    const float vx = mo[2] - A * A, vy = mo[3] - B * B, vd = mo[4] - dm * dm;
+    const float a = sx + A, m = sy + B;
+    const float A1 = 2.f * (a * m) + c1, B1 = (a * a + m * m) + c1;
+    const float vv = vx + vy, A2 = (vv - vd) + c2, B2 = vv + c2;
+    const float i1 = 1.f / B1, i2 = 1.f / B2, i12 = i1 * i2;
+    const float S = (A1 * A2) * i12;
+    if constexpr (VALUE) ssim_sum += (double)S;
+    if constexpr (MAPS) {
+      const float Pq = -(S * i2), Pr = 2.f * (A1 * i12);
+      const float U = 2.f * ((m * A2) * i12) - 2.f * ((a * S) * i1);
+      const size_t o = (size_t)p * out_w;
+      mp[o] = (U - 2.f * (A * Pq)) - B * Pr;
+      mp[plane + o] = 2.f * Pq;
+      mp[2 * plane + o] = Pr;
+    }
+  }
 };
-
-// Blocking of a rows x cols field of outputs (the map in launch 1, the frame in launch 2): strips of 64 columns, bands of rows
-// halved while the grid is small.  A training batch is tens of frames, not the hundreds the metric pass sees: the launch is
-// latency bound until the grid fills the device, so the bands go down to the size of the halo.
-struct Plan {
-  int rows, cols, strips, band, bands;
-  __host__ __device__ long long blocks_per_frame() const { return (long long)strips * bands; }
-};
-
-Plan plan_for(int n, int rows, int cols) {
-  Plan p;
-  p.rows = rows;
-  p.cols = cols;
-  p.strips = (cols + kStrip - 1) / kStrip;
-  p.band = rows;
-  while ((long long)n * p.strips * ((rows + p.band - 1) / p.band) < 512 && p.band > kTaps) p.band = (p.band + 1) / 2;
-  p.bands = (rows + p.band - 1) / p.band;
-  return p;
-}
 
 // blockDim.x = 64 * C.  MAPS: maps[((n C + c) 3 + k) plane + p out_w + q].  VALUE: part[block] = sum of S over the block's
 // positions and channels.
@@ -71,113 +79,22 @@ __global__ __launch_bounds__(256) void ssim_maps_k(const float* __restrict__ pre
   __shared__ float ys[kMaxC][kTaps][kLdsCols];
   __shared__ double scratch[16];
 
-  const long long bpf = pl.blocks_per_frame();
-  const long long n = blockIdx.x / bpf;
-  const int b = (int)(blockIdx.x - n * bpf);
-  const int strip = b % pl.strips, band = b / pl.strips;
-  const int q0 = strip * kStrip, p0 = band * pl.band;
-  const int out_h = pl.rows, out_w = pl.cols;
-  const int rows_out = min(pl.band, out_h - p0);
-  const int rows_in = rows_out + kHalo;
-  const int cols_in = min(kCols, W - q0);
-  const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const size_t frame = (size_t)n * H * W * C;
-  const size_t row_elems = (size_t)W * C;
-  const bool live = c < C;
-  const float sx = live ? pred[frame + c] : 0.f, sy = live ? truth[frame + c] : 0.f;
-  const bool col_ok = q0 + lane < out_w;
-  const size_t plane = (size_t)out_h * out_w;
-  float* const mp = MAPS ? maps + ((size_t)n * C + (live ? c : 0)) * 3 * plane : nullptr;
+  const Tile tl = tile_of(pl);
+  const size_t frame = (size_t)tl.n * H * W * C;
+  const bool live = tl.c < C;
+  LossEpilogue<MAPS, VALUE> ep;
+  ep.sx = live ? pred[frame + tl.c] : 0.f;
+  ep.sy = live ? truth[frame + tl.c] : 0.f;
+  ep.c1 = c1;
+  ep.c2 = c2;
+  ep.plane = (size_t)pl.rows * pl.cols;
+  ep.out_w = pl.cols;
+  ep.mp = MAPS ? maps + ((size_t)tl.n * C + (live ? tl.c : 0)) * 3 * ep.plane + (size_t)tl.p0 * pl.cols + (tl.q0 + tl.lane) : nullptr;
+  ep.ssim_sum = 0.0;
+  ep = moments_pass<VEC>(pred, truth, xs, ys, tl, pl, H, W, C, C, win, ep.sx, ep.sy, ep);
 
-  float acc[kTaps][5];
-#pragma unroll
-  for (int s = 0; s < kTaps; ++s)
-#pragma unroll
-    for (int k = 0; k < 5; ++k) acc[s][k] = 0.f;
-  double ssim_sum = 0.0;
-
-  const int seg = cols_in * C;  // elements of one input row this block reads
-  for (int r0 = 0; r0 < rows_in; r0 += kTaps) {
-    const int nr = min(kTaps, rows_in - r0);
-    __syncthreads();  // the previous chunk has been read
-    if constexpr (VEC) {
-      const int seg4 = (seg + 3) >> 2;  // rows and q0 * C are multiples of 4 elements: a vector never crosses the row end
-      for (int e = threadIdx.x; e < nr * seg4; e += blockDim.x) {
-        const int i = e / seg4, e4 = (e - i * seg4) << 2;
-        const size_t o = frame + (size_t)(p0 + r0 + i) * row_elems + (size_t)q0 * C + e4;
-        const float4 tx = *reinterpret_cast<const float4*>(pred + o);
-        const float4 ty = *reinterpret_cast<const float4*>(truth + o);
-        const float vx[4] = {tx.x, tx.y, tx.z, tx.w}, vy[4] = {ty.x, ty.y, ty.z, ty.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int el = e4 + j, col = el / C, ch = el - col * C;
-          if (col < cols_in) { xs[ch][i][col] = vx[j]; ys[ch][i][col] = vy[j]; }
-        }
-      }
-    } else {
-      for (int e = threadIdx.x; e < nr * seg; e += blockDim.x) {
-        const int i = e / seg, el = e - i * seg, col = el / C, ch = el - col * C;
-        const size_t o = frame + (size_t)(p0 + r0 + i) * row_elems + (size_t)q0 * C + el;
-        xs[ch][i][col] = pred[o];
-        ys[ch][i][col] = truth[o];
-      }
-    }
-    __syncthreads();
-    if (live) {
-#pragma unroll
-      for (int i = 0; i < kTaps; ++i) {
-        if (i < nr) {
-          const int r = r0 + i;
-          // horizontal pass (columns past the frame's edge hold stale values: they only reach outputs with col_ok false)
-          float h[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int t = 0; t < kTaps; ++t) {
-            const float x = xs[c][i][lane + t] - sx, y = ys[c][i][lane + t] - sy, d = x - y, g = win.g[t];
-            const float gx = g * x, gy = g * y, gd = g * d;
-            h[0] = h[0] + gx;
-            h[1] = h[1] + gy;
-            h[2] = fmaf(gx, x, h[2]);
-            h[3] = fmaf(gy, y, h[3]);
-            h[4] = fmaf(gd, d, h[4]);
-          }
-          // vertical pass: input row r feeds output row r - k with weight g[k]; the slot of output p is p mod 11 = (r - k) mod 11
-          // and r = r0 + i with r0 a multiple of 11, so every slot index is a compile-time constant.  Outputs p < 0 land in
-          // slots that are cleared below before their own first row.
-#pragma unroll
-          for (int k = 0; k < kTaps; ++k) {
-            const int s = (i - k + kTaps) % kTaps;
-#pragma unroll
-            for (int q = 0; q < 5; ++q) acc[s][q] = fmaf(win.g[k], h[q], acc[s][q]);
-          }
-          // output p = r - 10 is complete (slot (i + 1) mod 11)
-          const int s = (i + 1) % kTaps;
-          const int p = r - kHalo;
-          if (p >= 0 && col_ok) {
-            const float A = acc[s][0], B = acc[s][1], dm = A - B;
-            const float vx = acc[s][2] - A * A, vy = acc[s][3] - B * B, vd = acc[s][4] - dm * dm;
-            const float a = sx + A, m = sy + B;
-            const float A1 = 2.f * (a * m) + c1, B1 = (a * a + m * m) + c1;
-            const float vv = vx + vy, A2 = (vv - vd) + c2, B2 = vv + c2;
-            const float i1 = 1.f / B1, i2 = 1.f / B2, i12 = i1 * i2;
-            const float S = (A1 * A2) * i12;
-            if constexpr (VALUE) ssim_sum += (double)S;
-            if constexpr (MAPS) {
-              const float Pq = -(S * i2), Pr = 2.f * (A1 * i12);
-              const float U = 2.f * ((m * A2) * i12) - 2.f * ((a * S) * i1);
-              const size_t o = (size_t)(p0 + p) * out_w + (q0 + lane);
-              mp[o] = (U - 2.f * (A * Pq)) - B * Pr;
-              mp[plane + o] = 2.f * Pq;
-              mp[2 * plane + o] = Pr;
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < 5; ++q) acc[s][q] = 0.f;
-        }
-      }
-    }
-  }
   if constexpr (VALUE) {
-    const double s1 = acg::block_sum(ssim_sum, scratch);
+    const double s1 = acg::block_sum(ep.ssim_sum, scratch);
     if (threadIdx.x == 0) part[blockIdx.x] = s1;
   }
 }
@@ -190,15 +107,11 @@ __global__ __launch_bounds__(256) void ssim_adjoint_k(const float* __restrict__ 
   __shared__ float ms[3][kMaxC][kTaps][kLdsCols];
   __shared__ __align__(16) float os[kTaps][kStrip * kMaxC];
 
-  const long long bpf = pl.blocks_per_frame();
-  const long long n = blockIdx.x / bpf;
-  const int b = (int)(blockIdx.x - n * bpf);
-  const int strip = b % pl.strips, band = b / pl.strips;
-  const int j0 = strip * kStrip, i0 = band * pl.band;
-  const int rows_out = min(pl.band, H - i0);
-  const int rows_in = rows_out + kHalo;       // rows of the zero-bordered map: local row rl is map row i0 - 10 + rl
-  const int cols = min(kStrip, W - j0);       // pixel columns of this strip
-  const int c = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const Tile tl = tile_of(pl);
+  const long long n = tl.n;
+  const int j0 = tl.q0, i0 = tl.p0, c = tl.c, lane = tl.lane;
+  const int rows_in = tl.rows_in;             // rows of the zero-bordered map: local row rl is map row i0 - 10 + rl
+  const int cols = tl.cols_in - kHalo;        // pixel columns of this strip
   const size_t frame = (size_t)n * H * W * C;
   const size_t row_elems = (size_t)W * C;
   const bool live = c < C;
@@ -288,16 +201,6 @@ __global__ __launch_bounds__(256) void ssim_loss_finalize_k(const double* __rest
   if (threadIdx.x == 0) value[0] = (float)total;
 }
 
-Window gaussian_window() {
-  double g[kTaps], s = 0.0;
-  for (int t = 0; t < kTaps; ++t) { const double u = t - kHalo / 2; g[t] = exp(-u * u / (2.0 * 1.5 * 1.5)); s += g[t]; }
-  Window w;
-  for (int t = 0; t < kTaps; ++t) w.g[t] = (float)(g[t] / s);
-  return w;
-}
-
-bool aligned(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
-
 bool supported(int n, int h, int w, int c) { return n >= 1 && h >= kTaps && w >= kTaps && c >= 1 && c <= kMaxC; }
 
 // the maps first (float32, rounded up to a multiple of 8 bytes), the float64 partials behind them
@@ -312,7 +215,7 @@ extern "C" {
 
 size_t acg_ssim_loss_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c) {
   if (!supported(n, h, w, c)) return 0;
-  const Plan pm = plan_for(n, h - kHalo, w - kHalo);
+  const Plan pm = loss_plan(n, h - kHalo, w - kHalo);
   return maps_bytes(n, h, w, c) + (size_t)n * pm.blocks_per_frame() * sizeof(double);
 }
 
@@ -325,7 +228,7 @@ int32_t acg_ssim_loss(const float* pred, const float* truth, float* value, float
   ACG_REQUIRE(value || dpred, ACG_ERR_INVALID_ARG, "ssim_loss: neither the value nor the gradient is asked for");
   ACG_REQUIRE(data_range > 0.f, ACG_ERR_INVALID_ARG, "ssim_loss: data_range must be positive");
   const int out_h = h - kHalo, out_w = w - kHalo;
-  const Plan pm = plan_for(n, out_h, out_w), pa = plan_for(n, h, w);
+  const Plan pm = loss_plan(n, out_h, out_w), pa = loss_plan(n, h, w);
   const long long nblk_m = (long long)n * pm.blocks_per_frame(), nblk_a = (long long)n * pa.blocks_per_frame();
   ACG_REQUIRE(nblk_m < (1LL << 31) && nblk_a < (1LL << 31), ACG_ERR_INVALID_ARG, "ssim_loss: %lld blocks", nblk_a);
   ACG_REQUIRE(workspace && aligned(workspace, 8) && ws_bytes >= acg_ssim_loss_workspace_bytes(n, h, w, c), ACG_ERR_WORKSPACE,

@@ -95,6 +95,21 @@ def test_channel_pitch_and_determinism(dt):
     assert torch.equal(s3, s5)
 
 
+@pytest.mark.parametrize('dt', [torch.float32, torch.bfloat16])
+def test_loader_paths_agree_to_the_bit(dt):
+    """The four cases of the row loader on one input.  (2, 23, 75, 3) is two strips, the second ragged; a row is 225 elements at
+    pitch 3 (scalar loads, unpitched), 300 at pitch 4 (vector loads, pitched) and 375 at pitch 5 (scalar loads, pitched); the
+    vector loader without a pitch is what every 64 x 64 x 3 case above runs."""
+    rng = np.random.default_rng(23)
+    x, y = _inputs('uniform', (2, 23, 75, 3), rng)
+    a, b = _stored(x, dt), _stored(y, dt)
+    s3, q3 = _check(a, b, ('pitch 3', dt))
+    for pitch in (4, 5):
+        pad = lambda t: torch.cat([t, torch.zeros(t.shape[:-1] + (pitch - 3,), dtype=t.dtype, device=t.device)], dim=-1).contiguous()   # noqa: E731
+        s, q = M.frame_metrics(pad(a), pad(b), channels=3)
+        assert torch.equal(s, s3) and torch.equal(q, q3), pitch
+
+
 def test_too_small_frames_raise():
     x = torch.zeros(2, 10, 64, 3, device=DEV)
     with pytest.raises(_lib.AcgError, match='smaller than the 11 x 11'):

@@ -15,6 +15,7 @@ import train_cases as TC
 from action_conditioned_gans_amd import _lib
 from action_conditioned_gans_amd import evaluate as E
 from action_conditioned_gans_amd import graph as G
+from action_conditioned_gans_amd import metrics as M
 from action_conditioned_gans_amd import ops as O
 from action_conditioned_gans_amd import optim
 from action_conditioned_gans_amd import train as T
@@ -125,6 +126,19 @@ def test_value_only_and_gradient_only_equal_the_combined_call(shape):
     none2, g_only = _call(ref['x'], ref['y'], value=False)
     assert none is None and none2 is None
     assert torch.equal(v_only, val) and torch.equal(g_only, dp)
+
+
+@pytest.mark.parametrize('shape', [(2, 33, 75, 3), (1, 21, 27, 4)], ids=str)
+def test_trained_ssim_is_the_reported_ssim(shape):
+    """The loss value against sum_n (1 - ssim_n) of frame_metrics on the same float32 frames: each side is held to float64 at
+    1e-5 per frame (VALUE_BAR above, SSIM_BAR in tests/test_gpu_eval.py), so the two are within the sum of the two bars."""
+    ref = _reference('smooth', shape)
+    val, _ = _call(ref['x'], ref['y'], grad=False)
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)   # noqa: E731
+    ssim, _ = M.frame_metrics(to_dev(ref['x']), to_dev(ref['y']))
+    reported = float((1.0 - ssim.double()).sum().item())
+    print('%s: loss value %.7f, from the metric %.7f' % (shape, float(val.item()), reported))
+    assert abs(float(val.item()) - reported) <= 2 * shape[0] * VALUE_BAR
 
 
 def test_invalid_arguments_are_errors():

@@ -1,5 +1,5 @@
 // Host stand-in for <hip/hip_runtime.h>: runs a kernel's blocks one after another, the threads of a block as real threads
-// that meet at a barrier for __syncthreads().  Only what csrc/ssim_loss.hip and csrc/common.h use.
+// that meet at a barrier for __syncthreads().  Only what csrc/ssim_loss.hip, csrc/ssim_window.h and csrc/common.h use.
 #pragma once
 #include <math.h>
 #include <pthread.h>
