@@ -47,75 +47,15 @@ __device__ __forceinline__ void conv16g_body(const ConvArgs& p, char* smem) {
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gsrc), 0, p.g_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dense), 0, p.d_bytes, 0x00020000);
 
-  // ---- geometry (as conv16_body) --------------------------------------------------------------------------------
-  const int Cin8 = (p.C + 7) & ~7, K8 = (p.K + 7) & ~7;
-  int M, N, Kdim, Cp, ntaps;
-  int ph = 0, pw = 0, i0 = 0, j0 = 0, nti = 1, ntj = 1, dp0 = 0, dq0 = 0, Hc = 0, Wc = 0;
-  if constexpr (MODE == MODE_FWD) {
-    Cp = Cin8; ntaps = p.KH * p.KW;
-    M = p.batch * p.OH * p.OW; N = p.K; Kdim = ntaps * Cp;
-  } else {
-    const int cls = blockIdx.y;
-    ph = cls / p.sw; pw = cls - ph * p.sw;
-    Hc = ph < p.H ? (p.H - ph + p.sh - 1) / p.sh : 0;
-    Wc = pw < p.W ? (p.W - pw + p.sw - 1) / p.sw : 0;
-    Cp = K8;
-    M = p.batch * Hc * Wc; N = p.C;
-    i0 = (ph + p.pt) % p.sh; j0 = (pw + p.pl) % p.sw;
-    nti = i0 < p.KH ? (p.KH - i0 + p.sh - 1) / p.sh : 0;
-    ntj = j0 < p.KW ? (p.KW - j0 + p.sw - 1) / p.sw : 0;
-    dp0 = (ph + p.pt - i0) / p.sh; dq0 = (pw + p.pl - j0) / p.sw;
-    ntaps = nti * ntj; Kdim = ntaps * Cp;
-  }
-  if (p.Nv > 0) N = p.Nv;
-  const int tiles_n = (N + GBN - 1) / GBN;
-  int bid = blockIdx.x;
-  {      // XCD-aware tile order: each XCD a contiguous run of tiles (bijective for any grid size)
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, slot = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  const int m0 = tm * GBM, n0 = tn * GBN;
-  if (m0 >= M) return;
-  const int nk = (Kdim + BKH - 1) / BKH;
-
-  // ---- tap tables and row infos -------------------------------------------------------------------------------------
-  if (tid < kMaxTaps && tid < ntaps) {
-    const int t = tid;
-    if constexpr (MODE == MODE_DGRAD) {
-      const int ti = t / ntj, tj = t - ti * ntj;
-      tapA[t] = -(ti * p.OW + tj) * K8;
-      tapB[t] = ((i0 + p.sh * ti) * p.KW + (j0 + p.sw * tj)) * p.C * K8;      // filter copy [tap][c][o8]
-    } else {
-      const int i = t / p.KW, j = t - i * p.KW;
-      const int u = p.tap_classes ? tap_class_pos(i, j, p.KH, p.KW) : t;      // position in the K order
-      tapA[u] = (i * p.W + j) * Cin8;
-      tapB[u] = t * p.K * Cin8;                                               // filter copy [tap][o][c8]
-    }
-  }
-  if (tid < GBM) {
-    RowInfo ri; ri.base = 0; ri.mask_lo = 0; ri.mask_hi = 0; ri.out_off = 0;
-    const int m = m0 + tid;
-    if (m < M) {
-      if constexpr (MODE == MODE_FWD) {
-        const int t2 = div_fast(m, p.mg_ow, p.sh_ow), q = m - t2 * p.OW;
-        const int b = div_fast(t2, p.mg_oh, p.sh_oh), pp = t2 - b * p.OH;
-        const int y0 = pp * p.sh - p.pt, x0 = q * p.sw - p.pl;
-        ri.base = ((b * p.H + y0) * p.W + x0) * Cin8;
-        const unsigned long long mk = p.tap_classes ? tap_mask_classes(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KH, p.KW)
-                                                    : tap_mask(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KW);
-        ri.mask_lo = (unsigned)mk; ri.mask_hi = (unsigned)(mk >> 32);
-      } else {
-        const int w2 = m % Wc; const int t2 = m / Wc; const int h2 = t2 % Hc; const int b = t2 / Hc;
-        const int y0 = h2 + dp0, x0 = w2 + dq0;
-        ri.base = ((b * p.OH + y0) * p.OW + x0) * K8;
-        ri.out_off = ((b * p.H + h2 * p.sh + ph) * p.W + (w2 * p.sw + pw)) * Cin8;
-        const unsigned long long mk = tap_mask(max(0, y0 - p.OH + 1), min(nti, y0 + 1), max(0, x0 - p.OW + 1), min(ntj, x0 + 1), ntj);
-        ri.mask_lo = (unsigned)mk; ri.mask_hi = (unsigned)(mk >> 32);
-      }
-    }
-    rows[tid] = ri;
-  }
+  // ---- geometry, tap tables and row infos (conv_tile.h) ------------------------------------------------------------------
+  using TR = Bf16Tensors<>;
+  const TileGeom g = tile_geometry<MODE, TR>(p, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x, GBM, GBN);
+  if (g.empty) return;
+  const int M = g.M, N = g.N, Cp = g.Cp, ntaps = g.ntaps;
+  const int tm = g.tm, m0 = g.m0, n0 = g.n0;
+  const int nk = (g.Kdim + BKH - 1) / BKH;
+  fill_taps<MODE, TR>(p, g, tapA, tapB, tid);
+  if (tid < GBM) rows[tid] = row_info<MODE, TR, false, false>(p, g, m0 + tid, M);
   __syncthreads();
 
   // ---- loader: wave w owns the 8-row chunks w, w + 8, ... of both tiles; lane -> (row chunk * 8 + lane / 8, slot lane & 7) --
@@ -304,62 +244,14 @@ __device__ __forceinline__ void conv16g_body(const ConvArgs& p, char* smem) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the two masked tail K-steps: nothing of ours may still write LDS
   __syncthreads();
 
-  // ---- epilogue (as conv16_body: bf16 activation at pitch round8, or float32 for a head layer; optional BatchNorm partials) --
+  // ---- epilogue (as conv16_body: bf16 activation at pitch round8, or float32 for a head layer; optional BatchNorm partials) ----
+  // never split, never the merged input gradient: the slab and shuffle layouts of store_tile are compiled out
   const bool to_bf16 = !p.out_f32;
   if (p.stats != nullptr) {
-    int g = 0, blk;
-    if constexpr (MODE == MODE_DGRAD) { blk = (int)blockIdx.y * p.stats_tpg + tm; } else { g = tm / p.stats_tpg; blk = tm - g * p.stats_tpg; }
     tile_stats_epilogue<GBM, GBN, WM, TA, TB>([&](int a, int b, int r) { return to_bf16 ? (float)(__bf16)acc[a][b][r] : acc[a][b][r]; }, reinterpret_cast<float*>(smem),
-                                              p.stats + ((long long)g * p.stats_nblk + blk) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
+                                              p.stats + stats_block<MODE>(p, (int)blockIdx.y, tm) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
   }
-  float* const outf = p.out;
-  __bf16* const outh = reinterpret_cast<__bf16*>(p.out);
-  const long long pitch = MODE == MODE_DGRAD ? Cin8 : K8;
-  if (m0 + GBM <= M) {
-    // full row tiles (every tile of the layers this kernel is planned for): straight-line stores, one base per 32 x 32
-    // sub-tile; a ragged last column tile only masks lanes
-#pragma unroll
-    for (int b = 0; b < TB; ++b) {
-      const int n = n0 + wn0 + 32 * b + lrow;
-      if (n < N) {
-#pragma unroll
-        for (int a = 0; a < TA; ++a) {
-          if constexpr (MODE == MODE_DGRAD) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const long long off = (long long)rows[wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk].out_off + n;
-              if (to_bf16) outh[off] = (__bf16)acc[a][b][r];
-              else outf[off] = acc[a][b][r];
-            }
-          } else {
-            const long long o = (long long)(m0 + wm0 + 32 * a + 4 * lk) * pitch + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const long long off = o + (long long)((r & 3) + 8 * (r >> 2)) * pitch;
-              if (to_bf16) outh[off] = (__bf16)acc[a][b][r];
-              else outf[off] = acc[a][b][r];
-            }
-          }
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int b = 0; b < TB; ++b) {
-    const int n = n0 + wn0 + 32 * b + lrow;
-    if (n >= N) continue;
-#pragma unroll
-    for (int a = 0; a < TA; ++a)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk;
-        if (m0 + row >= M) continue;
-        const long long off = (MODE == MODE_DGRAD ? (long long)rows[row].out_off : (long long)(m0 + row) * pitch) + n;
-        if (to_bf16) outh[off] = (__bf16)acc[a][b][r];
-        else outf[off] = acc[a][b][r];
-      }
-  }
+  store_tile<MODE, GBM, TA, TB, true>(acc, out_map<MODE, TR, false, false>(p, g), rows, p.out, to_bf16, wm0, wn0, lrow, lk);
 }
 
 template <int MODE, int VAR = 0>

@@ -61,90 +61,20 @@ __device__ __forceinline__ void conv16_body(const ConvArgs& p, const int bx, con
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gsrc), 0, p.g_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dense), 0, p.d_bytes, 0x00020000);
 
-  // ---- geometry (wave-uniform); Cp = channels of the gathered tensor = its pitch in memory (multiple of 8) ------
-  const int Cin8 = (p.C + 7) & ~7, K8 = (p.K + 7) & ~7;
-  int M, N, Kdim, Cp, ntaps;
-  int ph = 0, pw = 0, i0 = 0, j0 = 0, nti = 1, ntj = 1, dp0 = 0, dq0 = 0, Hc = 0, Wc = 0;
-  if constexpr (MODE == MODE_FWD) {
-    Cp = Cin8; ntaps = p.KH * p.KW;
-    M = p.batch * p.OH * p.OW; N = p.K; Kdim = ntaps * Cp;
-  } else if constexpr (MODE == MODE_DGRAD) {
-    const int cls = by;
-    ph = cls / p.sw; pw = cls - ph * p.sw;
-    Hc = ph < p.H ? (p.H - ph + p.sh - 1) / p.sh : 0;
-    Wc = pw < p.W ? (p.W - pw + p.sw - 1) / p.sw : 0;
-    Cp = K8;
-    M = p.batch * Hc * Wc; N = p.C;
-    i0 = (ph + p.pt) % p.sh; j0 = (pw + p.pl) % p.sw;
-    nti = i0 < p.KH ? (p.KH - i0 + p.sh - 1) / p.sh : 0;
-    ntj = j0 < p.KW ? (p.KW - j0 + p.sw - 1) / p.sw : 0;
-    dp0 = (ph + p.pt - i0) / p.sh; dq0 = (pw + p.pl - j0) / p.sw;
-    ntaps = nti * ntj; Kdim = ntaps * Cp;
-  } else {
-    Cp = Cin8; ntaps = p.KH * p.KW;
-    M = ntaps * Cp; N = p.K; Kdim = p.batch * p.OH * p.OW;
-  }
-  if (MODE != MODE_WGRAD && p.Nv > 0) N = p.Nv;      // only the first Nv output columns (acg_conv_desc dgrad_c / adj_dgrad_c)
-  const int tiles_n = (N + BN - 1) / BN;
-  int bid = bx;
-  if constexpr (MODE != MODE_WGRAD) {      // (weight gradients are placed by wgrad_xcd_map in the kernel wrappers)
-    const int nwg = gx, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, slot = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-  if (m0 >= M) return;
-
-  const int nk = (Kdim + BKH - 1) / BKH;
-  const int per = (nk + p.splits - 1) / p.splits;
-  const int ks_begin = bz * per;
-  const int ks_end = min(nk, ks_begin + per);
-
-  // ---- tap tables (element offsets) ------------------------------------------------------------
-  if (tid < kMaxTaps && tid < ntaps) {
-    const int t = tid;
-    if constexpr (MODE == MODE_DGRAD) {
-      const int ti = t / ntj, tj = t - ti * ntj;
-      tapA[t] = -(ti * p.OW + tj) * K8;
-      tapB[t] = ((i0 + p.sh * ti) * p.KW + (j0 + p.sw * tj)) * p.C * K8;      // filter copy [tap][c][o8]
-    } else {
-      const int i = t / p.KW, j = t - i * p.KW;
-      const int u = (MODE == MODE_FWD && p.tap_classes) ? tap_class_pos(i, j, p.KH, p.KW) : t;      // position in the K order
-      tapA[u] = (i * p.W + j) * Cin8;
-      tapB[u] = t * p.K * Cin8;                                               // filter copy [tap][o][c8] (FWD)
-    }
-  }
-
-  auto fill_row_fwd = [&](int r, int limit) -> RowInfo {
-    RowInfo ri; ri.base = 0; ri.mask_lo = 0; ri.mask_hi = 0; ri.out_off = 0;
-    if (r < limit) {
-      const int t2 = div_fast(r, p.mg_ow, p.sh_ow), q = r - t2 * p.OW;
-      const int b = div_fast(t2, p.mg_oh, p.sh_oh), pp = t2 - b * p.OH;
-      const int y0 = pp * p.sh - p.pt, x0 = q * p.sw - p.pl;
-      ri.base = ((b * p.H + y0) * p.W + x0) * Cin8;
-      if (p.shuf_c) ri.out_off = ((b * (2 * p.OH) + 2 * pp) * p.shuf_w + 2 * q) * p.shuf_pitch;     // merged input gradient (ConvArgs::shuf_c)
-      const unsigned long long m = (MODE == MODE_FWD && p.tap_classes) ? tap_mask_classes(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KH, p.KW)
-                                                                      : tap_mask(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KW);
-      ri.mask_lo = (unsigned)m; ri.mask_hi = (unsigned)(m >> 32);
-    }
-    return ri;
-  };
-  if constexpr (MODE == MODE_FWD) {
-    for (int r = tid; r < BM; r += 256) rows[r] = fill_row_fwd(m0 + r, M);
-  } else if constexpr (MODE == MODE_DGRAD) {
-    for (int r = tid; r < BM; r += 256) {
-      RowInfo ri; ri.base = 0; ri.mask_lo = 0; ri.mask_hi = 0; ri.out_off = 0;
-      const int m = m0 + r;
-      if (m < M) {
-        const int w2 = m % Wc; const int t2 = m / Wc; const int h2 = t2 % Hc; const int b = t2 / Hc;
-        const int y0 = h2 + dp0, x0 = w2 + dq0;
-        ri.base = ((b * p.OH + y0) * p.OW + x0) * K8;
-        ri.out_off = ((b * p.H + h2 * p.sh + ph) * p.W + (w2 * p.sw + pw)) * (EPI ? p.Cx : (p.slab_rows ? 4 : Cin8));      // EPI: dense float32 rows
-        const unsigned long long mk = tap_mask(max(0, y0 - p.OH + 1), min(nti, y0 + 1), max(0, x0 - p.OW + 1), min(ntj, x0 + 1), ntj);
-        ri.mask_lo = (unsigned)mk; ri.mask_hi = (unsigned)(mk >> 32);
-      }
-      rows[r] = ri;
-    }
+  // ---- geometry, tap tables (element offsets), per-row gather info (conv_tile.h) ------------------------------
+  // Cp = channels of the gathered tensor = its pitch in memory (a multiple of 8); the filter copies are [tap][o][c8] (FWD)
+  // and [tap][c][o8] (DGRAD)
+  using TR = Bf16Tensors<EPI>;
+  const TileGeom g = tile_geometry<MODE, TR>(p, bx, by, gx, BM, BN);
+  if (g.empty) return;
+  const int M = g.M, N = g.N, Kdim = g.Kdim, Cp = g.Cp, ntaps = g.ntaps;
+  const int tm = g.tm, m0 = g.m0, n0 = g.n0;
+  const int K8 = TR::y_pitch(p);
+  const KRange kr = split_range((Kdim + BKH - 1) / BKH, p.splits, bz);
+  const int ks_begin = kr.begin, ks_end = kr.end;
+  fill_taps<MODE, TR>(p, g, tapA, tapB, tid);
+  if constexpr (MODE != MODE_WGRAD) {
+    for (int r = tid; r < BM; r += 256) rows[r] = row_info<MODE, TR, false>(p, g, m0 + r, M);
   }
   __syncthreads();
 
@@ -338,7 +268,7 @@ __device__ __forceinline__ void conv16_body(const ConvArgs& p, const int bx, con
 
   // WGRAD row infos: 4 K-steps (256 pixel rows, one per thread) per chunk, two chunks resident
   auto wgrad_rows = [&](int chunk) {
-    if constexpr (MODE == MODE_WGRAD) rows[(chunk & 1) * 256 + tid] = fill_row_fwd((ks_begin + 4 * chunk) * BKH + tid, Kdim);
+    if constexpr (MODE == MODE_WGRAD) rows[(chunk & 1) * 256 + tid] = row_info<MODE, TR, false>(p, g, (ks_begin + 4 * chunk) * BKH + tid, Kdim);
   };
 
   if (ks_begin < ks_end) {
@@ -401,107 +331,16 @@ __device__ __forceinline__ void conv16_body(const ConvArgs& p, const int bx, con
     }
   }
   if constexpr (MODE != MODE_WGRAD) {
-    if (p.stats != nullptr) {     // BatchNorm statistics of this tile, of the bf16 values as stored (ConvArgs::stats, conv_f32_kernel.h)
-      int g = 0, blk;
-      if constexpr (MODE == MODE_DGRAD) { blk = by * p.stats_tpg + tm; } else { g = tm / p.stats_tpg; blk = tm - g * p.stats_tpg; }
+    if (p.stats != nullptr) {     // BatchNorm statistics of this tile, of the bf16 values as stored (ConvArgs::stats, conv_tile.h)
       tile_stats_epilogue<BM, BN, WM, TA, TB>([&](int a, int b, int r) { return to_bf16 ? (float)(__bf16)acc[a][b][r] : acc[a][b][r]; }, reinterpret_cast<float*>(smem),
-                                              p.stats + ((long long)g * p.stats_nblk + blk) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
+                                              p.stats + stats_block<MODE>(p, by, tm) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
     }
   }
   float* const outf = p.out + (p.splits > 1 ? (long long)bz * p.out_numel : 0ll);
-  __bf16* const outh = reinterpret_cast<__bf16*>(p.out);
-  if constexpr (MODE != MODE_WGRAD) {
-    // (A packed variant - neighbouring lanes trade registers over DPP so that each stores 4 bytes, half the store
-    // instructions - measured SLOWER in the same session: conv stack of config 5 2246 vs 2088 us, of config 3 908 vs 864 us,
-    // profiles/r2/c_epilogue_ab.txt; the plain 2-byte stores below stay.)
-  }
-  // Full tiles - all of them in the layers that matter - take a straight-line path: one base pointer per 32 x 32 sub-tile,
-  // sixteen stores at row strides, no per-element bounds test, branch or 64-bit index multiply.  (The general loop below
-  // costs ~1600 instructions and ~190 branches per thread on a 128 x 128 tile: 4.8 us of an 8.7 us one-K-step launch,
-  // tools/fixed_cost_probe.py.)
-  // (rows full; a ragged last column tile - 25 or 121 output channels - only masks lanes, once per 32-column sub-tile)
-  const bool full = m0 + BM <= M && (MODE != MODE_WGRAD || (Cp == p.C && !(p.splits == 1 && p.accumulate != 0.f)));
-  // column term of an element's offset: n, or in the quad slab layout (ConvArgs::slab_rows; float32 slabs only) the quad's
-  // run of rows + n & 3
-  const bool quads = MODE != MODE_WGRAD && p.slab_rows > 0;
-  const bool shuf = MODE == MODE_FWD && p.shuf_c > 0;      // merged input gradient: rows by their out_off, columns by (2 x 2 pixel, channel)
-  auto col_off = [&](int n) -> long long {
-    if (shuf) { const int cls = n / p.shuf_c; return (long long)((cls >> 1) * p.shuf_w + (cls & 1)) * p.shuf_pitch + (n - cls * p.shuf_c); }
-    return quads ? (long long)(n >> 2) * p.slab_rows * 4 + (n & 3) : (long long)n;
-  };
-  if (full) {
-    auto store_rows = [&](auto* base, long long pitch, int a, int b) {
-      using T = std::remove_pointer_t<decltype(base)>;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) base[(long long)((r & 3) + 8 * (r >> 2)) * pitch] = (T)acc[a][b][r];
-    };
-    if (MODE == MODE_DGRAD || shuf) {
-#pragma unroll
-      for (int b = 0; b < TB; ++b) {
-        if (n0 + wn0 + 32 * b + lrow < N) {
-          const long long co = col_off(n0 + wn0 + 32 * b + lrow);
-#pragma unroll
-          for (int a = 0; a < TA; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const long long off = rows[wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk].out_off + co;
-              if (to_bf16) outh[off] = (__bf16)acc[a][b][r];
-              else outf[off] = acc[a][b][r];
-            }
-        }
-      }
-    } else {
-      const long long pitch = MODE == MODE_WGRAD ? N : (quads ? 4 : K8);
-#pragma unroll
-      for (int b = 0; b < TB; ++b) {
-        if (n0 + wn0 + 32 * b + lrow < N) {
-#pragma unroll
-          for (int a = 0; a < TA; ++a) {
-            const long long o = (long long)(m0 + wm0 + 32 * a + 4 * lk) * pitch + col_off(n0 + wn0 + 32 * b + lrow);
-            if (to_bf16) store_rows(outh + o, pitch, a, b);
-            else store_rows(outf + o, pitch, a, b);
-          }
-        }
-      }
-    }
-    return;
-  }
-  // partial row tiles (the last tile of a weight gradient whose taps x channels is no multiple of the tile; tiny layers): per
-  // ROW one validity test and one base index (the weight gradient's division by the padded channel count included), per
-  // element only the column mask
-  const bool acc_out = MODE == MODE_WGRAD && p.splits == 1 && p.accumulate != 0.f;
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk;
-      const int m = m0 + row;
-      if (m >= M) continue;
-      long long base;
-      if (MODE == MODE_DGRAD || shuf) {
-        base = rows[row].out_off;
-      } else if constexpr (MODE == MODE_WGRAD) {
-        const int t = div_fast(m, p.mg_cp, p.sh_cp), c = m - t * Cp;
-        if (c >= p.C) continue;
-        base = ((long long)t * p.C + c) * N;
-      } else {
-        base = (long long)m * (quads ? 4 : K8);
-      }
-#pragma unroll
-      for (int b = 0; b < TB; ++b) {
-        const int n = n0 + wn0 + 32 * b + lrow;
-        if (n < N) {
-          const long long o = base + col_off(n);
-          float v = acc[a][b][r];
-          if (MODE == MODE_WGRAD || !to_bf16) {
-            if (acc_out) v += p.accumulate * outf[o];
-            outf[o] = v;
-          } else {
-            outh[o] = (__bf16)v;
-          }
-        }
-      }
-    }
+  // (A packed variant - neighbouring lanes trade registers over DPP so that each stores 4 bytes, half the store
+  // instructions - measured SLOWER in the same session: conv stack of config 5 2246 vs 2088 us, of config 3 908 vs 864 us,
+  // profiles/r2/c_epilogue_ab.txt; the plain 2-byte stores of store_tile stay.)
+  store_tile<MODE, BM, TA, TB, MODE != MODE_WGRAD>(acc, out_map<MODE, TR, false>(p, g), rows, outf, to_bf16, wm0, wn0, lrow, lk);
 }
 
 template <int MODE, int BM, int BN, bool EPI = false>

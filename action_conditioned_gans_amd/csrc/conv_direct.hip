@@ -13,7 +13,8 @@
 // Round 1's direct kernel (one output per 8-lane group, a serial chain of dependent loads: 73-129 us) was the wrong shape,
 // not the wrong idea.  float32 only: the bf16 tiled path does not split these layers and already runs them in ~5 us, and
 // with 16 output channels (g/sconv4) a lane's strided loads make the launch latency-bound (profiles/r3/d_direct_small_convs.txt).
-#include "conv_bf16_kernel.h"
+#include "common.h"
+#include "conv_tile.h"
 
 namespace acgconv {
 

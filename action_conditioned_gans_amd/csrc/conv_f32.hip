@@ -330,7 +330,7 @@ Plan make_plan(const acg_conv_desc& d, int which, bool bf16 = false, bool wide_o
   s = std::max<long long>(s, 1);
   if (!bf16 && which != ACG_CONV_WGRAD && pl.tiles * s <= 256 && pl.nk / s >= 50) s *= pl.nk / s >= 100 ? 4 : 2;
   // Weight gradients: every output tile of one K range gathers the SAME pixels (at its own taps), so the blocks of a split
-  // are placed on ONE XCD and share that range in its L2 (wgrad_xcd_map, conv_f32_kernel.h) - which needs the split count
+  // are placed on ONE XCD and share that range in its L2 (wgrad_xcd_map, conv_tile.h) - which needs the split count
   // to be a multiple of the 8 XCDs.
   static const int xcd_splits = env_int("ACG_PLAN_WGRAD_XCD", 1);
   if (xcd_splits && bf16 && which == ACG_CONV_WGRAD && s >= 6 && (s + 7) / 8 * 8 <= pl.nk) s = (s + 7) / 8 * 8;   // (fp32: the swept split counts stay - rounding them cost 1.3 % of the step)
@@ -409,40 +409,25 @@ int prepare(Job& j, int which, const float* gsrc, const float* dense, float* out
     const long long nd = which == ACG_CONV_WGRAD ? ny : nw;                       // dense operand
     a.g_bytes = (unsigned)(ng * 4); a.d_bytes = (unsigned)(nd * 4);
   }
-  a.Cx = d->in_pitch > 0 ? d->in_pitch : d->in_c;
-  a.Ky = d->out_pitch > 0 ? d->out_pitch : d->out_c;
-  a.batch = d->batch; a.H = d->in_h; a.W = d->in_w; a.C = d->in_c; a.OH = d->out_h; a.OW = d->out_w; a.K = d->out_c;
-  a.KH = d->kh; a.KW = d->kw; a.sh = d->stride_h; a.sw = d->stride_w; a.pt = d->pad_top; a.pl = d->pad_left;
   a.splits = pl.splits;
-  a.Nv = which == ACG_CONV_DGRAD ? d->dgrad_c : (which == ACG_CONV_FWD ? d->adj_dgrad_c : 0);
   {     // bf16 forward / input gradient with 128 or more gathered channels in whole 64-channel chunks: chunk-major K order (option)
     static const int korder = env_int("ACG_CONV16_KORDER", 0);      // measured level (c5 +0.4 %, c3 -0.3 %, profiles/r4/f_korder_ab.txt): off; tuning builds can switch it on
     const int cp = which == ACG_CONV_DGRAD ? cout8 : cin8;
     a.korder = (h && which != ACG_CONV_WGRAD && korder && cp >= 128 && cp % 64 == 0) ? 1 : 0;
   }
-  {     // strided forward convolutions walk their taps class by class (conv_f32_kernel.h, tap_class_pos): the L2 then holds a tile's window
-    static const int tap_classes = env_int("ACG_CONV_TAP_CLASSES", 0);      // tuning hook: bit 0 bf16, bit 1 float32; measured: K-loop of a 5x5 / stride-2 forward -10 % at >= 128 channels, whole steps level (profiles/r4/h_bf16_kloop_load_path.txt): off
-    a.tap_classes = ((tap_classes & (h ? 1 : 2)) && which == ACG_CONV_FWD && d->stride_h == 2 && d->stride_w == 2 && d->kh * d->kw > 1 && d->kh * d->kw <= 64) ? 1 : 0;
-  }
-  // small maps: pixel-major rows + only the taps a tile's rows can see (ConvArgs::compact); not with epilogue statistics,
-  // whose partial blocks are runs of rows of one group
-  // measured: pays only where more than half of the taps are dead (a 4 x 4 map under a 5 x 5 / stride-2 filter: d/conv5) - from
-  // 16 pixels per class on, what the pixel-major order loses in gather reuse inside a tile eats the skipped K-steps
-  static const int compact_max = env_int("ACG_PLAN_COMPACT", 4);
-  {
-    const int hc = (d->in_h + d->stride_h - 1) / d->stride_h, wc = (d->in_w + d->stride_w - 1) / d->stride_w;
-    const int px = which == ACG_CONV_DGRAD ? hc * wc : d->out_h * d->out_w;
-    a.compact = (which != ACG_CONV_WGRAD && !h && stats == nullptr && !pl.direct && px <= compact_max && d->batch >= 8 && d->kh * d->kw > 1) ? 1 : 0;
-  }
   if (slab_layout != ACG_SLABS_ROWS) {      // slabs for the layer's BatchNorm in the layout its one-launch kernels read (acgan_hip.h)
     const long long orows = which == ACG_CONV_DGRAD ? (long long)d->batch * d->in_h * d->in_w : (long long)d->batch * d->out_h * d->out_w;
-    const int oc = which == ACG_CONV_DGRAD ? d->in_c : d->out_c, opitch = which == ACG_CONV_DGRAD ? (h ? cin8 : a.Cx) : (h ? cout8 : a.Ky);
+    const int oc = which == ACG_CONV_DGRAD ? d->in_c : d->out_c, xp = d->in_pitch > 0 ? d->in_pitch : d->in_c, yp = d->out_pitch > 0 ? d->out_pitch : d->out_c;
+    const int opitch = which == ACG_CONV_DGRAD ? (h ? cin8 : xp) : (h ? cout8 : yp);
     ACG_REQUIRE(slab_layout == ACG_SLABS_QUADS && slabs_only && which != ACG_CONV_WGRAD, ACG_ERR_INVALID_ARG, "%s: slab layout %d", who, slab_layout);
     ACG_REQUIRE(((oc + 3) & ~3) <= opitch && orows * 4 < (1ll << 31), ACG_ERR_UNSUPPORTED, "%s: the quad slab layout needs round4(channels) <= pitch", who);
-    a.slab_rows = (int)orows;
   }
-  { const FastDiv fw = fast_div(d->out_w), fh = fast_div(d->out_h); a.mg_ow = fw.magic; a.sh_ow = fw.shift; a.mg_oh = fh.magic; a.sh_oh = fh.shift;
-    const FastDiv fc = fast_div(which == ACG_CONV_DGRAD ? (h ? cout8 : (d->out_c + 3) & ~3) : (h ? cin8 : (d->in_c + 3) & ~3)); a.mg_cp = fc.magic; a.sh_cp = fc.shift; }
+  // The geometry fields (conv_tile.h).  Strided forward convolutions can walk their taps class by class (tap_class_pos: the L2
+  // then holds a tile's window) - a tuning hook: bit 0 bf16, bit 1 float32; measured: K-loop of a 5x5 / stride-2 forward -10 % at
+  // >= 128 channels, whole steps level (profiles/r4/h_bf16_kloop_load_path.txt): off.  Small maps: pixel-major rows + only the
+  // taps a tile's rows can see (ConvArgs::compact); not with epilogue statistics, whose partial blocks are runs of rows of one group
+  static const int tap_classes = env_int("ACG_CONV_TAP_CLASSES", 0), compact_max = env_int("ACG_PLAN_COMPACT", 4);
+  fill_geometry(a, *d, which, h, GeomFlags{(stats == nullptr && !pl.direct) ? compact_max : 0, (tap_classes & (h ? 1 : 2)) != 0, slab_layout != ACG_SLABS_ROWS});
   if (stats != nullptr) {
     int tpg = 0;
     const int nblk = stats_blocks(pl, *d, which, stats_groups, &tpg);

@@ -7,9 +7,9 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace acgconv {
-
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -17,8 +17,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
-enum { MODE_FWD = 0, MODE_DGRAD = 1, MODE_WGRAD = 2 };
 
 // f(0), f(1), ... f(N-1) while f returns true; false as soon as one call does
 template <int I, int N, class F>
@@ -39,130 +37,6 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 constexpr int BK = 32;  // k per K-step = 8 quads
-constexpr int kMaxTaps = 64;
-
-struct ConvArgs {
-  const float* gsrc;   // gathered tensor: x (FWD, WGRAD) or dy (DGRAD)
-  const float* dense;  // w (FWD, DGRAD) or dy (WGRAD)
-  float* out;          // final tensor (splits == 1) or `splits` slabs of out_numel floats
-  long long out_numel;
-  unsigned g_bytes, d_bytes;   // sizes of gsrc / dense for the buffer descriptors (hardware range check)
-  float accumulate;    // WGRAD with splits == 1: out = accumulate * out + value
-  int batch, H, W, C, OH, OW, K, KH, KW, sh, sw, pt, pl;
-  int Cx;              // channel pitch of x / dx in memory (>= C)
-  int Ky;              // channel pitch of y / dy in memory (>= K)
-  int splits;
-  unsigned mg_ow, mg_oh, mg_cp;   // magic multipliers: r / OW = (r * mg_ow) >> sh_ow for 0 <= r < 2^31 (host: fast_div)
-  int sh_ow, sh_oh, sh_cp;        // _cp: division by the gathered channel count padded to a multiple of 4
-  // FWD / DGRAD with splits == 1, optional: the layer's BatchNorm statistics out of the epilogue.  Each block leaves the
-  // per-channel SUM of ITS tile rows (of the values as stored) and their sum of squared deviations from the tile's own
-  // mean (M2) at stats[((g * stats_nblk + b) * 2 + {0: sum, 1: M2}) * N + n]; bn.hip merges the tiles (tile_stats below);
-  // FWD: g = tile_row / stats_tpg, b = tile_row % stats_tpg; DGRAD (one group): b = class * stats_tpg + tile_row.
-  float* stats;
-  int stats_nblk, stats_tpg;
-  // FWD / DGRAD slabs (splits > 1) handed to the layer's BatchNorm: 0 = each slab [rows][pitch] like the tensor; > 0 = the
-  // ACG_SLABS_QUADS layout [channels / 4][slab_rows][4] (slab_rows = all rows of the tensor), element (m, n) at
-  // ((n >> 2) * slab_rows + m) * 4 + (n & 3)
-  int slab_rows;
-  // FWD launched as the merged input gradient of a stride-2 layer with few input channels (conv_f32.hip run_merged): the N =
-  // 4 * shuf_c output columns of pixel (b, p, q) are the shuf_c channels of the 2 x 2 output pixels (2p + ph, 2q + pw) of a
-  // tensor that is shuf_w pixels wide at the channel pitch shuf_pitch; column n = (2 ph + pw) * shuf_c + c.  0 = off.
-  int shuf_c, shuf_w, shuf_pitch;
-  // Small maps (DGRAD; conv_f32.hip prepare): rows are ordered pixel-major - m = pixel * batch + b, so a tile covers one or
-  // two pixels over the batch - and the tile walks only the taps ANY of its rows can see: on a 4 x 4 map half the taps of a
-  // 5 x 5 filter fall into the padding for every row of such a tile, and their K-steps would multiply zeros.
-  int compact;
-  int Nv;              // FWD / DGRAD: only the first Nv output columns are computed (acg_conv_desc dgrad_c / adj_dgrad_c); 0 = all
-  int tap_classes;     // FWD, stride > 1: 1 = the taps are walked class by class (tap_class_pos below); 0 = row-major
-  int korder;          // bf16 kernels, FWD / DGRAD, gathered channels a multiple of 64: 1 = K-steps walk the taps of one 64-channel chunk
-                       // before the next chunk (0: all channels of a tap before the next tap) - conv_bf16_kernel.h
-  int out_f32;         // bf16 kernels, FWD / DGRAD: the result is stored as float32 (at the bf16 tensor's pitch, round8): a head layer
-  // EPI kernel variants only (acg_deconv2d_fwd_bias_act): out = act(acc + bias[n]), stored as float32 at the pitch Cx
-  const float* bias;
-  int act;
-  float leak;
-};
-
-// Division by a launch-constant through multiply-high (Granlund-Montgomery, N = 31): a runtime integer division is
-// ~40 VALU instructions on this ISA, and WGRAD derives 32 gather rows per K-step.
-struct FastDiv { unsigned magic; int shift; };
-static inline FastDiv fast_div(int d) {
-  int s = 0;
-  while ((1ll << s) < d) ++s;
-  const unsigned long long num = 1ull << (31 + s);
-  return FastDiv{(unsigned)((num + (unsigned long long)d - 1) / (unsigned long long)d), 31 + s};
-}
-__device__ __forceinline__ int div_fast(int r, unsigned magic, int shift) {
-  return (int)(((unsigned long long)(unsigned)r * magic) >> shift);
-}
-
-// Weight-gradient blocks: block l of gx * splits (x fastest) -> (tile, split).  The hardware deals workgroups round-robin
-// over the 8 XCDs in dispatch order, so blocks l, l+8, l+16 ... share an XCD; all gx tiles of one split read the same
-// pixel range of both operands (each at its own filter taps): give them to ONE XCD, so that range comes out of HBM / the
-// Infinity Cache once instead of once per XCD (measured: g/tconv4's pair at 128x128 fetched 878 MB per launch, 6x its
-// operands).  Splits that are not a multiple of 8 keep the plain order.  Placement only: results do not change.
-__device__ __forceinline__ void wgrad_xcd_map(int l, int gx, int splits, int& tile, int& split) {
-  if ((splits & 7) == 0) {
-    const int x8 = l & 7, q = l >> 3, grp = q / gx;
-    tile = q - grp * gx;
-    split = grp * 8 + x8;
-  } else {
-    split = l / gx;
-    tile = l - split * gx;
-  }
-}
-
-struct alignas(16) RowInfo {
-  int base;            // element offset of the row's (tap 0, channel 0) source element (may be virtual)
-  unsigned mask_lo, mask_hi;  // bit t set <=> filter tap t reads inside the tensor
-  int out_off;         // DGRAD: element offset of the output pixel; unused otherwise
-};
-
-__device__ __forceinline__ unsigned long long tap_mask(int lo_a, int hi_a, int lo_b, int hi_b, int nb) {
-  // bits (a * nb + b) for a in [lo_a, hi_a), b in [lo_b, hi_b)
-  if (hi_a <= lo_a || hi_b <= lo_b) return 0ull;
-  const unsigned long long row = ((1ull << (hi_b - lo_b)) - 1ull) << lo_b;
-  unsigned long long m = 0ull;
-  for (int a = lo_a; a < hi_a; ++a) m |= row << (a * nb);
-  return m;
-}
-
-// Class-major tap order of a STRIDED forward convolution (ConvArgs::tap_classes).  Tap (i, j) of a stride-(sh, sw) conv reads
-// the input lattice (y = sh * p + i - pt, x = sw * q + j - pl): taps with equal (i % sh, j % sw) read the SAME sub-lattice of the
-// input, shifted by whole output pixels, and taps of different classes read DISJOINT sub-lattices.  In row-major order the taps
-// that share a cache line are up to two filter rows (10 K-steps x channel chunks x every tile running on the XCD) apart: the
-// vertical re-use misses the 4 MB L2 and every input byte is fetched from the memory side ~3.5 times (TCC_MISS 36 % of the
-// K-loop's requests, profiles/r4/h_bf16_kloop_load_path.txt).  Walking one class after the other keeps a tile on one sub-lattice - its
-// window / (sh * sw), 43 KB for a 256-row tile of 64 channels - for all of the class's taps; it is a permutation of the K index
-// only (tap tables and row masks are built in that order), so results differ by summation order alone.
-// Built for stride 2 x 2 (every strided layer of the reference's models): class (a, b) = (i & 1, j & 1), na(a) x nb(b) taps each.
-__device__ __forceinline__ int tap_class_pos(int i, int j, int KH, int KW) {
-  const int a = i & 1, b = j & 1;
-  const int na0 = (KH + 1) >> 1, nb0 = (KW + 1) >> 1;
-  const int na = a ? KH >> 1 : na0, nb = b ? KW >> 1 : nb0;
-  return (a ? na0 * KW : 0) + (b ? na * nb0 : 0) + (i >> 1) * nb + (j >> 1);
-}
-__device__ __forceinline__ unsigned long long tap_mask_classes(int lo_i, int hi_i, int lo_j, int hi_j, int KH, int KW) {
-  // the rectangle [lo_i, hi_i) x [lo_j, hi_j) of taps is a rectangle of (ti, tj) in each of the four classes
-  unsigned long long m = 0ull;
-  const int na0 = (KH + 1) >> 1, nb0 = (KW + 1) >> 1;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int na = a ? KH >> 1 : na0, nb = b ? KW >> 1 : nb0;
-      const int base = (a ? na0 * KW : 0) + (b ? na * nb0 : 0);
-      m |= tap_mask(max(0, (lo_i - a + 1) >> 1), max(0, (hi_i - a + 1) >> 1), max(0, (lo_j - b + 1) >> 1), max(0, (hi_j - b + 1) >> 1), nb) << base;
-    }
-  return m;
-}
-
-// 32-bit operations only: 64-bit shifts and compares are quarter-rate on the VALU, and a wave's VALU work does NOT
-// hide behind its own MFMAs (tools/conv_kloop.py experiments in profiles/), so every instruction in the K-loop counts
-__device__ __forceinline__ bool tap_ok(const RowInfo& ri, int t) {
-  const unsigned w = t < 32 ? ri.mask_lo : ri.mask_hi;
-  return (w >> (t & 31)) & 1u;
-}
 
 // Branch-free guarded loads through buffer descriptors.  A divergent `if (ok) load` makes hipcc wait for every
 // load inside its branch (vmcnt(0) per load: the loads of a K-step serialise), and selecting the loaded VALUE
@@ -171,7 +45,6 @@ __device__ __forceinline__ bool tap_ok(const RowInfo& ri, int t) {
 // and the load returns zeros without touching memory.  One v_cndmask on a 32-bit offset per load, no 64-bit
 // pointer arithmetic, and every load of a stage issues back to back; the first wait is NST-1 K-steps later.
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
-constexpr unsigned kOob = 0xFFFFFF00u;   // >= any num_records (tensors are < 2^30 elements)
 
 __device__ __forceinline__ f4 guarded_quad(__amdgpu_buffer_rsrc_t rs, int elem_off, bool ok) {
   const unsigned off = ok ? (unsigned)elem_off * 4u : kOob;
@@ -316,138 +189,24 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gsrc), 0, p.g_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dense), 0, p.d_bytes, 0x00020000);
 
-  // ---- problem geometry (wave-uniform) -------------------------------------------------------
-  // Cs: channels of the gathered tensor; Cp: Cs padded to a multiple of 4 (quad granularity per tap).
-  int M, N, Kdim, Cs, Cp, ntaps;
-  int ph = 0, pw = 0, i0 = 0, j0 = 0, nti = 1, ntj = 1, dp0 = 0, dq0 = 0, Hc = 0, Wc = 0;
-  if constexpr (MODE == MODE_FWD) {
-    Cs = p.C; Cp = (Cs + 3) & ~3; ntaps = p.KH * p.KW;
-    M = p.batch * p.OH * p.OW; N = p.K; Kdim = ntaps * Cp;
-  } else if constexpr (MODE == MODE_DGRAD) {
-    const int cls = by;
-    ph = cls / p.sw; pw = cls - ph * p.sw;
-    Hc = ph < p.H ? (p.H - ph + p.sh - 1) / p.sh : 0;
-    Wc = pw < p.W ? (p.W - pw + p.sw - 1) / p.sw : 0;
-    Cs = p.K; Cp = (Cs + 3) & ~3;
-    M = p.batch * Hc * Wc; N = p.C;
-    i0 = (ph + p.pt) % p.sh; j0 = (pw + p.pl) % p.sw;
-    nti = i0 < p.KH ? (p.KH - i0 + p.sh - 1) / p.sh : 0;
-    ntj = j0 < p.KW ? (p.KW - j0 + p.sw - 1) / p.sw : 0;
-    dp0 = (ph + p.pt - i0) / p.sh; dq0 = (pw + p.pl - j0) / p.sw;
-    ntaps = nti * ntj; Kdim = ntaps * Cp;
-  } else {
-    Cs = p.C; Cp = (Cs + 3) & ~3; ntaps = p.KH * p.KW;
-    M = ntaps * Cp; N = p.K; Kdim = p.batch * p.OH * p.OW;
-  }
-  // NS: floats between two rows of the dense operand (FWD: filter rows W[(tap, c)][0..K)); N: the columns computed
-  const int NS = MODE == MODE_FWD ? p.K : N;
-  if (MODE != MODE_WGRAD && p.Nv > 0) N = p.Nv;
-  const int tiles_n = (N + BN - 1) / BN;
-  // XCD-aware order: consecutive workgroup ids are dealt round-robin over the 8 XCDs (each with its own L2), so
-  // give every XCD a CONTIGUOUS run of tiles - neighbours in the run share A rows / filter columns in that L2.
-  // Bijective for any grid size; placement affects speed only.
-  int bid = bx;
-  if constexpr (MODE != MODE_WGRAD) {      // (weight gradients are placed by wgrad_xcd_map in the kernel wrappers)
-    const int nwg = gx, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, slot = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-  if (m0 >= M) return;  // block-uniform: DGRAD classes smaller than class 0
-
-  int nk = (Kdim + BK - 1) / BK;
-  int per = (nk + p.splits - 1) / p.splits;
-  int ks_begin = bz * per;
-  int ks_end = min(nk, ks_begin + per);
-
-  // ---- tap tables ------------------------------------------------------------------------------
-  if (tid < kMaxTaps && tid < ntaps) {
-    const int t = tid;
-    if constexpr (MODE == MODE_DGRAD) {
-      const int ti = t / ntj, tj = t - ti * ntj;
-      tapA[t] = -(ti * p.OW + tj) * p.Ky;
-      tapB[t] = ((i0 + p.sh * ti) * p.KW + (j0 + p.sw * tj)) * p.C * p.K;
-    } else {
-      const int i = t / p.KW, j = t - i * p.KW;
-      const int u = (MODE == MODE_FWD && p.tap_classes) ? tap_class_pos(i, j, p.KH, p.KW) : t;      // position in the K order
-      tapA[u] = (i * p.W + j) * p.Cx;
-      tapB[u] = MODE == MODE_FWD ? t * p.C * p.K : 0;      // FWD: first filter row of the tap (the table-driven dense rows below)
-    }
-  }
-
-  // ---- per-row gather info -------------------------------------------------------------------
-  auto fill_row_fwd = [&](int r /* global row (b,p,q) */, int limit) -> RowInfo {
-    RowInfo ri; ri.base = 0; ri.mask_lo = 0; ri.mask_hi = 0; ri.out_off = 0;
-    if (r < limit) {
-      int q, b, pp;
-      if (MODE == MODE_FWD && p.compact) { b = r % p.batch; const int px = r / p.batch; q = px % p.OW; pp = px / p.OW; }    // pixel-major rows
-      else { const int t2 = div_fast(r, p.mg_ow, p.sh_ow); q = r - t2 * p.OW; b = div_fast(t2, p.mg_oh, p.sh_oh); pp = t2 - b * p.OH; }
-      const int y0 = pp * p.sh - p.pt, x0 = q * p.sw - p.pl;
-      ri.base = ((b * p.H + y0) * p.W + x0) * p.Cx;
-      if (p.shuf_c) ri.out_off = ((b * (2 * p.OH) + 2 * pp) * p.shuf_w + 2 * q) * p.shuf_pitch;
-      else if (MODE == MODE_FWD && p.compact) ri.out_off = ((b * p.OH + pp) * p.OW + q) * (p.slab_rows ? 4 : p.Ky);
-      const unsigned long long m = (MODE == MODE_FWD && p.tap_classes) ? tap_mask_classes(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KH, p.KW)
-                                                                      : tap_mask(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KW);
-      ri.mask_lo = (unsigned)m; ri.mask_hi = (unsigned)(m >> 32);
-    }
-    return ri;
-  };
-  if constexpr (MODE == MODE_FWD) {
-    for (int r = tid; r < BM; r += 256) rows[r] = fill_row_fwd(m0 + r, M);
-  } else if constexpr (MODE == MODE_DGRAD) {
-    for (int r = tid; r < BM; r += 256) {
-      RowInfo ri; ri.base = 0; ri.mask_lo = 0; ri.mask_hi = 0; ri.out_off = 0;
-      const int m = m0 + r;
-      if (m < M) {
-        int w2, h2, b;
-        if (p.compact) { b = m % p.batch; const int pq = m / p.batch; w2 = pq % Wc; h2 = pq / Wc; }     // pixel-major rows
-        else { w2 = m % Wc; const int t2 = m / Wc; h2 = t2 % Hc; b = t2 / Hc; }
-        const int y0 = h2 + dp0, x0 = w2 + dq0;  // dY coordinates of tap (0,0)
-        ri.base = ((b * p.OH + y0) * p.OW + x0) * p.Ky;
-        ri.out_off = ((b * p.H + h2 * p.sh + ph) * p.W + (w2 * p.sw + pw)) * (p.slab_rows ? 4 : p.Cx);
-        // tap (ti,tj) reads dY[y0 - ti][x0 - tj]
-        const unsigned long long mk = tap_mask(max(0, y0 - p.OH + 1), min(nti, y0 + 1), max(0, x0 - p.OW + 1), min(ntj, x0 + 1), ntj);
-        ri.mask_lo = (unsigned)mk; ri.mask_hi = (unsigned)(mk >> 32);
-      }
-      rows[r] = ri;
-    }
+  // ---- problem geometry, tap tables, per-row gather info (conv_tile.h) ---------------------------------
+  constexpr bool COMPACT = MODE != MODE_WGRAD;      // small maps: pixel-major rows, dead taps dropped (ConvArgs::compact)
+  TileGeom g = tile_geometry<MODE, F32Tensors>(p, bx, by, gx, BM, BN);
+  if (g.empty) return;  // block-uniform: DGRAD classes smaller than class 0
+  fill_taps<MODE, F32Tensors>(p, g, tapA, tapB, tid);
+  if constexpr (MODE != MODE_WGRAD) {
+    for (int r = tid; r < BM; r += 256) rows[r] = row_info<MODE, F32Tensors, COMPACT>(p, g, g.m0 + r, g.M);
   }
   __syncthreads();
-  if constexpr (MODE != MODE_WGRAD) {
-    if (p.compact) {      // block-uniform.  Keep only the taps a row of this tile can see: tap tables and row masks in compact order.
-      __shared__ unsigned umask[2];
-      if (tid < 2) umask[tid] = 0u;
-      __syncthreads();
-      if (tid < BM) {
-        const RowInfo ri = rows[tid];
-        if (ri.mask_lo) atomicOr(&umask[0], ri.mask_lo);
-        if (ri.mask_hi) atomicOr(&umask[1], ri.mask_hi);
-      }
-      __syncthreads();
-      const unsigned long long U = (unsigned long long)umask[0] | ((unsigned long long)umask[1] << 32);
-      int ta = 0, tb = 0;
-      const bool mine = tid < ntaps && ((U >> tid) & 1ull);
-      if (mine) { ta = tapA[tid]; tb = tapB[tid]; }
-      unsigned long long rm = 0ull;        // this row's mask over the compact taps
-      if (tid < BM) {
-        const RowInfo ri = rows[tid];
-        const unsigned long long old = (unsigned long long)ri.mask_lo | ((unsigned long long)ri.mask_hi << 32);
-        int pos = 0;
-        for (int t = 0; t < ntaps; ++t)
-          if ((U >> t) & 1ull) { rm |= ((old >> t) & 1ull) << pos; ++pos; }
-      }
-      __syncthreads();
-      if (mine) { const int pos = __popcll(U & ((1ull << tid) - 1ull)); tapA[pos] = ta; tapB[pos] = tb; }
-      if (tid < BM) { rows[tid].mask_lo = (unsigned)rm; rows[tid].mask_hi = (unsigned)(rm >> 32); }
-      ntaps = __popcll(U);
-      Kdim = ntaps * Cp;
-      nk = (Kdim + BK - 1) / BK;
-      per = (nk + p.splits - 1) / p.splits;
-      ks_begin = bz * per;
-      ks_end = min(nk, ks_begin + per);
-      __syncthreads();
-    }
+  if constexpr (COMPACT) {
+    if (p.compact) { g.ntaps = compact_taps<BM>(g.ntaps, rows, tapA, tapB, tid); g.Kdim = g.ntaps * g.Cp; }      // block-uniform
   }
+  // Cs: channels of the gathered tensor; Cp: Cs padded to a multiple of 4 (quad granularity per tap).
+  const int M = g.M, N = g.N, Kdim = g.Kdim, Cs = g.Cs, Cp = g.Cp, ntaps = g.ntaps;
+  const int tm = g.tm, m0 = g.m0, n0 = g.n0;
+  const int NS = p.K;      // floats between two rows of the dense operand (FWD: filter rows W[(tap, c)][0..K))
+  const KRange kr = split_range((Kdim + BK - 1) / BK, p.splits, bz);
+  const int ks_begin = kr.begin, ks_end = kr.end;
 
   // ---- loaders: NST register stages ---------------------------------------------------------------
   // k-fast operands (A of FWD/DGRAD, B of DGRAD) are gathered one quad per (row, k/4); the others
@@ -756,7 +515,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // one per thread) at a time into the half of `rows` selected by the chunk parity, one barrier ahead of their
   // first use, so the K-loop itself carries no divergent "first 32 threads" section.
   auto wgrad_rows = [&](int chunk) {
-    if constexpr (MODE == MODE_WGRAD) rows[(chunk & 1) * 256 + tid] = fill_row_fwd((ks_begin + 8 * chunk) * BK + tid, Kdim);
+    if constexpr (MODE == MODE_WGRAD) rows[(chunk & 1) * 256 + tid] = row_info<MODE, F32Tensors, false>(p, g, (ks_begin + 8 * chunk) * BK + tid, Kdim);
   };
 
   // prologue: stages 0..NST-1 <- steps ks_begin..+NST-1; step ks_begin -> LDS buffer 0
@@ -822,10 +581,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // ---- epilogue: C/D layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) --------------
   if constexpr (MODE != MODE_WGRAD) {
     if (p.stats != nullptr) {     // BatchNorm statistics of this tile (ConvArgs::stats): thread -> lane-half pair -> waves of a column
-      int g = 0, blk;
-      if constexpr (MODE == MODE_DGRAD) { blk = by * p.stats_tpg + tm; } else { g = tm / p.stats_tpg; blk = tm - g * p.stats_tpg; }
       tile_stats_epilogue<BM, BN, WM, TA, TB>([&](int a, int b, int r) { return acc[a][b][r]; }, reinterpret_cast<float*>(smem),
-                                              p.stats + ((long long)g * p.stats_nblk + blk) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
+                                              p.stats + stats_block<MODE>(p, by, tm) * 2 * N, N, M, m0, n0, wm0, wn0, wr, lrow, lk, tid);
     }
   }
   if constexpr (EPI) {          // bias + activation of a layer built with normalizer_fn = None (models.py:20-21: tanh(deconv + b))
@@ -840,73 +597,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     }
   }
   float* outp = p.out + (p.splits > 1 ? (long long)bz * p.out_numel : 0ll);
-  // Full tiles take a straight-line path - one base per 32 x 32 sub-tile, sixteen stores at row strides - instead of a
-  // bounds test, a branch and a 64-bit index multiply per element (conv_bf16_kernel.h has the measurement).
-  // (rows full; a ragged last column tile - 3, 6, 25 or 138 output channels - only masks lanes, once per 32-column sub-tile)
-  const bool full = m0 + BM <= M && (MODE != MODE_WGRAD || (Cp == Cs && !(p.splits == 1 && p.accumulate != 0.f)));
-  // column term of an element's offset: n, or in the quad slab layout (ConvArgs::slab_rows) the quad's run of rows + n & 3
-  const bool quads = MODE != MODE_WGRAD && p.slab_rows > 0;
-  // FWD rows addressed by their out_off: the merged input gradient (columns = 2 x 2 pixel, channel) and pixel-major small maps
-  const bool shuf = MODE == MODE_FWD && (p.shuf_c > 0 || p.compact);
-  auto col_off = [&](int n) -> long long {
-    if (MODE == MODE_FWD && p.shuf_c > 0) { const int cls = n / p.shuf_c; return (long long)((cls >> 1) * p.shuf_w + (cls & 1)) * p.shuf_pitch + (n - cls * p.shuf_c); }
-    return quads ? (long long)(n >> 2) * p.slab_rows * 4 + (n & 3) : (long long)n;
-  };
-  const long long row_pitch = MODE == MODE_WGRAD ? N : (quads ? 4 : p.Ky);
-  if (full) {
-#pragma unroll
-    for (int b = 0; b < TB; ++b) {
-      if (n0 + wn0 + 32 * b + lrow < N) {
-        const long long co = col_off(n0 + wn0 + 32 * b + lrow);
-        if (MODE == MODE_DGRAD || shuf) {
-#pragma unroll
-          for (int a = 0; a < TA; ++a)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              outp[(long long)rows[wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk].out_off + co] = acc[a][b][r];
-        } else {
-#pragma unroll
-          for (int a = 0; a < TA; ++a) {
-            float* const o = outp + (long long)(m0 + wm0 + 32 * a + 4 * lk) * row_pitch + co;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[(long long)((r & 3) + 8 * (r >> 2)) * row_pitch] = acc[a][b][r];
-          }
-        }
-      }
-    }
-    return;
-  }
-  // partial row tiles: per ROW one validity test and one base index (the weight gradient's division by the padded channel count
-  // included), per element only the column mask
-  const bool acc_out = MODE == MODE_WGRAD && p.splits == 1 && p.accumulate != 0.f;
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = wm0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk;
-      const int m = m0 + row;
-      if (m >= M) continue;
-      long long base;
-      if (MODE == MODE_DGRAD || shuf) {
-        base = rows[row].out_off;
-      } else if constexpr (MODE == MODE_WGRAD) {
-        const int t = div_fast(m, p.mg_cp, p.sh_cp), c = m - t * Cp;      // (Cp == Cs: c < Cs always)
-        if (c >= Cs) continue;
-        base = ((long long)t * Cs + c) * N;
-      } else {
-        base = (long long)m * row_pitch;
-      }
-#pragma unroll
-      for (int b = 0; b < TB; ++b) {
-        const int n = n0 + wn0 + 32 * b + lrow;
-        if (n < N) {
-          const long long o = base + col_off(n);
-          float v = acc[a][b][r];
-          if (acc_out) v += p.accumulate * outp[o];
-          outp[o] = v;
-        }
-      }
-    }
+  store_tile<MODE, BM, TA, TB, false>(acc, out_map<MODE, F32Tensors, COMPACT>(p, g), rows, outp, false, wm0, wn0, lrow, lk);
 }
 
 template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false>

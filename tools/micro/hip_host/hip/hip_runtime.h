@@ -1,5 +1,6 @@
 // Host stand-in for <hip/hip_runtime.h>: runs a kernel's blocks one after another, the threads of a block as real threads
-// that meet at a barrier for __syncthreads().  Only what csrc/ssim_loss.hip, csrc/ssim_window.h and csrc/common.h use.
+// that meet at a barrier for __syncthreads().  Only what csrc/ssim_loss.hip, csrc/ssim_window.h, csrc/grad_norm.hip,
+// csrc/conv_tile.h and csrc/common.h use.
 #pragma once
 #include <math.h>
 #include <pthread.h>
@@ -32,6 +33,9 @@ extern double emu_exchange[1024];
 static inline void __syncthreads() { pthread_barrier_wait(&emu_barrier); }
 using std::min;
 using std::max;
+// (csrc/conv_tile.h: compact_taps)
+static inline unsigned atomicOr(unsigned* p, unsigned v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
+static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 
 // called by every thread of the block at the same place (block_sum): exchange through memory
 template <typename T>
