@@ -40,6 +40,18 @@ class ConvDesc(ctypes.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
+class ConvPath(ctypes.Structure):
+    """struct acg_conv_path (include/acgan_conv_plan.h)."""
+    FAMILIES = ('direct', 'mfma_f32', 'mfma_bf16', 'glds_bf16')
+    REDUCES = ('none', 'plain', 'bf16', 'cols')
+    _fields_ = [(n, c_int32) for n in (
+        'family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce',
+        'direct_nb')]
+
+
+PAIR_KINDS = ('refused', 'direct_pair', 'conv_pair_f32', 'conv_pair_bf16', 'two_launches', 'merged')      # ACG_PAIR_*
+
+
 class ReduceList(ctypes.Structure):
     """struct acg_reduce_list (ACG_REDUCE_MAX = 32 entries)."""
     _fields_ = [('slabs', c_void_p * 32), ('out', c_void_p * 32), ('numel', c_int64 * 32), ('splits', c_int32 * 32),
@@ -221,6 +233,11 @@ EXTENSIONS = {
         'acg_ssim_loss_workspace_bytes': (c_size_t, [c_int32] * 4),
         'acg_ssim_loss': (STATUS, [_P, _P, _P, _P, c_float, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
                                    _P, c_size_t, _P]),
+    }),
+    # which kernel a conv call would launch: a query for the tests (tests/conv_path_cases.py) and the tools, nothing launches
+    'conv_plan': Extension('include/acgan_conv_plan.h', 'the kernel paths are those of the HIP library only', {
+        'acg_conv2d_path': (STATUS, [_D, c_int32, c_int32, c_int32, ctypes.POINTER(ConvPath)]),
+        'acg_conv2d_pair_path': (c_int32, [_D, c_int32, c_int32, c_int32]),
     }),
 }
 

@@ -26,6 +26,7 @@
 // slabs that a second kernel sums in fixed order (deterministic; no float atomics).
 #include <stdlib.h>
 
+#include "../../include/acgan_conv_plan.h"
 #include "conv_bf16_kernel.h"
 
 using namespace acgconv;
@@ -275,7 +276,10 @@ Plan make_plan(const acg_conv_desc& d, int which, bool bf16 = false, bool wide_o
   // (g/sconv4) lose - every lane then walks 16 strided dword loads per pixel and the launch is latency-bound at 10-19 us
   // against 9 us tiled - and the bf16 tiled path, which does not split these layers, is already at 5 us
   // (profiles/r3/d_direct_small_convs.txt).
-  if (direct_on && !bf16 && g_force_cfg < 0 && g_force_splits < 0 && d.out_c <= 8 && flops <= 8.0e6) {
+  // Not with a channel limit below the channel count (dgrad_c / adj_dgrad_c): the direct kernels store every channel of dx, the
+  // tiled ones stop at ConvArgs::Nv.  No layer of the models is both that small and limited.
+  const bool limited = (which == ACG_CONV_DGRAD && d.dgrad_c > 0 && d.dgrad_c < d.in_c) || (which == ACG_CONV_FWD && d.adj_dgrad_c > 0 && d.adj_dgrad_c < d.out_c);
+  if (direct_on && !bf16 && g_force_cfg < 0 && g_force_splits < 0 && d.out_c <= 8 && flops <= 8.0e6 && !limited) {
     pl.direct = true; pl.cfg = 9; pl.bm = pl.bn = 64; pl.tiles = 1; pl.splits = 1; pl.ragged = false; pl.nvec = true;
     return pl;
   }
@@ -374,6 +378,12 @@ int stats_blocks(const Plan& pl, const acg_conv_desc& d, int which, int groups, 
   return (int)nblk;
 }
 
+// What prepare() hands to fill_geometry (conv_tile.h) - and the path query with it.
+GeomFlags geom_flags(const Plan& pl, bool bf16, bool stats, bool quad_slabs) {
+  static const int tap_classes = env_int("ACG_CONV_TAP_CLASSES", 0), compact_max = env_int("ACG_PLAN_COMPACT", 4);
+  return GeomFlags{(!stats && !pl.direct) ? compact_max : 0, (tap_classes & (bf16 ? 1 : 2)) != 0, quad_slabs};
+}
+
 // slabs_only (weight gradients whose reduction is deferred to acg_splitk_reduce_many): the contraction leaves its
 // `splits` partial slabs in the workspace and `out` is not touched.
 int prepare(Job& j, int which, const float* gsrc, const float* dense, float* out, float accumulate, const acg_conv_desc* d,
@@ -426,8 +436,7 @@ int prepare(Job& j, int which, const float* gsrc, const float* dense, float* out
   // then holds a tile's window) - a tuning hook: bit 0 bf16, bit 1 float32; measured: K-loop of a 5x5 / stride-2 forward -10 % at
   // >= 128 channels, whole steps level (profiles/r4/h_bf16_kloop_load_path.txt): off.  Small maps: pixel-major rows + only the
   // taps a tile's rows can see (ConvArgs::compact); not with epilogue statistics, whose partial blocks are runs of rows of one group
-  static const int tap_classes = env_int("ACG_CONV_TAP_CLASSES", 0), compact_max = env_int("ACG_PLAN_COMPACT", 4);
-  fill_geometry(a, *d, which, h, GeomFlags{(stats == nullptr && !pl.direct) ? compact_max : 0, (tap_classes & (h ? 1 : 2)) != 0, slab_layout != ACG_SLABS_ROWS});
+  fill_geometry(a, *d, which, h, geom_flags(pl, h, stats != nullptr, slab_layout != ACG_SLABS_ROWS));
   if (stats != nullptr) {
     int tpg = 0;
     const int nblk = stats_blocks(pl, *d, which, stats_groups, &tpg);
@@ -450,8 +459,18 @@ int launch(const Job& j, hipStream_t st) {
   return launch_mode<MODE_WGRAD>(j.pl, j.a, st);
 }
 
+// Which kernel sums the slabs of a job (ACG_REDUCE_*, acgan_conv_plan.h): none for an unsplit or slabs-only job; the column-wise
+// one where the contraction computes fewer channels than the output's pitch; the bf16 one for bf16-stored activations.
+int reduce_kind(const Job& j) {
+  if (j.pl.splits <= 1 || j.slabs_only) return ACG_REDUCE_NONE;
+  if (j.which != ACG_CONV_WGRAD && j.pl.out_cols < j.pl.out_pitch) return ACG_REDUCE_COLS;
+  if (j.pl.bf16 && j.which != ACG_CONV_WGRAD && !j.a.out_f32) return ACG_REDUCE_BF16;
+  return ACG_REDUCE_PLAIN;
+}
+
 int reduce(const Job& j, hipStream_t st) {
-  if (j.pl.splits > 1 && !j.slabs_only && j.which != ACG_CONV_WGRAD && j.pl.out_cols < j.pl.out_pitch) {
+  const int kind = reduce_kind(j);
+  if (kind == ACG_REDUCE_COLS) {
     if (j.pl.bf16 && !j.a.out_f32)
       ACG_LAUNCH(splitk_reduce_cols<__bf16>, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, (__bf16*)j.out, j.pl.out_numel,
                  j.pl.splits, j.pl.out_pitch, j.pl.out_cols);
@@ -460,11 +479,11 @@ int reduce(const Job& j, hipStream_t st) {
                  j.pl.splits, j.pl.out_pitch, j.pl.out_cols);
     return acg::check_launch("splitk_reduce_cols");
   }
-  if (j.pl.splits > 1 && !j.slabs_only && j.pl.bf16 && j.which != ACG_CONV_WGRAD && !j.a.out_f32) {
+  if (kind == ACG_REDUCE_BF16) {
     ACG_LAUNCH(splitk_reduce_bf16, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, (__bf16*)j.out, j.pl.out_numel, j.pl.splits);
     return acg::check_launch("splitk_reduce_bf16");
   }
-  if (j.pl.splits > 1 && !j.slabs_only) {
+  if (kind == ACG_REDUCE_PLAIN) {
     ACG_LAUNCH(splitk_reduce, dim3(reduce_blocks(j.pl.out_numel)), dim3(256), 0, st, (const float*)j.ws, j.out, j.pl.out_numel, j.pl.splits,
                j.which == ACG_CONV_WGRAD ? j.accumulate : 0.f);
     return acg::check_launch("splitk_reduce");
@@ -513,6 +532,15 @@ Merged merged_dgrad(const acg_conv_desc& d, bool bf16) {
 }
 size_t merged_slab_bytes(const Merged& m, int splits) { return splits > 1 ? (((size_t)splits * (size_t)m.out_numel * sizeof(float) + 255) & ~(size_t)255) : 0; }
 
+// the forward problem as prepare() plans it; its result tensor is then redirected to dx (pixel-shuffle epilogue, ConvArgs::shuf_c)
+int prepare_merged(Job& j, const Merged& m, const float* dy, const float* wm, float* out, const acg_conv_desc* d, int dtype, void* ws, const char* who,
+                   bool slabs_only) {
+  if (int rc = prepare(j, ACG_CONV_FWD, dy, wm, out, 0.f, &m.syn, dtype, ws, (size_t)1 << 40, who, slabs_only)) return rc;
+  j.pl.out_numel = m.out_numel; j.a.out_numel = m.out_numel; j.pl.out_pitch = m.pitch; j.pl.out_cols = d->in_c;
+  j.a.shuf_c = d->in_c; j.a.shuf_w = d->in_w; j.a.shuf_pitch = m.pitch;
+  return ACG_OK;
+}
+
 int run_merged(const Merged& m, const float* dy, const float* w, float* out, const acg_conv_desc* d, int dtype, void* ws, size_t ws_bytes,
                acg_stream_t stream, const char* who, bool slabs_only, int slab_layout) {
   const bool h = acg::dt_valid(dtype) && acg::dt_first(dtype) == ACG_BF16;
@@ -532,10 +560,7 @@ int run_merged(const Merged& m, const float* dy, const float* w, float* out, con
   else ACG_LAUNCH(merge_dgrad_weights_f32, dim3((unsigned)acg::ceil_div(total, 256)), dim3(256), 0, st, w, wm, m.g, total);
   if (int rc = acg::check_launch("merge_dgrad_weights")) return rc;
   Job j;
-  // the forward problem as prepare() plans it; its result tensor is then redirected to dx (pixel-shuffle epilogue, ConvArgs::shuf_c)
-  if (int rc = prepare(j, ACG_CONV_FWD, dy, wm, out, 0.f, &m.syn, dtype, ws, (size_t)1 << 40, who, slabs_only)) return rc;
-  j.pl.out_numel = m.out_numel; j.a.out_numel = m.out_numel; j.pl.out_pitch = m.pitch; j.pl.out_cols = d->in_c;
-  j.a.shuf_c = d->in_c; j.a.shuf_w = d->in_w; j.a.shuf_pitch = m.pitch;
+  if (int rc = prepare_merged(j, m, dy, wm, out, d, dtype, ws, who, slabs_only)) return rc;
   if (int rc = launch(j, st)) return rc;
   return reduce(j, st);
 }
@@ -554,38 +579,50 @@ int run(int which, const float* gsrc, const float* dense, float* out, float accu
   return reduce(j, st);
 }
 
-// Input gradient A (whichA = DGRAD, or FWD for a transposed layer) and weight gradient B of one layer: ONE launch when
-// the pair kernel covers the shapes (conv_f32_pair.hip), two otherwise; same results either way.
-int run_pair(int whichA, const float* gsrcA, const float* denseA, float* outA, const float* gsrcB, const float* denseB, float* outB,
-             float accumulateB, const acg_conv_desc* d, int dtype, void* wsA, size_t wsbA, void* wsB, size_t wsbB, int slab_flags,
-             acg_stream_t stream, const char* who) {
-  if (whichA == ACG_CONV_DGRAD && d != nullptr && validate(d, who) == ACG_OK && merged_dgrad(*d, acg::dt_valid(dtype) && acg::dt_first(dtype) == ACG_BF16).ok) {
-    // the merged input gradient (run_merged) is a launch of its own: same results as the separate entries, which take it too
-    if (int rc = run(ACG_CONV_DGRAD, gsrcA, denseA, outA, 0.f, d, dtype, wsA, wsbA, stream, who, (slab_flags & 2) != 0, nullptr, 0,
-                     (slab_flags & 4) ? ACG_SLABS_QUADS : ACG_SLABS_ROWS)) return rc;
-    return run(ACG_CONV_WGRAD, gsrcB, denseB, outB, accumulateB, d, dtype, wsB, wsbB, stream, who, (slab_flags & 1) != 0);
-  }
-  Job ja, jb;
+// The three decisions of run_pair below, shared with the path query (acg_conv2d_pair_path).
+bool pair_merged(int whichA, const acg_conv_desc* d, int dtype, const char* who) {
+  return whichA == ACG_CONV_DGRAD && d != nullptr && validate(d, who) == ACG_OK && merged_dgrad(*d, acg::dt_valid(dtype) && acg::dt_first(dtype) == ACG_BF16).ok;
+}
+int prepare_pair(Job& ja, Job& jb, int whichA, const float* gsrcA, const float* denseA, float* outA, const float* gsrcB, const float* denseB,
+                 float* outB, float accumulateB, const acg_conv_desc* d, int dtype, void* wsA, size_t wsbA, void* wsB, size_t wsbB, int slab_flags,
+                 const char* who) {
   const bool slabs_only_B = (slab_flags & 1) != 0, slabs_only_A = (slab_flags & 2) != 0;
   ACG_REQUIRE(!(slab_flags & 4) || slabs_only_A, ACG_ERR_INVALID_ARG, "%s: flag 4 (quad slab layout) without flag 2", who);
   // the 256 x 128 LDS-DMA kernel has no paired form: a pair keeps A on the 128 x 128 tile (ACG_PAIR_WIDE = 1, tuning builds: A on
   // the wide kernel, the weight gradient as a launch of its own)
   static const int pair_wide = env_int("ACG_PAIR_WIDE", 0);
   if (int rc = prepare(ja, whichA, gsrcA, denseA, outA, 0.f, d, dtype, wsA, wsbA, who, slabs_only_A, nullptr, 0, (slab_flags & 4) ? ACG_SLABS_QUADS : ACG_SLABS_ROWS, pair_wide != 0)) return rc;
-  if (int rc = prepare(jb, ACG_CONV_WGRAD, gsrcB, denseB, outB, accumulateB, d, dtype, wsB, wsbB, who, slabs_only_B)) return rc;
-  hipStream_t st = acg::to_stream(stream);
+  return prepare(jb, ACG_CONV_WGRAD, gsrcB, denseB, outB, accumulateB, d, dtype, wsB, wsbB, who, slabs_only_B);
+}
+int pair_kind(int whichA, const Job& ja, const Job& jb) {
   static const int enabled = env_int("ACG_CONV_PAIR", 1);       // 0: always two launches (A/B comparison)
-  if (ja.pl.direct || jb.pl.direct) {
-    if (enabled && ja.pl.direct && jb.pl.direct && whichA == ACG_CONV_DGRAD) {
-      if (int rc = launch_direct_pair(ja.a, jb.a, st)) return rc;
-    } else {
-      if (int rc = launch(ja, st)) return rc;
-      if (int rc = launch(jb, st)) return rc;
-    }
-  } else if (enabled && g_force_cfg < 0 && ja.pl.bf16 && jb.pl.bf16 && ja.pl.cfg != 4 && (whichA == ACG_CONV_FWD || whichA == ACG_CONV_DGRAD) &&
-      (long long)ja.pl.tiles * ja.pl.splits + (long long)jb.pl.tiles * jb.pl.splits < (1ll << 30)) {
+  if (ja.pl.direct || jb.pl.direct) return (enabled && ja.pl.direct && jb.pl.direct && whichA == ACG_CONV_DGRAD) ? ACG_PAIR_DIRECT : ACG_PAIR_TWO;
+  if (enabled && g_force_cfg < 0 && ja.pl.bf16 && jb.pl.bf16 && ja.pl.cfg != 4 && (whichA == ACG_CONV_FWD || whichA == ACG_CONV_DGRAD) &&
+      (long long)ja.pl.tiles * ja.pl.splits + (long long)jb.pl.tiles * jb.pl.splits < (1ll << 30)) return ACG_PAIR_BF16;
+  if (enabled && g_force_cfg < 0 && pair_supported(whichA, ja.pl, jb.pl)) return ACG_PAIR_F32;
+  return ACG_PAIR_TWO;
+}
+
+// Input gradient A (whichA = DGRAD, or FWD for a transposed layer) and weight gradient B of one layer: ONE launch when
+// the pair kernel covers the shapes (conv_f32_pair.hip), two otherwise; same results either way.
+int run_pair(int whichA, const float* gsrcA, const float* denseA, float* outA, const float* gsrcB, const float* denseB, float* outB,
+             float accumulateB, const acg_conv_desc* d, int dtype, void* wsA, size_t wsbA, void* wsB, size_t wsbB, int slab_flags,
+             acg_stream_t stream, const char* who) {
+  if (pair_merged(whichA, d, dtype, who)) {
+    // the merged input gradient (run_merged) is a launch of its own: same results as the separate entries, which take it too
+    if (int rc = run(ACG_CONV_DGRAD, gsrcA, denseA, outA, 0.f, d, dtype, wsA, wsbA, stream, who, (slab_flags & 2) != 0, nullptr, 0,
+                     (slab_flags & 4) ? ACG_SLABS_QUADS : ACG_SLABS_ROWS)) return rc;
+    return run(ACG_CONV_WGRAD, gsrcB, denseB, outB, accumulateB, d, dtype, wsB, wsbB, stream, who, (slab_flags & 1) != 0);
+  }
+  Job ja, jb;
+  if (int rc = prepare_pair(ja, jb, whichA, gsrcA, denseA, outA, gsrcB, denseB, outB, accumulateB, d, dtype, wsA, wsbA, wsB, wsbB, slab_flags, who)) return rc;
+  hipStream_t st = acg::to_stream(stream);
+  const int kind = pair_kind(whichA, ja, jb);
+  if (kind == ACG_PAIR_DIRECT) {
+    if (int rc = launch_direct_pair(ja.a, jb.a, st)) return rc;
+  } else if (kind == ACG_PAIR_BF16) {
     if (int rc = launch_pair16(whichA == ACG_CONV_FWD ? MODE_FWD : MODE_DGRAD, ja.pl, ja.a, jb.pl, jb.a, st)) return rc;
-  } else if (enabled && g_force_cfg < 0 && pair_supported(whichA, ja.pl, jb.pl)) {
+  } else if (kind == ACG_PAIR_F32) {
     if (int rc = launch_pair(whichA, ja.pl, ja.a, jb.pl, jb.a, st)) return rc;
   } else {
     if (int rc = launch(ja, st)) return rc;
@@ -746,6 +783,52 @@ int32_t acg_deconv2d_bwd_pair(const void* dy, const void* w, const void* x, void
   // adjoint's WGRAD with the roles of x and dy exchanged (acg_deconv2d_dgrad / acg_deconv2d_wgrad)
   return run_pair(ACG_CONV_FWD, (const float*)dy, (const float*)w, (float*)dx, (const float*)dy, (const float*)x, dw, dw_accumulate,
                   adj, dtype, ws_dgrad, wsb_dgrad, ws_wgrad, wsb_wgrad, wgrad_slabs_only, s, "deconv2d_bwd_pair");
+}
+
+// ---- acgan_conv_plan.h: the path a call would take, out of the jobs the entries above prepare (nothing is launched, the
+// tensor pointers of these jobs are never followed)
+static int path_job(Job& j, bool* merged, const acg_conv_desc* d, int which, int dtype, bool as_pair_a, const char* who) {
+  alignas(16) static const float probe[4] = {0.f, 0.f, 0.f, 0.f};
+  float* const p = const_cast<float*>(probe);
+  *merged = false;
+  if (which == ACG_CONV_DGRAD && !as_pair_a && d != nullptr && validate(d, who) == ACG_OK) {       // run()
+    const Merged m = merged_dgrad(*d, acg::dt_valid(dtype) && acg::dt_first(dtype) == ACG_BF16);
+    if (m.ok) { *merged = true; return prepare_merged(j, m, p, p, p, d, dtype, p, who, false); }
+  }
+  static const int pair_wide = env_int("ACG_PAIR_WIDE", 0);
+  return prepare(j, which, p, p, p, 0.f, d, dtype, p, ~(size_t)0, who, false, nullptr, 0, ACG_SLABS_ROWS, !as_pair_a || pair_wide != 0);
+}
+
+int32_t acg_conv2d_path(const acg_conv_desc* d, int32_t which, int32_t dtype, int32_t as_pair_a, acg_conv_path* out) {
+  ACG_REQUIRE(out != nullptr && which >= 0 && which <= 2, ACG_ERR_INVALID_ARG, "conv2d_path: contraction %d", which);
+  Job j;
+  bool merged;
+  if (int rc = path_job(j, &merged, d, which, dtype, as_pair_a != 0, "conv2d_path")) return rc;
+  const Plan& pl = j.pl;
+  acg_conv_path o{};
+  o.family = pl.direct ? ACG_PATH_DIRECT : !pl.bf16 ? ACG_PATH_MFMA_F32 : pl.cfg == 4 ? ACG_PATH_GLDS_BF16 : ACG_PATH_MFMA_BF16;
+  o.tile_rows = pl.bm; o.tile_cols = pl.bn; o.tiles = (int32_t)std::min<long long>(pl.tiles, 0x7fffffff);
+  o.classes = pl.classes; o.nk = pl.nk; o.splits = pl.splits;
+  if (o.family == ACG_PATH_MFMA_F32) {
+    o.ragged = pl.ragged; o.nvec = pl.nvec; o.compact = j.a.compact;
+    o.lin = lin_variant(j.which == ACG_CONV_FWD ? MODE_FWD : j.which == ACG_CONV_DGRAD ? MODE_DGRAD : MODE_WGRAD, pl, j.a);
+  }
+  o.merged = merged;
+  o.reduce = reduce_kind(j);
+  o.direct_nb = pl.direct ? (j.a.K <= 1 ? 1 : 8) : 0;      // (launch_direct / launch_direct_pair, conv_direct.hip: NB = 1 for a.K <= 1, else 8)
+  *out = o;
+  return ACG_OK;
+}
+
+int32_t acg_conv2d_pair_path(const acg_conv_desc* d, int32_t transposed, int32_t dtype, int32_t flags) {
+  alignas(16) static const float probe[4] = {0.f, 0.f, 0.f, 0.f};
+  float* const p = const_cast<float*>(probe);
+  const int whichA = transposed ? ACG_CONV_FWD : ACG_CONV_DGRAD;
+  if (d == nullptr || validate(d, "conv2d_pair_path") != ACG_OK) return 0;
+  if (pair_merged(whichA, d, dtype, "conv2d_pair_path")) return ACG_PAIR_MERGED;
+  Job ja, jb;
+  if (prepare_pair(ja, jb, whichA, p, p, p, p, p, p, 0.f, d, dtype, p, ~(size_t)0, p, ~(size_t)0, flags, "conv2d_pair_path") != ACG_OK) return 0;
+  return pair_kind(whichA, ja, jb);
 }
 
 int32_t acg_splitk_reduce_many(const acg_reduce_list* list, int32_t count, acg_stream_t stream) {

@@ -658,11 +658,20 @@ int launch_mode(const Plan& pl, const ConvArgs& a, hipStream_t st);
 
 // conv_f32_pair.hip: A (modeA = MODE_FWD or MODE_DGRAD) and a weight gradient B in one launch; fp32, float4-able dense
 // operands, both gathers ragged or neither (pair_supported) - the caller launches the two separately otherwise.
-bool pair_supported(int modeA, const Plan& pa, const Plan& pb);
+static inline bool pair_supported(int modeA, const Plan& pa, const Plan& pb) {
+  return (modeA == MODE_FWD || modeA == MODE_DGRAD) && !pa.bf16 && !pb.bf16 && pa.ragged == pb.ragged && pa.nvec && pb.nvec &&
+         (long long)pa.tiles * pa.splits + (long long)pb.tiles * pb.splits < (1ll << 30);
+}
 // conv_f32_dgrad.hip / conv_bf16_dgrad.hip: the one EPI instantiation each (a transposed layer's forward on the 128x32 tile)
 int launch_deconv_fwd_epi(const Plan& pl, const ConvArgs& a, hipStream_t st);
 int launch_deconv_fwd_epi16(const Plan& pl, const ConvArgs& a, hipStream_t st);
 int launch_pair(int modeA, const Plan& pa, const ConvArgs& a, const Plan& pb, const ConvArgs& b, hipStream_t st);
+
+// The LIN variant (filter rows linear in k; FWD with float4-able operands only): gathered channels a multiple of 4 and the taps in
+// natural order.  One rule for the single launch (launch_cfg), the paired one (launch_pair) and the path query (acgan_conv_plan.h).
+static inline bool lin_variant(int mode, const Plan& pl, const ConvArgs& a) {
+  return mode == MODE_FWD && !pl.ragged && pl.nvec && (a.C & 3) == 0 && !a.compact && !a.tap_classes;
+}
 
 template <int MODE, bool RAGGED, bool NVEC>
 static inline void launch_cfg(const Plan& pl, const ConvArgs& a, hipStream_t st) {
@@ -670,7 +679,7 @@ static inline void launch_cfg(const Plan& pl, const ConvArgs& a, hipStream_t st)
   // two tile shapes: 128x32 for narrow N, 64x64 otherwise.  128x128 / 128x64 variants existed through v4; with the
   // one-barrier pipeline they lost every layer of the tuning sweep (profiles/r1) and were dropped.
   if constexpr (MODE == MODE_FWD && !RAGGED && NVEC) {
-    if ((a.C & 3) == 0 && !a.compact && !a.tap_classes) {     // gathered channels a multiple of 4, taps in natural order: the LIN variant (filter rows linear in k)
+    if (lin_variant(MODE, pl, a)) {
       if (pl.cfg == 2) ACG_LAUNCH((conv_mfma_f32<MODE, 128, 32, 4, 1, RAGGED, NVEC, false, true>), grid, dim3(256), 0, st, a);
       else ACG_LAUNCH((conv_mfma_f32<MODE, 64, 64, 2, 2, RAGGED, NVEC, false, true>), grid, dim3(256), 0, st, a);
       return;

@@ -3,11 +3,6 @@
 
 namespace acgconv {
 
-bool pair_supported(int modeA, const Plan& pa, const Plan& pb) {
-  return (modeA == MODE_FWD || modeA == MODE_DGRAD) && !pa.bf16 && !pb.bf16 && pa.ragged == pb.ragged && pa.nvec && pb.nvec &&
-         (long long)pa.tiles * pa.splits + (long long)pb.tiles * pb.splits < (1ll << 30);
-}
-
 namespace {
 template <int MODE_A, int BMA, int BNA, int WMA, int WNA, bool RAGGED, bool LIN_A>
 void launch_b(const Plan& pb, const ConvArgs& a, const ConvArgs& b, const PairGeom& g, unsigned blocks, hipStream_t st) {
@@ -31,7 +26,7 @@ int launch_pair(int modeA, const Plan& pa, const ConvArgs& a, const Plan& pb, co
   if (modeA == MODE_FWD) {
     // (pair_supported: the dense operands are float4-able; gathered channels a multiple of 4 -> the LIN variant of A)
     if (pa.ragged) launch_a<MODE_FWD, true>(pa, pb, a, b, g, blocks, st);
-    else if ((a.C & 3) == 0 && !a.compact) launch_a<MODE_FWD, false, true>(pa, pb, a, b, g, blocks, st);
+    else if (lin_variant(MODE_FWD, pa, a)) launch_a<MODE_FWD, false, true>(pa, pb, a, b, g, blocks, st);
     else launch_a<MODE_FWD, false>(pa, pb, a, b, g, blocks, st);
   } else {
     if (pa.ragged) launch_a<MODE_DGRAD, true>(pa, pb, a, b, g, blocks, st);

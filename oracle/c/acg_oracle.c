@@ -78,7 +78,7 @@ int32_t acg_conv2d_fwd(const void* xv, const void* wv, void* yv, const acg_conv_
   (void)ws; (void)wsb; (void)s; REQUIRE_F32(dtype);
   const float* x = xv; const float* w = wv; float* y = yv;
   for (int b = 0; b < d->batch; b++) for (int p = 0; p < d->out_h; p++) for (int q = 0; q < d->out_w; q++)
-    for (int o = 0; o < d->out_c; o++) {
+    for (int o = 0; o < (d->adj_dgrad_c > 0 ? d->adj_dgrad_c : d->out_c); o++) {   /* channels at or beyond adj_dgrad_c untouched */
       double acc = 0;
       for (int i = 0; i < d->kh; i++) { int yy = p * d->stride_h - d->pad_top + i; if (yy < 0 || yy >= d->in_h) continue;
         for (int j = 0; j < d->kw; j++) { int xx = q * d->stride_w - d->pad_left + j; if (xx < 0 || xx >= d->in_w) continue;
@@ -102,7 +102,7 @@ int32_t acg_conv2d_dgrad(const void* dyv, const void* wv, void* dxv, const acg_c
         for (int c = 0; c < d->in_c; c++) { double a = 0;
           for (int o = 0; o < d->out_c; o++) a += (double)dy[YI(d, b, p, q, o)] * w[WI(d, i, j, c, o)];
           acc[XI(d, b, yy, xx, c)] += a; } } }
-  for (size_t k = 0; k < n; k++) if ((int)(k % XPITCH(d)) < d->in_c) dx[k] = (float)acc[k];   /* pad channels untouched */
+  for (size_t k = 0; k < n; k++) if ((int)(k % XPITCH(d)) < (d->dgrad_c > 0 ? d->dgrad_c : d->in_c)) dx[k] = (float)acc[k];   /* pad channels and channels at or beyond dgrad_c untouched */
   free(acc);
   return ACG_OK;
 }

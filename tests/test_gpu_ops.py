@@ -122,12 +122,28 @@ def test_bwd_pair_bf16(hip_abi_bf16):
 
 @pytest.mark.parametrize('shape', [(32, 64, 64, 64, 128, 5, 2, 'SAME')], ids=str)
 def test_conv_bf16_big_tiles(hip_abi_bf16, shape):
-    """Large enough for the planner's 128x128 tiles in all three contractions (256 output tiles; wgrad: long K)."""
+    """Large enough for the planner's 128x128 tiles in the forward (256 output tiles) and the weight gradient (long K)."""
+    _table_premise(hip_abi_bf16, shape[:7], False, {'fwd': 'mfma_bf16 128x128', 'wgrad': 'mfma_bf16 128x128'})
     C.case_conv_bf16(hip_abi_bf16, shape, TOL_BF16, TOL_CONV)
 
 
 def test_deconv_bf16_big_tiles(hip_abi_bf16):
+    _table_premise(hip_abi_bf16, (16, 32, 32, 128, 128, 5, 2), True, {'fwd': 'mfma_bf16 128x128', 'wgrad': 'mfma_bf16 128x128'})
     C.case_conv_bf16(hip_abi_bf16, (16, 32, 32, 128, 128, 5, 2), TOL_BF16, TOL_CONV, transposed=True)
+
+
+def _table_premise(abi, shape, transposed, kernels):
+    """The shape's row in tests/conv_path_cases.py (BIG_ROWS): acg_conv2d_path must answer the row's expectations, and these name
+    the kernel this test is there for.  ``shape``: (B, H, W, Cin, Cout, k, stride) of a conv, (B, IH, IW, Cin, Cout, k, stride) of
+    a transposed layer."""
+    import conv_path_cases as P
+    b, h, w, cin, cout, k, s = shape
+    desc = P._sq(b, h * s, w * s, cout, cin, k, s) if transposed else P._sq(b, h, w, cin, cout, k, s)
+    rows = [r for r in P.BIG_ROWS if r.desc == desc and r.transposed == transposed and all(c in r.expect for c in kernels)]
+    assert len(rows) == 1, 'no row for %s in conv_path_cases.BIG_ROWS' % (shape,)
+    P.check_premise(abi.lib, rows[0])
+    for c, kernel in kernels.items():
+        assert rows[0].expect[c].startswith(kernel), 'test premise: %s of %s is "%s", not the %s kernel' % (c, rows[0].name, rows[0].expect[c], kernel)
 
 
 # Shapes whose forward or input gradient the planner hands to the 256 x 128 LDS-DMA kernel (conv_bf16_glds.h: more than 64
@@ -139,7 +155,7 @@ def test_deconv_bf16_big_tiles(hip_abi_bf16):
                                          ((48, 32, 32, 160, 128, 3, 1, 'SAME'), 0)], ids=str)
 def test_conv_bf16_wide_tiles(hip_abi_bf16, shape, which):
     b, h, w, cin, cout, k, s, pad = shape
-    assert C.tile_rows(hip_abi_bf16, which, b, h, w, cin, k, cout, s, pad) == 256, 'test premise: the planner does not pick the wide kernel'
+    _table_premise(hip_abi_bf16, shape[:7], False, {('fwd', 'dgrad')[which]: 'glds_bf16 256x128'})
     C.case_conv_bf16(hip_abi_bf16, shape, TOL_BF16, TOL_CONV)
 
 
@@ -147,7 +163,7 @@ def test_conv_bf16_wide_tiles(hip_abi_bf16, shape, which):
 def test_deconv_bf16_wide_tiles(hip_abi_bf16, shape):
     """A transposed layer's forward as four stride classes of the wide kernel; 121 output channels = g/tconv4 at config 5."""
     b, ih, iw, cin, cout, k, s = shape
-    assert C.tile_rows(hip_abi_bf16, 1, b, ih * s, iw * s, cout, k, cin, s, 'SAME') == 256, 'test premise: the planner does not pick the wide kernel'
+    _table_premise(hip_abi_bf16, shape, True, {'fwd': 'glds_bf16 256x128'})
     C.case_conv_bf16(hip_abi_bf16, shape, TOL_BF16, TOL_CONV, transposed=True)
 
 

@@ -364,12 +364,12 @@ def test_c_abi_exports_every_declared_symbol():
 def test_extension_tables_are_disjoint_and_values_are_marked():
     """One owner per entry point, and the int32 results that are values - everything else int32 is a checked STATUS."""
     tables = [_lib.SIGNATURES] + [ext.signatures for ext in _lib.EXTENSIONS.values()]
-    assert list(_lib.EXTENSIONS) == ['metrics', 'cdna', 'rollout', 'bn_infer', 'ema', 'ssim_loss']
+    assert list(_lib.EXTENSIONS) == ['metrics', 'cdna', 'rollout', 'bn_infer', 'ema', 'ssim_loss', 'conv_plan']
     names = [n for t in tables for n in t]
     assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
     values = {n for t in tables for n, (res, _) in t.items() if res is ctypes.c_int32}
     assert values == {'acg_version', 'acg_conv2d_splits', 'acg_conv2d_tile', 'acg_bn_bwd_slabs_ok', 'acg_bn_slabs_layout',
-                      'acg_conv2d_slab_layouts', 'acg_conv2d_stats_blocks', 'acg_conv2d_stats_layout', 'acg_deconv2d_fwd_bias_act_ok'}
+                      'acg_conv2d_slab_layouts', 'acg_conv2d_stats_blocks', 'acg_conv2d_stats_layout', 'acg_deconv2d_fwd_bias_act_ok', 'acg_conv2d_pair_path'}
     lib = _lib.get()
     for n in values:                                # bound as the ctypes function itself, not behind the status check
         assert getattr(lib, n[4:]).restype is ctypes.c_int32, n
