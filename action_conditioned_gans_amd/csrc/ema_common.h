@@ -1,5 +1,6 @@
 // The weight average's per-element update, its coefficient prologue and its in-launch counter advance (include/acgan_ema.h),
-// shared by the stand-alone kernel (ema.hip) and the optimizer kernels that carry the update (optim.hip).
+// shared by the stand-alone kernel (ema.hip) and the optimizer kernels that carry the update (optim.hip); the counter advance
+// (retire) is also what the scheduled optimizer entries advance their update counter with (include/acgan_rollout.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,17 +36,20 @@ __device__ __forceinline__ void ema4(float4& s, const float4& p, float omd, int 
   s.z = ema1(s.z, p.z, omd, seed); s.w = ema1(s.w, p.w, omd, seed);
 }
 
-// Called by the thread that called coef(), behind a block barrier that follows it.  The last block of the grid to get here
-// writes the counter and resets the word; nobody waits on either.  Relaxed is enough: this thread's read of the counter has
-// RETURNED (its value went through shared memory in front of the barrier), so it was performed before this add, and the
-// one store to the counter comes after the add that saw every other block's - after every read of this launch.  The next
-// launch (or graph node) on the stream sees counter and word through the kernel boundary.
-__device__ __forceinline__ void retire(long long* num_updates, unsigned* done, long long k) {
+// A device counter that the launch which read it advances: called by the ONE thread of each block that read the counter (coef()
+// above for the average's num_updates; the learning-rate schedule's update counter in optim.hip), behind a block barrier that
+// follows the read.  `done` is the counter's own state word: one word belongs to one counter, a launch that advances two
+// counters calls this twice with two words.  The last block of the grid to get here writes the counter and resets the word;
+// nobody waits on either.  Relaxed is enough: this thread's read of the counter has RETURNED (its value went through shared
+// memory in front of the barrier), so it was performed before this add, and the one store to the counter comes after the add
+// that saw every other block's - after every read of this launch.  The next launch (or graph node) on the stream sees counter
+// and word through the kernel boundary.
+__device__ __forceinline__ void retire(long long* counter, unsigned* done, long long k) {
   const unsigned total = gridDim.x * gridDim.y * gridDim.z;
   const unsigned prev = __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (prev + 1u == total) {
     __hip_atomic_store(done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *num_updates = k + 1;
+    *counter = k + 1;
   }
 }
 

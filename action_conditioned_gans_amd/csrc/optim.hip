@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "../../include/acgan_ema.h"
+#include "../../include/acgan_rollout.h"
 #include "common.h"
 #include "ema_common.h"
 
@@ -36,18 +37,47 @@ struct OptScalars {
   int use_clip;
 };
 
+// ---- the learning-rate schedule of the *_step_lr entries (include/acgan_rollout.h acg_lr_schedule) -------------------------------
+// The launch's own view of the schedule: the shape as the host read it, the update counter the launch advances, that counter's
+// state word, and where block 0 leaves the rate it used.
+struct LrArgs {
+  int kind;
+  long long warmup, decay_steps;
+  float final_factor;
+  long long* updates;
+  unsigned* done;
+  float* out;
+};
+
+// lr_k, the rate of update k: all of it in double, one rounding to float32 at the end (the header states the formulas).  ONE
+// thread per block evaluates it, in the prologue that holds Adam's two pow calls anyway.
+__device__ __forceinline__ float lr_at(float lr, const LrArgs& s, long long k) {
+  const double F = (double)s.final_factor;
+  const double w = (s.warmup > 0 && k < s.warmup) ? (double)(k + 1) / (double)s.warmup : 1.0;
+  double f = 1.0;
+  if (s.kind != ACG_LR_CONSTANT) {
+    const double j = (double)(k > s.warmup ? k - s.warmup : 0);
+    const double t = fmin(j / (double)s.decay_steps, 1.0);
+    if (s.kind == ACG_LR_LINEAR) f = 1.0 - (1.0 - F) * t;
+    else if (s.kind == ACG_LR_COSINE) f = F + (1.0 - F) * 0.5 * (1.0 + cos(3.14159265358979323846 * t));
+    else f = pow(F, j / (double)s.decay_steps);
+  }
+  return (float)((double)lr * w * f);
+}
+
 // ---- the update rules: what a kernel below is instantiated with -----------------------------------------------------------------
 // kSlots: the slot buffers the rule reads and writes (a one-slot rule never touches s2); kPrologue: `rate` must be derived by
-// one thread of the block before any element is updated; one(): the update of one element, given that rate.
+// one thread of the block before any element is updated; one(): the update of one element, given that rate.  `lr`: the base
+// rate of this launch - the argument, or what the schedule makes of it.
 struct Adam {
   static constexpr int kSlots = 2;
   static constexpr bool kPrologue = true;
   // lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)   (SURVEY A.6); fp64 pow keeps the tiny 1-b^t differences exact.  ONE thread per
   // block evaluates it: a dependent read of the step counter and two double-precision pow calls, several hundred
   // instructions (~1 us) - more than the whole update of the one or two float4 a thread owns.
-  static __device__ __forceinline__ float rate(const OptScalars& a, const int* step) {
+  static __device__ __forceinline__ float rate(float lr, const OptScalars& a, const int* step) {
     const int t = *step;
-    return (float)((double)a.lr * sqrt(1.0 - pow((double)a.b2, (double)t)) / (1.0 - pow((double)a.b1, (double)t)));
+    return (float)((double)lr * sqrt(1.0 - pow((double)a.b2, (double)t)) / (1.0 - pow((double)a.b1, (double)t)));
   }
   static __device__ __forceinline__ void one(float& p, float g, float& m, float& v, float lr_t, const OptScalars& a) {
     adam1(p, g, m, v, lr_t, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi);
@@ -56,7 +86,7 @@ struct Adam {
 struct RmsProp {
   static constexpr int kSlots = 1;
   static constexpr bool kPrologue = false;
-  static __device__ __forceinline__ float rate(const OptScalars& a, const int*) { return a.lr; }
+  static __device__ __forceinline__ float rate(float lr, const OptScalars&, const int*) { return lr; }
   static __device__ __forceinline__ void one(float& p, float g, float& ms, float&, float lr, const OptScalars& a) {
     rms1(p, g, ms, lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
   }
@@ -75,11 +105,15 @@ __device__ __forceinline__ void four(float4& p, const float4& g, float4& s1, flo
 // instead of two, and the average costs a read and a write of the shadow instead of those plus a second read of the parameters;
 // parameters and slots come out as without it, the shadow as ema_update_k behind the plain kernel leaves it.  The prologue
 // thread then also derives the average's coefficient, and retires the launch's count of it at the end.
-template <class R, bool EMA>
+// SCHED: the base rate is the schedule's (lr_at) at the update counter `lr.updates`, which the prologue thread reads in front of
+// the rule's own rate() and retires at the end as the average's is; block 0 leaves the rate in lr.out.  A rule without a
+// prologue gets one.  Every block reads the counter before the last one to retire stores it, so all use the same rate.
+template <class R, bool EMA, bool SCHED = false>
 __device__ __forceinline__ void flat_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
                                             float* __restrict__ s2, const int* __restrict__ step, long long n, const OptScalars& a,
-                                            float* __restrict__ sh, float ema_decay, long long* num_updates, unsigned* done) {
-  constexpr bool kTwo = R::kSlots == 2, kPrologue = R::kPrologue || EMA;
+                                            float* __restrict__ sh, float ema_decay, long long* num_updates, unsigned* done,
+                                            const LrArgs& lr = LrArgs{}) {
+  constexpr bool kTwo = R::kSlots == 2, kRate = R::kPrologue || SCHED, kPrologue = kRate || EMA;
   __shared__ float s_rate;
   __shared__ acg_ema::Coef s_c;
   const long long stride = (long long)gridDim.x * 256;
@@ -89,7 +123,7 @@ __device__ __forceinline__ void flat_update(float* __restrict__ p, const float* 
   const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
   float rate = a.lr, omd = 0.f;
   int seed = 0;
-  long long k = 0;
+  long long k = 0, lr_k = 0;
   float4 pp, gg, aa, bb, ss;
   auto load = [&](long long i) {
     pp = reinterpret_cast<float4*>(p)[i]; aa = reinterpret_cast<float4*>(s1)[i];
@@ -107,15 +141,22 @@ __device__ __forceinline__ void flat_update(float* __restrict__ p, const float* 
   if constexpr (kPrologue) {
     // Round 5: the first float4 of every thread (the grid is sized so that it is nearly the only one) is loaded BEFORE the
     // prologue, during which the whole chip used to wait with nothing in flight (19.4 us for 133 MB in situ, 3.2 TB/s).
-    // A kernel without a prologue has nothing to hide the load behind and keeps its plain loop.
+    // A kernel without a prologue has nothing to hide the load behind and keeps its plain loop (rmsprop_k; the scheduled
+    // RMSProp has one and takes this path).  A scheduled launch runs fewer blocks (flat_step) and hides the first of its loads.
     const bool have = i0 < n4;
     if (have) load(i0);
     if (threadIdx.x == 0) {
-      if constexpr (R::kPrologue) s_rate = R::rate(a, step);
+      float base = a.lr;
+      if constexpr (SCHED) {
+        lr_k = *lr.updates;
+        base = lr_at(a.lr, lr, lr_k);
+        if (blockIdx.x == 0) *lr.out = base;
+      }
+      if constexpr (kRate) s_rate = R::rate(base, a, step);
       if constexpr (EMA) s_c = acg_ema::coef(num_updates, ema_decay, &k);
     }
     __syncthreads();
-    if constexpr (R::kPrologue) rate = s_rate;
+    if constexpr (kRate) rate = s_rate;
     if constexpr (EMA) { omd = s_c.omd; seed = s_c.seed; }
     if (have) update(i0);
     i += stride;
@@ -127,6 +168,7 @@ __device__ __forceinline__ void flat_update(float* __restrict__ p, const float* 
     if constexpr (EMA) sh[i] = acg_ema::ema1(sh[i], p[i], omd, seed);
   }
   if constexpr (EMA) if (threadIdx.x == 0) acg_ema::retire(num_updates, done, k);
+  if constexpr (SCHED) if (threadIdx.x == 0) acg_ema::retire(lr.updates, lr.done, lr_k);
 }
 
 // (the kernels keep their names: tools/insitu_times.py, tools/gap_analysis.py and the committed traces find them by name)
@@ -154,6 +196,16 @@ __global__ __launch_bounds__(256) void rmsprop_ema_k(float* __restrict__ p, cons
                                                      float lo, float hi, float* __restrict__ sh, float ema_decay,
                                                      long long* num_updates, unsigned* done) {
   flat_update<RmsProp, true>(p, g, ms, nullptr, nullptr, n, OptScalars{lr, decay, 0.f, eps, gs, lo, hi, use_clip}, sh, ema_decay, num_updates, done);
+}
+
+// The scheduled entries (acg_adam_step_lr / acg_rmsprop_step_lr): the same body, with or without the average.  RMSProp
+// passes no second slot and no step counter.
+template <class R, bool EMA>
+__global__ __launch_bounds__(256) void step_lr_k(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                                 float* __restrict__ s2, const int* __restrict__ step, long long n, const OptScalars a,
+                                                 const LrArgs lr, float* __restrict__ sh, float ema_decay, long long* num_updates,
+                                                 unsigned* done) {
+  flat_update<R, EMA, true>(p, g, s1, s2, step, n, a, sh, ema_decay, num_updates, done, lr);
 }
 
 __global__ __launch_bounds__(256) void clip_k(float* __restrict__ p, long long n, float lo, float hi) {
@@ -189,7 +241,7 @@ __global__ __launch_bounds__(256) void opt_prepare_k(float* __restrict__ p, cons
   // Adam's bias-corrected learning rate: one thread derives it (a dependent read of the step counter + double-precision pow,
   // ~1-2 us); the block picks it up with `sync_lr()` - in the float4 path AFTER its loads are in flight (round 5)
   constexpr bool kTwo = R::kSlots == 2;
-  if (R::kPrologue && threadIdx.x == 0) s_lr_t = R::rate(a, step);
+  if (R::kPrologue && threadIdx.x == 0) s_lr_t = R::rate(a.lr, a, step);
   auto sync_lr = [&]() { if (R::kPrologue) { __syncthreads(); lr_t = s_lr_t; } };     // block-uniform call sites only
   auto upd = [&](long long i) -> float {
     float none;
@@ -266,8 +318,9 @@ struct EmaArgs {
   uint32_t* state;
 };
 
+// `lr`: the schedule the launch evaluates (the *_step_lr entries), or null.
 int32_t flat_step(const char* who, bool adam, float* p, const float* g, float* s1, float* s2, const int32_t* step, int64_t n,
-                  const OptScalars& a, const EmaArgs* e, acg_stream_t stream) {
+                  const OptScalars& a, const EmaArgs* e, acg_stream_t stream, const LrArgs* lr = nullptr) {
   ACG_REQUIRE(n > 0 && p && g && s1 && (!adam || (s2 && step)), ACG_ERR_INVALID_ARG, "%s: bad argument", who);
   if (e) {
     ACG_REQUIRE(e->shadow && e->num_updates && e->state, ACG_ERR_INVALID_ARG, "%s: null shadow / counter / state word", who);
@@ -275,10 +328,25 @@ int32_t flat_step(const char* who, bool adam, float* p, const float* g, float* s
     ACG_REQUIRE((reinterpret_cast<uintptr_t>(e->num_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(e->state) & 3) == 0,
                 ACG_ERR_INVALID_ARG, "%s: the counter must be 8-byte and the state word 4-byte aligned", who);
   }
-  const dim3 grid(acg::grid_for(n / 4 + 1)), block(256);
+  // A scheduled launch retires its update counter with one atomic per block, all on one word, and they drain one after the other
+  // once the streaming is over: ~9 ns each, 26 us behind the 13 us update of config 2's generator at the plain kernels' 2804
+  // blocks (measured, profiles/lr_schedule/).  So it runs at most kLrGrid blocks - one per compute unit - and lets the
+  // grid-stride loop do the rest: ~4 us over adam_k there.  The plain and the _ema launches keep the grid they have.
+  constexpr int kLrGrid = 256;
+  const dim3 grid(lr ? std::min(acg::grid_for(n / 4 + 1), kLrGrid) : acg::grid_for(n / 4 + 1)), block(256);
   hipStream_t st = acg::to_stream(stream);
   long long* count = e ? reinterpret_cast<long long*>(e->num_updates) : nullptr;
   unsigned* done = e ? reinterpret_cast<unsigned*>(e->state) : nullptr;
+  if (lr) {
+    float* sh = e ? e->shadow : nullptr;
+    const float decay = e ? e->decay : 0.f;
+    const int* st_dev = reinterpret_cast<const int*>(step);
+    if (adam && e) ACG_LAUNCH((step_lr_k<Adam, true>), grid, block, 0, st, p, g, s1, s2, st_dev, (long long)n, a, *lr, sh, decay, count, done);
+    else if (adam) ACG_LAUNCH((step_lr_k<Adam, false>), grid, block, 0, st, p, g, s1, s2, st_dev, (long long)n, a, *lr, sh, decay, count, done);
+    else if (e) ACG_LAUNCH((step_lr_k<RmsProp, true>), grid, block, 0, st, p, g, s1, s2, st_dev, (long long)n, a, *lr, sh, decay, count, done);
+    else ACG_LAUNCH((step_lr_k<RmsProp, false>), grid, block, 0, st, p, g, s1, s2, st_dev, (long long)n, a, *lr, sh, decay, count, done);
+    return acg::check_launch(who);
+  }
   if (adam && e)
     ACG_LAUNCH(adam_ema_k, grid, block, 0, st, p, g, s1, s2, step, (long long)n, a.lr, a.b1, a.b2, a.eps, a.gs, a.use_clip, a.lo, a.hi,
                e->shadow, e->decay, count, done);
@@ -290,6 +358,33 @@ int32_t flat_step(const char* who, bool adam, float* p, const float* g, float* s
   else
     ACG_LAUNCH(rmsprop_k, grid, block, 0, st, p, g, s1, (long long)n, a.lr, a.b1, a.eps, a.gs, a.use_clip, a.lo, a.hi);
   return acg::check_launch(who);
+}
+
+// The two scheduled entries: the schedule's own argument check, then flat_step with it (and with the average when `shadow` is
+// not null).
+int32_t flat_step_lr(const char* who, bool adam, float* p, const float* g, float* s1, float* s2, const int32_t* step, int64_t n,
+                     const OptScalars& a, const acg_lr_schedule* sched, int64_t* lr_updates, uint32_t* lr_state, float* lr_out,
+                     const EmaArgs& e, acg_stream_t stream) {
+  ACG_REQUIRE(sched && lr_updates && lr_state && lr_out, ACG_ERR_INVALID_ARG, "%s: null schedule / update counter / state word / lr_out", who);
+  ACG_REQUIRE((reinterpret_cast<uintptr_t>(lr_updates) & 7) == 0 && (reinterpret_cast<uintptr_t>(lr_state) & 3) == 0 &&
+              (reinterpret_cast<uintptr_t>(lr_out) & 3) == 0, ACG_ERR_INVALID_ARG,
+              "%s: the update counter must be 8-byte, its state word and lr_out 4-byte aligned", who);
+  ACG_REQUIRE(a.lr > 0.f && a.lr <= 3.402823466e38f, ACG_ERR_INVALID_ARG, "%s: lr %g is not finite and > 0", who, (double)a.lr);
+  ACG_REQUIRE(sched->kind >= ACG_LR_CONSTANT && sched->kind <= ACG_LR_EXPONENTIAL, ACG_ERR_INVALID_ARG,
+              "%s: schedule kind %d (0 constant, 1 linear, 2 cosine, 3 exponential)", who, sched->kind);
+  ACG_REQUIRE(sched->warmup >= 0, ACG_ERR_INVALID_ARG, "%s: warmup %lld < 0", who, (long long)sched->warmup);
+  if (sched->kind != ACG_LR_CONSTANT) {
+    const float F = sched->final_factor;
+    ACG_REQUIRE(sched->decay_steps >= 1, ACG_ERR_INVALID_ARG, "%s: decay_steps %lld < 1", who, (long long)sched->decay_steps);
+    ACG_REQUIRE(F <= 1.f && (sched->kind == ACG_LR_EXPONENTIAL ? F > 0.f : F >= 0.f), ACG_ERR_INVALID_ARG,
+                "%s: final_factor %g is not in %s", who, (double)F, sched->kind == ACG_LR_EXPONENTIAL ? "(0, 1]" : "[0, 1]");
+  }
+  if (e.shadow)
+    ACG_REQUIRE(lr_updates != e.num_updates && static_cast<void*>(lr_state) != static_cast<void*>(e.state), ACG_ERR_INVALID_ARG,
+                "%s: the schedule and the average share a counter or a state word", who);
+  const LrArgs lr{sched->kind, (long long)sched->warmup, (long long)sched->decay_steps, sched->final_factor,
+                  reinterpret_cast<long long*>(lr_updates), reinterpret_cast<unsigned*>(lr_state), lr_out};
+  return flat_step(who, adam, p, g, s1, s2, step, n, a, e.shadow ? &e : nullptr, stream, &lr);
 }
 
 }  // namespace
@@ -323,6 +418,23 @@ int32_t acg_rmsprop_step_ema(float* param, const float* grad, float* ms, int64_t
   const EmaArgs e{shadow, ema_decay, num_updates, state};
   return flat_step("rmsprop_step_ema", false, param, grad, ms, nullptr, nullptr, n,
                    {lr, decay, 0.f, eps, grad_scale, clip_lo, clip_hi, use_clip}, &e, stream);
+}
+
+int32_t acg_adam_step_lr(float* param, const float* grad, float* m, float* v, const int32_t* step_dev, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float grad_scale, int32_t use_clip, float clip_lo, float clip_hi,
+                         const acg_lr_schedule* sched, int64_t* lr_updates, uint32_t* lr_state, float* lr_out, float* shadow,
+                         float ema_decay, int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
+  return flat_step_lr("adam_step_lr", true, param, grad, m, v, step_dev, n, {lr, beta1, beta2, eps, grad_scale, clip_lo, clip_hi, use_clip},
+                      sched, lr_updates, lr_state, lr_out, EmaArgs{shadow, ema_decay, num_updates, state}, stream);
+}
+
+int32_t acg_rmsprop_step_lr(float* param, const float* grad, float* ms, int64_t n, float lr, float decay, float eps,
+                            float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, const acg_lr_schedule* sched,
+                            int64_t* lr_updates, uint32_t* lr_state, float* lr_out, float* shadow, float ema_decay,
+                            int64_t* num_updates, uint32_t* state, acg_stream_t stream) {
+  return flat_step_lr("rmsprop_step_lr", false, param, grad, ms, nullptr, nullptr, n,
+                      {lr, decay, 0.f, eps, grad_scale, clip_lo, clip_hi, use_clip}, sched, lr_updates, lr_state, lr_out,
+                      EmaArgs{shadow, ema_decay, num_updates, state}, stream);
 }
 
 int32_t acg_clip(float* param, int64_t n, float lo, float hi, acg_stream_t stream) {

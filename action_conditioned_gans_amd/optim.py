@@ -13,7 +13,8 @@ shape (train.py:91-102) and TensorFlow-1.0's update formulas.  ``mi
    optimizer step runs behind all of them;
 4. appends ONE fused update launch over the flat buffers (+ the weight clip when it is fetched with it); with ``ema=`` that
    launch also updates the scope's weight average (WeightAverage); with ``clip_norm=`` one ClipNormOp in front of it measures
-   the gradient's global norm and scales the flat gradient buffer to a bound (GradNorm).
+   the gradient's global norm and scales the flat gradient buffer to a bound (GradNorm); with ``lr_schedule=`` the launch
+   evaluates its learning rate itself, from an update counter on the device that it advances (LrSchedule).
 """
 import math
 
@@ -189,6 +190,61 @@ class GradNorm:
         return [self.build().stats]
 
 
+class LrSchedule:
+    """A learning-rate schedule of one scope's updates - linear warmup, then a constant, linear, cosine or exponential decay - that
+    the optimizer's launch evaluates on the device: what ``Optimizer.minimize(..., lr_schedule=)`` takes.  Every StepOp given the
+    same object advances the same update counter (acg_adam_step_lr / acg_rmsprop_step_lr, include/acgan_rollout.h, which states
+    the formulas): with k the counter as an update finds it and ``lr`` the optimizer's rate, the update uses
+    float32(lr * w(k) * f(k)), w = (k + 1) / warmup while k < warmup, f the decay from 1 towards ``final`` over ``decay_steps``
+    updates behind the warmup (exponential: final ** (j / decay_steps), not clamped), and leaves the counter at k + 1.  The rate is
+    no kernel argument, so a captured HIP graph of the step follows the schedule as it is replayed, with no host in the loop.
+
+    State - graph state, no variable, no optimizer slot: ``<scope>/lr/updates`` int64 [1] (named: a checkpoint key, a restored
+    run continues its schedule; a checkpoint without it leaves the counter at 0), one unnamed 32-bit word (the retired-block count
+    of the counter advance) and one unnamed float32 [1], the rate the last update used (0 before the first).  Created by ``build``
+    (at the latest when the first StepOp that carries it is compiled), like WeightAverage's, so that a caller can create it last
+    and leave every other state where it was."""
+
+    def __init__(self, kind, scope, warmup=0, decay_steps=0, final=0.0, graph=None):
+        if kind not in _lib.LrSched.KINDS:
+            raise ValueError('LrSchedule: kind must be one of %s, got %r' % (', '.join(_lib.LrSched.KINDS), kind))
+        for what, v in (('warmup', warmup), ('decay_steps', decay_steps)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 63:
+                raise ValueError('LrSchedule: %s must be an integer >= 0, got %r' % (what, v))
+        try:
+            f = float(final)
+        except (TypeError, ValueError):
+            raise ValueError('LrSchedule: final must be a number in [0, 1], got %r' % (final,))
+        if kind != 'constant':
+            if int(decay_steps) < 1:
+                raise ValueError('LrSchedule: a %s schedule needs decay_steps >= 1, got %r' % (kind, decay_steps))
+            low_ok = 0.0 < _f32(f) if kind == 'exponential' else 0.0 <= f
+            if isinstance(final, bool) or not (low_ok and f <= 1.0):
+                raise ValueError('LrSchedule: final must lie in %s for a %s schedule, got %r'
+                                 % ('(0, 1]' if kind == 'exponential' else '[0, 1]', kind, final))
+        self.kind, self.scope, self.graph = kind, scope, graph or G.get_default_graph()
+        self.warmup, self.decay_steps, self.final = int(warmup), int(decay_steps), _f32(f)
+        self.updates = self.done = self.lr = None
+
+    def build(self):
+        if self.updates is None:
+            self.updates = self.graph.new_state((1,), 0, self.scope + '/lr/updates', dtype=torch.int64)
+            self.done = self.graph.new_state((1,), 0, None, dtype=torch.int32)
+            self.lr = self.graph.new_state((1,), 0.0, None)
+        return self
+
+    def tensors(self):
+        self.build()
+        return [self.updates, self.done, self.lr]
+
+    def args(self):
+        """(schedule, counter, state word, lr_out): what the acg_*_step_lr argument lists hold behind the plain entry's; the
+        first is the ctypes struct itself (the call reads it on the host), to be passed by reference and kept alive."""
+        self.build()
+        sched = _lib.LrSched(_lib.LrSched.KINDS.index(self.kind), self.warmup, self.decay_steps, self.final)
+        return (sched, _p(self.updates.buf), _p(self.done.buf), _p(self.lr.buf))
+
+
 class ClipNormOp(G.Op):
     """acg_grad_clip_norm over a scope's flat gradient buffer, immediately in front of the StepOp it was made for: measures
     grad_scale * g per variable and in all, and multiplies g by min(1, max_norm / norm) in place (never with max_norm = inf).
@@ -224,21 +280,26 @@ class StepOp(G.Op):
     scope's weight average is updated from the new parameters behind the update -
     float32 graph, Adam / RMSProp: inside the optimizer's launch (acg_adam_step_ema / acg_rmsprop_step_ema);
     bf16 graph: acg_ema_update behind the update-and-refresh launch(es), which stay as they are;
-    where the fused entry is declined (Session(fuse_ema=False)): acg_ema_update behind the plain step."""
+    where the fused entry is declined (Session(fuse_ema=False)): acg_ema_update behind the plain step.
+    ``lr_schedule`` (an LrSchedule of the scope, or None): the flat entry is the scheduled one (acg_adam_step_lr /
+    acg_rmsprop_step_lr), which also carries the average where the plain one would; a bf16 graph then takes the two-launch form
+    (the scheduled flat entry, then the refresh of the filter copies) - the one-launch update-and-refresh has no scheduled form."""
     is_optimizer_step = True
     joins_side = True        # reads every gradient of its scope, whichever stream produced it
 
-    def __init__(self, opt, scope, var_names, flat_param, flat_grad, slots, deps, grad_scale, ema=None):
+    def __init__(self, opt, scope, var_names, flat_param, flat_grad, slots, deps, grad_scale, ema=None, lr_schedule=None):
         super().__init__(flat_param.graph, opt.name + '/update', [flat_param, flat_grad] + slots, [], control_inputs=deps)
         self.opt, self.scope, self.var_names, self.grad_scale = opt, scope, list(var_names), grad_scale
         self.program_clip = None
-        self.ema = ema
+        self.ema, self.lr_schedule = ema, lr_schedule
         self._copies = [t for t3 in flat_param.graph.weight_copies.get(scope, []) for t in t3[1:]]
 
     @property
     def extras(self):
-        """What the launch touches besides its inputs (the session materialises it): the bf16 filter copies, the average's state."""
-        return self._copies + (self.ema.tensors() if self.ema is not None else [])
+        """What the launch touches besides its inputs (the session materialises it): the bf16 filter copies, the average's state,
+        the schedule's."""
+        return (self._copies + (self.ema.tensors() if self.ema is not None else [])
+                + (self.lr_schedule.tensors() if self.lr_schedule is not None else []))
 
     def bind(self, rt):
         opt, ema, clip, update = self.opt, self.ema, self.program_clip, None
@@ -250,7 +311,7 @@ class StepOp(G.Op):
                 return opt._bind_flat(rt, self, clip, ema)
         # bf16 pipeline: the conv kernels read bf16 copies of the filters, which follow the update.  Round 4: update and
         # refresh are ONE launch (acg_opt_step_prepare_bf16: the blocks that write a filter's copies update its elements) where
-        # every copy of the scope fits one list; else two launches as before
+        # every copy of the scope fits one list; else two launches as before (also with a learning-rate schedule)
         step = opt._bind_prepared(rt, self, clip) if rt.fuse_weight_refresh else None
         if step is None:
             step = _chain(opt._bind_flat(rt, self, clip), O.prepare_weights_launch(rt, self.graph, self.scope))
@@ -302,22 +363,30 @@ class Optimizer:
         return None
 
     def _bind_flat(self, rt, op, clip, ema=None):
-        """The flat entry over the scope's buffers; with ``ema`` the one that updates that weight average in the same launch."""
+        """The flat entry over the scope's buffers; with ``ema`` the one that updates that weight average in the same launch.
+        An op with a learning-rate schedule takes ``<entry>_lr``, whose tail holds the average's arguments or NULLs."""
         _, entry, hyper, slots, step = self._describe(op)
         p, g = op.inputs[:2]
         lo, hi = clip if clip else (0.0, 0.0)
         buffers = [p, g] + slots + ([step] if step is not None else [])
         args = tuple(_p(t.buf) for t in buffers) + (p.numel,) + tuple(h for h in hyper if h is not None)
-        args += (op.grad_scale, 1 if clip else 0, lo, hi) + (ema.args() if ema is not None else ())
+        args += (op.grad_scale, 1 if clip else 0, lo, hi)
+        if op.lr_schedule is not None:
+            import ctypes
+            sched, *state = op.lr_schedule.args()
+            args += (ctypes.byref(sched),) + tuple(state) + (ema.args() if ema is not None else (None, 0.0, None, None))
+            fn = _lib.entry(rt.lib, entry + '_lr')
+            return _chain(self._before(rt, op, step), lambda s, _keep=sched: fn(*args, s))
+        args += ema.args() if ema is not None else ()
         fn = _lib.entry(rt.lib, entry + ('_ema' if ema is not None else ''))
         return _chain(self._before(rt, op, step), lambda s: fn(*args, s))
 
     def _bind_prepared(self, rt, op, clip):
         """One launch for the update of the scope and the refresh of its bf16 filter copies, or None (no copies: a float32
-        graph; more filters than one list holds)."""
+        graph; more filters than one list holds; an update with a learning-rate schedule - acg_opt_args is ABI and holds none)."""
         import ctypes
         entries = op.graph.weight_copies.get(op.scope) or []
-        if not entries or len(entries) > _lib.PREP_MAX:
+        if not entries or len(entries) > _lib.PREP_MAX or op.lr_schedule is not None:
             return None
         kind, _, hyper, slots, step = self._describe(op)
         pl = _lib.PrepList()
@@ -335,10 +404,12 @@ class Optimizer:
         launch._keep = (oa, pl)
         return launch
 
-    def minimize(self, loss, var_list=None, slots_of=None, ema=None, clip_norm=None):
+    def minimize(self, loss, var_list=None, slots_of=None, ema=None, clip_norm=None, lr_schedule=None):
         """``ema``: a WeightAverage of the variables' scope; the update then also advances it (StepOp).
         ``clip_norm``: a GradNorm of the variables' scope; a ClipNormOp then sits between the gradients and the update
         (``step_op.clip_norm_op``) and the update waits for it alone.  None: nothing is built.
+        ``lr_schedule``: an LrSchedule of the variables' scope; the update then takes its rate from it and advances its counter
+        (StepOp).  Every StepOp given the same object shares the counter.  None: the rate is this optimizer's constant.
         ``slots_of``: the StepOp of an earlier ``minimize`` by an optimizer of this kind over the same scope; this update then
         continues that one's state (moments, step counter) instead of owning slots of its own - a second loss of one training
         run (train.Trainer's rollout G step continues the one-step G step's optimizer, and checkpoints hold one set of slots)."""
@@ -359,6 +430,8 @@ class Optimizer:
             if clip_norm.scope != scope or clip_norm.graph is not g:
                 raise ValueError('minimize: clip_norm measures scope %r, the variables are of scope %r' % (clip_norm.scope, scope))
             clip_norm.segments()         # (more variables than one segment list holds: ValueError before anything is built)
+        if lr_schedule is not None and (lr_schedule.scope != scope or lr_schedule.graph is not g):
+            raise ValueError('minimize: lr_schedule counts the updates of scope %r, the variables are of scope %r' % (lr_schedule.scope, scope))
         offsets, total, flat_param = g.layout(scope)
         flat_grad = g.new_state((total,), 0.0, self.name + '/flat_grad')
         heads = {}
@@ -386,7 +459,8 @@ class Optimizer:
         if clip_norm is not None:
             clip_op = ClipNormOp(clip_norm, flat_grad, deps, 1.0 / dp.world_size, self.name + '/clip_norm')
             deps = [clip_op]
-        step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size, ema=ema)
+        step_op = StepOp(self, scope, [v.name for v in var_list], flat_param, flat_grad, slots, deps, 1.0 / dp.world_size, ema=ema,
+                         lr_schedule=lr_schedule)
         step_op.clip_norm_op = clip_op
         step_op.reduce_ops = reduce_ops        # one of them can carry the step counter's increment (_step_inc_launch)
         return step_op

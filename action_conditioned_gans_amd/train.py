@@ -42,7 +42,8 @@ ACTION_DIM, STATE_DIM = 10, 5
 class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
-                 ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0):
+                 ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
+                 g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -95,7 +96,26 @@ class Trainer:
         stream), the 0 / 1 factor that switches the noise is not.  bf16 graphs take it (the action vector is float32 there too).
         More than one rank is allowed - the rank is the stream id of the draw, so ranks draw different z from one seed - but not
         verified.  Declined here: the look-ahead pair pass is switched off for Z > 0 (as it is for rollout_steps > 1), and
-        Z > 0 with ``rollout_steps`` > 1 or with ``bn_inference`` is a ValueError, as is Z outside 0..64."""
+        Z > 0 with ``rollout_steps`` > 1 or with ``bn_inference`` is a ValueError, as is Z outside 0..64.
+        ``g_lr`` / ``d_lr`` (None: the reference's constant - 1e-3 for Adam, 5e-5 for RMSProp; else finite and > 0): the learning rate
+        of every generator update (``pretrain_g``, ``train_g``, the two rollout steps) / of ``train_d``.  ``beta1`` (None: 0.9; else
+        0 <= beta1 < 1): Adam's first-moment decay for all of them; with ``arg_opt='rmsprop'`` a ValueError.  Plain floats to the
+        existing entries: no op, no state.
+        ``lr_schedule`` 'constant' | 'linear' | 'cosine' | 'exponential', ``lr_warmup``, ``lr_decay_steps``, ``lr_final`` (no
+        reference counterpart; 'constant' with ``lr_warmup=0`` builds nothing: the existing entries run, whatever the rates are):
+        each scope's rate rises linearly over its first ``lr_warmup`` updates and then decays from 1 x to ``lr_final`` x the scope's
+        rate over ``lr_decay_steps`` updates (optim.LrSchedule; exponential: lr_final ** (j / lr_decay_steps), not clamped).  One
+        LrSchedule per scope, the same shape for G and D - ``lr_warmup`` / ``lr_decay_steps`` are counts of UPDATES and may be given
+        as a pair (G's, D's) where the two scopes update at different paces - and each scope counts its own updates on the device:
+        ``pretrain_g``, ``train_g`` and the two rollout steps share G's counter (so it counts the pretraining updates too),
+        ``train_d`` has D's, which exists only with ``arg_adv``.  The optimizer's launch evaluates the rate itself (acg_adam_step_lr /
+        acg_rmsprop_step_lr), so the replayed HIP graph of a step follows the schedule with no host in the loop; no op is added, and
+        ``g/lr/updates`` / ``d/lr/updates`` are the only new checkpoint keys (a restored run continues its schedule; a checkpoint
+        without them starts at 0).  Every generator, bf16 graphs (the update and the refresh of the bf16 filter copies are then two
+        launches, not one), the look-ahead path, rollout_steps > 1, ema_decay, ssim_weight, the clip norms, noise and bn_inference
+        take it.  With more than one rank every rank advances its own, identical counter: allowed, not verified there.
+        ``learning_rates()`` reads the rates the last updates used."""
+        self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
         ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.ssim_weight = check_ssim_weight(ssim_weight)
@@ -223,21 +243,30 @@ class Trainer:
         self.d_vars = graph.trainable_variables('d')
         self.clip_d = [optim.clip_by_value_assign(p, -CLIP_VALUE, CLIP_VALUE) for p in self.d_vars]
 
+        la = self.lr_args
         if arg_opt == 'rmsprop':
-            make = lambda name: optim.RMSPropOptimizer(RMSPROP_LR, name=name)
+            make = lambda name: optim.RMSPropOptimizer(la['d_lr' if name.startswith('d_') else 'g_lr'], name=name)
         elif arg_opt == 'adam':
-            make = lambda name: optim.AdamOptimizer(ADAM_LR, name=name)
+            adam_kw = {} if la['beta1'] is None else {'beta1': la['beta1']}
+            make = lambda name: optim.AdamOptimizer(la['d_lr' if name.startswith('d_') else 'g_lr'], name=name, **adam_kw)
         else:
             raise ValueError('unexpected opt argument')
+        # scope -> the optim.LrSchedule every update of the scope shares (None: the scope's rate is its constant)
+        self.lr_sched = {'g': None, 'd': None}
+        if la['scheduled']:
+            for k, scope in enumerate('gd' if arg_adv else 'g'):
+                self.lr_sched[scope] = optim.LrSchedule(la['schedule'], scope, la['warmup'][k], la['decay_steps'][k], la['final'])
+        g_sched, d_sched = self.lr_sched['g'], self.lr_sched['d']
         self.ema = optim.WeightAverage(ema_decay, 'g') if ema_decay else None      # shared by every G update of this Trainer
         self._ema_swapped = False
         # scope -> the optim.GradNorm every update of the scope shares (None: neither clipped nor measured)
         self.grad_norm = {'g': optim.GradNorm(self.g_clip_norm or math.inf, 'g') if self.g_clip_norm or grad_norms else None,
                           'd': optim.GradNorm(self.d_clip_norm or math.inf, 'd') if arg_adv and (self.d_clip_norm or grad_norms) else None}
         g_norm, d_norm = self.grad_norm['g'], self.grad_norm['d']
-        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm)
-        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm)
-        self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars, clip_norm=d_norm)
+        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm, lr_schedule=g_sched)
+        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm,
+                                                                 lr_schedule=g_sched)
+        self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars, clip_norm=d_norm, lr_schedule=d_sched)
 
         # the seven tf.summary scalars of ops.py:48-49 / train.py:104-111, names kept
         self.summaries.update({'discriminator_loss': self.d_loss, 'g_loss': self.g_loss, 'g_l2_loss': g_l2_loss,
@@ -268,6 +297,24 @@ class Trainer:
         for norm in self.grad_norm.values():
             if norm is not None:
                 norm.build()        # (the same: after everything else)
+        for sched in self.lr_sched.values():
+            if sched is not None:
+                sched.build()       # (and the schedules' counters last of all)
+
+    # ---- learning rates (g_lr / d_lr / lr_schedule)
+    def learning_rates(self):
+        """-> {'g': {'lr', 'updates'}, 'd': {...}}: the rate the last update of the scope used, as the float32 the kernel read, and
+        the scope's update counter.  A scope without a schedule reports its constant and ``updates`` None (it keeps no counter); a
+        scheduled scope reports 0.0 before its first update.  One small device-to-host copy per scheduled scope and value (a
+        synchronisation)."""
+        out = {}
+        for scope in ('g', 'd'):
+            sched = self.lr_sched[scope]
+            if sched is None:
+                out[scope] = {'lr': float(np.float32(self.lr_args[scope + '_lr'])), 'updates': None}
+            else:
+                out[scope] = {'lr': float(self.sess._materialize(sched.lr).item()), 'updates': int(self.sess._materialize(sched.updates).item())}
+        return out
 
     # ---- the generator's noise input (noise_dim > 0)
     def _check_noise_mode(self, noise):
@@ -509,10 +556,10 @@ class Trainer:
                 act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
         total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
         self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op, ema=self.ema,
-                                                               clip_norm=self.grad_norm['g'])
+                                                               clip_norm=self.grad_norm['g'], lr_schedule=self.lr_sched['g'])
         self.g_rollout_pretrain_opt_op = make('g_pretrain_opt_rollout').minimize(l2_total / K, var_list=self.g_vars,
                                                                                 slots_of=self.g_pretrain_opt_op, ema=self.ema,
-                                                                                clip_norm=self.grad_norm['g'])
+                                                                                clip_norm=self.grad_norm['g'], lr_schedule=self.lr_sched['g'])
 
     def _rollout_feed(self, frames, actions, states):
         """frames [B, K+1, H, W, 3] (t .. t+K), actions [B, K, 10] (a_t .. a_{t+K-1}, state half read at step 0 only by the DNA
@@ -794,6 +841,62 @@ def check_clip_norm(value, what='clip_norm'):
     return x
 
 
+LR_SCHEDULES = ('constant', 'linear', 'cosine', 'exponential')
+
+
+def check_lr(g_lr=None, d_lr=None, beta1=None, arg_opt='adam', lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0):
+    """ValueError for learning-rate arguments the Trainer does not take: a rate that is not finite and > 0 (in float32 too),
+    ``beta1`` outside [0, 1) or given with RMSProp, an unknown schedule, a negative or non-integer ``lr_warmup`` / ``lr_decay_steps``
+    (an int, or a pair (G's, D's)), a decaying schedule with ``lr_decay_steps`` < 1, ``lr_final`` outside [0, 1] (exponential:
+    (0, 1]).  -> {'g_lr', 'd_lr' (None replaced by the reference's constant), 'beta1' (or None), 'schedule', 'warmup' and
+    'decay_steps' (pairs), 'final', 'scheduled' (whether anything but the existing entries is needed)}."""
+    default = RMSPROP_LR if arg_opt == 'rmsprop' else ADAM_LR
+    rates = {}
+    for what, v in (('g_lr', g_lr), ('d_lr', d_lr)):
+        if v is None:
+            rates[what] = default
+            continue
+        try:
+            x = float(v)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a finite number > 0, got %r' % (what, v))
+        if isinstance(v, bool) or not 0.0 < x <= float(np.finfo(np.float32).max) or float(np.float32(x)) == 0.0:
+            raise ValueError('%s must be finite and > 0, got %r' % (what, v))
+        rates[what] = x
+    if beta1 is not None:
+        if arg_opt == 'rmsprop':
+            raise ValueError("beta1 is Adam's: it does not go with the rmsprop optimizer")
+        try:
+            b = float(beta1)
+        except (TypeError, ValueError):
+            raise ValueError('beta1 must be a number in [0, 1), got %r' % (beta1,))
+        if isinstance(beta1, bool) or not 0.0 <= b < 1.0 or not float(np.float32(b)) < 1.0:
+            raise ValueError('beta1 must lie in [0, 1), got %r' % (beta1,))
+        beta1 = b
+    if lr_schedule not in LR_SCHEDULES:
+        raise ValueError('lr_schedule must be one of %s, got %r' % (', '.join(LR_SCHEDULES), lr_schedule))
+    counts = {}
+    for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
+        pair = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if len(pair) != 2 or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < 2 ** 63 for c in pair):
+            raise ValueError("%s must be an integer >= 0 (or a pair of them: G's, D's), got %r" % (what, v))
+        counts[what] = (int(pair[0]), int(pair[1]))
+    try:
+        final = float(lr_final)
+    except (TypeError, ValueError):
+        raise ValueError('lr_final must be a number in [0, 1], got %r' % (lr_final,))
+    if isinstance(lr_final, bool) or not 0.0 <= final <= 1.0:
+        raise ValueError('lr_final must lie in [0, 1], got %r' % (lr_final,))
+    if lr_schedule != 'constant':
+        if min(counts['lr_decay_steps']) < 1:
+            raise ValueError('lr_schedule %r needs lr_decay_steps >= 1, got %r' % (lr_schedule, lr_decay_steps))
+        if lr_schedule == 'exponential' and not float(np.float32(final)) > 0.0:
+            raise ValueError("lr_schedule 'exponential' needs lr_final in (0, 1], got %r" % (lr_final,))
+    return {'g_lr': rates['g_lr'], 'd_lr': rates['d_lr'], 'beta1': beta1, 'schedule': lr_schedule, 'warmup': counts['lr_warmup'],
+            'decay_steps': counts['lr_decay_steps'], 'final': final,
+            'scheduled': lr_schedule != 'constant' or max(counts['lr_warmup']) > 0}
+
+
 def check_noise_seed(seed):
     """ValueError for a noise seed (or counter) that is not an integer in [0, 2^64); -> it as an int."""
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
@@ -971,10 +1074,13 @@ class _PairSelections:
         return self.queue.pop(0)
 
 
-def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0):
+def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0,
+                 rates=None):
     """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
     the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
-    ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0."""
+    ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0.
+    ``rates``: Trainer.learning_rates() of a run with a learning-rate schedule (None: no field is added) -> ``g_lr`` / ``d_lr``, the
+    rates the iteration's last updates used."""
     record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
                   **({'g_ema': ema_decay} if ema_decay else {}),
                   **({'ssim_weight': ssim_weight} if ssim_weight else {}),
@@ -984,6 +1090,8 @@ def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_wei
         record[scope + '_clip_scale'] = grad_stats[scope]['scale']
     for scope in sorted(clip_bounds or {}, reverse=True):
         record[scope + '_clip_norm'] = clip_bounds[scope]
+    for scope in sorted(rates or {}, reverse=True):
+        record[scope + '_lr'] = rates[scope]['lr']
     return record
 
 
@@ -998,7 +1106,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           eval_every=500, resume=None, dtype='f32', sync_bn=False, exact_global_batch=False, dp_collectives=None, buckets=0,
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
-          noise_dim=0, noise_seed=0):
+          noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
+          lr_final=0.0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1028,7 +1137,17 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     interval (the scopes that are measured) and the configured bounds once, in its first record.  Checkpoints are unchanged.
     ``noise_dim`` Z > 0 / ``noise_seed``: the generator reads Z noise values drawn on the device (Trainer, same keywords); the loop
     takes the plain call path (no look-ahead pass), checkpoints hold ``g/noise/state``, ``train.jsonl`` records ``noise_dim`` and
-    the evaluation block predicts with z = 0."""
+    the evaluation block predicts with z = 0.
+    ``g_lr`` / ``d_lr`` / ``beta1``: the rates of the G and D updates and Adam's beta1 (Trainer, same keywords; None: the
+    reference's).  ``lr_schedule`` / ``lr_warmup`` / ``lr_decay_steps`` / ``lr_final``: a learning-rate schedule (Trainer, same
+    keywords), with ``lr_warmup`` and ``lr_decay_steps`` given in TRAINING ITERATIONS: D's schedule gets them multiplied by its
+    updates per iteration (``n_critic``; 5 for the wass loss, else 1), G's gets them as they are.  G's counter also counts the
+    ``pretrain_iter`` pretraining updates, so its warmup starts there.  With a schedule ``train.jsonl`` records ``g_lr`` / ``d_lr``,
+    the rates of the iteration's last updates, and checkpoints hold the counters; without one both are unchanged."""
+    for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
+        if isinstance(v, (tuple, list)):
+            raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
+    la = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)
     noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
     ema_decay = check_ema_decay(ema_decay)
     ssim_weight = check_ssim_weight(ssim_weight)
@@ -1061,7 +1180,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
                               select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
                               ema_decay=ema_decay, ssim_weight=ssim_weight, g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm,
-                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed)
+                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed, lr_args=la)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -1077,8 +1196,15 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
                 num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
-                noise_dim=0, noise_seed=0):
+                noise_dim=0, noise_seed=0, lr_args=None):
     ema = {'ema_decay': ema_decay} if ema_decay else {}
+    D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
+    la = lr_args or check_lr(arg_opt=arg_opt)
+    if la != check_lr(arg_opt=arg_opt):
+        ema.update(g_lr=la['g_lr'], d_lr=la['d_lr'], beta1=la['beta1'])
+    if la['scheduled']:                 # iterations -> updates: D takes D_per_G of them per iteration
+        ema.update(lr_schedule=la['schedule'], lr_final=la['final'], lr_warmup=(la['warmup'][0], la['warmup'][0] * D_per_G),
+                   lr_decay_steps=(la['decay_steps'][0], la['decay_steps'][0] * D_per_G))
     if noise_dim:
         ema.update(noise_dim=noise_dim, noise_seed=noise_seed)
     if ssim_weight:
@@ -1102,7 +1228,6 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             eval_data = PushDataset(input_path, batch_size, training=False, img_size=img_size, seed=1007)
         except RuntimeError:
             eval_data = PushDataset(input_path, batch_size, training=True, img_size=img_size, seed=1007)
-    D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
     log_file = os.path.join(log_dir, 'train.jsonl') if log_dir else None
     t0 = time.time()
     bounds_logged = False
@@ -1159,7 +1284,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             if log_file and summ:
                 stats = {sc: trainer.grad_norm_stats(sc) for sc, norm in trainer.grad_norm.items() if norm is not None}
                 bounds = None if bounds_logged or not stats else {'g': g_clip_norm, 'd': d_clip_norm}
-                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds, noise_dim))
+                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds, noise_dim,
+                                                    trainer.learning_rates() if la['scheduled'] else None))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
@@ -1270,6 +1396,28 @@ def check_noise_args(parser, args):
         parser.error('--noise_dim / --noise_seed: %s' % e)
 
 
+def add_lr_args(parser):
+    """The learning-rate flags: the rates of G and D, Adam's beta1 and the schedule."""
+    parser.add_argument('--g_lr', type=float, default=None, metavar='LR', help='learning rate of the generator updates (default: 1e-3 for adam, 5e-5 for rmsprop)')
+    parser.add_argument('--d_lr', type=float, default=None, metavar='LR', help='learning rate of the discriminator updates (same default)')
+    parser.add_argument('--beta1', type=float, default=None, metavar='B', help="Adam's beta1 for every update (0 <= B < 1; default 0.9; --opt adam only)")
+    parser.add_argument('--lr_schedule', type=str, default='constant',
+                        help='constant, linear, cosine or exponential: how the rates decay behind the warmup, evaluated on the device '
+                             'inside the optimizer launch (constant with --lr_warmup 0: off)')
+    parser.add_argument('--lr_warmup', type=int, default=0, metavar='N', help='raise the rates linearly over the first N training iterations')
+    parser.add_argument('--lr_decay_iters', type=int, default=0, metavar='N', help='training iterations over which the rates decay (behind the warmup)')
+    parser.add_argument('--lr_final', type=float, default=0.0, metavar='F',
+                        help='the rates end at F x their value (0 <= F <= 1; exponential: F x per --lr_decay_iters iterations, 0 < F)')
+
+
+def check_lr_args(parser, args):
+    """parser.error for learning-rate flags the Trainer does not take (before anything is created)."""
+    try:
+        check_lr(args.g_lr, args.d_lr, args.beta1, args.opt, args.lr_schedule, args.lr_warmup, args.lr_decay_iters, args.lr_final)
+    except ValueError as e:
+        parser.error('--g_lr / --d_lr / --beta1 / --lr_*: %s' % e)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='action-conditioned video-prediction GAN on MI355X')
     parser.add_argument('input_path', type=str)
@@ -1323,7 +1471,9 @@ def main(argv=None):
                         help='record the gradient norms of G and D in train.jsonl (g_grad_norm, d_grad_norm, ..._clip_scale), also '
                              'where no bound is set')
     add_noise_args(parser)
+    add_lr_args(parser)
     args = parser.parse_args(argv)
+    check_lr_args(parser, args)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
     try:
@@ -1361,7 +1511,9 @@ def main(argv=None):
                     data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
                     data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema,
                     ssim_weight=args.ssim_weight, g_clip_norm=args.g_clip_norm, d_clip_norm=args.d_clip_norm,
-                    grad_norms=args.log_grad_norms, noise_dim=args.noise_dim, noise_seed=args.noise_seed)
+                    grad_norms=args.log_grad_norms, noise_dim=args.noise_dim, noise_seed=args.noise_seed, g_lr=args.g_lr, d_lr=args.d_lr,
+                    beta1=args.beta1, lr_schedule=args.lr_schedule, lr_warmup=args.lr_warmup, lr_decay_steps=args.lr_decay_iters,
+                    lr_final=args.lr_final)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

@@ -15,6 +15,12 @@
  *
  * The action vector on the device is this header's, so the generator's noise input - a latent drawn on the device and appended
  * to that vector, the last entry below - is declared here as well: same conventions, same table, no atomics.
+ *
+ * acg_grad_clip_norm is "what sits in front of the optimizer update", and so is the learning rate: the two optimizer steps whose
+ * rate follows a schedule evaluated INSIDE their launch, from an update counter on the device that the launch advances itself
+ * (acg_adam_step_lr / acg_rmsprop_step_lr, at the end of this header).  A rate passed by value is frozen into a captured graph of
+ * the step; this one changes with every replay and no host in the loop.  Same conventions, same table; the only atomics are
+ * those of the counter advance, which is the weight average's (include/acgan_ema.h).
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -91,6 +97,48 @@ int32_t acg_grad_clip_norm(float* grad, int64_t n, const acg_norm_segments* segs
 #define ACG_NOISE_VALUES_MAX 8192
 int32_t acg_noise_concat(const float* actions, uint64_t* state, const float* scale, float* out, int32_t batch, int32_t action_dim,
                          int32_t noise_dim, int32_t stream_id, acg_stream_t stream);
+
+/* Optimizer steps with a learning-rate schedule.  acg_adam_step / acg_rmsprop_step (acgan_hip.h) with the base rate `lr` replaced
+ * by lr_k, the schedule's rate at k = lr_updates[0] as the launch finds it; with `shadow` not NULL the launch also carries the
+ * weight average, exactly as acg_adam_step_ema / acg_rmsprop_step_ema do (acgan_ema.h; shadow NULL: no average, ema_decay,
+ * num_updates and state are ignored).  With F = (double)final_factor, everything in double:
+ *   w = (warmup > 0 && k < warmup) ? (k + 1) / warmup : 1
+ *   j = max(k - warmup, 0),   t = min(j / decay_steps, 1)
+ *   ACG_LR_CONSTANT:     f = 1                                          (decay_steps and final_factor are not read)
+ *   ACG_LR_LINEAR:       f = 1 - (1 - F) * t
+ *   ACG_LR_COSINE:       f = F + (1 - F) * 0.5 * (1 + cos(pi * t))
+ *   ACG_LR_EXPONENTIAL:  f = pow(F, j / decay_steps)                    (not clamped: tf.train.exponential_decay, no staircase)
+ *   lr_k = (float)((double)lr * w * f)
+ * and Adam's bias-corrected rate is (float)((double)lr_k * sqrt(1 - beta2^t) / (1 - beta1^t)) with its own step counter t, as
+ * before.  Given the same rate the update is that of the plain entries bit for bit: parameters, slots and shadow come out as
+ * acg_adam_step / acg_rmsprop_step (or their _ema forms) called with lr = lr_k leave them.
+ * `sched` is read on the host during the call and copied into the kernel arguments: nothing of it is referenced afterwards, a
+ * captured graph replays the call.  One launch: one thread of every block reads the counter and evaluates lr_k (every block the
+ * same value), block 0 stores lr_out[0] = lr_k, and the last block to retire stores lr_updates[0] = k + 1 and resets lr_state[0]
+ * - the rule of the average's counter (acgan_ema.h), each counter with a state word of its own: one state word belongs to one
+ * counter.  lr_updates int64 [1] (8-byte aligned), lr_state uint32 [1] (0 before the first launch), lr_out float32 [1], all in
+ * device memory and distinct from the average's.  Calls that share a counter must be stream-ordered.
+ * Checked on the host before anything is launched: sched, lr_updates, lr_state, lr_out not NULL and aligned; lr finite and > 0;
+ * kind one of the four; warmup >= 0; for every kind but constant decay_steps >= 1 and 0 <= final_factor <= 1 (exponential:
+ * 0 < final_factor <= 1); the average's arguments as in acgan_ema.h. */
+#define ACG_LR_CONSTANT 0
+#define ACG_LR_LINEAR 1
+#define ACG_LR_COSINE 2
+#define ACG_LR_EXPONENTIAL 3
+typedef struct acg_lr_schedule {
+  int32_t kind;
+  int64_t warmup;
+  int64_t decay_steps;
+  float final_factor;
+} acg_lr_schedule;
+int32_t acg_adam_step_lr(float* param, const float* grad, float* m, float* v, const int32_t* step_dev, int64_t n, float lr,
+                         float beta1, float beta2, float eps, float grad_scale, int32_t use_clip, float clip_lo, float clip_hi,
+                         const acg_lr_schedule* sched, int64_t* lr_updates, uint32_t* lr_state, float* lr_out, float* shadow,
+                         float ema_decay, int64_t* num_updates, uint32_t* state, acg_stream_t stream);
+int32_t acg_rmsprop_step_lr(float* param, const float* grad, float* ms, int64_t n, float lr, float decay, float eps,
+                            float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, const acg_lr_schedule* sched,
+                            int64_t* lr_updates, uint32_t* lr_state, float* lr_out, float* shadow, float ema_decay,
+                            int64_t* num_updates, uint32_t* state, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
