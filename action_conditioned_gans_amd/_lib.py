@@ -75,6 +75,12 @@ class LrSched(ctypes.Structure):
     _fields_ = [('kind', c_int32), ('warmup', c_int64), ('decay_steps', c_int64), ('final_factor', c_float)]
 
 
+class SsSched(ctypes.Structure):
+    """struct acg_ss_schedule (acg_sched_sample_draw; include/acgan_rollout.h)."""
+    KINDS = ('constant', 'linear', 'inverse_sigmoid')               # ACG_SS_*
+    _fields_ = [('kind', c_int32), ('offset', c_int64), ('decay_steps', c_int64), ('start', c_float), ('final', c_float)]
+
+
 class OptArgs(ctypes.Structure):
     """struct acg_opt_args (acg_opt_step_prepare_bf16)."""
     _fields_ = [('kind', c_int32), ('lr', c_float), ('beta1_or_decay', c_float), ('beta2', c_float), ('eps', c_float),
@@ -211,9 +217,9 @@ EXTENSIONS = {
     # gradient buffer that bounds them (optim.ClipNormOp); the header owns the device-side action vector, so the noise that is
     # appended to it - drawn on the device, the counter advanced by the kernel (ops.NoiseOp) - is here too; and, beside the clip as
     # "what sits in front of the optimizer update", the optimizer steps that evaluate a learning-rate schedule inside their launch
-    # from an update counter they advance themselves (optim.LrSchedule)
-    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, the gradient clip, the noise input and learning-rate '
-                         'schedules run on the HIP library only', {
+    # from an update counter they advance themselves (optim.LrSchedule); and scheduled sampling of the rollout's fed-back inputs
+    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, scheduled sampling, the gradient clip, the noise input '
+                         'and learning-rate schedules run on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
         'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
@@ -223,6 +229,10 @@ EXTENSIONS = {
                                       ctypes.POINTER(LrSched), _P, _P, _P, _P, c_float, _P, _P, _P]),
         'acg_rmsprop_step_lr': (STATUS, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, c_float,
                                          ctypes.POINTER(LrSched), _P, _P, _P, _P, c_float, _P, _P, _P]),
+        # scheduled sampling of the K-step rollout (ops.SchedSampleDrawOp / SchedSampleOp): coins, row select, adjoint
+        'acg_sched_sample_draw': (STATUS, [_P, ctypes.POINTER(SsSched), _P, _P, c_int32, c_int32, c_int32, _P]),
+        'acg_sched_sample_fwd': (STATUS, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int32, c_int32, _P]),
+        'acg_sched_sample_bwd': (STATUS, [_P, _P, _P, c_int64, _P, _P, c_int32, c_int32, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)

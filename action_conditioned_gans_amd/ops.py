@@ -1228,6 +1228,109 @@ class NoiseOp(G.Op):
         return [SliceOp(gouts[0], 0, a.shape[-1], a.shape, self.name + '/bwd').outputs[0] if needs[0] else None]
 
 
+SCHED_SAMPLING_STATE = 'g/sched_sampling/state'
+SCHED_SAMPLING_KINDS = _lib.SsSched.KINDS
+
+
+def sched_sampling_state(seed=0):
+    """The scheduled-sampling state of the graph, created by the first call (``seed`` is read by that call alone):
+    ``g/sched_sampling/state``, {seed, counter} - uint64 [2] to the kernel, which advances the counter (the number of K-step
+    updates so far); torch holds the same bits as int64 [2] - initialised to {seed, 0}; named graph state and so a checkpoint key,
+    exactly as ``g/noise/state`` is."""
+    g = G.get_default_graph()
+    if 'sched_sampling' not in g.collections:
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError('scheduled-sampling seed must be in [0, 2^64), got %r' % (seed,))
+        g.collections['sched_sampling'] = g.new_state((2,), (seed - 2 ** 64 if seed >= 2 ** 63 else seed, 0), SCHED_SAMPLING_STATE,
+                                                      dtype=torch.int64)
+    return g.collections['sched_sampling']
+
+
+class SchedSampleDrawOp(G.Op):
+    """The coins of a K-step program (acg_sched_sample_draw): -> mask [steps, B] float32 (1: the step that follows slot s reads the
+    truth) and prob [1], the probability of truth the schedule ``kind`` gives at the graph's scheduled-sampling counter, which the
+    launch advances - a program that holds this op draws fresh coins, further along the schedule, every time it runs, replayed
+    from a captured graph or not.  The stream id of the draw is the data-parallel rank.  No inputs, no gradient."""
+
+    def __init__(self, steps, batch, kind, start, final, decay_steps, offset, name):
+        if kind not in SCHED_SAMPLING_KINDS:
+            raise ValueError('sched_sample_draw: kind must be one of %s, got %r' % (', '.join(SCHED_SAMPLING_KINDS), kind))
+        steps, batch = int(steps), int(batch)
+        if not 1 <= steps * batch <= _lib.NOISE_VALUES_MAX or steps < 1:
+            raise ValueError('sched_sample_draw: %d x %d coins (1 <= steps * batch <= %d)' % (steps, batch, _lib.NOISE_VALUES_MAX))
+        self.sched = (SCHED_SAMPLING_KINDS.index(kind), int(offset), int(decay_steps), float(start), float(final))
+        self.extras = [sched_sampling_state()]
+        super().__init__(G.get_default_graph(), name, [], [_new((steps, batch), name + ':mask'), _new((1,), name + ':prob')])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'sched_sample_draw')
+        mask, prob = self.outputs
+        self._sched = _lib.SsSched(*self.sched)        # read by the call itself, nothing of it is referenced afterwards
+        args = (_p(self.extras[0].buf), ctypes.byref(self._sched), _p(mask.buf), _p(prob.buf), mask.shape[0], mask.shape[1], int(rt.rank))
+        return lambda s: fn(*args, s)
+
+
+class SchedSampleOp(G.Op):
+    """Scheduled sampling at one fed-back position (acg_sched_sample_fwd): row b of the result is the true frame (and state) where
+    ``mask_row`` [B] is set and the predicted one elsewhere, a copy of bits, frame and state under the same coin in one launch.
+    ``pred_state`` / ``true_state`` None: the frame alone (the plain generator).  The gradient goes to the predicted inputs only
+    (SchedSampleBwdOp: zero rows where the truth was read); the truth and the mask are inputs without one."""
+
+    def __init__(self, mask_row, pred, truth, pred_state, true_state, name):
+        b = pred.shape[0]
+        pairs = [(pred, truth)] + ([(pred_state, true_state)] if pred_state is not None else [])
+        if (pred_state is None) != (true_state is None):
+            raise ValueError('sched_sample: the predicted and the true state come together')
+        for p, t in pairs:
+            if p.shape != t.shape or p.shape[0] != b or p.dtype != torch.float32 or t.dtype != torch.float32 or p.valid_c or t.valid_c:
+                raise ValueError('sched_sample: predicted %s %s and true %s %s must be dense float32 of one shape' % (p.dtype, p.shape, t.dtype, t.shape))
+        if mask_row.shape != (b,) or mask_row.dtype != torch.float32:
+            raise ValueError('sched_sample: mask row %s %s, expected float32 [%d]' % (mask_row.dtype, mask_row.shape, b))
+        self.with_state = pred_state is not None
+        outs = [_new(pred.shape, name + ':0')] + ([_new(pred_state.shape, name + ':state')] if self.with_state else [])
+        super().__init__(G.get_default_graph(), name, [mask_row] + [t for pair in pairs for t in pair], outs)
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'sched_sample_fwd')
+        mask, pred, truth = self.inputs[:3]
+        b = pred.shape[0]
+        st = [_p(t.buf) for t in (self.inputs[3], self.inputs[4], self.outputs[1])] if self.with_state else [None, None, None]
+        args = (_p(mask.buf), _p(pred.buf), _p(truth.buf), _p(self.outputs[0].buf), pred.numel // b, *st,
+                self.inputs[3].numel // b if self.with_state else 0, b)
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        want = [needs[1] and gouts[0] is not None, self.with_state and needs[3] and gouts[1] is not None]
+        if not any(want):
+            return [None] * len(self.inputs)
+        op = SchedSampleBwdOp(self.inputs[0], gouts[0] if want[0] else None, gouts[1] if want[1] else None, self.name + '/bwd')
+        return [None, op.dframe, None] + ([op.dstate, None] if self.with_state else [])
+
+
+class SchedSampleBwdOp(G.Op):
+    """acg_sched_sample_bwd: the gradient of the predicted frame and state of a SchedSampleOp - the output's gradient in the rows
+    that read the prediction, +0 in the rows that read the truth; one launch for both (either may be None)."""
+
+    def __init__(self, mask_row, dout, dout_state, name):
+        self.dframe = _new(dout.shape, name + ':0') if dout is not None else None
+        self.dstate = _new(dout_state.shape, name + ':state') if dout_state is not None else None
+        super().__init__(G.get_default_graph(), name, [mask_row] + [t for t in (dout, dout_state) if t is not None],
+                         [t for t in (self.dframe, self.dstate) if t is not None])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'sched_sample_bwd')
+        mask = self.inputs[0]
+        b = mask.shape[0]
+        rest = list(self.inputs[1:])
+        dout = rest.pop(0) if self.dframe is not None else None
+        dstate = rest.pop(0) if self.dstate is not None else None
+        args = (_p(mask.buf), _p(dout.buf) if dout is not None else None, _p(self.dframe.buf) if dout is not None else None,
+                dout.numel // b if dout is not None else 0, _p(dstate.buf) if dstate is not None else None,
+                _p(self.dstate.buf) if dstate is not None else None, dstate.numel // b if dstate is not None else 0, b)
+        return lambda s: fn(*args, s)
+
+
 class ConcatChannelsOp(G.Op):
     """a ++ b on the channel axis; ``pitch`` > ca+cb stores the result with zero pad channels (``valid_c`` set);
     ``act``: the result is an activation (the conv-facing discriminator input: bf16 in a bf16 graph)."""
@@ -1627,6 +1730,17 @@ def rollout_actions(command, state, name='rollout_actions'):
     if len(command.shape) != 2 or len(state.shape) != 2 or command.shape[0] != state.shape[0]:
         raise ValueError('rollout_actions: [B, A] command and [B, S] state expected, got %s and %s' % (command.shape, state.shape))
     return ConcatChannelsOp(command, state, _scope_name(name)).outputs[0]
+
+
+def sched_sample_draw(steps, batch, kind, start=1.0, final=0.0, decay_steps=0, offset=0, name='sched_sample/draw'):
+    """The coins of a K-step program: -> (mask [steps, batch], prob [1]) (SchedSampleDrawOp)."""
+    return tuple(SchedSampleDrawOp(steps, batch, kind, start, final, decay_steps, offset, _scope_name(name)).outputs)
+
+
+def sched_sample(mask_row, pred, truth, pred_state=None, true_state=None, name='sched_sample'):
+    """Per sample the true or the predicted frame (and state) by ``mask_row`` [B]: -> (frame, state or None) (SchedSampleOp)."""
+    outs = SchedSampleOp(mask_row, pred, truth, pred_state, true_state, _scope_name(name)).outputs
+    return outs[0], (outs[1] if len(outs) > 1 else None)
 
 
 def append_noise(actions, noise_dim, name='noise'):

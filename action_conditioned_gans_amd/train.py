@@ -43,7 +43,8 @@ class Trainer:
     def __init__(self, sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size=64, img_size=64, ksize=5,
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
                  ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
-                 g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0):
+                 g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
+                 sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -114,9 +115,29 @@ class Trainer:
         without them starts at 0).  Every generator, bf16 graphs (the update and the refresh of the bf16 filter copies are then two
         launches, not one), the look-ahead path, rollout_steps > 1, ema_decay, ssim_weight, the clip norms, noise and bn_inference
         take it.  With more than one rank every rank advances its own, identical counter: allowed, not verified there.
-        ``learning_rates()`` reads the rates the last updates used."""
+        ``learning_rates()`` reads the rates the last updates used.
+        ``sched_sampling`` 'off' | 'constant' | 'linear' | 'inverse_sigmoid', ``ss_start``, ``ss_final``, ``ss_decay_steps``,
+        ``ss_offset``, ``ss_seed`` (no reference counterpart; 'off' builds nothing: ops, op order, state names and checkpoint keys are
+        those of a Trainer without the arguments; any other kind needs ``rollout_steps`` > 1): scheduled sampling (Bengio et al. 2015)
+        of the K-step programs.  At each of the K - 1 fed-back positions a coin per sample decides whether step j reads the true
+        frame t + j and state s_{t+j} (the values fed as ``rollout/next_frame{j-1}`` / ``rollout/next_state{j-1}``) or the ones step
+        j - 1 predicted - frame and state under the same coin; the plain generator mixes frames only.  The probability of truth is
+        ``ss_start`` ('constant'), or moves from ``ss_start`` to ``ss_final`` over ``ss_decay_steps`` K-step updates, linearly or
+        along Bengio's inverse sigmoid, starting after ``ss_offset`` updates (ops.SchedSampleDrawOp; acg_sched_sample_draw has the
+        formulas).  At p = 1 the program is K teacher-forced steps, at p = 0 the rollout step without the arguments (the same
+        frames bit for bit).  The coins are drawn on the device inside the program - one draw per program, one select and one
+        adjoint launch per fed-back position, 1 + 2 (K - 1) launches in all - from the graph state ``g/sched_sampling/state`` =
+        {``ss_seed``, counter}, which the draw advances: the counter is the number of K-step updates, ``pretrain_g_rollout``'s
+        included, and a replayed HIP graph draws fresh coins and moves along the schedule with no host in the loop.  The state is
+        the only new checkpoint key (a restored run continues its coins and its schedule; a checkpoint without it starts at 0); no
+        variable and no optimizer slot is added.  The losses of step j and its D(fake) input are built on the mixed input.
+        ``sched_sampling_last()`` reads the last program's probability and coins; ``test`` / ``test_sequence`` / ``rollout_metrics``
+        never sample.  A coin per batch row, not per pixel; whatever ``rollout_steps`` > 1 declines (bf16, more than one rank, the
+        CDNA generator, noise) is declined here too."""
         self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
+        self.sched_sampling = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, ss_offset, ss_seed, rollout_steps,
+                                                   batch_size)      # (None: off)
         ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.ssim_weight = check_ssim_weight(ssim_weight)
         self.g_clip_norm, self.d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
@@ -360,6 +381,35 @@ class Trainer:
         state.copy_(torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64))
         self._announced = None
 
+    # ---- scheduled sampling of the K-step programs (sched_sampling != 'off')
+    def _require_sched_sampling(self):
+        if self.sched_sampling is None:
+            raise RuntimeError("this Trainer was built with sched_sampling='off': its K-step programs draw no coins")
+
+    def sched_sampling_last(self):
+        """-> {'prob': the probability of truth the last K-step program used (the float32 the kernel compared with), 'mask': bool
+        [K - 1, B], True where step j + 1 read the truth at position j}; prob 0.0 and no truth before the first program.  One
+        device-to-host copy of both (a synchronisation)."""
+        self._require_sched_sampling()
+        vals = torch.cat([self.sess._materialize(self._ss_prob).detach().reshape(-1),
+                          self.sess._materialize(self._ss_mask).detach().reshape(-1)]).cpu().numpy()
+        return {'prob': float(vals[0]), 'mask': (vals[1:] != 0).reshape(self._ss_mask.shape)}
+
+    def sched_sampling_state(self):
+        """-> (seed, counter) of ``g/sched_sampling/state`` as Python ints in [0, 2^64): the counter is the number of K-step
+        updates so far."""
+        self._require_sched_sampling()
+        seed, counter = (int(v) % 2 ** 64 for v in self.sess._materialize(O.sched_sampling_state()).cpu().numpy())
+        return seed, counter
+
+    def set_sched_sampling_state(self, seed, counter=0):
+        """Restart the coins at (seed, counter): the K-step updates that follow draw what a fresh Trainer built with that seed
+        draws after ``counter`` updates, at the schedule's value there."""
+        self._require_sched_sampling()
+        vals = [check_noise_seed(seed, 'seed'), check_noise_seed(counter, 'counter')]
+        state = self.sess._materialize(O.sched_sampling_state())
+        state.copy_(torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64))
+
     # ---- gradient norms (g_clip_norm / d_clip_norm / grad_norms)
     def grad_norm_stats(self, scope):
         """-> {'norm', 'scale', 'per_variable': {variable name: norm}} of the last update of ``scope`` ('g' or 'd') that ran: the
@@ -534,6 +584,14 @@ class Trainer:
         # fed action input of each step: the whole vector at step 0 (and every step of the plain generator), the command half else
         self.roll_action_ph = [G.placeholder((B, ACTION_DIM if (j == 0 or not dna) else 5), name='rollout/action%d' % j) for j in range(K)]
         img, act = self.roll_img_ph, self.roll_action_ph[0]
+        self._ss_mask = self._ss_prob = None
+        ss = self.sched_sampling
+        if ss is not None:
+            # scheduled sampling: ONE draw for the K - 1 fed-back positions, shared by both K-step programs (each run of either
+            # advances the counter); step j mixes under row j - 1 of the mask
+            O.sched_sampling_state(ss['seed'])
+            self._ss_mask, self._ss_prob = O.sched_sample_draw(K - 1, B, ss['kind'], ss['start'], ss['final'], ss['decay_steps'],
+                                                               ss['offset'], name='rollout/sched_sample/draw')
         self.rollout_frames, self.rollout_states, self.rollout_losses, l2_losses = [], [], [], []
         for j in range(K):
             frame, state = build_g(img, act, B, True)
@@ -552,6 +610,10 @@ class Trainer:
             self.rollout_losses.append(loss)
             l2_losses.append(l2)
             if j + 1 < K:
+                if ss is not None:      # per sample the truth (what step j was scored against) or the prediction, by the step's coins
+                    frame, state = O.sched_sample(self._ss_mask.view(j * B, (B,), name='rollout/sched_sample/mask%d' % (j + 1)), frame,
+                                                  self.roll_next_ph[j], state if dna else None, self.roll_state_ph[j] if dna else None,
+                                                  name='rollout/sched_sample%d' % (j + 1))
                 img = frame
                 act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
         total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
@@ -897,10 +959,11 @@ def check_lr(g_lr=None, d_lr=None, beta1=None, arg_opt='adam', lr_schedule='cons
             'scheduled': lr_schedule != 'constant' or max(counts['lr_warmup']) > 0}
 
 
-def check_noise_seed(seed):
-    """ValueError for a noise seed (or counter) that is not an integer in [0, 2^64); -> it as an int."""
+def check_noise_seed(seed, what='noise_seed'):
+    """ValueError for a seed (or counter) of a device-side draw - the noise input's, the scheduled-sampling coins' - that is not an
+    integer in [0, 2^64); -> it as an int."""
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
-        raise ValueError('noise_seed must be an integer in [0, 2^64), got %r' % (seed,))
+        raise ValueError('%s must be an integer in [0, 2^64), got %r' % (what, seed))
     return int(seed)
 
 
@@ -918,6 +981,45 @@ def check_noise(noise_dim, noise_seed=0, rollout_steps=1, bn_inference=False, ba
     if z * int(batch_size) > _lib.NOISE_VALUES_MAX:
         raise ValueError('noise_dim %d at batch %d: one draw holds at most %d values' % (z, batch_size, _lib.NOISE_VALUES_MAX))
     return z
+
+
+SCHED_SAMPLING = ('off',) + O.SCHED_SAMPLING_KINDS
+
+
+def check_sched_sampling(sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, rollout_steps=1,
+                         batch_size=1):
+    """ValueError for scheduled-sampling arguments the Trainer does not take: an unknown kind, a kind other than 'off' without
+    ``rollout_steps`` > 1, ``ss_start`` / ``ss_final`` outside [0, 1], a negative or non-integer ``ss_decay_steps`` / ``ss_offset``, a
+    decaying kind with ``ss_decay_steps`` < 1, a bad ``ss_seed``, more than 8192 coins per program.  -> None for 'off', else
+    {'kind', 'start', 'final', 'decay_steps', 'offset', 'seed'}."""
+    if sched_sampling not in SCHED_SAMPLING:
+        raise ValueError('sched_sampling must be one of %s, got %r' % (', '.join(SCHED_SAMPLING), sched_sampling))
+    probs = {}
+    for what, v in (('ss_start', ss_start), ('ss_final', ss_final)):
+        try:
+            x = float(v)
+        except (TypeError, ValueError):
+            raise ValueError('%s must be a number in [0, 1], got %r' % (what, v))
+        if isinstance(v, bool) or not 0.0 <= x <= 1.0:                  # (nan fails too)
+            raise ValueError('%s must lie in [0, 1], got %r' % (what, v))
+        probs[what] = x
+    counts = {}
+    for what, v in (('ss_decay_steps', ss_decay_steps), ('ss_offset', ss_offset)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 63:
+            raise ValueError('%s must be an integer >= 0, got %r' % (what, v))
+        counts[what] = int(v)
+    seed = check_noise_seed(ss_seed, 'ss_seed')
+    if sched_sampling == 'off':
+        return None
+    if int(rollout_steps) <= 1:
+        raise ValueError('sched_sampling %r needs rollout_steps > 1 (a one-step program feeds nothing back)' % (sched_sampling,))
+    if sched_sampling != 'constant' and counts['ss_decay_steps'] < 1:
+        raise ValueError('sched_sampling %r needs ss_decay_steps >= 1, got %r' % (sched_sampling, ss_decay_steps))
+    if (int(rollout_steps) - 1) * int(batch_size) > _lib.NOISE_VALUES_MAX:
+        raise ValueError('sched_sampling: %d fed-back steps at batch %d: one draw holds at most %d coins'
+                         % (int(rollout_steps) - 1, batch_size, _lib.NOISE_VALUES_MAX))
+    return {'kind': sched_sampling, 'start': probs['ss_start'], 'final': probs['ss_final'], 'decay_steps': counts['ss_decay_steps'],
+            'offset': counts['ss_offset'], 'seed': seed}
 
 
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
@@ -1075,12 +1177,13 @@ class _PairSelections:
 
 
 def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0,
-                 rates=None):
+                 rates=None, ss_prob=None):
     """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
     the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
     ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0.
     ``rates``: Trainer.learning_rates() of a run with a learning-rate schedule (None: no field is added) -> ``g_lr`` / ``d_lr``, the
-    rates the iteration's last updates used."""
+    rates the iteration's last updates used.  ``ss_prob``: the probability of truth of the iteration's K-step update in a run with
+    scheduled sampling (None: no field is added) -> ``ss_prob``."""
     record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
                   **({'g_ema': ema_decay} if ema_decay else {}),
                   **({'ssim_weight': ssim_weight} if ssim_weight else {}),
@@ -1092,6 +1195,8 @@ def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_wei
         record[scope + '_clip_norm'] = clip_bounds[scope]
     for scope in sorted(rates or {}, reverse=True):
         record[scope + '_lr'] = rates[scope]['lr']
+    if ss_prob is not None:
+        record['ss_prob'] = ss_prob
     return record
 
 
@@ -1107,7 +1212,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
           noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
-          lr_final=0.0):
+          lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1143,12 +1248,20 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     keywords), with ``lr_warmup`` and ``lr_decay_steps`` given in TRAINING ITERATIONS: D's schedule gets them multiplied by its
     updates per iteration (``n_critic``; 5 for the wass loss, else 1), G's gets them as they are.  G's counter also counts the
     ``pretrain_iter`` pretraining updates, so its warmup starts there.  With a schedule ``train.jsonl`` records ``g_lr`` / ``d_lr``,
-    the rates of the iteration's last updates, and checkpoints hold the counters; without one both are unchanged."""
+    the rates of the iteration's last updates, and checkpoints hold the counters; without one both are unchanged.
+    ``sched_sampling`` / ``ss_start`` / ``ss_final`` / ``ss_decay_steps`` / ``ss_seed``: scheduled sampling of the K-step updates
+    (Trainer, same keywords; needs ``rollout_steps`` > 1), ``ss_decay_steps`` in TRAINING ITERATIONS - there is one K-step update per
+    iteration.  The Trainer gets ``ss_offset = pretrain_iter``: the pretraining updates are teacher-forced at ``ss_start`` and the
+    decay begins behind them.  With sampling on ``train.jsonl`` records ``ss_prob``, the probability of truth of the iteration's
+    update, and checkpoints hold ``g/sched_sampling/state``; a pretraining iteration at a log interval then logs too (``ss_prob`` and
+    ``pretrain_g_loss``) and writes the interval's checkpoint.  With sampling off all of this is unchanged."""
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         if isinstance(v, (tuple, list)):
             raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
     la = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)
     noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
+    ss = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, max(int(pretrain_iter), 0), ss_seed, rollout_steps,
+                              batch_size)           # (the pretraining updates count too: the decay begins behind them)
     ema_decay = check_ema_decay(ema_decay)
     ssim_weight = check_ssim_weight(ssim_weight)
     g_clip_norm, d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
@@ -1180,7 +1293,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
                               batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
                               select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
                               ema_decay=ema_decay, ssim_weight=ssim_weight, g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm,
-                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed, lr_args=la)
+                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed, lr_args=la, ss_args=ss)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -1196,7 +1309,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
 def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
                 img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
                 num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
-                noise_dim=0, noise_seed=0, lr_args=None):
+                noise_dim=0, noise_seed=0, lr_args=None, ss_args=None):
     ema = {'ema_decay': ema_decay} if ema_decay else {}
     D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
     la = lr_args or check_lr(arg_opt=arg_opt)
@@ -1207,6 +1320,9 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                    lr_decay_steps=(la['decay_steps'][0], la['decay_steps'][0] * D_per_G))
     if noise_dim:
         ema.update(noise_dim=noise_dim, noise_seed=noise_seed)
+    if ss_args is not None:
+        ema.update(sched_sampling=ss_args['kind'], ss_start=ss_args['start'], ss_final=ss_args['final'], ss_decay_steps=ss_args['decay_steps'],
+                   ss_offset=ss_args['offset'], ss_seed=ss_args['seed'])
     if ssim_weight:
         ema['ssim_weight'] = ssim_weight
     if g_clip_norm or d_clip_norm or grad_norms:
@@ -1238,7 +1354,15 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
         if i < pretrain_iter:
             inp, nxt, acts, states = data.get_batch()
             if rollout_steps > 1:
-                trainer.pretrain_g_rollout(*window_batch(sels[0], inp, nxt, acts, states))
+                pre_loss = trainer.pretrain_g_rollout(*window_batch(sels[0], inp, nxt, acts, states))
+                if ss_args is not None and i % log_every == 0 and rank == 0:
+                    # scheduled sampling: ss_prob at EVERY log interval, the pretraining iterations' included (they advance the counter
+                    # the checkpoint holds), with the interval's checkpoint
+                    if log_file:
+                        _log_jsonl(log_file, train_record({'pretrain_g_loss': pre_loss}, i, time.time() - t0, rollout_steps,
+                                                          ss_prob=trainer.sched_sampling_last()['prob']))
+                    if model_dir:
+                        saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)
             else:
                 sm, em = sels[0]
                 trainer.pretrain_g(inp[sm], nxt[em], acts[sm], states[em])
@@ -1285,7 +1409,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 stats = {sc: trainer.grad_norm_stats(sc) for sc, norm in trainer.grad_norm.items() if norm is not None}
                 bounds = None if bounds_logged or not stats else {'g': g_clip_norm, 'd': d_clip_norm}
                 _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds, noise_dim,
-                                                    trainer.learning_rates() if la['scheduled'] else None))
+                                                    trainer.learning_rates() if la['scheduled'] else None,
+                                                    ss_prob=trainer.sched_sampling_last()['prob'] if ss_args is not None else None))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
@@ -1396,6 +1521,28 @@ def check_noise_args(parser, args):
         parser.error('--noise_dim / --noise_seed: %s' % e)
 
 
+def add_sched_sampling_args(parser):
+    """The scheduled-sampling flags of --rollout_steps > 1."""
+    parser.add_argument('--sched_sampling', type=str, default='off', metavar='KIND',
+                        help='off, constant, linear or inverse_sigmoid: at every fed-back position of a K-step update a coin per sample '
+                             'feeds the next step the true frame and state instead of the predicted ones, with a probability that '
+                             'follows this schedule (needs --rollout_steps > 1; drawn on the device inside the step)')
+    parser.add_argument('--ss_start', type=float, default=1.0, metavar='P', help='probability of truth at the start (and of constant)')
+    parser.add_argument('--ss_final', type=float, default=0.0, metavar='P', help='probability of truth at the end of the decay')
+    parser.add_argument('--ss_decay_iters', type=int, default=0, metavar='N',
+                        help='training iterations over which the probability decays, counted behind --pretrain_iter')
+    parser.add_argument('--ss_seed', type=int, default=0, metavar='S', help='seed of the coins (0 <= S < 2^64)')
+
+
+def check_sched_sampling_args(parser, args):
+    """parser.error for scheduled-sampling flags the Trainer does not take (before anything is created)."""
+    try:
+        check_sched_sampling(args.sched_sampling, args.ss_start, args.ss_final, args.ss_decay_iters, 0, args.ss_seed, args.rollout_steps,
+                             args.batch_size)
+    except ValueError as e:
+        parser.error('--sched_sampling / --ss_*: %s' % e)
+
+
 def add_lr_args(parser):
     """The learning-rate flags: the rates of G and D, Adam's beta1 and the schedule."""
     parser.add_argument('--g_lr', type=float, default=None, metavar='LR', help='learning rate of the generator updates (default: 1e-3 for adam, 5e-5 for rmsprop)')
@@ -1472,6 +1619,7 @@ def main(argv=None):
                              'where no bound is set')
     add_noise_args(parser)
     add_lr_args(parser)
+    add_sched_sampling_args(parser)
     args = parser.parse_args(argv)
     check_lr_args(parser, args)
     if args.buckets < 0:
@@ -1492,6 +1640,7 @@ def main(argv=None):
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
     check_noise_args(parser, args)
+    check_sched_sampling_args(parser, args)
     model_dir = os.path.join(args.output_path, 'models')
     log_dir = os.path.join(args.output_path, 'logs')
     os.makedirs(args.output_path)
@@ -1513,7 +1662,8 @@ def main(argv=None):
                     ssim_weight=args.ssim_weight, g_clip_norm=args.g_clip_norm, d_clip_norm=args.d_clip_norm,
                     grad_norms=args.log_grad_norms, noise_dim=args.noise_dim, noise_seed=args.noise_seed, g_lr=args.g_lr, d_lr=args.d_lr,
                     beta1=args.beta1, lr_schedule=args.lr_schedule, lr_warmup=args.lr_warmup, lr_decay_steps=args.lr_decay_iters,
-                    lr_final=args.lr_final)
+                    lr_final=args.lr_final, sched_sampling=args.sched_sampling, ss_start=args.ss_start, ss_final=args.ss_final,
+                    ss_decay_steps=args.ss_decay_iters, ss_seed=args.ss_seed)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

@@ -21,6 +21,10 @@
  * (acg_adam_step_lr / acg_rmsprop_step_lr, at the end of this header).  A rate passed by value is frozen into a captured graph of
  * the step; this one changes with every replay and no host in the loop.  Same conventions, same table; the only atomics are
  * those of the counter advance, which is the weight average's (include/acgan_ema.h).
+ *
+ * Scheduled sampling for the K-step rollout - the coins, drawn on the device by the noise input's generator from a state of their
+ * own, the per-sample select between the true and the predicted frame and state, and its adjoint - closes the header: same
+ * conventions, same table, no atomics.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -139,6 +143,57 @@ int32_t acg_rmsprop_step_lr(float* param, const float* grad, float* ms, int64_t 
                             float grad_scale, int32_t use_clip, float clip_lo, float clip_hi, const acg_lr_schedule* sched,
                             int64_t* lr_updates, uint32_t* lr_state, float* lr_out, float* shadow, float ema_decay,
                             int64_t* num_updates, uint32_t* state, acg_stream_t stream);
+
+/* Scheduled sampling (Bengio et al. 2015) for the K-step rollout: at every fed-back position a coin per sample decides whether the
+ * next step reads the true frame and state or the ones the generator predicted; the probability of truth follows a schedule over
+ * the K-step updates.  Three entries - the coins, the row select, its adjoint - with this header's conventions; none uses atomics:
+ * the same call on the same state gives the same bits.
+ *
+ * acg_sched_sample_draw: the coins of all `steps` fed-back positions of one program.  state uint64 [2] = {seed, counter} in device
+ * memory (a state of its own, laid out as the noise state above).  With k = counter as the launch finds it, j = max(k - offset, 0)
+ * and S = start, F = final, everything in double and every operation rounded on its own:
+ *   ACG_SS_CONSTANT:         p = S                                              (offset, decay_steps and final are not read)
+ *   ACG_SS_LINEAR:           p = S + (F - S) * min(j / decay_steps, 1)
+ *   ACG_SS_INVERSE_SIGMOID:  p = F + (S - F) * (d / (d + exp(j / d))),  d = decay_steps   (Bengio's eps_i = k / (k + exp(i / k)))
+ *   prob_out[0] = (float)p                                                      (device, float32 [1]).
+ * The coin of element e = s * batch + b (step slot s in [0, steps), sample b) is lane e % 4 of Philox4x32-10 block e / 4 with the
+ * counter words (lo32(k), hi32(k), e / 4, stream_id ^ ACG_SS_STREAM_TAG) and the key (lo32(seed), hi32(seed)) - the generator and
+ * the uniform u = ((x >> 9) + 0.5) * 2^-23 of acg_noise_concat; the tag keeps this stream apart from the noise stream of the same
+ * seed and stream id - and
+ *   mask[e] = u < prob_out[0] ? 1.f : 0.f          (1: read the truth; mask float32 [steps, batch]).
+ * u lies strictly inside (0, 1): p = 0 gives all zeros and p = 1 all ones, exactly.  After the draw the kernel stores counter + 1:
+ * a replayed graph draws fresh coins and moves along the schedule with no host in the loop.  One launch of one block.  `sched` is
+ * read on the host during the call and copied into the kernel arguments.  Checked on the host before anything is launched:
+ * pointers not NULL; kind one of the three; 0 <= start, final <= 1; offset >= 0; decay_steps >= 1 for every kind but constant;
+ * 1 <= steps * batch <= ACG_NOISE_VALUES_MAX.  Calls that share a state must be stream-ordered. */
+#define ACG_SS_CONSTANT 0
+#define ACG_SS_LINEAR 1
+#define ACG_SS_INVERSE_SIGMOID 2
+#define ACG_SS_STREAM_TAG 0x5353414Du
+typedef struct acg_ss_schedule {
+  int32_t kind;
+  int64_t offset;
+  int64_t decay_steps;
+  float start;
+  float final;
+} acg_ss_schedule;
+int32_t acg_sched_sample_draw(uint64_t* state, const acg_ss_schedule* sched, float* mask, float* prob_out, int32_t steps,
+                              int32_t batch, int32_t stream_id, acg_stream_t stream);
+
+/* The row select: out[b, :] = mask[b] != 0 ? truth[b, :] : pred[b, :], a copy of bits, for the frame (rows of per_sample float32)
+ * and the state (rows of state_dim float32) under the same coin; `mask` points at one step slot's [batch] row.  Either the frame
+ * triple (pred, truth, out) or the state triple may be NULL as a whole, not both.  One launch: one sample per blockIdx.y, so only
+ * the selected source of a row is read (the other may hold anything); 16-byte moves when per_sample % 4 == 0 and pred, truth and
+ * out are 16-byte aligned, a scalar path otherwise.  out must not overlap the inputs.  1 <= batch <= 65535. */
+int32_t acg_sched_sample_fwd(const float* mask, const float* pred, const float* truth, float* out, int64_t per_sample,
+                             const float* pred_state, const float* true_state, float* out_state, int32_t state_dim, int32_t batch,
+                             acg_stream_t stream);
+
+/* Its adjoint with respect to the predicted inputs: dpred[b, :] = mask[b] != 0 ? +0.f : dout[b, :] (dout of a truth row is not
+ * read), the same for the state pair; the pair (dout, dpred) or (dout_state, dpred_state) may be NULL as a whole, not both.  The
+ * launch shape and the limits of acg_sched_sample_fwd. */
+int32_t acg_sched_sample_bwd(const float* mask, const float* dout, float* dpred, int64_t per_sample, const float* dout_state,
+                             float* dpred_state, int32_t state_dim, int32_t batch, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
