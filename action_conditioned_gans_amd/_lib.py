@@ -217,9 +217,10 @@ EXTENSIONS = {
     # gradient buffer that bounds them (optim.ClipNormOp); the header owns the device-side action vector, so the noise that is
     # appended to it - drawn on the device, the counter advanced by the kernel (ops.NoiseOp) - is here too; and, beside the clip as
     # "what sits in front of the optimizer update", the optimizer steps that evaluate a learning-rate schedule inside their launch
-    # from an update counter they advance themselves (optim.LrSchedule); and scheduled sampling of the rollout's fed-back inputs
-    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, scheduled sampling, the gradient clip, the noise input '
-                         'and learning-rate schedules run on the HIP library only', {
+    # from an update counter they advance themselves (optim.LrSchedule); and scheduled sampling of the rollout's fed-back inputs;
+    # and the launches of the planner around the generator forwards (plan.Planner)
+    'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, scheduled sampling, the gradient clip, the noise input, '
+                         'learning-rate schedules and planning run on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
         'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
@@ -233,6 +234,10 @@ EXTENSIONS = {
         'acg_sched_sample_draw': (STATUS, [_P, ctypes.POINTER(SsSched), _P, _P, c_int32, c_int32, c_int32, _P]),
         'acg_sched_sample_fwd': (STATUS, [_P, _P, _P, _P, c_int64, _P, _P, _P, c_int32, c_int32, _P]),
         'acg_sched_sample_bwd': (STATUS, [_P, _P, _P, c_int64, _P, _P, c_int32, c_int32, _P]),
+        # planning by the cross-entropy method around the generator forwards (plan.sample_actions / accumulate_cost / refit)
+        'acg_plan_sample': (STATUS, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+        'acg_plan_cost': (STATUS, [_P, _P, _P, _P, c_float, c_float, _P, c_int32] + [c_int32] * 7 + [_P]),
+        'acg_plan_refit': (STATUS, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)
@@ -271,6 +276,10 @@ PREP_MAX = 32
 NORM_SEGMENTS_MAX = 64
 NOISE_DIM_MAX = 64            # acgan_rollout.h ACG_NOISE_DIM_MAX / ACG_NOISE_VALUES_MAX
 NOISE_VALUES_MAX = 8192
+PLAN_CANDIDATES_MAX = 1024    # acgan_rollout.h ACG_PLAN_*_MAX
+PLAN_HORIZON_MAX = 16
+PLAN_ACTION_DIM_MAX = 8
+PLAN_STATE_DIM_MAX = 16
 
 
 def dtype2(first, second):

@@ -25,6 +25,10 @@
  * Scheduled sampling for the K-step rollout - the coins, drawn on the device by the noise input's generator from a state of their
  * own, the per-sample select between the true and the predicted frame and state, and its adjoint - closes the header: same
  * conventions, same table, no atomics.
+ *
+ * And what the action-conditioned rollout is for - choosing the actions that lead to a wanted frame - ends it: the three launches
+ * of a cross-entropy-method planner around the generator forwards (acg_plan_sample / acg_plan_cost / acg_plan_refit), the draw by
+ * the same generator from a state of its own.  Same conventions, same table, no atomics.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -194,6 +198,57 @@ int32_t acg_sched_sample_fwd(const float* mask, const float* pred, const float* 
  * launch shape and the limits of acg_sched_sample_fwd. */
 int32_t acg_sched_sample_bwd(const float* mask, const float* dout, float* dpred, int64_t per_sample, const float* dout_state,
                              float* dpred_state, int32_t state_dim, int32_t batch, acg_stream_t stream);
+
+/* Planning with the generator by the cross-entropy method (CEM): draw N candidate action sequences of H steps from a diagonal
+ * Gaussian, roll each through the generator, score the predicted frames (and states) against a goal, refit the Gaussian to the E
+ * best, repeat.  The three entries are what runs around the generator forwards, so that the optimiser has no host in its loop: a
+ * replayed graph of an iteration draws fresh candidates.  This header's conventions; no float atomics, every sum in a fixed order:
+ * the same call on the same inputs gives the same bits.  1 <= N <= ACG_PLAN_CANDIDATES_MAX, 1 <= H <= ACG_PLAN_HORIZON_MAX,
+ * 1 <= A <= ACG_PLAN_ACTION_DIM_MAX, 1 <= E <= N; a value below 1 or a null pointer is ACG_ERR_INVALID_ARG, one above its limit
+ * ACG_ERR_UNSUPPORTED, and nothing is launched.
+ *
+ * acg_plan_sample: actions[n, t, a] = min(max(mean[t, a] + std[t, a] * z[n, t, a], lo[a]), hi[a])   (one fused multiply-add),
+ * mean and std float32 [H * A], lo and hi float32 [A], actions float32 [N, H, A] dense.  With keep_mean != 0 row n = 0 is
+ * min(max(mean, lo), hi) with no noise: the best guess so far is always a candidate.  z is the normal of acg_noise_concat - the
+ * same Philox4x32-10, uniform and Box-Muller pairing - for the element e = (n * H + t) * A + a: lane e % 4 of block e / 4 with the
+ * counter words (lo32(counter), hi32(counter), e / 4, stream_id ^ ACG_PLAN_STREAM_TAG) and the key (lo32(seed), hi32(seed)); the
+ * tag keeps the candidates apart from the noise and the scheduled-sampling coins of the same seed and stream id.  state uint64 [2]
+ * = {seed, counter} in device memory; after the draw the kernel stores counter + 1.  One launch of one block.  Calls that share a
+ * state must be stream-ordered.
+ *
+ * acg_plan_cost: cost[n] = (accumulate != 0 ? cost[n] : 0) + frame_weight * sum_{y, x, ch < c} (frames[n, y, x, ch] - goal[y, x, ch])^2
+ *                          + state_weight * sum_{s < state_dim} (states[n, s] - goal_state[s])^2.
+ * frames [N, h, w, pitch], storage dtype = ACG_F32 or ACG_BF16, channels ch < c <= pitch <= 64 are scored (the pad channels may hold
+ * anything); goal float32 [h, w, c] dense, one goal for all candidates; states float32 [N, state_dim] and goal_state float32
+ * [state_dim] are both NULL (state_dim = 0) or both given (1 <= state_dim <= ACG_PLAN_STATE_DIM_MAX); cost float32 [N].  With
+ * accumulate == 0 the old cost is not read: whatever the buffer held, a NaN included, is gone.  A weight of 0 multiplies its sum,
+ * it does not skip it.  One launch, one block per candidate: per-thread float32 partials over a strided share of the frame, the
+ * lanes of a wave summed by shuffles, the waves in order; no workspace.  16-byte loads (8-byte for bf16) when pitch == c and
+ * h * w * c % 4 == 0, or pitch == 4, and the pointers are aligned; a scalar path otherwise.
+ *
+ * acg_plan_refit: with key(n) = cost[n], a NaN read as +inf, the rank of candidate n is the number of m with key(m) < key(n), or
+ * key(m) == key(n) and m < n - a total, stable order: NaN and +inf come last, by index.  elite_idx[r] (int32 [E]) = the candidate
+ * of rank r < E.  For every (t, a), over the elites in rank order, two sequential float32 passes: mean_e = sum / E,
+ * std_e = sqrt(sum (x - mean_e)^2 / E) (population); then
+ *   mean[t, a] = alpha * mean[t, a] + (1 - alpha) * mean_e,   std[t, a] = max(alpha * std[t, a] + (1 - alpha) * std_e, min_std),
+ * and if key(elite_idx[0]) < best_cost[0] - strictly: an equal cost keeps the earlier plan - best_cost[0] and best_actions
+ * [H * A] take that candidate's key and actions (the host starts best_cost at +inf; with every cost NaN both stay untouched).
+ * history, when not NULL, receives best_cost[0] after the update (float32 [1]: the caller points it at its slot).  0 <= alpha <= 1,
+ * min_std finite and >= 0.  One launch of one block of up to 1024 threads (one per candidate; the ranks are counted out of LDS). */
+#define ACG_PLAN_CANDIDATES_MAX 1024
+#define ACG_PLAN_HORIZON_MAX 16
+#define ACG_PLAN_ACTION_DIM_MAX 8
+#define ACG_PLAN_STATE_DIM_MAX 16
+#define ACG_PLAN_STREAM_TAG 0x504C414Eu
+int32_t acg_plan_sample(const float* mean, const float* std, const float* lo, const float* hi, uint64_t* state, float* actions,
+                        int32_t candidates, int32_t horizon, int32_t action_dim, int32_t keep_mean, int32_t stream_id,
+                        acg_stream_t stream);
+int32_t acg_plan_cost(const void* frames, const float* goal, const float* states, const float* goal_state, float frame_weight,
+                      float state_weight, float* cost, int32_t accumulate, int32_t candidates, int32_t h, int32_t w, int32_t c,
+                      int32_t pitch, int32_t state_dim, int32_t dtype, acg_stream_t stream);
+int32_t acg_plan_refit(const float* cost, const float* actions, float* mean, float* std, float* best_cost, float* best_actions,
+                       int32_t* elite_idx, float* history, int32_t candidates, int32_t horizon, int32_t action_dim, int32_t elites,
+                       float alpha, float min_std, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
