@@ -14,29 +14,21 @@ namespace {
 
 constexpr int NTH = 256;
 
-using acg::philox4x32_10;      // philox.h: shared with the scheduled-sampling coins (sched_sample.hip)
-using acg::unit;
-
 __global__ __launch_bounds__(NTH) void noise_concat_kernel(const float* __restrict__ actions, unsigned long long* __restrict__ state,
                                                            const float* __restrict__ scale, float* __restrict__ out, int B, int A, int Z,
                                                            uint32_t stream_id) {
   const int tid = threadIdx.x, P = A + Z, n = B * Z;
-  const unsigned long long seed = state[0], counter = state[1];
+  const acg::DrawState draw = acg::load_draw_state(state);
   const float sc = scale[0];
   for (int idx = tid; idx < B * A; idx += NTH) {
     const int b = idx / A;
     out[b * P + idx - b * A] = actions[idx];
   }
   for (int i = tid; i * 4 < n; i += NTH) {
-    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)i, stream_id};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    uint32_t c[4];
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float r = sqrtf(-2.f * logf(unit(c[2 * h]))), t = 6.283185307179586f * unit(c[2 * h + 1]);
-      z[2 * h] = r * cosf(t);
-      z[2 * h + 1] = r * sinf(t);
-    }
+    acg::draw_block(draw, (uint32_t)i, stream_id, c);
+    acg::normals(c, z);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const int e = i * 4 + l;                 // the tail of the last Philox block is dropped
@@ -46,8 +38,7 @@ __global__ __launch_bounds__(NTH) void noise_concat_kernel(const float* __restri
       }
     }
   }
-  __syncthreads();                             // every thread has read the counter
-  if (tid == 0) state[1] = counter + 1;
+  acg::advance_draw_state(state, draw);
 }
 
 }  // namespace

@@ -35,17 +35,12 @@ __global__ __launch_bounds__(SAMPLE_MAX) void plan_sample_kernel(const float* __
                                                                  unsigned long long* __restrict__ state, float* __restrict__ actions,
                                                                  int n, int HA, int A, int keep_mean, uint32_t stream_word) {
   const int tid = threadIdx.x, nth = blockDim.x;
-  const unsigned long long seed = state[0], counter = state[1];
+  const acg::DrawState draw = acg::load_draw_state(state);
   for (int i = tid; i * 4 < n; i += nth) {
-    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)i, stream_word};
-    acg::philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    uint32_t c[4];
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float r = sqrtf(-2.f * logf(acg::unit(c[2 * h]))), t = 6.283185307179586f * acg::unit(c[2 * h + 1]);
-      z[2 * h] = r * cosf(t);
-      z[2 * h + 1] = r * sinf(t);
-    }
+    acg::draw_block(draw, (uint32_t)i, stream_word, c);
+    acg::normals(c, z);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const int e = i * 4 + l;                 // the tail of the last Philox block is dropped
@@ -57,8 +52,7 @@ __global__ __launch_bounds__(SAMPLE_MAX) void plan_sample_kernel(const float* __
       }
     }
   }
-  __syncthreads();                             // every thread has read the counter
-  if (tid == 0) state[1] = counter + 1;
+  acg::advance_draw_state(state, draw);
 }
 
 // ---- cost ---------------------------------------------------------------------------------------------------------------------

@@ -45,20 +45,19 @@ __global__ __launch_bounds__(NTH) void sched_sample_draw_kernel(unsigned long lo
                                                                 float* __restrict__ mask, float* __restrict__ prob_out, int n,
                                                                 uint32_t stream_word) {
   const int tid = threadIdx.x;
-  const unsigned long long seed = state[0], counter = state[1];
-  const float p = (float)probability(sc, counter);
+  const acg::DrawState draw = acg::load_draw_state(state);
+  const float p = (float)probability(sc, draw.counter);
   if (tid == 0) prob_out[0] = p;
   for (int i = tid; i * 4 < n; i += NTH) {
-    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)i, stream_word};
-    acg::philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    uint32_t c[4];
+    acg::draw_block(draw, (uint32_t)i, stream_word, c);
 #pragma unroll
     for (int l = 0; l < 4; ++l) {
       const int e = i * 4 + l;                 // the tail of the last Philox block is dropped
       if (e < n) mask[e] = acg::unit(c[l]) < p ? 1.f : 0.f;
     }
   }
-  __syncthreads();                             // every thread has read the counter
-  if (tid == 0) state[1] = counter + 1;
+  acg::advance_draw_state(state, draw);
 }
 
 // dst[b, :] = src[b, :] for the rows of this block's sample, or +0 when src == nullptr.  VEC: 16-byte moves (n % 4 == 0, aligned)

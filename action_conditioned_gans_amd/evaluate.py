@@ -119,23 +119,58 @@ def _use_ema_weights(trainer, ckpt):
     return updates
 
 
+def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn_stats='batch', weights='raw',
+                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate'):
+    """A checkpoint as a Trainer that predicts: a fresh graph and session, the generator ``transform`` / ``ksize`` / ``num_masks`` at
+    ``batch_size`` with what the modes need and nothing else - ``bn_stats`` 'stored' or 'calibrate': the stored-statistics instances;
+    ``weights='ema'``: the average (then copied into the variables, _use_ema_weights); ``noise_dim`` > 0: the noise input, its stream
+    restarted at ``noise_seed`` - initialised and restored from ``restore_from`` (default: ``ckpt``, which the messages name).  An int
+    ``noise_dim`` also makes the Saver's shape refusal ask about --noise_dim.  'stored' needs calibrated rows in the checkpoint (the
+    error names ``calibrate_with``).  -> (trainer, updates of the average or None, calibrated rows or None); the caller closes
+    ``trainer.sess``."""
+    from . import graph as G
+    from .saver import Saver
+    from .train import Trainer
+    extra = {'bn_inference': True} if bn_stats != 'batch' else {}      # ('batch' builds exactly the graph it always built)
+    if weights == 'ema':
+        extra['ema_decay'] = EMA_BUILD_DECAY
+    if noise_dim:
+        extra.update(noise_dim=noise_dim, noise_seed=noise_seed)
+    G.reset_default_graph()
+    sess = G.Session(device=device, dtype=dtype)
+    try:
+        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False,
+                          num_masks=num_masks, **extra)
+        sess.run(G.global_variables_initializer())
+        try:
+            Saver().restore(sess, restore_from or ckpt)
+        except ValueError as e:
+            if noise_dim is not None and 'has shape' in str(e):        # the Saver's shape refusal: the bottleneck layers are noise_dim channels wider
+                raise ValueError('%s - the generator is built with --noise_dim %d: does that match the run that wrote the checkpoint?'
+                                 % (e, noise_dim)) from None
+            raise
+        if noise_dim:
+            trainer.set_noise_state(noise_seed)        # the stream of this evaluation, not the training run's
+        ema_updates = _use_ema_weights(trainer, ckpt) if weights == 'ema' else None      # (copied into the variables: 'raw' from here on)
+        calibration_rows = trainer.bn_calibration_rows() if bn_stats == 'stored' else None
+        if bn_stats == 'stored' and calibration_rows < 1:
+            raise ValueError('--bn_stats stored: checkpoint %s holds no calibrated BatchNorm statistics (run %s first)'
+                             % (os.path.abspath(ckpt), calibrate_with))
+        return trainer, ema_updates, calibration_rows
+    except BaseException:
+        sess.close()
+        raise
+
+
 def calibrate(ckpt, save_prefix, input_path, actions_path, transform, ksize, img_size, dtype, pair_batch, num_batches, seq_len, device,
               num_masks, weights='raw'):
     """Restore ``ckpt`` into a generator built at batch ``pair_batch``, pool its BatchNorm statistics over ``num_batches`` batches
     of one-step pairs of ``input_path`` (Trainer.calibrate_bn) and save everything as ``save_prefix``.npz.  -> pairs pooled.
     ``weights='ema'``: calibrate (and save) the averaged weights (_use_ema_weights)."""
-    from . import graph as G
     from .saver import Saver
-    from .train import Trainer
-    G.reset_default_graph()
-    sess = G.Session(device=device, dtype=dtype)
+    trainer, _, _ = predicting_trainer(ckpt, transform, pair_batch, ksize, img_size, dtype, device, num_masks, 'calibrate', weights)
+    sess = trainer.sess
     try:
-        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=pair_batch, img_size=img_size, ksize=ksize, lookahead=False,
-                          num_masks=num_masks, bn_inference=True, **({'ema_decay': EMA_BUILD_DECAY} if weights == 'ema' else {}))
-        sess.run(G.global_variables_initializer())
-        Saver().restore(sess, ckpt)
-        if weights == 'ema':
-            _use_ema_weights(trainer, ckpt)
         trainer.reset_bn_statistics()
         rows = 0
         for frames, acts in _calibration_pairs(input_path, actions_path, pair_batch, img_size, seq_len, num_batches):
@@ -186,10 +221,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' (got %r)" % (noise_samples,))
     n_draws = int(noise_samples)
     transform = 'cdna' if cdna else dna
-    from . import graph as G
     from .metrics import SSIM_DEFINITION
-    from .saver import Saver, latest_checkpoint
-    from .train import Trainer
+    from .saver import latest_checkpoint
     from .util import save_samples
 
     ckpt = latest_checkpoint(model_path) if os.path.isdir(model_path) else model_path
@@ -204,33 +237,12 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         calibrate(ckpt, restore_from, calibrate_input, calibrate_actions, transform, ksize, img_size, dtype, calibrate_batch_size,
                   calibrate_batches, seq_len, device, num_masks, **({'weights': weights} if weights == 'ema' else {}))
     stored = bn_stats != 'batch'
-    extra = {'bn_inference': True} if stored else {}      # ('batch' builds exactly the graph it always built)
-    if weights == 'ema':
-        extra['ema_decay'] = EMA_BUILD_DECAY
-    if noise_dim:
-        extra.update(noise_dim=noise_dim, noise_seed=noise_seed)
     bn = 'stored' if stored else 'batch'
-    G.reset_default_graph()
-    sess = G.Session(device=device, dtype=dtype)
+    trainer, ema_updates, calibration_rows = predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn,
+                                                                weights, noise_dim, noise_seed, restore_from=restore_from)
+    sess = trainer.sess
     try:
-        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=batch_size, img_size=img_size, ksize=ksize, lookahead=False,
-                          num_masks=num_masks, **extra)
-        sess.run(G.global_variables_initializer())
-        try:
-            Saver().restore(sess, restore_from)
-        except ValueError as e:
-            if 'has shape' in str(e):        # the Saver's shape refusal: the bottleneck layers are noise_dim channels wider
-                raise ValueError('%s - the generator is built with --noise_dim %d: does that match the run that wrote the checkpoint?'
-                                 % (e, noise_dim)) from None
-            raise
-        if noise_dim:
-            trainer.set_noise_state(noise_seed)        # the stream of this evaluation, not the training run's
-        ema_updates = _use_ema_weights(trainer, ckpt) if weights == 'ema' else None
-        calibration_rows = trainer.bn_calibration_rows() if stored else None
-        if stored and calibration_rows < 1:
-            raise ValueError('--bn_stats stored: checkpoint %s holds no calibrated BatchNorm statistics (run --bn_stats calibrate first)'
-                             % os.path.abspath(ckpt))
-        keys = ('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
+        keys =('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
         acc = {k: [] for k in keys}
         draws = {'ssim': [], 'sqerr': []}        # noise 'sample': [n_draws, batch, steps] per batch
         valid, kept_frames, kept_pred, dumped = [], [], [], []

@@ -1179,22 +1179,42 @@ class ActionGradOp(G.Op):
         return lambda s: fn(*args, s)
 
 
+# ---- the {seed, counter} state of a device-side draw (the noise input, the scheduled-sampling coins, the planner's candidates):
+# uint64 [2] to the kernel, which advances the counter; torch holds the same bits as int64 [2]
+def _i64(v):
+    return v - 2 ** 64 if v >= 2 ** 63 else v
+
+
+def new_draw_state(name, seed, what):
+    """-> the named graph state ``name``, int64 [2] initialised to {seed, 0}: a checkpoint key like a BatchNorm layer's statistics."""
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError('%s seed must be in [0, 2^64), got %r' % (what, seed))
+    return G.get_default_graph().new_state((2,), (_i64(seed), 0), name, dtype=torch.int64)
+
+
+def read_draw_state(buf):
+    """-> (seed, counter) of a draw state's tensor as Python ints in [0, 2^64).  One small device-to-host copy."""
+    seed, counter = (int(v) % 2 ** 64 for v in buf.cpu().numpy())
+    return seed, counter
+
+
+def write_draw_state(buf, seed, counter=0):
+    """{seed, counter}, two checked ints in [0, 2^64), into a draw state's tensor."""
+    buf.copy_(torch.tensor([_i64(seed), _i64(counter)], dtype=torch.int64))
+
+
 NOISE_STATE = 'g/noise/state'
 
 
 def noise_state(seed=0):
     """The noise state every NoiseOp of the graph shares, created by the first call (``seed`` is read by that call alone):
-    -> (state, scale).  ``state``: ``g/noise/state``, {seed, counter} - uint64 [2] to the kernel, which advances the counter; torch
-    holds the same bits as int64 [2] - initialised to {seed, 0}, named graph state and so a checkpoint key like a BatchNorm
-    layer's statistics.  ``scale``: float32 [1], initialised to 1, unnamed (no checkpoint key): whoever runs the programs writes it
-    between them - 0 switches the noise off, the counter advances all the same."""
+    -> (state, scale).  ``state``: ``g/noise/state`` (new_draw_state).  ``scale``: float32 [1], initialised to 1, unnamed (no
+    checkpoint key): whoever runs the programs writes it between them - 0 switches the noise off, the counter advances all the
+    same."""
     g = G.get_default_graph()
     if 'noise' not in g.collections:
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError('noise seed must be in [0, 2^64), got %r' % (seed,))
-        g.collections['noise'] = (g.new_state((2,), (seed - 2 ** 64 if seed >= 2 ** 63 else seed, 0), NOISE_STATE, dtype=torch.int64),
-                                  g.new_state((1,), 1.0, None))
+        g.collections['noise'] = (new_draw_state(NOISE_STATE, seed, 'noise'), g.new_state((1,), 1.0, None))
     return g.collections['noise']
 
 
@@ -1234,16 +1254,11 @@ SCHED_SAMPLING_KINDS = _lib.SsSched.KINDS
 
 def sched_sampling_state(seed=0):
     """The scheduled-sampling state of the graph, created by the first call (``seed`` is read by that call alone):
-    ``g/sched_sampling/state``, {seed, counter} - uint64 [2] to the kernel, which advances the counter (the number of K-step
-    updates so far); torch holds the same bits as int64 [2] - initialised to {seed, 0}; named graph state and so a checkpoint key,
-    exactly as ``g/noise/state`` is."""
+    ``g/sched_sampling/state`` (new_draw_state), whose counter is the number of K-step updates so far; a checkpoint key, exactly
+    as ``g/noise/state`` is."""
     g = G.get_default_graph()
     if 'sched_sampling' not in g.collections:
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError('scheduled-sampling seed must be in [0, 2^64), got %r' % (seed,))
-        g.collections['sched_sampling'] = g.new_state((2,), (seed - 2 ** 64 if seed >= 2 ** 63 else seed, 0), SCHED_SAMPLING_STATE,
-                                                      dtype=torch.int64)
+        g.collections['sched_sampling'] = new_draw_state(SCHED_SAMPLING_STATE, seed, 'scheduled-sampling')
     return g.collections['sched_sampling']
 
 

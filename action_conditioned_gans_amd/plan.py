@@ -39,6 +39,7 @@ import torch
 
 from . import _lib
 from .metrics import _stream_handle
+from .ops import read_draw_state, write_draw_state
 
 COMMAND_DIM = 5             # the commanded half of the 10-dim action vector; columns 5..9 are the state
 COST_STEPS = ('all', 'last')
@@ -189,11 +190,6 @@ def check_plan(candidates, horizon, elites, iterations, init_std=DEFAULTS['init_
             'state_weight': float(state_weight), 'cost_steps': cost_steps, 'seed': check_noise_seed(seed, 'seed')}
 
 
-def _i64(v):
-    v = int(v) % 2 ** 64
-    return v - 2 ** 64 if v >= 2 ** 63 else v
-
-
 class Planner:
     """CEM over the rows of a Trainer's batch (module docstring).  ``trainer``: a ``train.Trainer`` on a GPU session; its batch
     size is the number of candidates N.  ``horizon`` H steps, the ``elites`` E best refit the Gaussian, ``iterations`` rounds.
@@ -227,7 +223,8 @@ class Planner:
         a = self.args
         self.N, self.H, self.A, self.E, self.I = trainer.batch_size, a['horizon'], COMMAND_DIM, a['elites'], a['iterations']
         dev, f32 = sess.rt.device, torch.float32
-        self.state = torch.tensor([_i64(a['seed']), 0], dtype=torch.int64, device=dev)
+        self.state = torch.empty(2, dtype=torch.int64, device=dev)
+        write_draw_state(self.state, a['seed'])
         self.lo, self.hi = torch.from_numpy(a['lo']).to(dev), torch.from_numpy(a['hi']).to(dev)
         self.mean = torch.zeros(self.H, self.A, dtype=f32, device=dev)
         self.std = torch.full((self.H, self.A), a['init_std'], dtype=f32, device=dev)
@@ -241,7 +238,7 @@ class Planner:
     # ---- the candidates' stream
     def plan_state(self):
         """-> (seed, counter) as Python ints in [0, 2^64): the counter is the number of draws (iterations) so far."""
-        return tuple(int(v) % 2 ** 64 for v in self.state.cpu().numpy())
+        return read_draw_state(self.state)
 
     # ---- inputs
     def _frame(self, value, what):
@@ -297,18 +294,6 @@ class Planner:
                 kept.append(frame)
         return torch.stack(kept, dim=1) if keep_frames else None
 
-    def _predicting(self):
-        """What every predicting call of the Trainer does first (Trainer.test): the mode checks and the noise switch; -> the
-        context the rollout runs in (the averaged weights, or nothing)."""
-        import contextlib
-        tr = self.trainer
-        tr._check_bn_mode(self.bn)
-        ema = tr._check_weights(self.weights)
-        if ema:
-            tr._ema_buffers()                            # (raises while the average has seen no update)
-        tr._set_noise('zero')
-        return tr.ema_weights() if ema else contextlib.nullcontext()
-
     def plan(self, frame, state, goal_frame, goal_state=None, keep_candidates=False):
         """One open-loop plan from ``frame`` [H, W, 3] / ``state`` [5] towards ``goal_frame`` [H, W, 3] (and ``goal_state`` [5]
         when ``state_weight`` > 0), starting from mean 0 and ``init_std``.  -> {'actions' [H, 5], 'cost', 'history' [iterations]
@@ -319,22 +304,21 @@ class Planner:
         a = self.args
         if a['state_weight'] != 0 and goal_state is None:
             raise ValueError('state_weight %r needs a goal_state' % (a['state_weight'],))
-        predicting = self._predicting()              # (the mode checks come before anything is uploaded or launched)
-        goal, gstate = self._goal(goal_frame, goal_state)
-        f0, s0 = self._start(frame, state)
-        self.mean.zero_()
-        self.std.fill_(a['init_std'])
-        self.best_cost.fill_(math.inf)
-        self.best_actions.zero_()
-        rank = self.sess.rt.rank
-        lib = self.sess.rt.lib
-        log = None
-        if keep_candidates:
-            dev, I = self.sess.rt.device, self.I
-            log = {'candidates': torch.empty((I,) + tuple(self.actions.shape), device=dev), 'costs': torch.empty(I, self.N, device=dev),
-                   'elites': torch.empty(I, self.E, dtype=torch.int32, device=dev), 'means': torch.empty(I, self.H, self.A, device=dev),
-                   'stds': torch.empty(I, self.H, self.A, device=dev)}
-        with predicting:
+        with self.trainer._predicting(self.bn, self.weights):      # (the mode checks come before anything is uploaded or launched)
+            goal, gstate = self._goal(goal_frame, goal_state)
+            f0, s0 = self._start(frame, state)
+            self.mean.zero_()
+            self.std.fill_(a['init_std'])
+            self.best_cost.fill_(math.inf)
+            self.best_actions.zero_()
+            rank = self.sess.rt.rank
+            lib = self.sess.rt.lib
+            log = None
+            if keep_candidates:
+                dev, I = self.sess.rt.device, self.I
+                log = {'candidates': torch.empty((I,) + tuple(self.actions.shape), device=dev), 'costs': torch.empty(I, self.N, device=dev),
+                       'elites': torch.empty(I, self.E, dtype=torch.int32, device=dev), 'means': torch.empty(I, self.H, self.A, device=dev),
+                       'stds': torch.empty(I, self.H, self.A, device=dev)}
             for i in range(self.I):
                 sample_actions(self.mean, self.std, self.lo, self.hi, self.state, self.actions, keep_mean=True, stream_id=rank, lib=lib)
                 self._rollout(f0, s0, self.actions, goal, gstate, self.cost)
@@ -359,14 +343,13 @@ class Planner:
         sampling.  -> costs [N] (numpy); with ``return_frames`` also the predicted frames [N, H, H, W, 3]."""
         if self.args['state_weight'] != 0 and goal_state is None:
             raise ValueError('state_weight %r needs a goal_state' % (self.args['state_weight'],))
-        predicting = self._predicting()
-        goal, gstate = self._goal(goal_frame, goal_state)
-        f0, s0 = self._start(frame, state)
-        acts = self.sess.upload(np.asarray(actions, np.float32) if not torch.is_tensor(actions) else actions)
-        if tuple(acts.shape) != (self.N, self.H, self.A):
-            raise ValueError('actions must be [%d, %d, %d], got %s' % (self.N, self.H, self.A, tuple(acts.shape)))
-        cost = torch.empty_like(self.cost)
-        with predicting:
+        with self.trainer._predicting(self.bn, self.weights):
+            goal, gstate = self._goal(goal_frame, goal_state)
+            f0, s0 = self._start(frame, state)
+            acts = self.sess.upload(np.asarray(actions, np.float32) if not torch.is_tensor(actions) else actions)
+            if tuple(acts.shape) != (self.N, self.H, self.A):
+                raise ValueError('actions must be [%d, %d, %d], got %s' % (self.N, self.H, self.A, tuple(acts.shape)))
+            cost = torch.empty_like(self.cost)
             frames = self._rollout(f0, s0, acts.contiguous(), goal, gstate, cost, keep_frames=return_frames)
         if return_frames:
             return cost.cpu().numpy(), frames.cpu().numpy()
@@ -380,10 +363,9 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
                    cost_steps='all', seed=0, num_sequences=None, seq_len=8, dump=False):
     """Restore ``model_path`` as evaluate.evaluate does and plan for the sequences of ``input_path`` (module docstring).
     -> the dict written to ``output_path``/plan.json."""
-    from . import graph as G
-    from .evaluate import EMA_BUILD_DECAY, _batches, _use_ema_weights
-    from .saver import Saver, latest_checkpoint
-    from .train import Trainer, model_kind
+    from .evaluate import _batches, predicting_trainer
+    from .saver import latest_checkpoint
+    from .train import model_kind
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
     if bn_stats not in ('batch', 'stored'):
@@ -401,21 +383,10 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
     if ckpt is None:
         raise FileNotFoundError('no checkpoint under %s' % model_path)
     os.makedirs(output_path, exist_ok=True)
-    stored = bn_stats == 'stored'
-    extra = {'bn_inference': True} if stored else {}
-    if weights == 'ema':
-        extra['ema_decay'] = EMA_BUILD_DECAY
-    G.reset_default_graph()
-    sess = G.Session(device=device, dtype=dtype)
+    trainer, ema_updates, _ = predicting_trainer(ckpt, transform, candidates, ksize, img_size, dtype, device, num_masks, bn_stats, weights,
+                                                 calibrate_with='evaluate --bn_stats calibrate')
+    sess = trainer.sess
     try:
-        trainer = Trainer(sess, False, 'bce', 'adam', transform, batch_size=candidates, img_size=img_size, ksize=ksize, lookahead=False,
-                          num_masks=num_masks, **extra)
-        sess.run(G.global_variables_initializer())
-        Saver().restore(sess, ckpt)
-        ema_updates = _use_ema_weights(trainer, ckpt) if weights == 'ema' else None      # (copied into the variables: 'raw' from here on)
-        if stored and trainer.bn_calibration_rows() < 1:
-            raise ValueError('--bn_stats stored: checkpoint %s holds no calibrated BatchNorm statistics (run evaluate --bn_stats calibrate '
-                             'first)' % os.path.abspath(ckpt))
         planner = Planner(trainer, horizon, elites, iterations, init_std=init_std, min_std=min_std, alpha=alpha, state_weight=state_weight,
                           cost_steps=cost_steps, seed=seed, bn=bn_stats)
         per_seq, plans, plan_frames, rollout_s = [], [], [], 0.0

@@ -138,7 +138,7 @@ class Trainer:
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
         self.sched_sampling = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, ss_offset, ss_seed, rollout_steps,
                                                    batch_size)      # (None: off)
-        ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
+        self.ema_decay = ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
         self.ssim_weight = check_ssim_weight(ssim_weight)
         self.g_clip_norm, self.d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
         grad_norms = bool(grad_norms)
@@ -235,25 +235,14 @@ class Trainer:
 
         # losses (train.py:72-85)
         self.g_psnr = O.build_psnr(self.next_frame_ph, self.g_next_frame)
-        l1, gdl = O.frame_losses(self.g_out, self.next_frame_ph)
-        g_l2_loss = l1 / B
-        if arg_transform:
-            with G.get_default_graph().side_branch():      # the state head's loss belongs to its side chain (models.py)
-                state_loss = O.l2_norm(self.g_state_out, self.next_state, name='g_state_loss')
-            g_l2_loss = g_l2_loss * L2_WEIGHT + state_loss / B
         self.summaries = {}
-        self.g_ssim_loss = None
-        if self.ssim_weight:
-            self.g_ssim_loss = O.ssim_loss(self.g_out, self.next_frame_ph) / B
-            g_l2_loss = g_l2_loss + self.g_ssim_loss * self.ssim_weight
-            self.summaries['g_ssim_loss'] = self.g_ssim_loss
+        g_l2_loss, self.g_ssim_loss, adv_loss, self.g_loss = self._step_losses(self.g_out, self.g_state_out, self.next_frame_ph, self.next_state,
+                                                                               self.d_out_gen, '', mean_ssim=True)
         self.g_l2_loss = g_l2_loss
+        if self.g_ssim_loss is not None:
+            self.summaries['g_ssim_loss'] = self.g_ssim_loss
         if arg_adv:
-            self.g_adv_loss = O.build_g_adv_loss(self.d_out_gen, arg_loss)
-            self.g_loss = g_l2_loss + self.g_adv_loss + gdl
-            self.summaries['g_adv_loss'] = self.g_adv_loss
-        else:
-            self.g_loss = g_l2_loss
+            self.g_adv_loss = self.summaries['g_adv_loss'] = adv_loss
         if batched_d:
             self.d_loss = O.build_d_loss_batched(self.d_out_both, arg_loss, summaries=self.summaries)
         else:
@@ -284,9 +273,11 @@ class Trainer:
         self.grad_norm = {'g': optim.GradNorm(self.g_clip_norm or math.inf, 'g') if self.g_clip_norm or grad_norms else None,
                           'd': optim.GradNorm(self.d_clip_norm or math.inf, 'd') if arg_adv and (self.d_clip_norm or grad_norms) else None}
         g_norm, d_norm = self.grad_norm['g'], self.grad_norm['d']
-        self.g_opt_op = make('g_opt').minimize(self.g_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm, lr_schedule=g_sched)
-        self.g_pretrain_opt_op = make('g_pretrain_opt').minimize(g_l2_loss, var_list=self.g_vars, ema=self.ema, clip_norm=g_norm,
-                                                                 lr_schedule=g_sched)
+
+        def minimize_g(name, loss, slots_of=None):       # every G update: the same variables, average, clip and schedule
+            return make(name).minimize(loss, var_list=self.g_vars, slots_of=slots_of, ema=self.ema, clip_norm=g_norm, lr_schedule=g_sched)
+        self.g_opt_op = minimize_g('g_opt', self.g_loss)
+        self.g_pretrain_opt_op = minimize_g('g_pretrain_opt', g_l2_loss)
         self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars, clip_norm=d_norm, lr_schedule=d_sched)
 
         # the seven tf.summary scalars of ops.py:48-49 / train.py:104-111, names kept
@@ -299,7 +290,7 @@ class Trainer:
         self._noise_on = None           # the 0 / 1 factor of the noise as last written (_noise_switch; None: not yet)
         self._skip_d = self._skip_g = None
         if self.rollout_steps > 1:
-            self._build_rollout(build_g, make)
+            self._build_rollout(build_g, minimize_g)
         if self.lookahead:
             # what the pair pass replaces.  D step: the whole batch-B generator and the launch that puts its frame into D's input.
             # G step: the generator up to and including the frame (an alias of the pair's first half) and, where the DNA kernel
@@ -338,17 +329,6 @@ class Trainer:
         return out
 
     # ---- the generator's noise input (noise_dim > 0)
-    def _check_noise_mode(self, noise):
-        if noise not in ('zero', 'sample'):
-            raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
-        if noise == 'sample' and not self.noise_dim:
-            raise RuntimeError("noise='sample': this Trainer was built without noise_dim, its generator reads no noise")
-        return noise == 'sample'
-
-    def _set_noise(self, noise):
-        """The predicting calls: the noise as their ``noise`` says."""
-        self._noise_switch(self._check_noise_mode(noise), always=True)
-
     def _noise_switch(self, on, always=False):
         """Write the 0 / 1 factor of the noise the next generator pass reads (ops.noise_state: outside the programs, on their
         stream).  The training steps switch it on and write only when they last wrote something else; a predicting call always
@@ -368,17 +348,15 @@ class Trainer:
         """-> (seed, counter) of ``g/noise/state`` as Python ints in [0, 2^64): the counter is the number of draws so far."""
         if not self.noise_dim:
             raise RuntimeError('this Trainer was built without noise_dim: it keeps no noise state')
-        seed, counter = (int(v) % 2 ** 64 for v in self.sess._materialize(O.noise_state()[0]).cpu().numpy())
-        return seed, counter
+        return O.read_draw_state(self.sess._materialize(O.noise_state()[0]))
 
     def set_noise_state(self, seed, counter=0):
         """Restart the noise stream at (seed, counter): the draws that follow are those of a fresh Trainer built with that seed
         after ``counter`` generator passes."""
         if not self.noise_dim:
             raise RuntimeError('this Trainer was built without noise_dim: it keeps no noise state')
-        vals = [check_noise_seed(seed), check_noise_seed(counter)]
-        state = self.sess._materialize(O.noise_state()[0])
-        state.copy_(torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64))
+        seed, counter = check_noise_seed(seed), check_noise_seed(counter)
+        O.write_draw_state(self.sess._materialize(O.noise_state()[0]), seed, counter)
         self._announced = None
 
     # ---- scheduled sampling of the K-step programs (sched_sampling != 'off')
@@ -399,16 +377,14 @@ class Trainer:
         """-> (seed, counter) of ``g/sched_sampling/state`` as Python ints in [0, 2^64): the counter is the number of K-step
         updates so far."""
         self._require_sched_sampling()
-        seed, counter = (int(v) % 2 ** 64 for v in self.sess._materialize(O.sched_sampling_state()).cpu().numpy())
-        return seed, counter
+        return O.read_draw_state(self.sess._materialize(O.sched_sampling_state()))
 
     def set_sched_sampling_state(self, seed, counter=0):
         """Restart the coins at (seed, counter): the K-step updates that follow draw what a fresh Trainer built with that seed
         draws after ``counter`` updates, at the schedule's value there."""
         self._require_sched_sampling()
-        vals = [check_noise_seed(seed, 'seed'), check_noise_seed(counter, 'counter')]
-        state = self.sess._materialize(O.sched_sampling_state())
-        state.copy_(torch.tensor([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=torch.int64))
+        seed, counter = check_noise_seed(seed, 'seed'), check_noise_seed(counter, 'counter')
+        O.write_draw_state(self.sess._materialize(O.sched_sampling_state()), seed, counter)
 
     # ---- gradient norms (g_clip_norm / d_clip_norm / grad_norms)
     def grad_norm_stats(self, scope):
@@ -487,12 +463,30 @@ class Trainer:
         self.sess._weights_dirty = True
         self._announced = None
 
-    def _check_weights(self, weights):
+    @contextlib.contextmanager
+    def _predicting(self, bn='batch', weights='raw', noise='zero', switch=True):
+        """The mode of a predicting call (``test``, ``test_sequence``, ``rollout_metrics``, plan.Planner).  Every argument is
+        checked before anything is launched; then, for ``weights='ema'``, the body runs inside ``ema_weights()``, a prepared
+        generator pass is dropped and the noise switch is written as ``noise`` says (``switch=False``: checked only - the caller
+        has checks of its own to make first, and the ``test`` it goes on to call writes it).  Yields whether the
+        stored-statistics instance predicts."""
         if weights not in ('raw', 'ema'):
             raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
         if weights == 'ema':
             self._require_ema()
-        return weights == 'ema'
+        if bn not in ('batch', 'stored'):
+            raise ValueError("bn must be 'batch' or 'stored', got %r" % (bn,))
+        if bn == 'stored':
+            self._require_calibrated()
+        if noise not in ('zero', 'sample'):
+            raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
+        if noise == 'sample' and not self.noise_dim:
+            raise RuntimeError("noise='sample': this Trainer was built without noise_dim, its generator reads no noise")
+        with self.ema_weights() if weights == 'ema' else contextlib.nullcontext():
+            self._announced = None
+            if switch:
+                self._noise_switch(noise == 'sample', always=True)
+            yield bn == 'stored'
 
     def _build_bn_inference(self, build_g):
         """Two more generator instances on the existing variables and placeholders (the modes arrive through the arg scope of
@@ -559,14 +553,32 @@ class Trainer:
         self._require_bn_inference()
         return {t.name: self.sess._materialize(t).detach().cpu().numpy().copy() for state in self._bn_state.values() for t in state}
 
-    def _check_bn_mode(self, bn):
-        if bn not in ('batch', 'stored'):
-            raise ValueError("bn must be 'batch' or 'stored', got %r" % (bn,))
-        if bn == 'stored':
-            self._require_calibrated()
-        return bn == 'stored'
+    def _step_losses(self, frame, state, next_frame, next_state, d_out, prefix, suffix='', mean_ssim=False):
+        """The losses of ONE generator step (train.py:72-85), for the one-step graph and every step of the rollout: L1 / B (times
+        L2_WEIGHT plus the state norm / B where the generator has a state head), plus the SSIM term, is the l2 part; the full loss
+        adds the adversarial term on ``d_out`` = D(fake) and the GDL with ``arg_adv``.  -> (l2 part, SSIM term or None, adversarial
+        term or None, full G loss).  ``mean_ssim``: the SSIM term is the unweighted mean sum_b (1 - SSIM_b) / B, which the one-step
+        graph reports as a summary (it divides, then weighs); the rollout steps weigh the sum by ssim_weight / B in one op."""
+        B = self.batch_size
+        l1, gdl = O.frame_losses(frame, next_frame)
+        l2 = l1 / B
+        if state is not None:
+            with G.get_default_graph().side_branch():      # the state head's loss belongs to its side chain (models.py)
+                state_loss = O.l2_norm(state, next_state, name='%sg_state_loss%s' % (prefix, suffix))
+            l2 = l2 * L2_WEIGHT + state_loss / B
+        ssim = None
+        if self.ssim_weight and mean_ssim:
+            ssim = O.ssim_loss(frame, next_frame) / B
+            l2 = l2 + ssim * self.ssim_weight
+        elif self.ssim_weight:
+            ssim = O.ssim_loss(frame, next_frame) * (self.ssim_weight / B)
+            l2 = l2 + ssim
+        if not self.arg_adv:
+            return l2, ssim, None, l2
+        adv = O.build_g_adv_loss(d_out, self.arg_loss)
+        return l2, ssim, adv, l2 + adv + gdl
 
-    def _build_rollout(self, build_g, make):
+    def _build_rollout(self, build_g, minimize_g):
         """K generator instances chained through their own predictions and K D(fake) instances, on the existing variables.
         Step j: x_{t+j+1}, s_{t+j+1} = G(in_j, act_j) with in_0 the fed frame and in_j the frame of step j-1; act_0 is fed, act_j
         is [command_j (fed), the state of step j-1] (the plain generator has no state head: act_j is fed whole, as test_sequence
@@ -575,7 +587,6 @@ class Trainer:
         The G loss is the mean of the K step losses, the pretraining loss the mean of their l2 parts; both updates continue the
         one-step optimizers' state (optim minimize slots_of)."""
         K, B, S = self.rollout_steps, self.batch_size, self.img_size
-        graph = G.get_default_graph()
         dna = self.model == 'dna'
         self.roll_img_ph = G.placeholder((B, S, S, 3), name='rollout/frame0')
         self.roll_img_ph.padded = self._roll_img_pad = G.placeholder((B, S, S, 3), name='rollout/frame0_conv', channel_pitch=O.cpad(3), act=True)
@@ -596,15 +607,7 @@ class Trainer:
         for j in range(K):
             frame, state = build_g(img, act, B, True)
             d_out = M.build_discriminator(O.concat([img, frame], axis=3, name='rollout/d_in%d' % j, pitch=8, act=True), act, reuse=True)
-            l1, gdl = O.frame_losses(frame, self.roll_next_ph[j])
-            l2 = l1 / B
-            if dna:
-                with graph.side_branch():
-                    state_loss = O.l2_norm(state, self.roll_state_ph[j], name='rollout/g_state_loss%d' % j)
-                l2 = l2 * L2_WEIGHT + state_loss / B
-            if self.ssim_weight:
-                l2 = l2 + O.ssim_loss(frame, self.roll_next_ph[j]) * (self.ssim_weight / B)
-            loss = l2 + O.build_g_adv_loss(d_out, self.arg_loss) + gdl if self.arg_adv else l2
+            l2, _, _, loss = self._step_losses(frame, state, self.roll_next_ph[j], self.roll_state_ph[j], d_out, 'rollout/', str(j))
             self.rollout_frames.append(frame)
             self.rollout_states.append(state)
             self.rollout_losses.append(loss)
@@ -617,11 +620,8 @@ class Trainer:
                 img = frame
                 act = O.rollout_actions(self.roll_action_ph[j + 1], state, name='rollout/actions%d' % (j + 1)) if dna else self.roll_action_ph[j + 1]
         total, l2_total = sum(self.rollout_losses[1:], self.rollout_losses[0]), sum(l2_losses[1:], l2_losses[0])
-        self.g_rollout_opt_op = make('g_opt_rollout').minimize(total / K, var_list=self.g_vars, slots_of=self.g_opt_op, ema=self.ema,
-                                                               clip_norm=self.grad_norm['g'], lr_schedule=self.lr_sched['g'])
-        self.g_rollout_pretrain_opt_op = make('g_pretrain_opt_rollout').minimize(l2_total / K, var_list=self.g_vars,
-                                                                                slots_of=self.g_pretrain_opt_op, ema=self.ema,
-                                                                                clip_norm=self.grad_norm['g'], lr_schedule=self.lr_sched['g'])
+        self.g_rollout_opt_op = minimize_g('g_opt_rollout', total / K, slots_of=self.g_opt_op)
+        self.g_rollout_pretrain_opt_op = minimize_g('g_pretrain_opt_rollout', l2_total / K, slots_of=self.g_pretrain_opt_op)
 
     def _rollout_feed(self, frames, actions, states):
         """frames [B, K+1, H, W, 3] (t .. t+K), actions [B, K, 10] (a_t .. a_{t+K-1}, state half read at step 0 only by the DNA
@@ -733,21 +733,17 @@ class Trainer:
         ``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
         summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames).
         ``weights='ema'`` (a Trainer built with ``ema_decay``): the same call inside ``ema_weights()``."""
-        if self._check_weights(weights):
-            with self.ema_weights():
-                return self.test(input_images, next_frame, actions, bn=bn, noise=noise)
-        self._announced = None
-        self._set_noise(noise)
-        if self._check_bn_mode(bn):
-            has_state = self.g_state_stored is not None
-            fd = {self.img_ph: input_images, self._img_pad: input_images, self.next_frame_ph: next_frame, self.action_ph: actions}
-            res = self.sess.run([self.g_out_stored] + ([self.g_state_stored] if has_state else []) + [[self._stored_psnr]], fd)
-            return res[0], (res[1] if has_state else None), {'g_psnr': float(np.asarray(res[-1][0]).reshape(-1)[0])}
-        tensors = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else []) + [self.merged_summaries]
-        res = self.sess.run(tensors, self._feed(input_images, next_frame, actions))
-        gen_next_frames, summ = res[0], res[-1]
-        gen_next_state = res[1] if self.g_state_out is not None else None      # defect D4
-        return gen_next_frames, gen_next_state, self._named(summ)
+        with self._predicting(bn, weights, noise) as stored:
+            if stored:
+                has_state = self.g_state_stored is not None
+                fd = {self.img_ph: input_images, self._img_pad: input_images, self.next_frame_ph: next_frame, self.action_ph: actions}
+                res = self.sess.run([self.g_out_stored] + ([self.g_state_stored] if has_state else []) + [[self._stored_psnr]], fd)
+                return res[0], (res[1] if has_state else None), {'g_psnr': float(np.asarray(res[-1][0]).reshape(-1)[0])}
+            tensors = [self.g_next_frame] + ([self.g_state_out] if self.g_state_out is not None else []) + [self.merged_summaries]
+            res = self.sess.run(tensors, self._feed(input_images, next_frame, actions))
+            gen_next_frames, summ = res[0], res[-1]
+            gen_next_state = res[1] if self.g_state_out is not None else None      # defect D4
+            return gen_next_frames, gen_next_state, self._named(summ)
 
     def test_sequence(self, input_images, test_next_frame, test_actions, steps=None, literal=False, device_loop=None, bn='batch',
                       weights='raw', noise='zero'):
@@ -765,40 +761,35 @@ class Trainer:
         and the second return value is ``current_frame[1:7]``, samples 1..6 of the last prediction.
         ``bn``: 'batch' (default: every step normalises with the statistics of its batch) or 'stored' (see ``test``).
         ``weights``: 'raw' or 'ema' (see ``test``).  ``noise``: 'zero' or 'sample' (see ``test``): every step draws its own z."""
-        if self._check_weights(weights):
-            with self.ema_weights():
-                return self.test_sequence(input_images, test_next_frame, test_actions, steps=steps, literal=literal,
-                                          device_loop=device_loop, bn=bn, noise=noise)
-        self._check_bn_mode(bn)
-        self._set_noise(noise)
-        if literal:
-            predicted = []
+        with self._predicting(bn, weights, noise):       # (the steps are ``test`` calls on the weights this has put in place)
+            if literal:
+                predicted = []
+                current_frame = input_images[:, 0]
+                current_state = test_actions[:, 0, 5:]
+                for j in range(0, 6):
+                    acs = np.concatenate((test_actions[:, j * 2, :5], current_state), axis=1).astype(np.float32)
+                    out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs, bn=bn, noise=noise)
+                    predicted.append(out)
+                    current_frame = out
+                    current_state = st if st is not None else test_actions[:, j * 2, 5:]      # plain generator: no state head (D4)
+                return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), current_frame[1:7]
+            steps = steps if steps is not None else test_next_frame.shape[1] - 1
+            if device_loop is None:
+                device_loop = self.sess.rt.is_cuda
+            if device_loop and steps >= 1:
+                predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps, bn=bn, noise=noise)
+                return predicted.cpu().numpy(), summ0
+            predicted, summ0 = [], None
             current_frame = input_images[:, 0]
             current_state = test_actions[:, 0, 5:]
-            for j in range(0, 6):
-                acs = np.concatenate((test_actions[:, j * 2, :5], current_state), axis=1).astype(np.float32)
-                out, st, _ = self.test(current_frame, test_next_frame[:, j * 2], acs, bn=bn, noise=noise)
+            for j in range(steps):
+                acs = np.concatenate((test_actions[:, j, :5], current_state), axis=1).astype(np.float32)
+                out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs, bn=bn, noise=noise)
+                summ0 = summ0 or summ
                 predicted.append(out)
                 current_frame = out
-                current_state = st if st is not None else test_actions[:, j * 2, 5:]      # plain generator: no state head (D4)
-            return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), current_frame[1:7]
-        steps = steps if steps is not None else test_next_frame.shape[1] - 1
-        if device_loop is None:
-            device_loop = self.sess.rt.is_cuda
-        if device_loop and steps >= 1:
-            predicted, summ0 = self._rollout_on_device(input_images, test_next_frame, test_actions, steps, bn=bn, noise=noise)
-            return predicted.cpu().numpy(), summ0
-        predicted, summ0 = [], None
-        current_frame = input_images[:, 0]
-        current_state = test_actions[:, 0, 5:]
-        for j in range(steps):
-            acs = np.concatenate((test_actions[:, j, :5], current_state), axis=1).astype(np.float32)
-            out, st, summ = self.test(current_frame, test_next_frame[:, j + 1], acs, bn=bn, noise=noise)
-            summ0 = summ0 or summ
-            predicted.append(out)
-            current_frame = out
-            current_state = st if st is not None else test_actions[:, j + 1, 5:]
-        return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), summ0
+                current_state = st if st is not None else test_actions[:, j + 1, 5:]
+            return np.transpose(np.array(predicted), (1, 0, 2, 3, 4)), summ0
 
     def _rollout_on_device(self, input_images, test_next_frame, test_actions, steps, bn='batch', noise='zero'):
         """The device loop of ``test_sequence``: -> (predicted [B, steps, H, W, 3] float32 on the device, summaries of step 0).
@@ -833,28 +824,23 @@ class Trainer:
         ``identity_sqerr``; with ``return_frames`` also ``frames`` [B, steps, H, W, 3] (the only device-to-host copy of frames).
         ``bn``: 'batch' or 'stored', ``weights``: 'raw' or 'ema', ``noise``: 'zero' or 'sample', as ``test`` takes them."""
         from . import metrics
-        if self._check_weights(weights):
-            with self.ema_weights():
-                return self.rollout_metrics(images, actions, steps=steps, identity=identity, return_frames=return_frames, bn=bn,
-                                            noise=noise)
-        self._check_bn_mode(bn)
-        self._check_noise_mode(noise)
-        if not self.sess.rt.is_cuda:
-            raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
-        steps = steps if steps is not None else images.shape[1] - 1
-        if steps < 1 or steps + 1 > images.shape[1]:
-            raise ValueError('rollout_metrics: %d steps need %d frames per sequence, got %d' % (steps, steps + 1, images.shape[1]))
-        predicted, _ = self._rollout_on_device(images, images, actions, steps, bn=bn, noise=noise)
-        seq = self.sess.upload(np.asarray(images[:, :steps + 1], np.float32))                # [B, steps + 1, H, W, 3], once
-        truth = seq[:, 1:]
-        ssim, sqerr = metrics.frame_metrics(predicted, truth)
-        out = {'ssim': ssim, 'sqerr': sqerr}
-        if identity:
-            out['identity_ssim'], out['identity_sqerr'] = metrics.frame_metrics(seq[:, :1].expand_as(truth), truth)
-        out = {k: v.cpu().numpy() for k, v in out.items()}
-        if return_frames:
-            out['frames'] = predicted.cpu().numpy()
-        return out
+        with self._predicting(bn, weights, noise, switch=False):
+            if not self.sess.rt.is_cuda:
+                raise RuntimeError('rollout_metrics scores on the GPU: the session has no GPU device')
+            steps = steps if steps is not None else images.shape[1] - 1
+            if steps < 1 or steps + 1 > images.shape[1]:
+                raise ValueError('rollout_metrics: %d steps need %d frames per sequence, got %d' % (steps, steps + 1, images.shape[1]))
+            predicted, _ = self._rollout_on_device(images, images, actions, steps, bn=bn, noise=noise)
+            seq = self.sess.upload(np.asarray(images[:, :steps + 1], np.float32))                # [B, steps + 1, H, W, 3], once
+            truth = seq[:, 1:]
+            ssim, sqerr = metrics.frame_metrics(predicted, truth)
+            out = {'ssim': ssim, 'sqerr': sqerr}
+            if identity:
+                out['identity_ssim'], out['identity_sqerr'] = metrics.frame_metrics(seq[:, :1].expand_as(truth), truth)
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            if return_frames:
+                out['frames'] = predicted.cpu().numpy()
+            return out
 
     def _named(self, values):
         return {k: float(np.asarray(v).reshape(-1)[0]) for k, v in zip(self._summary_names, values)}
@@ -869,38 +855,46 @@ def model_kind(arg_transform):
     return 'dna' if arg_transform else 'plain'
 
 
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _number(value, what, be, lie, ok):
+    """``value`` as a float when it is a number - no bool - that ``ok`` accepts (a range test, in float32 too where the kernel
+    reads a float32; nan fails every one of them); else ValueError: '<what> must be <be>' for no number, '<what> must <lie>'."""
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('%s must be %s, got %r' % (what, be, value))
+    if isinstance(value, bool) or not ok(x):
+        raise ValueError('%s must %s, got %r' % (what, lie, value))
+    return x
+
+
+def _is_count(value):
+    """An integer (no bool) in [0, 2^63): a number of updates or iterations the kernels take as int64."""
+    return not isinstance(value, bool) and isinstance(value, (int, np.integer)) and 0 <= int(value) < 2 ** 63
+
+
 def check_ema_decay(ema_decay):
     """ValueError for an ``ema_decay`` that is neither 0 (no average) nor inside (0, 1); -> the decay as a float."""
-    try:
-        d = float(ema_decay)
-    except (TypeError, ValueError):
-        raise ValueError('ema_decay must be 0 (off) or a number in (0, 1), got %r' % (ema_decay,))
-    if isinstance(ema_decay, bool) or not 0.0 <= d < 1.0 or (d > 0.0 and not 0.0 < float(np.float32(d)) < 1.0):
-        raise ValueError('ema_decay must be 0 (off) or lie in (0, 1), got %r' % (ema_decay,))
-    return d
+    return _number(ema_decay, 'ema_decay', '0 (off) or a number in (0, 1)', 'be 0 (off) or lie in (0, 1)',
+                   lambda d: 0.0 <= d < 1.0 and (d == 0.0 or 0.0 < _f32(d) < 1.0))
 
 
 def check_ssim_weight(ssim_weight):
     """ValueError for an ``ssim_weight`` that is not a finite number >= 0; -> the weight as a float (0: no SSIM term)."""
-    try:
-        w = float(ssim_weight)
-    except (TypeError, ValueError):
-        raise ValueError('ssim_weight must be a finite number >= 0, got %r' % (ssim_weight,))
-    if isinstance(ssim_weight, bool) or not 0.0 <= w <= float(np.finfo(np.float32).max):      # (finite in float32; nan fails too)
-        raise ValueError('ssim_weight must be finite and >= 0, got %r' % (ssim_weight,))
-    return w
+    return _number(ssim_weight, 'ssim_weight', 'a finite number >= 0', 'be finite and >= 0', lambda w: 0.0 <= w <= F32_MAX)
 
 
 def check_clip_norm(value, what='clip_norm'):
     """ValueError for a ``g_clip_norm`` / ``d_clip_norm`` that is not a finite number >= 0 (or is positive and rounds to 0 in
     float32); -> the bound as a float (0: no clip)."""
-    try:
-        x = float(value)
-    except (TypeError, ValueError):
-        raise ValueError('%s must be a finite number >= 0, got %r' % (what, value))
-    if isinstance(value, bool) or not 0.0 <= x <= float(np.finfo(np.float32).max) or (x > 0.0 and float(np.float32(x)) == 0.0):
-        raise ValueError('%s must be finite and >= 0 (0: off), got %r' % (what, value))
-    return x
+    return _number(value, what, 'a finite number >= 0', 'be finite and >= 0 (0: off)',
+                   lambda x: 0.0 <= x <= F32_MAX and (x == 0.0 or _f32(x) != 0.0))
 
 
 LR_SCHEDULES = ('constant', 'linear', 'cosine', 'exponential')
@@ -915,40 +909,21 @@ def check_lr(g_lr=None, d_lr=None, beta1=None, arg_opt='adam', lr_schedule='cons
     default = RMSPROP_LR if arg_opt == 'rmsprop' else ADAM_LR
     rates = {}
     for what, v in (('g_lr', g_lr), ('d_lr', d_lr)):
-        if v is None:
-            rates[what] = default
-            continue
-        try:
-            x = float(v)
-        except (TypeError, ValueError):
-            raise ValueError('%s must be a finite number > 0, got %r' % (what, v))
-        if isinstance(v, bool) or not 0.0 < x <= float(np.finfo(np.float32).max) or float(np.float32(x)) == 0.0:
-            raise ValueError('%s must be finite and > 0, got %r' % (what, v))
-        rates[what] = x
+        rates[what] = default if v is None else _number(v, what, 'a finite number > 0', 'be finite and > 0',
+                                                        lambda x: 0.0 < x <= F32_MAX and _f32(x) != 0.0)
     if beta1 is not None:
         if arg_opt == 'rmsprop':
             raise ValueError("beta1 is Adam's: it does not go with the rmsprop optimizer")
-        try:
-            b = float(beta1)
-        except (TypeError, ValueError):
-            raise ValueError('beta1 must be a number in [0, 1), got %r' % (beta1,))
-        if isinstance(beta1, bool) or not 0.0 <= b < 1.0 or not float(np.float32(b)) < 1.0:
-            raise ValueError('beta1 must lie in [0, 1), got %r' % (beta1,))
-        beta1 = b
+        beta1 = _number(beta1, 'beta1', 'a number in [0, 1)', 'lie in [0, 1)', lambda b: 0.0 <= b < 1.0 and _f32(b) < 1.0)
     if lr_schedule not in LR_SCHEDULES:
         raise ValueError('lr_schedule must be one of %s, got %r' % (', '.join(LR_SCHEDULES), lr_schedule))
     counts = {}
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         pair = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-        if len(pair) != 2 or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < 2 ** 63 for c in pair):
+        if len(pair) != 2 or not all(_is_count(c) for c in pair):
             raise ValueError("%s must be an integer >= 0 (or a pair of them: G's, D's), got %r" % (what, v))
         counts[what] = (int(pair[0]), int(pair[1]))
-    try:
-        final = float(lr_final)
-    except (TypeError, ValueError):
-        raise ValueError('lr_final must be a number in [0, 1], got %r' % (lr_final,))
-    if isinstance(lr_final, bool) or not 0.0 <= final <= 1.0:
-        raise ValueError('lr_final must lie in [0, 1], got %r' % (lr_final,))
+    final = _number(lr_final, 'lr_final', 'a number in [0, 1]', 'lie in [0, 1]', lambda x: 0.0 <= x <= 1.0)
     if lr_schedule != 'constant':
         if min(counts['lr_decay_steps']) < 1:
             raise ValueError('lr_schedule %r needs lr_decay_steps >= 1, got %r' % (lr_schedule, lr_decay_steps))
@@ -994,18 +969,11 @@ def check_sched_sampling(sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_de
     {'kind', 'start', 'final', 'decay_steps', 'offset', 'seed'}."""
     if sched_sampling not in SCHED_SAMPLING:
         raise ValueError('sched_sampling must be one of %s, got %r' % (', '.join(SCHED_SAMPLING), sched_sampling))
-    probs = {}
-    for what, v in (('ss_start', ss_start), ('ss_final', ss_final)):
-        try:
-            x = float(v)
-        except (TypeError, ValueError):
-            raise ValueError('%s must be a number in [0, 1], got %r' % (what, v))
-        if isinstance(v, bool) or not 0.0 <= x <= 1.0:                  # (nan fails too)
-            raise ValueError('%s must lie in [0, 1], got %r' % (what, v))
-        probs[what] = x
+    probs = {what: _number(v, what, 'a number in [0, 1]', 'lie in [0, 1]', lambda x: 0.0 <= x <= 1.0)
+             for what, v in (('ss_start', ss_start), ('ss_final', ss_final))}
     counts = {}
     for what, v in (('ss_decay_steps', ss_decay_steps), ('ss_offset', ss_offset)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 63:
+        if not _is_count(v):
             raise ValueError('%s must be an integer >= 0, got %r' % (what, v))
         counts[what] = int(v)
     seed = check_noise_seed(ss_seed, 'ss_seed')
@@ -1258,20 +1226,39 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         if isinstance(v, (tuple, list)):
             raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
+    # every option is checked here, before anything is created, and handed to the Trainer once: an option at its "off" value is
+    # not passed at all (the Trainer then builds the graph it built before the option existed)
+    D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
+    options = dict(arg_adv=arg_adv, arg_loss=arg_loss, arg_opt=arg_opt, arg_transform=arg_transform, batch_size=batch_size, img_size=img_size,
+                   ksize=ksize, num_masks=num_masks)
     la = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)
+    if (g_lr, d_lr, beta1) != (None, None, None):
+        options.update(g_lr=la['g_lr'], d_lr=la['d_lr'], beta1=la['beta1'])
+    if la['scheduled']:                 # iterations -> updates: D takes D_per_G of them per iteration
+        options.update(lr_schedule=la['schedule'], lr_final=la['final'], lr_warmup=(la['warmup'][0], la['warmup'][0] * D_per_G),
+                       lr_decay_steps=(la['decay_steps'][0], la['decay_steps'][0] * D_per_G))
     noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
+    if noise_dim:
+        options.update(noise_dim=noise_dim, noise_seed=noise_seed)
     ss = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, max(int(pretrain_iter), 0), ss_seed, rollout_steps,
                               batch_size)           # (the pretraining updates count too: the decay begins behind them)
-    ema_decay = check_ema_decay(ema_decay)
-    ssim_weight = check_ssim_weight(ssim_weight)
+    if ss is not None:
+        options.update(sched_sampling=ss['kind'], ss_start=ss['start'], ss_final=ss['final'], ss_decay_steps=ss['decay_steps'],
+                       ss_offset=ss['offset'], ss_seed=ss['seed'])
+    for key, value in (('ema_decay', check_ema_decay(ema_decay)), ('ssim_weight', check_ssim_weight(ssim_weight))):
+        if value:
+            options[key] = value
     g_clip_norm, d_clip_norm = check_clip_norm(g_clip_norm, 'g_clip_norm'), check_clip_norm(d_clip_norm, 'd_clip_norm')
+    if g_clip_norm or d_clip_norm or grad_norms:
+        options.update(g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm, grad_norms=bool(grad_norms))
     if data_frames not in ('selected', 'all'):
         raise ValueError("data_frames must be 'selected' or 'all'")
-    if int(rollout_steps) > 1:
+    if int(rollout_steps) > 1:          # (the K-step G step takes the plain call path: no pair instance to build)
         check_rollout(rollout_steps, model_kind(arg_transform), bf16=dtype == 'bf16',
                       data_parallel=world_size > 1 or sync_bn or exact_global_batch)
         if int(rollout_steps) > seq_len - 1:
             raise ValueError('rollout_steps %d needs sequences of more than %d frames (seq_len %d)' % (rollout_steps, rollout_steps, seq_len))
+        options.update(lookahead=False, rollout_steps=int(rollout_steps))
     np.random.seed(7)                                           # train.py:14
     synthetic = input_path in (None, '', 'synthetic')
     if synthetic:
@@ -1289,11 +1276,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
                             collectives=dp_collectives)
     sess = G.Session(device=device, world_size=world_size, rank=rank, process_group=process_group, dtype=dtype)
     try:
-        trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform,
-                              batch_size, img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume,
-                              select_frames=data_frames == 'selected', num_masks=num_masks, rollout_steps=int(rollout_steps),
-                              ema_decay=ema_decay, ssim_weight=ssim_weight, g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm,
-                              grad_norms=bool(grad_norms), noise_dim=noise_dim, noise_seed=noise_seed, lr_args=la, ss_args=ss)
+        trainer = _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, seq_len, train_iter, pretrain_iter, D_per_G,
+                              rank, log_every, quiet, eval_every, resume, select_frames=data_frames == 'selected', options=options)
         sess.rt.check_exchange_flags()     # a last look at the device-side flags of the iterations since the last log interval
     except BaseException:
         sess.close(check=False)            # tear the transport down; the exception on its way out is the one to report
@@ -1306,32 +1290,13 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     return trainer
 
 
-def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, arg_adv, arg_loss, arg_opt, arg_transform, batch_size,
-                img_size, seq_len, ksize, train_iter, pretrain_iter, n_critic, rank, log_every, quiet, eval_every, resume, select_frames=True,
-                num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
-                noise_dim=0, noise_seed=0, lr_args=None, ss_args=None):
-    ema = {'ema_decay': ema_decay} if ema_decay else {}
-    D_per_G = n_critic if n_critic else (5 if arg_loss == 'wass' else 1)      # train.py:217-220
-    la = lr_args or check_lr(arg_opt=arg_opt)
-    if la != check_lr(arg_opt=arg_opt):
-        ema.update(g_lr=la['g_lr'], d_lr=la['d_lr'], beta1=la['beta1'])
-    if la['scheduled']:                 # iterations -> updates: D takes D_per_G of them per iteration
-        ema.update(lr_schedule=la['schedule'], lr_final=la['final'], lr_warmup=(la['warmup'][0], la['warmup'][0] * D_per_G),
-                   lr_decay_steps=(la['decay_steps'][0], la['decay_steps'][0] * D_per_G))
-    if noise_dim:
-        ema.update(noise_dim=noise_dim, noise_seed=noise_seed)
-    if ss_args is not None:
-        ema.update(sched_sampling=ss_args['kind'], ss_start=ss_args['start'], ss_final=ss_args['final'], ss_decay_steps=ss_args['decay_steps'],
-                   ss_offset=ss_args['offset'], ss_seed=ss_args['seed'])
-    if ssim_weight:
-        ema['ssim_weight'] = ssim_weight
-    if g_clip_norm or d_clip_norm or grad_norms:
-        ema.update(g_clip_norm=g_clip_norm, d_clip_norm=d_clip_norm, grad_norms=grad_norms)
-    if rollout_steps > 1:               # (the K-step G step takes the plain call path: no pair instance to build)
-        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks,
-                          lookahead=False, rollout_steps=rollout_steps, **ema)
-    else:
-        trainer = Trainer(sess, arg_adv, arg_loss, arg_opt, arg_transform, batch_size, img_size, ksize, num_masks=num_masks, **ema)
+def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_dir, seq_len, train_iter, pretrain_iter, D_per_G, rank,
+                log_every, quiet, eval_every, resume, select_frames=True, options=None):
+    """The loop of ``train``: ``options`` are the Trainer's keywords as ``train`` checked and converted them; what the loop logs or
+    branches on it reads from the Trainer it builds."""
+    trainer = Trainer(sess, **options)
+    batch_size, img_size, rollout_steps = trainer.batch_size, trainer.img_size, trainer.rollout_steps
+    sampling, scheduled = trainer.sched_sampling is not None, trainer.lr_args['scheduled']
     sess.run(G.global_variables_initializer())
     saver = Saver()                                                           # train.py:215
     if resume:
@@ -1355,7 +1320,7 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
             inp, nxt, acts, states = data.get_batch()
             if rollout_steps > 1:
                 pre_loss = trainer.pretrain_g_rollout(*window_batch(sels[0], inp, nxt, acts, states))
-                if ss_args is not None and i % log_every == 0 and rank == 0:
+                if sampling and i % log_every == 0 and rank == 0:
                     # scheduled sampling: ss_prob at EVERY log interval, the pretraining iterations' included (they advance the counter
                     # the checkpoint holds), with the interval's checkpoint
                     if log_file:
@@ -1407,30 +1372,32 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 print('Iteration {:d}'.format(i))
             if log_file and summ:
                 stats = {sc: trainer.grad_norm_stats(sc) for sc, norm in trainer.grad_norm.items() if norm is not None}
-                bounds = None if bounds_logged or not stats else {'g': g_clip_norm, 'd': d_clip_norm}
-                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, ema_decay, ssim_weight, stats, bounds, noise_dim,
-                                                    trainer.learning_rates() if la['scheduled'] else None,
-                                                    ss_prob=trainer.sched_sampling_last()['prob'] if ss_args is not None else None))
+                bounds = None if bounds_logged or not stats else {'g': trainer.g_clip_norm, 'd': trainer.d_clip_norm}
+                _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, trainer.ema_decay, trainer.ssim_weight, stats, bounds,
+                                                    trainer.noise_dim, trainer.learning_rates() if scheduled else None,
+                                                    ss_prob=trainer.sched_sampling_last()['prob'] if sampling else None))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
         if eval_every and i % eval_every == 0 and rank == 0:
             # recursive rollout over T-1 steps on held-out sequences (train.py:278-309; defect D7: own states)
             t_img, _, t_acts, _ = eval_data.get_batch()
-            predicted, e_summ = trainer.test_sequence(t_img, t_img, t_acts)
-            psnr = [float(10.0 * np.log10(1.0 / max(np.mean((predicted[:, j] - t_img[:, j + 1]) ** 2), 1e-30)))
-                    for j in range(predicted.shape[1])]
-            if log_file:
+
+            def score(weights):
+                """-> (summaries of step 0, PSNR per step, SSIM per step or None) of the rollout with ``weights``."""
+                predicted, e_summ = trainer.test_sequence(t_img, t_img, t_acts, weights=weights)
+                psnr = [float(10.0 * np.log10(1.0 / max(np.mean((predicted[:, j] - t_img[:, j + 1]) ** 2), 1e-30)))
+                        for j in range(predicted.shape[1])]
+                if not log_file:
+                    return e_summ, psnr, None
                 # SSIM per step (mean over the batch) by the GPU kernel (metrics.frame_metrics) on the same predictions
                 ssim, _ = frame_metrics(sess.upload(predicted), sess.upload(np.asarray(t_img[:, 1:predicted.shape[1] + 1], np.float32)))
-                ssim = [float(v) for v in ssim.mean(dim=0, dtype=torch.float64).cpu().numpy()]
+                return e_summ, psnr, [float(v) for v in ssim.mean(dim=0, dtype=torch.float64).cpu().numpy()]
+            e_summ, psnr, ssim = score('raw')
+            if log_file:
                 record = dict(e_summ or {}, iteration=i, rollout_psnr=psnr, rollout_ssim=ssim)
-                if ema_decay and trainer.ema_updates() > 0:      # the same sequences through the averaged weights, scored the same way
-                    pred_e, _ = trainer.test_sequence(t_img, t_img, t_acts, weights='ema')
-                    record['rollout_psnr_ema'] = [float(10.0 * np.log10(1.0 / max(np.mean((pred_e[:, j] - t_img[:, j + 1]) ** 2), 1e-30)))
-                                                  for j in range(pred_e.shape[1])]
-                    ssim_e, _ = frame_metrics(sess.upload(pred_e), sess.upload(np.asarray(t_img[:, 1:pred_e.shape[1] + 1], np.float32)))
-                    record['rollout_ssim_ema'] = [float(v) for v in ssim_e.mean(dim=0, dtype=torch.float64).cpu().numpy()]
+                if trainer.ema is not None and trainer.ema_updates() > 0:      # the same sequences through the averaged weights
+                    _, record['rollout_psnr_ema'], record['rollout_ssim_ema'] = score('ema')
                 _log_jsonl(os.path.join(log_dir, 'test.jsonl'), record)
     if hasattr(eval_data, 'close'):
         eval_data.close()
@@ -1534,15 +1501,6 @@ def add_sched_sampling_args(parser):
     parser.add_argument('--ss_seed', type=int, default=0, metavar='S', help='seed of the coins (0 <= S < 2^64)')
 
 
-def check_sched_sampling_args(parser, args):
-    """parser.error for scheduled-sampling flags the Trainer does not take (before anything is created)."""
-    try:
-        check_sched_sampling(args.sched_sampling, args.ss_start, args.ss_final, args.ss_decay_iters, 0, args.ss_seed, args.rollout_steps,
-                             args.batch_size)
-    except ValueError as e:
-        parser.error('--sched_sampling / --ss_*: %s' % e)
-
-
 def add_lr_args(parser):
     """The learning-rate flags: the rates of G and D, Adam's beta1 and the schedule."""
     parser.add_argument('--g_lr', type=float, default=None, metavar='LR', help='learning rate of the generator updates (default: 1e-3 for adam, 5e-5 for rmsprop)')
@@ -1555,14 +1513,6 @@ def add_lr_args(parser):
     parser.add_argument('--lr_decay_iters', type=int, default=0, metavar='N', help='training iterations over which the rates decay (behind the warmup)')
     parser.add_argument('--lr_final', type=float, default=0.0, metavar='F',
                         help='the rates end at F x their value (0 <= F <= 1; exponential: F x per --lr_decay_iters iterations, 0 < F)')
-
-
-def check_lr_args(parser, args):
-    """parser.error for learning-rate flags the Trainer does not take (before anything is created)."""
-    try:
-        check_lr(args.g_lr, args.d_lr, args.beta1, args.opt, args.lr_schedule, args.lr_warmup, args.lr_decay_iters, args.lr_final)
-    except ValueError as e:
-        parser.error('--g_lr / --d_lr / --beta1 / --lr_*: %s' % e)
 
 
 def main(argv=None):
@@ -1621,26 +1571,25 @@ def main(argv=None):
     add_lr_args(parser)
     add_sched_sampling_args(parser)
     args = parser.parse_args(argv)
-    check_lr_args(parser, args)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
-    try:
-        check_ssim_weight(args.ssim_weight)
-    except ValueError:
-        parser.error('--ssim_weight must be finite and >= 0, got %r' % args.ssim_weight)
-    try:
-        check_ema_decay(args.g_ema)
-    except ValueError:
-        parser.error('--g_ema must be 0 (off) or lie in (0, 1), got %r' % args.g_ema)
-    for flag in ('g_clip_norm', 'd_clip_norm'):
-        try:
-            check_clip_norm(getattr(args, flag), flag)
-        except ValueError:
-            parser.error('--%s must be finite and >= 0, got %r' % (flag, getattr(args, flag)))
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
     check_noise_args(parser, args)
-    check_sched_sampling_args(parser, args)
+    # every other option: the check train() makes, its ValueError reported under the flags' names ({}: the check's own words)
+    for message, check in (
+            ('--g_lr / --d_lr / --beta1 / --lr_*: {}', lambda: check_lr(args.g_lr, args.d_lr, args.beta1, args.opt, args.lr_schedule,
+                                                                        args.lr_warmup, args.lr_decay_iters, args.lr_final)),
+            ('--ssim_weight must be finite and >= 0, got %r' % args.ssim_weight, lambda: check_ssim_weight(args.ssim_weight)),
+            ('--g_ema must be 0 (off) or lie in (0, 1), got %r' % args.g_ema, lambda: check_ema_decay(args.g_ema)),
+            ('--g_clip_norm must be finite and >= 0, got %r' % args.g_clip_norm, lambda: check_clip_norm(args.g_clip_norm)),
+            ('--d_clip_norm must be finite and >= 0, got %r' % args.d_clip_norm, lambda: check_clip_norm(args.d_clip_norm)),
+            ('--sched_sampling / --ss_*: {}', lambda: check_sched_sampling(args.sched_sampling, args.ss_start, args.ss_final, args.ss_decay_iters,
+                                                                           0, args.ss_seed, args.rollout_steps, args.batch_size))):
+        try:
+            check()
+        except ValueError as e:
+            parser.error(message.format(e))
     model_dir = os.path.join(args.output_path, 'models')
     log_dir = os.path.join(args.output_path, 'logs')
     os.makedirs(args.output_path)
@@ -1652,18 +1601,14 @@ def main(argv=None):
         # control plane only (bootstrap of the RCCL communicator, comm.py): gradients never go through torch.distributed
         torch.cuda.set_device(local_rank)
         torch.distributed.init_process_group('gloo')
+    # every other flag is a keyword of train() under its own name, but for these four
+    options = {k: v for k, v in vars(args).items() if k not in ('input_path', 'output_path', 'adv', 'loss', 'opt', 'dna', 'cdna')}
+    for flag, keyword in (('g_ema', 'ema_decay'), ('log_grad_norms', 'grad_norms'), ('lr_decay_iters', 'lr_decay_steps'),
+                          ('ss_decay_iters', 'ss_decay_steps')):
+        options[keyword] = options.pop(flag)
     trainer = train(args.input_path, os.path.join(args.output_path, 'train_output'), os.path.join(args.output_path, 'test_output'),
-                    log_dir, model_dir, args.adv, args.loss, args.opt, transform, batch_size=args.batch_size, img_size=args.img_size,
-                    seq_len=args.seq_len, ksize=args.ksize, train_iter=args.train_iter, pretrain_iter=args.pretrain_iter,
-                    n_critic=args.n_critic, device='cuda:%d' % local_rank, world_size=world_size, rank=rank, dtype=args.dtype,
-                    sync_bn=args.sync_bn, exact_global_batch=args.exact_global_batch, dp_collectives=args.dp_collectives, buckets=args.buckets,
-                    data_workers=args.data_workers, data_threads=args.data_threads, data_decode=args.data_decode, data_frames=args.data_frames,
-                    data_cache_gb=args.data_cache_gb, num_masks=args.num_masks, rollout_steps=args.rollout_steps, ema_decay=args.g_ema,
-                    ssim_weight=args.ssim_weight, g_clip_norm=args.g_clip_norm, d_clip_norm=args.d_clip_norm,
-                    grad_norms=args.log_grad_norms, noise_dim=args.noise_dim, noise_seed=args.noise_seed, g_lr=args.g_lr, d_lr=args.d_lr,
-                    beta1=args.beta1, lr_schedule=args.lr_schedule, lr_warmup=args.lr_warmup, lr_decay_steps=args.lr_decay_iters,
-                    lr_final=args.lr_final, sched_sampling=args.sched_sampling, ss_start=args.ss_start, ss_final=args.ss_final,
-                    ss_decay_steps=args.ss_decay_iters, ss_seed=args.ss_seed)
+                    log_dir, model_dir, args.adv, args.loss, args.opt, transform, device='cuda:%d' % local_rank, world_size=world_size,
+                    rank=rank, **options)
     if trainer is not None:
         trainer.sess.close()        # ncclCommDestroy under data parallelism + a last check of the device-side flags
 

@@ -62,9 +62,10 @@ def test_train_rejects_before_anything_is_created_and_offsets_by_pretraining(mon
     monkeypatch.setattr(T, '_train_loop', lambda *a, **kw: seen.update(kw))
     T.train('synthetic', None, None, None, None, True, 'bce', 'adam', True, batch_size=2, train_iter=9, pretrain_iter=7, rollout_steps=3,
             sched_sampling='linear', ss_decay_steps=4, ss_seed=5)
-    assert seen['ss_args'] == {'kind': 'linear', 'start': 1.0, 'final': 0.0, 'decay_steps': 4, 'offset': 7, 'seed': 5}
+    sampling = lambda: {k: v for k, v in seen['options'].items() if k == 'sched_sampling' or k.startswith('ss_')}     # noqa: E731
+    assert sampling() == {'sched_sampling': 'linear', 'ss_start': 1.0, 'ss_final': 0.0, 'ss_decay_steps': 4, 'ss_offset': 7, 'ss_seed': 5}
     T.train('synthetic', None, None, None, None, True, 'bce', 'adam', True, batch_size=2, train_iter=9, rollout_steps=3)
-    assert seen['ss_args'] is None
+    assert sampling() == {}                      # nothing at all for sampling off
 
 
 def test_train_record_holds_ss_prob_only_when_sampling_is_on():
