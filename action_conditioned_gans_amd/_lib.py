@@ -238,6 +238,8 @@ EXTENSIONS = {
         'acg_plan_sample': (STATUS, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
         'acg_plan_cost': (STATUS, [_P, _P, _P, _P, c_float, c_float, _P, c_int32] + [c_int32] * 7 + [_P]),
         'acg_plan_refit': (STATUS, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P]),
+        # the planner's designated-pixel cost on the maps the DNA tail advects (plan.accumulate_pixel_cost)
+        'acg_plan_pixel_cost': (STATUS, [_P, _P, c_float, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)
@@ -280,6 +282,8 @@ PLAN_CANDIDATES_MAX = 1024    # acgan_rollout.h ACG_PLAN_*_MAX
 PLAN_HORIZON_MAX = 16
 PLAN_ACTION_DIM_MAX = 8
 PLAN_STATE_DIM_MAX = 16
+PLAN_PIXEL_MAPS_MAX = 4       # acgan_rollout.h ACG_PLAN_PIXEL_MAPS_MAX / ACG_PLAN_MAP_SIDE_MAX
+PLAN_MAP_SIDE_MAX = 1024
 
 
 def dtype2(first, second):

@@ -12,6 +12,10 @@
 // read flat, a pitch-4 frame pixel by pixel), each thread sums its squares in float32, the 64 lanes of a wave by shuffles, the four
 // waves through LDS in wave order.  49 KB per candidate at 64 x 64 x 3; N blocks fill the part from N = 256 on.
 //
+// Pixel cost.  The cost kernel's shape on d <= 4 probability maps [h, w, d] instead of a frame: 4 d sums per candidate (mass, mass x
+// distance to the goal, mass x y, mass x x) in one pass, then the same block divides the maps it has just read by their mass.
+// 16 KB per candidate and map at 64 x 64: read once from memory, re-read from cache, written once.
+//
 // Refit.  One block of up to 1024 threads.  The keys (cost, NaN as +inf) go to LDS; thread n counts the keys that come before its
 // own - every lane of a wave reads the same 16 bytes of LDS in the same cycle, a broadcast, so the O(N^2) loop has no bank
 // conflict and costs N / 4 ds_read_b128 per thread.  The E best are scattered to LDS by rank; thread (t, a) then sums its
@@ -128,6 +132,119 @@ void launch_cost(int mode, hipStream_t st, int N, const void* frames, const floa
     ACG_LAUNCH((plan_cost_kernel<T, SCALAR>), dim3(N), dim3(NTH), 0, st, f, goal, states, goal_state, fw, sw, cost, accumulate, pixels, C, pitch, S);
 }
 
+// ---- pixel cost ---------------------------------------------------------------------------------------------------------------
+// one pixel of D interleaved maps; VEC: one 8- or 16-byte access (D = 2, 4 and an aligned base), else D scalar ones
+template <int D, bool VEC>
+__device__ __forceinline__ void ld_px(const float* p, float (&v)[D]) {
+  if constexpr (VEC && D == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+  else if constexpr (VEC && D == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[0] = t.x; v[1] = t.y; }
+  else {
+#pragma unroll
+    for (int j = 0; j < D; ++j) v[j] = p[j];
+  }
+}
+template <int D, bool VEC>
+__device__ __forceinline__ void st_px(float* p, const float (&v)[D]) {
+  if constexpr (VEC && D == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  else if constexpr (VEC && D == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+  else {
+#pragma unroll
+    for (int j = 0; j < D; ++j) p[j] = v[j];
+  }
+}
+
+// One block per candidate.  Pass 1: thread t sums mass, mass x distance, mass x y and mass x x of the pixels t, t + 256, ... of every
+// map; the 4 D partials go through the lanes by shuffles and through LDS in wave order, and EVERY thread adds the four wave sums
+// itself, so all of them hold the same totals without a broadcast.  Pass 2: the thread divides the pixels it read - nobody else's -
+// by the mass, out of the cache lines it has just pulled in.  A frame smaller than the block leaves threads without a pixel: their
+// partials are 0 and they take part in the shuffles and the barrier like everybody else.
+template <int D, bool VEC>
+__global__ __launch_bounds__(NTH) void plan_pixel_cost_kernel(float* __restrict__ maps, const float* __restrict__ goals, float pixel_weight,
+                                                              float* __restrict__ cost, int accumulate, float* __restrict__ expected,
+                                                              float* __restrict__ mass, int pixels, int W) {
+  __shared__ float part[4 * D][NTH / acg::kWave];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* P = maps + (long long)n * pixels * D;
+  float gy[D], gx[D], acc[4 * D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    gy[j] = goals[2 * j];
+    gx[j] = goals[2 * j + 1];
+    acc[4 * j] = acc[4 * j + 1] = acc[4 * j + 2] = acc[4 * j + 3] = 0.f;
+  }
+  for (int p = tid; p < pixels; p += NTH) {
+    const int yi = p / W;
+    const float y = (float)yi, x = (float)(p - yi * W);
+    float v[D];
+    ld_px<D, VEC>(P + p * D, v);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      const float dy = y - gy[j], dx = x - gx[j];
+      const float dist = sqrtf(fmaf(dy, dy, dx * dx));
+      acc[4 * j] += v[j];
+      acc[4 * j + 1] = fmaf(v[j], dist, acc[4 * j + 1]);
+      acc[4 * j + 2] = fmaf(v[j], y, acc[4 * j + 2]);
+      acc[4 * j + 3] = fmaf(v[j], x, acc[4 * j + 3]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4 * D; ++q) {
+    const float s = acg::wave_sum(acc[q]);
+    if (lane == 0) part[q][wave] = s;
+  }
+  __syncthreads();
+  float m0[D];
+  bool ok[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    m0[j] = ((part[4 * j][0] + part[4 * j][1]) + part[4 * j][2]) + part[4 * j][3];
+    ok[j] = m0[j] > 0.f && m0[j] < INFINITY;           // (a NaN fails both)
+  }
+  if (tid == 0) {
+    float sum = 0.f;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      const float m1 = ((part[4 * j + 1][0] + part[4 * j + 1][1]) + part[4 * j + 1][2]) + part[4 * j + 1][3];
+      const float ey = ((part[4 * j + 2][0] + part[4 * j + 2][1]) + part[4 * j + 2][2]) + part[4 * j + 2][3];
+      const float ex = ((part[4 * j + 3][0] + part[4 * j + 3][1]) + part[4 * j + 3][2]) + part[4 * j + 3][3];
+      if (ok[j]) sum += m1 / m0[j];
+      else bad = true;
+      if (expected) {
+        expected[(n * D + j) * 2] = ok[j] ? ey / m0[j] : NAN;
+        expected[(n * D + j) * 2 + 1] = ok[j] ? ex / m0[j] : NAN;
+      }
+      if (mass) mass[n * D + j] = m0[j];
+    }
+    const float c = bad ? INFINITY : pixel_weight * sum;   // a map without mass: +inf whatever the weight (0 * inf would be a NaN)
+    cost[n] = accumulate ? cost[n] + c : c;                // accumulate == 0: the old value is not read
+  }
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < D; ++j) any = any || ok[j];
+  if (!any) return;                                        // nothing to scale (uniform in the block)
+  for (int p = tid; p < pixels; p += NTH) {
+    float v[D];
+    ld_px<D, VEC>(P + p * D, v);
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+      if (ok[j]) v[j] = v[j] / m0[j];
+    st_px<D, VEC>(P + p * D, v);
+  }
+}
+
+template <int D>
+void launch_pixel_cost(bool vec, hipStream_t st, int N, float* maps, const float* goals, float pw, float* cost, int accumulate,
+                       float* expected, float* mass, int pixels, int W) {
+  if constexpr (D == 2 || D == 4) {                      // (D = 1 is a scalar access anyway, D = 3 has no vector form)
+    if (vec) {
+      ACG_LAUNCH((plan_pixel_cost_kernel<D, true>), dim3(N), dim3(NTH), 0, st, maps, goals, pw, cost, accumulate, expected, mass, pixels, W);
+      return;
+    }
+  }
+  ACG_LAUNCH((plan_pixel_cost_kernel<D, false>), dim3(N), dim3(NTH), 0, st, maps, goals, pw, cost, accumulate, expected, mass, pixels, W);
+}
+
 // ---- refit --------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(REFIT_MAX) void plan_refit_kernel(const float* __restrict__ cost, const float* __restrict__ actions,
                                                                float* __restrict__ mean, float* __restrict__ std,
@@ -237,6 +354,28 @@ int32_t acg_plan_cost(const void* frames, const float* goal, const float* states
     launch_cost<__bf16>(mode, st, candidates, frames, goal, states, goal_state, frame_weight, state_weight, cost, accumulate, pixels, c, pitch,
                         state_dim);
   return acg::check_launch("plan_cost");
+}
+
+int32_t acg_plan_pixel_cost(float* maps, const float* goals, float pixel_weight, float* cost, int32_t accumulate, float* expected,
+                            float* mass, int32_t candidates, int32_t h, int32_t w, int32_t d, acg_stream_t stream) {
+  ACG_REQUIRE(maps && goals && cost, ACG_ERR_INVALID_ARG, "plan_pixel_cost: null pointer");
+  ACG_REQUIRE(candidates >= 1 && h >= 1 && w >= 1 && d >= 1, ACG_ERR_INVALID_ARG,
+              "plan_pixel_cost: candidates %d, maps %d x %d x %d (all >= 1)", candidates, h, w, d);
+  ACG_REQUIRE(pixel_weight >= 0.f && pixel_weight < INFINITY, ACG_ERR_INVALID_ARG, "plan_pixel_cost: pixel_weight %g (finite, >= 0)",
+              (double)pixel_weight);
+  ACG_REQUIRE(candidates <= ACG_PLAN_CANDIDATES_MAX && d <= ACG_PLAN_PIXEL_MAPS_MAX && h <= ACG_PLAN_MAP_SIDE_MAX && w <= ACG_PLAN_MAP_SIDE_MAX,
+              ACG_ERR_UNSUPPORTED, "plan_pixel_cost: candidates %d, maps %d x %d x %d above %d, %d x %d x %d", candidates, h, w, d,
+              ACG_PLAN_CANDIDATES_MAX, ACG_PLAN_MAP_SIDE_MAX, ACG_PLAN_MAP_SIDE_MAX, ACG_PLAN_PIXEL_MAPS_MAX);
+  const int pixels = h * w;                              // <= 2^20, and pixels * d <= 2^22: the kernel's int indices
+  const bool vec = aligned(maps, 4 * d);                 // (every candidate's maps then are: pixels * d * 4 bytes apart)
+  const hipStream_t st = acg::to_stream(stream);
+  switch (d) {
+    case 1: launch_pixel_cost<1>(vec, st, candidates, maps, goals, pixel_weight, cost, accumulate, expected, mass, pixels, w); break;
+    case 2: launch_pixel_cost<2>(vec, st, candidates, maps, goals, pixel_weight, cost, accumulate, expected, mass, pixels, w); break;
+    case 3: launch_pixel_cost<3>(vec, st, candidates, maps, goals, pixel_weight, cost, accumulate, expected, mass, pixels, w); break;
+    default: launch_pixel_cost<4>(vec, st, candidates, maps, goals, pixel_weight, cost, accumulate, expected, mass, pixels, w); break;
+  }
+  return acg::check_launch("plan_pixel_cost");
 }
 
 int32_t acg_plan_refit(const float* cost, const float* actions, float* mean, float* std, float* best_cost, float* best_actions,

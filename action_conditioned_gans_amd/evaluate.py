@@ -120,13 +120,14 @@ def _use_ema_weights(trainer, ckpt):
 
 
 def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn_stats='batch', weights='raw',
-                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate'):
+                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate', pixel_maps=0):
     """A checkpoint as a Trainer that predicts: a fresh graph and session, the generator ``transform`` / ``ksize`` / ``num_masks`` at
     ``batch_size`` with what the modes need and nothing else - ``bn_stats`` 'stored' or 'calibrate': the stored-statistics instances;
     ``weights='ema'``: the average (then copied into the variables, _use_ema_weights); ``noise_dim`` > 0: the noise input, its stream
     restarted at ``noise_seed`` - initialised and restored from ``restore_from`` (default: ``ckpt``, which the messages name).  An int
     ``noise_dim`` also makes the Saver's shape refusal ask about --noise_dim.  'stored' needs calibrated rows in the checkpoint (the
-    error names ``calibrate_with``).  -> (trainer, updates of the average or None, calibrated rows or None); the caller closes
+    error names ``calibrate_with``).  ``pixel_maps`` > 0: the map path of plan.Planner's designated-pixel cost (DNA generator).
+    -> (trainer, updates of the average or None, calibrated rows or None); the caller closes
     ``trainer.sess``."""
     from . import graph as G
     from .saver import Saver
@@ -136,6 +137,8 @@ def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, devi
         extra['ema_decay'] = EMA_BUILD_DECAY
     if noise_dim:
         extra.update(noise_dim=noise_dim, noise_seed=noise_seed)
+    if pixel_maps:
+        extra['pixel_maps'] = pixel_maps
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
     try:

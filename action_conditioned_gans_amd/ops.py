@@ -1669,6 +1669,22 @@ def dna_gather(logits, image, ksize=DNA_KERN_SIZE, name='dna'):
     return DnaOp(logits, image, ksize, _scope_name(name), bias=bias).outputs[0]
 
 
+def dna_map_twin(frame_op, maps, name=None):
+    """The motion model of a DNA generator instance applied to something else than the frame: a second DnaOp on the SAME logits
+    tensor and the same folded bias as ``frame_op`` (the instance's DnaOp), its image ``maps`` [B, H, W, D] float32, D in 1..4 -
+    probability maps of designated pixels, moved by the kernels the instance predicts for its frame (plan.Planner).  The gather is
+    linear in its image: no variable, no state, no new kernel (acg_dna_fwd with c = D).  Nothing but the returned tensor reads the
+    twin, so only a program that fetches it contains it."""
+    if not isinstance(frame_op, DnaOp):
+        raise TypeError('dna_map_twin: %r is not a DnaOp (the DNA generator has the only per-pixel flow)' % (frame_op,))
+    _check_nhwc(maps, 'dna_map_twin')
+    logits, image = frame_op.inputs[:2]
+    if maps.shape[:3] != image.shape[:3] or not 1 <= maps.shape[3] <= 4 or maps.dtype != torch.float32:
+        raise ValueError('dna_map_twin: maps %s %s do not match the image %s (float32, 1..4 channels)' % (maps.shape, maps.dtype, image.shape))
+    bias = frame_op.inputs[2] if frame_op.has_bias else None
+    return DnaOp(logits, maps, frame_op.ksize, name or frame_op.name + '_map', bias=bias).outputs[0]
+
+
 RELU_SHIFT = 1e-12                                                # ops.py:13
 
 

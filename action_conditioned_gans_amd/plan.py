@@ -11,6 +11,18 @@ fallback: a library without the entries raises.
 ``sample_actions`` / ``accumulate_cost`` / ``refit`` are the three launches on torch device tensors; ``Planner`` is the loop
 around a ``train.Trainer``; ``main`` plans for the sequences of a dataset and writes OUTPUT/plan.json.
 
+The designated-pixel cost (Finn & Levine, "Deep Visual Foresight"; ``Planner(pixel_weight=W)``, ``--pixel Y,X --goal_pixel Y,X``):
+the user marks up to 4 pixels of the start frame and says where each should end up.  Every candidate carries a probability map per
+marked pixel, one-hot at the start; each step the DNA generator moves the maps with the per-pixel kernels it predicts for the frame
+(``Trainer(pixel_maps=D)``: a twin of the DNA gather on the same logits, the maps as its image), and ``accumulate_pixel_cost``
+(acg_plan_pixel_cost, the fourth launch) adds the expected distance of every map to its goal position and divides the map by its
+mass - the gather loses what it pushes over the border and does not sum to one otherwise either.  A whole-frame squared error
+mostly measures the arm and the background and needs a goal image; this cost needs none: with ``--frame_weight 0`` the goal frame
+is not scored (``goal_frame=None``).  The DNA generator only: the plain generator predicts no flow, and the CDNA generator is
+declined - its channel split, kept as written from the reference, transforms the colour channels of one mask with different
+kernels, so there is no single flow that a map could follow consistently with the frame.  One goal set serves all candidates.
+The map path is float32 in a bf16 graph too (as the DNA image is); it was not run in one.
+
 INPUT is evaluate's: a frames ``.npy`` with ``--actions``, a push TFRecord directory, or ``synthetic``.  For each sequence the
 start is frame 0 with the recorded state 0 and the goal is frame ``--goal_step`` (default: ``--horizon``) with its recorded
 state (read when ``--state_weight`` > 0).  plan.json holds per sequence ``actions`` [horizon, 5], ``cost``, ``history`` (the
@@ -21,9 +33,14 @@ and ``share_not_worse_than_recorded``, every setting, ``model`` / ``num_masks`` 
 metrics.json records them, and ``rollout_s``, the time spent in ``plan``.  With ``--bn_stats batch`` a row's prediction depends
 on the other rows of its batch, so costs of different batches compare only roughly; ``--bn_stats stored`` makes them exact.
 ``--dump`` also writes ``plans.npy`` [n, horizon, 5] and ``plan_frames.npy`` [n, horizon, H, W, 3], the frames predicted for
-each plan (row 0 of a batch whose other rows are zero commands).
+each plan (row 0 of a batch whose other rows are zero commands).  With pixels (``--pixel`` / ``--goal_pixel``, repeatable, for
+every sequence; or ``--pixels`` / ``--goal_pixels`` FILE.npy [n, D, 2] per sequence; ``--pixel_weight``, default 1) the settings
+gain ``pixels`` / ``goal_pixels`` / ``pixel_weight``, every plan ``pixel_expected`` [D, 2] (the expected positions after the
+plan's last step), ``pixel_distance`` [D] (their distances to the goals) and ``recorded_pixel_distance`` (the same for the
+dataset's own commands), and ``--dump`` also writes ``plan_maps.npy`` [n, horizon, H, W, D].
 
-Not covered: a designated-pixel or mask cost (the cost is the squared error of whole frames, plus the state's); replanning
+Not covered: a mask cost, per-candidate goal pixels, CDNA maps (above), a gather that moves frame and maps in one launch (the maps
+cost one more DNA launch per step); replanning
 against a simulator or a robot (one open-loop plan per call); sampling the generator's noise (z = 0 always); gradient-based
 refinement of the plan; more than one rank; bf16 end to end (the cost kernel reads bf16 frames, a bf16 Planner was never run).
 """
@@ -119,6 +136,29 @@ def accumulate_cost(frames, goal, cost, states=None, goal_state=None, frame_weig
     return cost
 
 
+def accumulate_pixel_cost(maps, goals, cost, pixel_weight=1.0, accumulate=False, expected=None, mass=None, stream=None, lib=None):
+    """``cost`` [N] (float32, written) = (``accumulate``: its old value, else 0) + pixel_weight * sum_j of the expected distance of
+    map j of ``maps`` [N, H, W, D] (float32, D in 1..4) to ``goals`` [D, 2] (float32, (y, x), may be fractional): sum P * dist /
+    sum P.  ``maps`` is rewritten in place, every map divided by its mass.  ``expected`` [N, D, 2] / ``mass`` [N, D] (float32,
+    optional) receive the maps' expected positions and their masses before the division.  A map whose mass is not finite or not
+    > 0 makes the row's cost +inf and stays as it is.  One launch of acg_plan_pixel_cost, one block per candidate, fixed
+    summation order: bit-identical across launches."""
+    run = _lib.entry(lib or _lib.get(), 'plan_pixel_cost')
+    _device_f32('accumulate_pixel_cost', maps=maps, goals=goals, cost=cost, expected=expected, mass=mass)
+    if maps.dim() != 4:
+        raise ValueError('accumulate_pixel_cost: maps [N, H, W, D] expected, got %s' % (tuple(maps.shape),))
+    n, h, w, d = maps.shape
+    if tuple(goals.shape) != (d, 2):
+        raise ValueError('accumulate_pixel_cost: goals must be %s, got %s' % ((d, 2), tuple(goals.shape)))
+    for name, t, k in (('maps', maps, n * h * w * d), ('goals', goals, 2 * d), ('cost', cost, n), ('expected', expected, 2 * n * d),
+                       ('mass', mass, n * d)):
+        if t is not None:
+            _want('accumulate_pixel_cost', name, t, torch.float32, k)
+    run(_p(maps), _p(goals), float(pixel_weight), _p(cost), 1 if accumulate else 0, _p(expected), _p(mass), n, h, w, d,
+        _stream_handle(stream, maps.device))
+    return cost
+
+
 def refit(cost, actions, mean, std, best_cost, best_actions, elite_idx, alpha, min_std, history=None, stream=None, lib=None):
     """One CEM update on the device (acg_plan_refit): rank the N candidates by ``cost`` (NaN as +inf; ties by index),
     ``elite_idx`` [E] (int32, written) = the E best in rank order, ``mean`` / ``std`` [H, A] move to the elites' mean and
@@ -157,7 +197,7 @@ def _bounds(value, what):
 
 def check_plan(candidates, horizon, elites, iterations, init_std=DEFAULTS['init_std'], min_std=DEFAULTS['min_std'],
                alpha=DEFAULTS['alpha'], lo=DEFAULTS['lo'], hi=DEFAULTS['hi'], frame_weight=1.0, state_weight=0.0, cost_steps='all',
-               seed=0, has_state_head=True):
+               seed=0, has_state_head=True, pixel_weight=0.0):
     """ValueError for settings the planner does not take, each naming its argument; -> the checked values as a dict."""
     from .train import check_noise_seed
     for name, v, top in (('horizon', horizon, _lib.PLAN_HORIZON_MAX), ('elites', elites, _lib.PLAN_CANDIDATES_MAX),
@@ -185,9 +225,12 @@ def check_plan(candidates, horizon, elites, iterations, init_std=DEFAULTS['init_
         raise ValueError('state_weight %r: the plain generator predicts no state (state_weight must be 0)' % (state_weight,))
     if cost_steps not in COST_STEPS:
         raise ValueError("cost_steps must be 'all' or 'last', got %r" % (cost_steps,))
+    if not _finite(pixel_weight) or pixel_weight < 0:
+        raise ValueError('pixel_weight must be finite and >= 0, got %r' % (pixel_weight,))
     return {'horizon': int(horizon), 'elites': int(elites), 'iterations': int(iterations), 'init_std': float(init_std),
             'min_std': float(min_std), 'alpha': float(alpha), 'lo': lo, 'hi': hi, 'frame_weight': float(frame_weight),
-            'state_weight': float(state_weight), 'cost_steps': cost_steps, 'seed': check_noise_seed(seed, 'seed')}
+            'state_weight': float(state_weight), 'cost_steps': cost_steps, 'seed': check_noise_seed(seed, 'seed'),
+            'pixel_weight': float(pixel_weight)}
 
 
 class Planner:
@@ -199,19 +242,27 @@ class Planner:
     head and a ``goal_state``); ``cost_steps``: 'all' sums the cost over the H predicted frames, 'last' scores the last one.
     ``seed``: the candidates' stream, {seed, counter} on the device, one draw per iteration.  ``bn`` / ``weights``: as
     ``Trainer.test`` takes them ('stored' needs ``bn_inference`` and a calibration, 'ema' an average).  The generator's noise,
-    where it has one, is zero.  Builds nothing in the graph: the steps are the Trainer's own predict program."""
+    where it has one, is zero.  Builds nothing in the graph: the steps are the Trainer's own predict program.
+    ``pixel_weight`` W (0: nothing new is built or launched, ``plan`` is the one without the argument bit for bit; > 0 needs a
+    Trainer built with ``pixel_maps`` >= 1): adds W times the designated-pixel cost (acg_plan_pixel_cost) - ``plan`` and
+    ``evaluate_actions`` then take ``pixels`` and ``goal_pixels``, each step also moves the pixels' probability maps through the
+    Trainer's map twin, and the maps are scored (and renormalised) at the steps ``cost_steps`` names, after the frame / state cost
+    of the step."""
 
     def __init__(self, trainer, horizon, elites, iterations, init_std=DEFAULTS['init_std'], min_std=DEFAULTS['min_std'],
                  alpha=DEFAULTS['alpha'], lo=DEFAULTS['lo'], hi=DEFAULTS['hi'], frame_weight=1.0, state_weight=0.0, cost_steps='all',
-                 seed=0, bn='batch', weights='raw'):
+                 seed=0, bn='batch', weights='raw', pixel_weight=0.0):
         self.args = check_plan(trainer.batch_size, horizon, elites, iterations, init_std, min_std, alpha, lo, hi, frame_weight,
-                               state_weight, cost_steps, seed, has_state_head=trainer.model != 'plain')
+                               state_weight, cost_steps, seed, has_state_head=trainer.model != 'plain', pixel_weight=pixel_weight)
+        pixel = self.args['pixel_weight'] > 0
+        if pixel and not getattr(trainer, 'pixel_maps', 0):
+            raise ValueError('pixel_weight %r needs a Trainer built with pixel_maps >= 1 (the DNA generator\'s map path)' % (pixel_weight,))
         if bn not in ('batch', 'stored'):
             raise ValueError("bn must be 'batch' or 'stored', got %r" % (bn,))
         if weights not in ('raw', 'ema'):
             raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
         sess = trainer.sess
-        for name in ('plan_sample', 'plan_cost', 'plan_refit'):
+        for name in (('plan_pixel_cost',) if pixel else ()) + ('plan_sample', 'plan_cost', 'plan_refit'):
             _lib.entry(sess.rt.lib, name)                # (the C oracle: the AcgError that names the entry and its header)
         if not sess.rt.is_cuda:
             raise RuntimeError('the planner runs on the GPU: the session has no GPU device')
@@ -254,7 +305,46 @@ class Planner:
             raise ValueError('%s must be [%d], got %s' % (what, n, tuple(t.shape)))
         return t.contiguous()
 
+    def _check_pixels(self, goal_frame, pixels, goal_pixels):
+        """The designated pixels of a call against the Planner's weights, before anything is uploaded or launched.
+        -> (pixels int64 [D, 2], goal_pixels float32 [D, 2]) as numpy arrays, or (None, None) without a pixel cost."""
+        a = self.args
+        if a['pixel_weight'] == 0:
+            if pixels is not None or goal_pixels is not None:
+                raise ValueError('pixels / goal_pixels: this Planner was built with pixel_weight 0, it scores no pixels')
+            if goal_frame is None:
+                raise ValueError('goal_frame may be None only with a pixel cost (pixel_weight > 0)')
+            return None, None
+        if pixels is None or goal_pixels is None:
+            raise ValueError('pixel_weight %r needs pixels and goal_pixels' % (a['pixel_weight'],))
+        if goal_frame is None and (a['frame_weight'] != 0 or a['state_weight'] != 0):
+            raise ValueError('goal_frame may be None only when frame_weight and state_weight are 0 (they are %r and %r)'
+                             % (a['frame_weight'], a['state_weight']))
+        D, S = self.trainer.pixel_maps, self.trainer.img_size
+        px, gp = np.asarray(pixels), np.asarray(goal_pixels)
+        if px.shape != (D, 2) or px.dtype.kind not in 'iu':
+            raise ValueError('pixels must be an integer [%d, 2] array of (y, x) (the Trainer has pixel_maps=%d), got %s %s'
+                             % (D, D, px.dtype, px.shape))
+        if (px < 0).any() or (px >= S).any():
+            raise ValueError('pixels must lie inside the %d x %d image, got %s' % (S, S, px.tolist()))
+        if gp.shape != (D, 2) or gp.dtype.kind not in 'iuf':
+            raise ValueError('goal_pixels must be a float [%d, 2] array of (y, x), got %s %s' % (D, gp.dtype, gp.shape))
+        gp = gp.astype(np.float32)
+        if not np.isfinite(gp).all() or (gp < 0).any() or (gp > S - 1).any():
+            raise ValueError('goal_pixels must lie within [0, %d], got %s' % (S - 1, gp.tolist()))
+        return px.astype(np.int64), gp
+
+    def _start_maps(self, px, gp):
+        """-> (one-hot maps [N, S, S, D] at ``px``, the same in every row; the goals [D, 2]) on the device."""
+        S, D = self.trainer.img_size, len(px)
+        maps = torch.zeros(self.N, S, S, D, dtype=torch.float32, device=self.sess.rt.device)
+        for j, (y, x) in enumerate(px.tolist()):
+            maps[:, y, x, j] = 1.0
+        return maps, self.sess.upload(gp).contiguous()
+
     def _goal(self, goal_frame, goal_state):
+        if goal_frame is None:               # (_check_pixels: the frame and the state are not scored)
+            return None, None
         goal = self._frame(goal_frame, 'goal_frame')
         use_state = self.args['state_weight'] != 0
         return goal, (self._vector(goal_state, 'goal_state', 5) if use_state else None)
@@ -266,47 +356,77 @@ class Planner:
         return f0, s0
 
     # ---- the rollout: the predict program and the feeding of Trainer._rollout_on_device, from step 0 on
-    def _rollout(self, f0, s0, actions, goal, goal_state, cost, keep_frames=False):
+    def _rollout(self, f0, s0, actions, goal, goal_state, cost, keep_frames=False, maps=None, goal_pixels=None, keep_maps=False,
+                 expected=None):
         """Roll ``actions`` [N, H, A] out from (f0, s0) and leave the cost of every row in ``cost``; nothing comes to the host.
-        -> the predicted frames [N, H, ...] on the device with ``keep_frames``."""
+        ``goal`` None: the frames and states are not scored.  ``maps`` [N, S, S, D] / ``goal_pixels`` [D, 2]: the designated pixels'
+        maps go through the map twin at every step and are scored - and renormalised in place - where the frames are, after
+        them; ``expected`` [N, D, 2] receives the last step's expected positions.
+        -> (the predicted frames [N, H, ...] with ``keep_frames`` else None, the maps [N, H, S, S, D] with ``keep_maps`` else None)
+        on the device."""
         tr, a = self.trainer, self.args
         stored = self.bn == 'stored'
         has_state = tr.g_state_out is not None
         fetches = [tr.g_out_stored] + ([tr.g_state_stored] if has_state else []) if stored else \
                   [tr.g_next_frame] + ([tr.g_state_out] if has_state else [])
-        frame, state, kept = f0, s0, []
+        if maps is not None:
+            fetches = fetches + [tr.g_map_stored if stored else tr.g_map_out]
+        frame, state, kept, kept_maps = f0, s0, [], []
         every = a['cost_steps'] == 'all'
+        wrote = False                        # whether a launch of this rollout has written ``cost`` already
+        lib = self.sess.rt.lib
         for t in range(self.H):
             acs = torch.cat([actions[:, t], state], dim=1)
             tr._announced = None
-            res = self.sess.run(fetches, tr._feed(frame, frame, acs), device_fetch=True)       # (next_frame is not read by this program)
+            feed = tr._feed(frame, frame, acs)                                                 # (next_frame is not read by this program)
+            if maps is not None:
+                feed[tr.pixel_map_ph] = maps
+            res = self.sess.run(fetches, feed, device_fetch=True)
             out = res[0] if res[0].is_contiguous() else res[0].contiguous()
             if has_state:
                 state = res[1].float().contiguous()
+            if maps is not None:
+                maps = res[-1]               # the twin's own buffer: scaled in place below, copied into the placeholder by the next feed
             if every or t == self.H - 1:
-                accumulate_cost(out, goal, cost, states=state if goal_state is not None else None, goal_state=goal_state,
-                                frame_weight=a['frame_weight'], state_weight=a['state_weight'], accumulate=every and t > 0,
-                                lib=self.sess.rt.lib)
+                if goal is not None:
+                    accumulate_cost(out, goal, cost, states=state if goal_state is not None else None, goal_state=goal_state,
+                                    frame_weight=a['frame_weight'], state_weight=a['state_weight'], accumulate=every and t > 0, lib=lib)
+                    wrote = True
+                if maps is not None:
+                    accumulate_pixel_cost(maps, goal_pixels, cost, pixel_weight=a['pixel_weight'], accumulate=wrote,
+                                          expected=expected if t == self.H - 1 else None, lib=lib)
+                    wrote = True
+            if keep_maps:
+                kept_maps.append(maps.clone())
             # the fetch is the tensor's own buffer and the next step overwrites it - after the feed has copied it into the
             # placeholders, so only a frame that is kept needs a copy of its own
             frame = out.float().clone() if keep_frames else out.float()
             if keep_frames:
                 kept.append(frame)
-        return torch.stack(kept, dim=1) if keep_frames else None
+        return (torch.stack(kept, dim=1) if keep_frames else None), (torch.stack(kept_maps, dim=1) if keep_maps else None)
 
-    def plan(self, frame, state, goal_frame, goal_state=None, keep_candidates=False):
+    def plan(self, frame, state, goal_frame, goal_state=None, keep_candidates=False, pixels=None, goal_pixels=None):
         """One open-loop plan from ``frame`` [H, W, 3] / ``state`` [5] towards ``goal_frame`` [H, W, 3] (and ``goal_state`` [5]
         when ``state_weight`` > 0), starting from mean 0 and ``init_std``.  -> {'actions' [H, 5], 'cost', 'history' [iterations]
         (the best cost after each iteration), 'mean', 'std' [H, 5]} as numpy arrays and a float, copied to the host once, after the
         last iteration; with
         ``keep_candidates`` also 'candidates' [I, N, H, 5], 'costs' [I, N], 'elites' [I, E], 'means' / 'stds' [I, H, 5] (what
-        each round drew, scored and refitted to; device-side copies per round, and one more host copy each at the end)."""
+        each round drew, scored and refitted to; device-side copies per round, and one more host copy each at the end).
+        With a pixel cost (``pixel_weight`` > 0): ``pixels`` [D, 2], integer (y, x) inside the image, one per map of the Trainer, and
+        ``goal_pixels`` [D, 2], float (y, x) within [0, S - 1], where each should end up; ``goal_frame`` may then be None when
+        ``frame_weight`` and ``state_weight`` are 0 (acg_plan_cost is not launched).  Every candidate starts from one-hot maps at
+        ``pixels``.  The result gains 'pixel_expected' [D, 2] and 'pixel_distance' [D]: the expected positions after the last
+        step of the best plan and their distances to the goals, from one more batch whose row 0 is the plan and whose other rows
+        are zero commands (``evaluate_actions``'s rollout)."""
         a = self.args
         if a['state_weight'] != 0 and goal_state is None:
             raise ValueError('state_weight %r needs a goal_state' % (a['state_weight'],))
+        px, gp = self._check_pixels(goal_frame, pixels, goal_pixels)
+        expected = None
         with self.trainer._predicting(self.bn, self.weights):      # (the mode checks come before anything is uploaded or launched)
             goal, gstate = self._goal(goal_frame, goal_state)
             f0, s0 = self._start(frame, state)
+            maps0, gpix = self._start_maps(px, gp) if px is not None else (None, None)
             self.mean.zero_()
             self.std.fill_(a['init_std'])
             self.best_cost.fill_(math.inf)
@@ -321,13 +441,18 @@ class Planner:
                        'stds': torch.empty(I, self.H, self.A, device=dev)}
             for i in range(self.I):
                 sample_actions(self.mean, self.std, self.lo, self.hi, self.state, self.actions, keep_mean=True, stream_id=rank, lib=lib)
-                self._rollout(f0, s0, self.actions, goal, gstate, self.cost)
+                self._rollout(f0, s0, self.actions, goal, gstate, self.cost, maps=maps0, goal_pixels=gpix)
                 refit(self.cost, self.actions, self.mean, self.std, self.best_cost, self.best_actions, self.elite_idx, a['alpha'],
                       a['min_std'], history=self.history[i:i + 1], lib=lib)
                 if log is not None:
                     for k, src in (('candidates', self.actions), ('costs', self.cost), ('elites', self.elite_idx), ('means', self.mean),
                                    ('stds', self.std)):
                         log[k][i].copy_(src)
+            if px is not None:
+                rows = torch.zeros_like(self.actions)
+                rows[0].copy_(self.best_actions)
+                expected = torch.empty(self.N, len(px), 2, dtype=torch.float32, device=self.sess.rt.device)
+                self._rollout(f0, s0, rows, goal, gstate, torch.empty_like(self.cost), maps=maps0, goal_pixels=gpix, expected=expected)
         ha = self.H * self.A
         flat = torch.cat([self.history, self.best_cost, self.best_actions.view(-1), self.mean.view(-1), self.std.view(-1)]).cpu().numpy()
         I = self.I
@@ -336,33 +461,81 @@ class Planner:
                'std': flat[I + 1 + 2 * ha:].reshape(self.H, self.A).copy()}
         if log is not None:
             out.update({k: v.cpu().numpy() for k, v in log.items()})
+        if expected is not None:
+            out['pixel_expected'] = expected[0].cpu().numpy()
+            out['pixel_distance'] = np.sqrt(((out['pixel_expected'].astype(np.float64) - gp) ** 2).sum(axis=1))
         return out
 
-    def evaluate_actions(self, frame, state, actions, goal_frame, goal_state=None, return_frames=False):
-        """The cost of given command sequences ``actions`` [N, H, 5]: the rollout and the cost kernel of ``plan`` without the
-        sampling.  -> costs [N] (numpy); with ``return_frames`` also the predicted frames [N, H, H, W, 3]."""
+    def evaluate_actions(self, frame, state, actions, goal_frame, goal_state=None, return_frames=False, pixels=None, goal_pixels=None,
+                         return_maps=False, return_expected=False):
+        """The cost of given command sequences ``actions`` [N, H, 5]: the rollout and the cost kernels of ``plan`` without the
+        sampling; ``pixels`` / ``goal_pixels`` as ``plan`` takes them.  -> costs [N] (numpy); then, in this order, with
+        ``return_frames`` the predicted frames [N, H, H, W, 3], with ``return_maps`` the pixels' maps [N, H, H, W, D] (after every
+        scored step normalised to mass 1; with ``cost_steps='last'`` the earlier steps are as the gather left them), with
+        ``return_expected`` the expected positions after the last step [N, D, 2]."""
         if self.args['state_weight'] != 0 and goal_state is None:
             raise ValueError('state_weight %r needs a goal_state' % (self.args['state_weight'],))
+        px, gp = self._check_pixels(goal_frame, pixels, goal_pixels)
+        if (return_maps or return_expected) and px is None:
+            raise ValueError('return_maps / return_expected need a pixel cost (pixel_weight > 0)')
         with self.trainer._predicting(self.bn, self.weights):
             goal, gstate = self._goal(goal_frame, goal_state)
             f0, s0 = self._start(frame, state)
+            maps0, gpix = self._start_maps(px, gp) if px is not None else (None, None)
             acts = self.sess.upload(np.asarray(actions, np.float32) if not torch.is_tensor(actions) else actions)
             if tuple(acts.shape) != (self.N, self.H, self.A):
                 raise ValueError('actions must be [%d, %d, %d], got %s' % (self.N, self.H, self.A, tuple(acts.shape)))
             cost = torch.empty_like(self.cost)
-            frames = self._rollout(f0, s0, acts.contiguous(), goal, gstate, cost, keep_frames=return_frames)
-        if return_frames:
-            return cost.cpu().numpy(), frames.cpu().numpy()
-        return cost.cpu().numpy()
+            expected = torch.empty(self.N, len(px), 2, dtype=torch.float32, device=cost.device) if return_expected else None
+            frames, maps = self._rollout(f0, s0, acts.contiguous(), goal, gstate, cost, keep_frames=return_frames, maps=maps0,
+                                         goal_pixels=gpix, keep_maps=return_maps, expected=expected)
+        extra = [t.cpu().numpy() for t, asked in ((frames, return_frames), (maps, return_maps), (expected, return_expected)) if asked]
+        return (cost.cpu().numpy(),) + tuple(extra) if extra else cost.cpu().numpy()
+
+
+def check_pixel_args(pixels, goal_pixels, pixel_weight, model, img_size):
+    """The designated pixels of a run - [D, 2] for every sequence or [n, D, 2] per sequence - against the generator ``model``.
+    ValueError for what the planner does not take; -> (pixels int64, goal_pixels float32, pixel_weight), or (None, None, 0.0)
+    without pixels."""
+    if pixels is None and goal_pixels is None:
+        if pixel_weight:
+            raise ValueError('pixel_weight %r without pixels' % (pixel_weight,))
+        return None, None, 0.0
+    if pixels is None or goal_pixels is None:
+        raise ValueError('pixels and goal_pixels go together')
+    if model != 'dna':
+        from .train import check_pixel_maps
+        check_pixel_maps(1, model)                       # (the Trainer's own refusal, with its reason)
+    px, gp = np.asarray(pixels), np.asarray(goal_pixels)
+    if px.dtype.kind not in 'iu' or px.ndim not in (2, 3) or px.shape[-1] != 2:
+        raise ValueError('pixels must be integer (y, x) pairs, [D, 2] or [n, D, 2], got %s %s' % (px.dtype, px.shape))
+    if gp.dtype.kind not in 'iuf' or gp.shape != px.shape:
+        raise ValueError('goal_pixels must be float (y, x) pairs of the shape of pixels %s, got %s %s' % (px.shape, gp.dtype, gp.shape))
+    if not 1 <= px.shape[-2] <= _lib.PLAN_PIXEL_MAPS_MAX:
+        raise ValueError('1..%d pixels per sequence, got %d' % (_lib.PLAN_PIXEL_MAPS_MAX, px.shape[-2]))
+    if px.ndim == 3 and len(px) < 1:
+        raise ValueError('pixels for no sequence')
+    gp = gp.astype(np.float32)
+    if (px < 0).any() or (px >= img_size).any():
+        raise ValueError('pixels must lie inside the %d x %d image' % (img_size, img_size))
+    if not np.isfinite(gp).all() or (gp < 0).any() or (gp > img_size - 1).any():
+        raise ValueError('goal_pixels must lie within [0, %d]' % (img_size - 1))
+    weight = 1.0 if pixel_weight is None else pixel_weight
+    if not _finite(weight) or weight <= 0:
+        raise ValueError('pixel_weight must be finite and > 0 with pixels, got %r' % (pixel_weight,))
+    return px.astype(np.int64), gp, float(weight)
 
 
 # ---- CLI -----------------------------------------------------------------------------------------------------------------------------
 def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=False, cdna=False, num_masks=10, ksize=5, img_size=64,
                    dtype='f32', device='cuda:0', bn_stats='batch', weights='raw', candidates=64, elites=8, iterations=3, horizon=5,
                    goal_step=None, init_std=DEFAULTS['init_std'], min_std=DEFAULTS['min_std'], alpha=DEFAULTS['alpha'], state_weight=0.0,
-                   cost_steps='all', seed=0, num_sequences=None, seq_len=8, dump=False):
+                   cost_steps='all', seed=0, num_sequences=None, seq_len=8, dump=False, pixels=None, goal_pixels=None, pixel_weight=None,
+                   frame_weight=1.0):
     """Restore ``model_path`` as evaluate.evaluate does and plan for the sequences of ``input_path`` (module docstring).
-    -> the dict written to ``output_path``/plan.json."""
+    ``pixels`` (int) / ``goal_pixels`` (float): [D, 2] for every sequence or [n, D, 2], one set per sequence - the designated-pixel
+    cost, weighted ``pixel_weight`` (None: 1.0 with pixels, 0 without); ``frame_weight`` 0 with ``state_weight`` 0: the goal frame
+    is not scored.  -> the dict written to ``output_path``/plan.json."""
     from .evaluate import _batches, predicting_trainer
     from .saver import latest_checkpoint
     from .train import model_kind
@@ -374,8 +547,15 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
     transform = 'cdna' if cdna else dna
     goal_step = horizon if goal_step is None else goal_step
-    checked = check_plan(candidates, horizon, elites, iterations, init_std, min_std, alpha, state_weight=state_weight, cost_steps=cost_steps,
-                         seed=seed, has_state_head=model_kind(transform) != 'plain')
+    pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, pixel_weight, model_kind(transform), img_size)
+    checked = check_plan(candidates, horizon, elites, iterations, init_std, min_std, alpha, frame_weight=frame_weight,
+                         state_weight=state_weight, cost_steps=cost_steps, seed=seed, has_state_head=model_kind(transform) != 'plain',
+                         pixel_weight=pixel_weight)
+    if pixels is None and checked['frame_weight'] == 0 and checked['state_weight'] == 0:
+        raise ValueError('frame_weight 0 and state_weight 0 without pixels: nothing is scored')
+    if pixels is not None and pixels.ndim == 3 and num_sequences is not None and len(pixels) < num_sequences:
+        raise ValueError('pixels for %d sequences, %d are planned' % (len(pixels), num_sequences))
+    score_frames = pixels is None or checked['frame_weight'] != 0 or checked['state_weight'] != 0
     if isinstance(goal_step, bool) or not isinstance(goal_step, (int, np.integer)) or goal_step < 1:
         raise ValueError('goal_step must be an integer >= 1, got %r' % (goal_step,))
     need = max(goal_step + 1, horizon)
@@ -384,12 +564,13 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         raise FileNotFoundError('no checkpoint under %s' % model_path)
     os.makedirs(output_path, exist_ok=True)
     trainer, ema_updates, _ = predicting_trainer(ckpt, transform, candidates, ksize, img_size, dtype, device, num_masks, bn_stats, weights,
-                                                 calibrate_with='evaluate --bn_stats calibrate')
+                                                 calibrate_with='evaluate --bn_stats calibrate',
+                                                 pixel_maps=0 if pixels is None else pixels.shape[-2])
     sess = trainer.sess
     try:
-        planner = Planner(trainer, horizon, elites, iterations, init_std=init_std, min_std=min_std, alpha=alpha, state_weight=state_weight,
-                          cost_steps=cost_steps, seed=seed, bn=bn_stats)
-        per_seq, plans, plan_frames, rollout_s = [], [], [], 0.0
+        planner = Planner(trainer, horizon, elites, iterations, init_std=init_std, min_std=min_std, alpha=alpha, frame_weight=frame_weight,
+                          state_weight=state_weight, cost_steps=cost_steps, seed=seed, bn=bn_stats, pixel_weight=pixel_weight)
+        per_seq, plans, plan_frames, plan_maps, used_pixels, used_goals, rollout_s = [], [], [], [], [], [], 0.0
         for frames, acts in _batches(input_path, actions_path, 16, img_size, max(seq_len, need), num_sequences):
             if frames.shape[2:4] != (img_size, img_size):
                 raise ValueError('frames of %s x %s, the model is built for --img_size %d' % (frames.shape[2], frames.shape[3], img_size))
@@ -398,19 +579,39 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
             for f, ac in zip(frames, acts):
                 start, state0, goal, gstate = f[0], ac[0, COMMAND_DIM:], f[goal_step], ac[goal_step, COMMAND_DIM:]
                 gs = gstate if checked['state_weight'] != 0 else None
+                pkw = {}
+                if pixels is not None:
+                    k = len(per_seq)
+                    if pixels.ndim == 3 and k >= len(pixels):
+                        raise ValueError('pixels for %d sequences, %s holds more' % (len(pixels), input_path))
+                    pkw = {'pixels': pixels[k] if pixels.ndim == 3 else pixels, 'goal_pixels': goal_pixels[k] if pixels.ndim == 3 else goal_pixels}
+                    used_pixels.append(pkw['pixels'].tolist())
+                    used_goals.append(pkw['goal_pixels'].tolist())
+                    if not score_frames:
+                        goal = None
                 t0 = time.perf_counter()
-                res = planner.plan(start, state0, goal, goal_state=gs, keep_candidates=True)
+                res = planner.plan(start, state0, goal, goal_state=gs, keep_candidates=True, **pkw)
                 rollout_s += time.perf_counter() - t0
                 rows = np.zeros((candidates, horizon, COMMAND_DIM), np.float32)
                 rows[0] = ac[:horizon, :COMMAND_DIM]
-                recorded = planner.evaluate_actions(start, state0, rows, goal, goal_state=gs)
+                if pixels is None:
+                    recorded = planner.evaluate_actions(start, state0, rows, goal, goal_state=gs)
+                else:
+                    recorded, rec_exp = planner.evaluate_actions(start, state0, rows, goal, goal_state=gs, return_expected=True, **pkw)
                 per_seq.append({'actions': res['actions'].tolist(), 'cost': res['cost'], 'history': [float(v) for v in res['history']],
                                 'recorded_cost': float(recorded[0]), 'zero_cost': float(res['costs'][0, 0])})
+                if pixels is not None:
+                    rec_dist = np.sqrt(((rec_exp[0].astype(np.float64) - pkw['goal_pixels']) ** 2).sum(axis=1))
+                    per_seq[-1].update({'pixel_expected': res['pixel_expected'].tolist(), 'pixel_distance': res['pixel_distance'].tolist(),
+                                        'recorded_pixel_distance': rec_dist.tolist()})
                 if dump:
                     rows[0] = res['actions']
-                    _, pf = planner.evaluate_actions(start, state0, rows, goal, goal_state=gs, return_frames=True)
+                    got = planner.evaluate_actions(start, state0, rows, goal, goal_state=gs, return_frames=True, return_maps=pixels is not None,
+                                                   **pkw)
                     plans.append(res['actions'])
-                    plan_frames.append(pf[0])
+                    plan_frames.append(got[1][0])
+                    if pixels is not None:
+                        plan_maps.append(got[2][0])
         if not per_seq:
             raise ValueError('%s holds no sequences' % input_path)
         result = {
@@ -430,11 +631,17 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         }
         if weights == 'ema':
             result['ema_updates'] = int(ema_updates)
+        if pixels is not None:
+            per_sequence = pixels.ndim == 3
+            result['settings'].update({'pixels': used_pixels if per_sequence else used_pixels[0],
+                                       'goal_pixels': used_goals if per_sequence else used_goals[0], 'pixel_weight': checked['pixel_weight']})
         with open(os.path.join(output_path, 'plan.json'), 'w') as fh:
             json.dump(result, fh, indent=1)
         if dump:
             np.save(os.path.join(output_path, 'plans.npy'), np.stack(plans))
             np.save(os.path.join(output_path, 'plan_frames.npy'), np.stack(plan_frames))
+            if pixels is not None:
+                np.save(os.path.join(output_path, 'plan_maps.npy'), np.stack(plan_maps))
         return result
     finally:
         sess.close()
@@ -469,16 +676,42 @@ def main(argv=None):
     parser.add_argument('--seed', type=int, default=0)
     parser.add_argument('--num_sequences', type=int, default=None)
     parser.add_argument('--seq_len', type=int, default=8, help='sequence length of the synthetic source')
-    parser.add_argument('--dump', action='store_true', help='save the plans and their predicted frames as .npy')
+    parser.add_argument('--dump', action='store_true', help='save the plans and their predicted frames (and pixel maps) as .npy')
+    parser.add_argument('--pixel', type=str, action='append', default=None, metavar='Y,X',
+                        help='a designated pixel of frame 0, for every sequence (repeatable, up to 4; needs --dna)')
+    parser.add_argument('--goal_pixel', type=str, action='append', default=None, metavar='Y,X',
+                        help='where the --pixel of the same position should end up (may be fractional)')
+    parser.add_argument('--pixels', type=str, default=None, metavar='FILE.npy', help='designated pixels per sequence, int [n, D, 2]')
+    parser.add_argument('--goal_pixels', type=str, default=None, metavar='FILE.npy', help='their goals, float [n, D, 2]')
+    parser.add_argument('--pixel_weight', type=float, default=None, help='weight of the designated-pixel cost (default 1.0 once pixels are given)')
+    parser.add_argument('--frame_weight', type=float, default=1.0, help='weight of the frame cost; 0 (with --state_weight 0): the goal frame is not scored')
     args = parser.parse_args(argv)
     transform = check_model_args(parser, args)
     from .train import model_kind
     goal_step = args.horizon if args.goal_step is None else args.goal_step
+    pixels = goal_pixels = None
+    if (args.pixel or args.goal_pixel) and (args.pixels or args.goal_pixels):
+        parser.error('--pixel / --goal_pixel and --pixels / --goal_pixels exclude each other')
     try:
-        check_plan(args.candidates, args.horizon, args.elites, args.iterations, args.init_std, args.min_std, args.alpha,
-                   state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed, has_state_head=model_kind(transform) != 'plain')
-    except ValueError as e:
+        if args.pixel or args.goal_pixel:
+            if len(args.pixel or []) != len(args.goal_pixel or []):
+                parser.error('%d --pixel and %d --goal_pixel: the counts must be equal' % (len(args.pixel or []), len(args.goal_pixel or [])))
+            pixels = np.array([[int(v) for v in p.split(',')] for p in args.pixel], np.int64).reshape(len(args.pixel), -1)
+            goal_pixels = np.array([[float(v) for v in p.split(',')] for p in args.goal_pixel], np.float64).reshape(len(args.pixel), -1)
+        elif args.pixels or args.goal_pixels:
+            if not (args.pixels and args.goal_pixels):
+                parser.error('--pixels and --goal_pixels go together')
+            pixels, goal_pixels = np.load(args.pixels), np.load(args.goal_pixels)
+            if pixels.ndim != 3:
+                parser.error('%s: expected pixels [n, D, 2], got %s' % (args.pixels, pixels.shape))
+        pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, args.pixel_weight, model_kind(transform), args.img_size)
+        checked = check_plan(args.candidates, args.horizon, args.elites, args.iterations, args.init_std, args.min_std, args.alpha,
+                             frame_weight=args.frame_weight, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
+                             has_state_head=model_kind(transform) != 'plain', pixel_weight=pixel_weight)
+    except (OSError, ValueError) as e:
         parser.error(str(e))
+    if pixels is None and checked['frame_weight'] == 0 and checked['state_weight'] == 0:
+        parser.error('--frame_weight 0 and --state_weight 0 without pixels: nothing is scored')
     if goal_step < 1:
         parser.error('--goal_step must be >= 1')
     if args.num_sequences is not None and args.num_sequences < 1:
@@ -500,12 +733,17 @@ def main(argv=None):
             parser.error('frames %s and actions %s disagree in N or T' % (frames.shape[:2], actions.shape[:2]))
         if frames.shape[1] < need:
             parser.error('sequences of %d frames: --goal_step %d and --horizon %d need %d' % (frames.shape[1], goal_step, args.horizon, need))
+        if pixels is not None and pixels.ndim == 3 and args.num_sequences is None and len(pixels) < frames.shape[0]:
+            parser.error('%s holds pixels for %d sequences, %d are planned' % (args.pixels, len(pixels), frames.shape[0]))
+    if pixels is not None and pixels.ndim == 3 and args.num_sequences is not None and len(pixels) < args.num_sequences:
+        parser.error('%s holds pixels for %d sequences, %d are planned' % (args.pixels, len(pixels), args.num_sequences))
     return plan_sequences(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, cdna=args.cdna,
                           num_masks=args.num_masks, ksize=args.ksize, img_size=args.img_size, dtype=args.dtype, device=args.device,
                           bn_stats=args.bn_stats, weights=args.weights, candidates=args.candidates, elites=args.elites,
                           iterations=args.iterations, horizon=args.horizon, goal_step=goal_step, init_std=args.init_std,
                           min_std=args.min_std, alpha=args.alpha, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
-                          num_sequences=args.num_sequences, seq_len=args.seq_len, dump=args.dump)
+                          num_sequences=args.num_sequences, seq_len=args.seq_len, dump=args.dump, pixels=pixels, goal_pixels=goal_pixels,
+                          pixel_weight=pixel_weight if pixels is not None else None, frame_weight=args.frame_weight)
 
 
 if __name__ == '__main__':

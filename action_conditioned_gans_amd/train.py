@@ -44,7 +44,7 @@ class Trainer:
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
                  ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
                  g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
-                 sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0):
+                 sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -133,7 +133,18 @@ class Trainer:
         variable and no optimizer slot is added.  The losses of step j and its D(fake) input are built on the mixed input.
         ``sched_sampling_last()`` reads the last program's probability and coins; ``test`` / ``test_sequence`` / ``rollout_metrics``
         never sample.  A coin per batch row, not per pixel; whatever ``rollout_steps`` > 1 declines (bf16, more than one rank, the
-        CDNA generator, noise) is declined here too."""
+        CDNA generator, noise) is declined here too.
+        ``pixel_maps`` D (no reference counterpart; 0 builds nothing: ops, op order, state names, variables and checkpoint keys are
+        those of a Trainer without the argument; else an integer in 1..4, DNA generator only): a map path through the motion model
+        for plan.Planner's designated-pixel cost.  A float32 placeholder ``pixel_map`` [B, S, S, D] (float32 in bf16 graphs too, as the
+        DNA image is) and, for every predicting generator instance, a twin of its DnaOp on the same logits and the same folded
+        ``g/tconv4`` bias with the maps as its image (ops.dna_map_twin: acg_dna_fwd with c = D): ``g_map_out`` beside
+        ``g_next_frame`` and, with ``bn_inference``, ``g_map_stored`` beside ``g_out_stored``.  No variable, no state, no kernel of
+        its own; nothing but a fetch reads a twin, so the training programs, the rollout instances and the look-ahead pair do not
+        contain it.  The plain generator has no flow and is a ValueError; so is the CDNA generator: its channel split, kept as
+        written from the reference, transforms the colour channels of one mask with different kernels, so there is no single flow
+        that a map could follow consistently with the frame."""
+        self.pixel_maps = check_pixel_maps(pixel_maps, model_kind(arg_transform))      # (before anything is created)
         self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
         self.sched_sampling = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, ss_offset, ss_seed, rollout_steps,
@@ -304,6 +315,13 @@ class Trainer:
         self.bn_inference = bool(bn_inference)
         if self.bn_inference:
             self._build_bn_inference(build_g)
+        self.pixel_map_ph = self.g_map_out = self.g_map_stored = None
+        if self.pixel_maps:
+            # behind every generator instance, the look-ahead pair's alias walk and the rollout: the twins are nobody's ancestors
+            self.pixel_map_ph = G.placeholder((B, S, S, self.pixel_maps), name='pixel_map')
+            self.g_map_out = O.dna_map_twin(self.g_out.op, self.pixel_map_ph, 'g_map')
+            if self.bn_inference:
+                self.g_map_stored = O.dna_map_twin(self.g_out_stored.op, self.pixel_map_ph, 'g_map_stored')
         if self.ema is not None:
             self.ema.build()        # last: every op of the graph keeps the place it has without the average
         for norm in self.grad_norm.values():
@@ -988,6 +1006,19 @@ def check_sched_sampling(sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_de
                          % (int(rollout_steps) - 1, batch_size, _lib.NOISE_VALUES_MAX))
     return {'kind': sched_sampling, 'start': probs['ss_start'], 'final': probs['ss_final'], 'decay_steps': counts['ss_decay_steps'],
             'offset': counts['ss_offset'], 'seed': seed}
+
+
+def check_pixel_maps(pixel_maps, model):
+    """ValueError for a ``pixel_maps`` the Trainer does not take with the generator ``model``; -> D (0: no map path)."""
+    if isinstance(pixel_maps, bool) or not isinstance(pixel_maps, (int, np.integer)) or not 0 <= pixel_maps <= _lib.PLAN_PIXEL_MAPS_MAX:
+        raise ValueError('pixel_maps must be an integer in 0..%d, got %r' % (_lib.PLAN_PIXEL_MAPS_MAX, pixel_maps))
+    if pixel_maps and model == 'plain':
+        raise ValueError('pixel_maps %d: the plain generator predicts no flow a map could follow (DNA generator only)' % pixel_maps)
+    if pixel_maps and model == 'cdna':
+        raise ValueError('pixel_maps %d: the CDNA generator is declined - its channel split, kept as written from the reference, '
+                         'transforms the colour channels of one mask with different kernels, so there is no single flow that a map '
+                         'could follow consistently with the frame (DNA generator only)' % pixel_maps)
+    return int(pixel_maps)
 
 
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):

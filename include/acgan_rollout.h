@@ -28,7 +28,8 @@
  *
  * And what the action-conditioned rollout is for - choosing the actions that lead to a wanted frame - ends it: the three launches
  * of a cross-entropy-method planner around the generator forwards (acg_plan_sample / acg_plan_cost / acg_plan_refit), the draw by
- * the same generator from a state of its own.  Same conventions, same table, no atomics.
+ * the same generator from a state of its own.  Same conventions, same table, no atomics.  acg_plan_pixel_cost, the last entry,
+ * is the planner's second cost: the expected distance of designated pixels' probability maps to their goal positions.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -249,6 +250,30 @@ int32_t acg_plan_cost(const void* frames, const float* goal, const float* states
 int32_t acg_plan_refit(const float* cost, const float* actions, float* mean, float* std, float* best_cost, float* best_actions,
                        int32_t* elite_idx, float* history, int32_t candidates, int32_t horizon, int32_t action_dim, int32_t elites,
                        float alpha, float min_std, acg_stream_t stream);
+
+/* The designated-pixel cost of visual MPC (Finn & Levine, "Deep Visual Foresight"): the user marks d pixels and says where each
+ * should end up; the generator moves a probability map of every marked pixel with the per-pixel kernels it predicts for the frame
+ * (acg_dna_fwd on the map, c = d), and the cost of a candidate is the expected distance of each map to its goal position.
+ * maps float32 [N, h, w, d] dense, READ AND REWRITTEN in place; goals float32 [d, 2] as (y, x), may be fractional, one goal set for
+ * all candidates.  For every candidate n and map j < d, with P = maps[n, :, :, j] and (gy, gx) = goals[j]:
+ *   m0 = sum_{y, x} P[y, x]                                  (the mass: the DNA gather does not conserve it)
+ *   m1 = sum_{y, x} P[y, x] * sqrt((y - gy)^2 + (x - gx)^2)
+ *   ey = sum_{y, x} P[y, x] * y,   ex = sum_{y, x} P[y, x] * x
+ *   cost[n] = (accumulate != 0 ? cost[n] : 0) + pixel_weight * sum_j m1_j / m0_j       (accumulate == 0: the old value is not read)
+ *   P <- P / m0                                              (the published model renormalises every step; a long rollout
+ *                                                             stays inside float32 range)
+ *   expected[n, j] = (ey / m0, ex / m0),   mass[n, j] = m0   (float32 [N, d, 2] and [N, d]; either may be NULL)
+ * A map whose m0 is not finite or not > 0 makes what is added to cost[n] +inf - whatever pixel_weight is; acg_plan_refit ranks
+ * +inf last - is left unscaled, and its expected entries are NaN (its mass is m0 as it came out).
+ * One launch, one block per candidate, as acg_plan_cost: per-thread float32 partials over a strided share of the pixels, the lanes
+ * of a wave summed by shuffles, the waves in order; no atomics, no workspace, the same call gives the same bits.  The second pass,
+ * the scale, re-reads what the block just read.  1 <= N <= ACG_PLAN_CANDIDATES_MAX, 1 <= d <= ACG_PLAN_PIXEL_MAPS_MAX,
+ * 1 <= h, w <= ACG_PLAN_MAP_SIDE_MAX, pixel_weight finite and >= 0; a NULL maps / goals / cost or a value below 1 is
+ * ACG_ERR_INVALID_ARG, one above its limit ACG_ERR_UNSUPPORTED, and nothing is launched. */
+#define ACG_PLAN_PIXEL_MAPS_MAX 4
+#define ACG_PLAN_MAP_SIDE_MAX 1024
+int32_t acg_plan_pixel_cost(float* maps, const float* goals, float pixel_weight, float* cost, int32_t accumulate, float* expected,
+                            float* mass, int32_t candidates, int32_t h, int32_t w, int32_t d, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
