@@ -219,8 +219,9 @@ EXTENSIONS = {
     # "what sits in front of the optimizer update", the optimizer steps that evaluate a learning-rate schedule inside their launch
     # from an update counter they advance themselves (optim.LrSchedule); and scheduled sampling of the rollout's fed-back inputs;
     # and the launches of the planner around the generator forwards (plan.Planner)
+    # and instance noise on the discriminator's inputs with the statistics of its logits (train.Trainer d_noise / d_stats)
     'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, scheduled sampling, the gradient clip, the noise input, '
-                         'learning-rate schedules and planning run on the HIP library only', {
+                         'learning-rate schedules, planning and instance noise run on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
         'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
@@ -240,6 +241,11 @@ EXTENSIONS = {
         'acg_plan_refit': (STATUS, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P]),
         # the planner's designated-pixel cost on the maps the DNA tail advects (plan.accumulate_pixel_cost)
         'acg_plan_pixel_cost': (STATUS, [_P, _P, c_float, _P, c_int32, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+        # instance noise on the discriminator's inputs (ops.InstNoisePrepareOp / InstNoiseOp) and the statistics of its logits
+        # (ops.LogitStatsOp)
+        'acg_inst_noise_prepare': (STATUS, [_P, _P, _P, _P, c_float, c_float, c_int64, c_int64, c_int32, _P]),
+        'acg_inst_noise_add': (STATUS, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+        'acg_logit_stats': (STATUS, [_P, _P, c_int32, _P, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)

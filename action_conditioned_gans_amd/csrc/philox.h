@@ -4,7 +4,8 @@
 // (lo32(counter), hi32(counter), block, stream word) and the key (lo32(seed), hi32(seed)): every thread reads the pair
 // (load_draw_state), thread i takes the Philox blocks i, i + blockDim.x, ... (draw_block; the tail of the last block is dropped by
 // the kernel's own element loop), and advance_draw_state closes the launch.  No atomics: a draw is a pure function of
-// (seed, counter, stream word, element index).
+// (seed, counter, stream word, element index).  The instance noise on the discriminator's inputs (d_noise.hip) is the one
+// multi-block draw: its blocks call draw_block on a {seed, counter} SNAPSHOT that a one-thread launch took and advanced before.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1346,6 +1346,99 @@ class SchedSampleBwdOp(G.Op):
         return lambda s: fn(*args, s)
 
 
+INST_NOISE_STATE, INST_NOISE_UPDATES = 'd/inst_noise/state', 'd/inst_noise/updates'
+INST_NOISE_SLOTS = 64         # stream id of a draw = rank * INST_NOISE_SLOTS + the D instance's slot
+
+
+def inst_noise_state(seed=0):
+    """The instance-noise state of the graph, created by the first call (``seed`` is read by that call alone): -> (state,
+    updates).  ``d/inst_noise/state`` (new_draw_state: {seed, counter}, the counter is the number of draws so far) and
+    ``d/inst_noise/updates`` int64 [1], the schedule position; both are checkpoint keys."""
+    g = G.get_default_graph()
+    if 'inst_noise' not in g.collections:
+        g.collections['inst_noise'] = (new_draw_state(INST_NOISE_STATE, seed, 'instance-noise'),
+                                       g.new_state((1,), 0, INST_NOISE_UPDATES, dtype=torch.int64))
+    return g.collections['inst_noise']
+
+
+class InstNoisePrepareOp(G.Op):
+    """The counter protocol of the instance noise (acg_inst_noise_prepare), one launch per program that runs D: -> ``key`` int64
+    [2], the {seed, counter} snapshot the program's InstNoiseOps draw from, and ``sigma`` float32 [1], the level the schedule gives
+    at the graph's position (``sigma_start`` -> ``sigma_final`` over ``decay_steps`` positions behind ``offset``; 0 steps: constant).
+    The launch advances the counter - a program that holds this op draws fresh noise every time it runs, replayed from a captured
+    graph or not - and, with ``advance_schedule``, the position.  ``advance_schedule``: 1, 0, or an Op - the position then advances
+    in exactly the programs that hold that op (the Trainer names D's optimizer step: a D(fake) instance shared by the D step and
+    the G step moves the schedule in the D step alone).  key and sigma are plain tensors, not state: no checkpoint key.  No
+    inputs, no gradient."""
+
+    def __init__(self, sigma_start, sigma_final, decay_steps, offset, advance_schedule, name):
+        self.sched = (float(sigma_start), float(sigma_final), int(offset), int(decay_steps))
+        if not (0.0 <= self.sched[0] < math.inf and 0.0 <= self.sched[1] < math.inf and self.sched[2] >= 0 and self.sched[3] >= 0):
+            raise ValueError('inst_noise_prepare: levels must be finite and >= 0 and the counts >= 0, got %r' % (self.sched,))
+        self.advance_schedule = advance_schedule
+        self.extras = list(inst_noise_state())
+        self.key, self.sigma = _new((2,), name + ':key', torch.int64), _new((1,), name + ':sigma')
+        super().__init__(G.get_default_graph(), name, [], [self.key, self.sigma])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'inst_noise_prepare')
+        adv = self.advance_schedule
+        advance = int(id(adv) in rt.program_ops) if isinstance(adv, G.Op) else int(bool(adv))
+        state, updates = self.extras
+        args = (_p(state.buf), _p(updates.buf), _p(self.key.buf), _p(self.sigma.buf)) + self.sched + (advance,)
+        return lambda s: fn(*args, s)
+
+
+class InstNoiseOp(G.Op):
+    """x [.., pitch] + sigma * z on the channels [c0, c0 + cn) -> a new activation tensor with the shape, pitch and storage type
+    of ``x`` (acg_inst_noise_add; float32 or bf16); every other channel, the pad channels included, is copied.  ``key`` and
+    ``sigma`` are an InstNoisePrepareOp's; ``stream_id`` in 0..63 is the slot of the D instance that reads the result - the
+    draw's stream id is rank * 64 + slot, so instances and ranks draw different z from one key.  The noise is an additive constant:
+    the gradient of ``x`` is the output's gradient tensor itself (same layout: the window acg_dna_bwd reads stays where it is)."""
+
+    def __init__(self, x, key, sigma, c0, cn, stream_id, name):
+        pitch, c = x.shape[-1], x.valid_c or x.shape[-1]
+        self.c0, self.cn, self.slot = int(c0), int(cn), int(stream_id)
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError('inst_noise: float32 or bf16 input, got %s' % x.dtype)
+        if not (1 <= self.cn <= 4 and self.c0 >= 0 and self.c0 + self.cn <= c):
+            raise ValueError('inst_noise: channels [%d, %d + %d) of %d (1 <= cn <= 4)' % (self.c0, self.c0, self.cn, c))
+        if not 0 <= self.slot < INST_NOISE_SLOTS:
+            raise ValueError('inst_noise: stream_id (the instance slot) must be in 0..%d, got %d' % (INST_NOISE_SLOTS - 1, self.slot))
+        if not 1 <= x.numel // pitch < 2 ** 32:
+            raise ValueError('inst_noise: %d pixels (1 <= pixels < 2^32)' % (x.numel // pitch))
+        y = _new(x.shape, name + ':0', x.dtype)
+        y.valid_c = x.valid_c
+        super().__init__(G.get_default_graph(), name, [x, key, sigma], [y])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'inst_noise_add')
+        x, key, sigma = self.inputs
+        pitch = x.shape[-1]
+        args = (_p(x.buf), _p(self.outputs[0].buf), _p(key.buf), _p(sigma.buf), x.numel // pitch, x.valid_c or pitch, pitch, self.c0, self.cn,
+                _code(x), int(rt.rank) * INST_NOISE_SLOTS + self.slot)
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        return [gouts[0] if needs[0] else None, None, None]
+
+
+class LogitStatsOp(G.Op):
+    """acg_logit_stats: -> float32 [4] = {mean D(fake) logit, mean D(real) logit, share of fake logits < 0, share of real logits
+    > 0} of two equally long float32 logit tensors.  One launch of one block; no gradient."""
+
+    def __init__(self, fake, real, name):
+        if fake.numel != real.numel or fake.dtype != torch.float32 or real.dtype != torch.float32:
+            raise ValueError('logit_stats: two float32 tensors of one length, got %r and %r' % (fake, real))
+        super().__init__(G.get_default_graph(), name, [fake, real], [_new((4,), name + ':0')])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'logit_stats')
+        fake, real = self.inputs
+        args = (_p(fake.buf), _p(real.buf), fake.numel, _p(self.outputs[0].buf))
+        return lambda s: fn(*args, s)
+
+
 class ConcatChannelsOp(G.Op):
     """a ++ b on the channel axis; ``pitch`` > ca+cb stores the result with zero pad channels (``valid_c`` set);
     ``act``: the result is an activation (the conv-facing discriminator input: bf16 in a bf16 graph)."""

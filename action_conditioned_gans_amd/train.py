@@ -44,7 +44,8 @@ class Trainer:
                  seed=0, batched_d=True, lookahead=True, num_masks=10, rollout_steps=1, bn_inference=False, ema_decay=0.0,
                  ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
                  g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
-                 sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0):
+                 sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0,
+                 d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -143,7 +144,32 @@ class Trainer:
         its own; nothing but a fetch reads a twin, so the training programs, the rollout instances and the look-ahead pair do not
         contain it.  The plain generator has no flow and is a ValueError; so is the CDNA generator: its channel split, kept as
         written from the reference, transforms the colour channels of one mask with different kernels, so there is no single flow
-        that a map could follow consistently with the frame."""
+        that a map could follow consistently with the frame.
+        ``d_noise`` S, ``d_noise_final`` F, ``d_noise_decay_steps``, ``d_noise_offset``, ``d_noise_seed`` (no reference counterpart;
+        S = 0 builds nothing: ops, op order, variables, state names, checkpoint keys and summaries are those of a Trainer without
+        the arguments; else finite and > 0, needs ``arg_adv``): instance noise (Sonderby et al. 2016; Arjovsky & Bottou 2017) on
+        every frame the discriminator judges.  D(both) - D(real) and D(fake) with ``batched_d=False`` - and the G step's D(fake) read
+        a copy of their input whose channels 3..5, the judged frame, carry sigma * z with z ~ N(0, 1) per value; the conditioning
+        frame in channels 0..2 is left alone (ops.InstNoiseOp, acg_inst_noise_add).  sigma moves linearly from S to F over
+        ``d_noise_decay_steps`` D UPDATES that begin after ``d_noise_offset`` of them (0 steps: constant S).  The noise is drawn on
+        the device inside the program: one ops.InstNoisePrepareOp per program that runs D snapshots the graph state
+        ``d/inst_noise/state`` = {``d_noise_seed``, counter} as the program's key, advances the counter and evaluates sigma at
+        ``d/inst_noise/updates``, which it advances in the program that holds D's optimizer step and in no other - a replayed HIP
+        graph draws fresh noise and follows the schedule with no host in the loop; the G step and ``test`` draw at the current level
+        and leave the schedule alone.  Every D instance has a stream id of its own (rank * 64 + slot: gen 0, real 1, both 2).  The
+        two state tensors are the only new checkpoint keys (a restored run continues its key and its schedule; a checkpoint without
+        them starts at 0); no variable and no optimizer slot is added.  The noise is an additive constant: the gradient of the
+        generated frame is the gradient of D's noisy input.  ``d_noise_last()`` reads sigma and the key of the last program.
+        float32 and bf16 graphs, every generator, ema_decay, ssim_weight, the clip norms, the lr schedules and noise_dim
+        take it; more than one rank is allowed - the rank is part of the stream id - and not verified.  The look-ahead
+        pair pass is switched off, as it is for noise_dim.  Declined before anything is created: ``rollout_steps`` > 1 (the K-step
+        programs' D(fake) instances read no noise), ``arg_adv=False``, a negative or non-finite level.
+        ``d_stats=True`` (False adds nothing): the summaries ``d_fake_logit`` / ``d_real_logit`` - the mean logit of D on the
+        generated and on the real half - and ``d_fake_acc`` / ``d_real_acc`` - the share of fake logits < 0 and of real logits > 0 -
+        computed on the device from the logits the D loss reads (ops.LogitStatsOp), and with ``d_noise`` > 0 ``d_noise_sigma``, the
+        level of the program that computed them."""
+        self.d_noise = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, d_noise_offset, d_noise_seed, rollout_steps,
+                                     arg_adv)         # (before anything is created; None: off)
         self.pixel_maps = check_pixel_maps(pixel_maps, model_kind(arg_transform))      # (before anything is created)
         self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
@@ -177,7 +203,8 @@ class Trainer:
         graph = G.get_default_graph()
         dp = graph.collections.get('data_parallel')
         # (synchronised BatchNorm builds other ops per layer and is a validation mode: it keeps the plain call path)
-        self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn) and not self.noise_dim
+        self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn) and not self.noise_dim \
+            and self.d_noise is None
         self._noise = None            # the [B, 10 + Z] vector the generator reads (noise_dim > 0)
 
         def build_g(images, actions, batch, reuse):
@@ -235,14 +262,27 @@ class Trainer:
         else:
             d_in_gen = O.concat([self.img_ph, self.g_next_frame], axis=3, name='d_in_gen', pitch=8, act=True)
             d_in_real = O.concat([self.img_ph, self.next_frame_ph], axis=3, name='d_in_real', pitch=8, act=True)
-        self.d_out_gen = M.build_discriminator(d_in_gen, self.action_ph, reuse=False)
+        # what the D instances read: their inputs, or (d_noise) a noisy copy each, drawn under the instance's own stream id
+        d_x_gen, d_x_real, d_x_both = d_in_gen, d_in_real, d_in_both if batched_d else None
+        self._d_noise_prep, self.d_noisy = None, {}
+        if self.d_noise is not None:
+            dn = self.d_noise
+            O.inst_noise_state(dn['seed'])
+            prep = self._d_noise_prep = O.InstNoisePrepareOp(dn['start'], dn['final'], dn['decay_steps'], dn['offset'], 0, 'd/inst_noise/prepare')
+            noisy = lambda t, slot, name: O.InstNoiseOp(t, prep.key, prep.sigma, 3, 3, slot, name).outputs[0]     # noqa: E731
+            d_x_gen = self.d_noisy['gen'] = noisy(d_in_gen, 0, 'd_in_gen/noisy')
+            if batched_d:
+                d_x_both = self.d_noisy['both'] = noisy(d_in_both, 2, 'd_in_both/noisy')
+            else:
+                d_x_real = self.d_noisy['real'] = noisy(d_in_real, 1, 'd_in_real/noisy')
+        self.d_out_gen = M.build_discriminator(d_x_gen, self.action_ph, reuse=False)
         if batched_d:
             with O.arg_scope([O.batch_norm], groups=2):
-                self.d_out_both = M.build_discriminator(d_in_both, O.repeat_batch(self.action_ph, 2), reuse=True)
+                self.d_out_both = M.build_discriminator(d_x_both, O.repeat_batch(self.action_ph, 2), reuse=True)
             self.d_out_real = self.d_out_both.view(self.d_out_gen.numel, self.d_out_gen.shape, name='d_out_real')
         else:
             self.d_out_both = None
-            self.d_out_real = M.build_discriminator(d_in_real, self.action_ph, reuse=True)
+            self.d_out_real = M.build_discriminator(d_x_real, self.action_ph, reuse=True)
 
         # losses (train.py:72-85)
         self.g_psnr = O.build_psnr(self.next_frame_ph, self.g_next_frame)
@@ -258,6 +298,14 @@ class Trainer:
             self.d_loss = O.build_d_loss_batched(self.d_out_both, arg_loss, summaries=self.summaries)
         else:
             self.d_loss = O.build_d_loss(self.d_out_real, self.d_out_gen, arg_loss, summaries=self.summaries)
+        if d_stats:
+            # on the logits the D loss reads: the first half of D(both), or D(fake) of the two-instance D step
+            fake = self.d_out_both.view(0, self.d_out_gen.shape, name='d_out_fake') if batched_d else self.d_out_gen
+            stats = O.LogitStatsOp(fake, self.d_out_real, 'd_stats').outputs[0]
+            for k, name in enumerate(('d_fake_logit', 'd_real_logit', 'd_fake_acc', 'd_real_acc')):
+                self.summaries[name] = stats.view(k, (1,), name='d_stats/' + name)
+            if self._d_noise_prep is not None:
+                self.summaries['d_noise_sigma'] = self._d_noise_prep.sigma
 
         graph = G.get_default_graph()
         self.g_vars = graph.trainable_variables('g')
@@ -290,6 +338,8 @@ class Trainer:
         self.g_opt_op = minimize_g('g_opt', self.g_loss)
         self.g_pretrain_opt_op = minimize_g('g_pretrain_opt', g_l2_loss)
         self.d_opt_op = make('d_opt').minimize(self.d_loss, var_list=self.d_vars, clip_norm=d_norm, lr_schedule=d_sched)
+        if self._d_noise_prep is not None:
+            self._d_noise_prep.advance_schedule = self.d_opt_op      # sigma's schedule counts D updates: the D step's program alone
 
         # the seven tf.summary scalars of ops.py:48-49 / train.py:104-111, names kept
         self.summaries.update({'discriminator_loss': self.d_loss, 'g_loss': self.g_loss, 'g_l2_loss': g_l2_loss,
@@ -376,6 +426,25 @@ class Trainer:
         seed, counter = check_noise_seed(seed), check_noise_seed(counter)
         O.write_draw_state(self.sess._materialize(O.noise_state()[0]), seed, counter)
         self._announced = None
+
+    # ---- instance noise on the discriminator's inputs (d_noise > 0)
+    def _require_d_noise(self):
+        if self.d_noise is None:
+            raise RuntimeError('this Trainer was built without d_noise: its discriminator reads no instance noise')
+
+    def d_noise_last(self):
+        """-> {'sigma': the level the last program that ran D used (the float32 the kernel read), 'key': (seed, counter) that
+        program drew from}; sigma 0.0 and key (0, 0) before the first one.  Two small device-to-host copies (a synchronisation)."""
+        self._require_d_noise()
+        prep = self._d_noise_prep
+        return {'sigma': float(self.sess._materialize(prep.sigma).item()), 'key': O.read_draw_state(self.sess._materialize(prep.key))}
+
+    def d_noise_state(self):
+        """-> (seed, counter, updates) of ``d/inst_noise/state`` and ``d/inst_noise/updates`` as Python ints: the number of draws
+        and the schedule position (the number of D updates) so far."""
+        self._require_d_noise()
+        state, updates = O.inst_noise_state()
+        return O.read_draw_state(self.sess._materialize(state)) + (int(self.sess._materialize(updates).item()) % 2 ** 64,)
 
     # ---- scheduled sampling of the K-step programs (sched_sampling != 'off')
     def _require_sched_sampling(self):
@@ -1008,6 +1077,31 @@ def check_sched_sampling(sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_de
             'offset': counts['ss_offset'], 'seed': seed}
 
 
+def check_d_noise(d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, rollout_steps=1, arg_adv=True):
+    """ValueError for instance-noise arguments the Trainer does not take: a level that is not a finite number >= 0 (in float32
+    too), a negative or non-integer ``d_noise_decay_steps`` / ``d_noise_offset``, a bad ``d_noise_seed``, and ``d_noise`` > 0 together
+    with ``rollout_steps`` > 1 or without ``arg_adv``.  -> None for ``d_noise`` = 0 (off, whatever the other arguments are), else
+    {'start', 'final', 'decay_steps', 'offset', 'seed'}."""
+    levels = {what: _number(v, what, 'a finite number >= 0', 'be finite and >= 0', lambda x: 0.0 <= x <= F32_MAX)
+              for what, v in (('d_noise', d_noise), ('d_noise_final', d_noise_final))}
+    counts = {}
+    for what, v in (('d_noise_decay_steps', d_noise_decay_steps), ('d_noise_offset', d_noise_offset)):
+        if not _is_count(v):
+            raise ValueError('%s must be an integer >= 0, got %r' % (what, v))
+        counts[what] = int(v)
+    seed = check_noise_seed(d_noise_seed, 'd_noise_seed')
+    if levels['d_noise'] == 0.0:
+        return None
+    if _f32(levels['d_noise']) == 0.0:
+        raise ValueError('d_noise must be finite and >= 0 (0: off), got %r: it rounds to 0 in float32' % (d_noise,))
+    if int(rollout_steps) > 1:
+        raise ValueError("d_noise > 0 does not go with rollout_steps > 1 (the K-step programs' D(fake) instances read no noise)")
+    if not arg_adv:
+        raise ValueError('d_noise > 0 needs an adversarial trainer (arg_adv): without one nothing is trained against the discriminator')
+    return {'start': levels['d_noise'], 'final': levels['d_noise_final'], 'decay_steps': counts['d_noise_decay_steps'],
+            'offset': counts['d_noise_offset'], 'seed': seed}
+
+
 def check_pixel_maps(pixel_maps, model):
     """ValueError for a ``pixel_maps`` the Trainer does not take with the generator ``model``; -> D (0: no map path)."""
     if isinstance(pixel_maps, bool) or not isinstance(pixel_maps, (int, np.integer)) or not 0 <= pixel_maps <= _lib.PLAN_PIXEL_MAPS_MAX:
@@ -1211,7 +1305,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           data_workers='thread', data_threads=None, data_decode='exact', data_frames='selected', data_cache_gb=0.0, synthetic_pool=0,
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
           noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
-          lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0):
+          lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0, d_noise=0.0, d_noise_final=0.0,
+          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1253,7 +1348,14 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     iteration.  The Trainer gets ``ss_offset = pretrain_iter``: the pretraining updates are teacher-forced at ``ss_start`` and the
     decay begins behind them.  With sampling on ``train.jsonl`` records ``ss_prob``, the probability of truth of the iteration's
     update, and checkpoints hold ``g/sched_sampling/state``; a pretraining iteration at a log interval then logs too (``ss_prob`` and
-    ``pretrain_g_loss``) and writes the interval's checkpoint.  With sampling off all of this is unchanged."""
+    ``pretrain_g_loss``) and writes the interval's checkpoint.  With sampling off all of this is unchanged.
+    ``d_noise`` / ``d_noise_final`` / ``d_noise_decay_steps`` / ``d_noise_seed``: instance noise on the discriminator's inputs (Trainer,
+    same keywords; needs ``arg_adv`` and ``rollout_steps`` = 1), ``d_noise_decay_steps`` in TRAINING ITERATIONS: the Trainer gets them
+    multiplied by D's updates per iteration, as the learning-rate schedule does (the pretraining iterations update no D: no
+    offset).  The loop takes the plain call path (no look-ahead pass) and checkpoints hold ``d/inst_noise/state`` and
+    ``d/inst_noise/updates``.  ``d_stats``: ``train.jsonl`` records ``d_fake_logit`` / ``d_real_logit`` / ``d_fake_acc`` /
+    ``d_real_acc`` of the interval's last D step and, with ``d_noise`` > 0, its ``d_noise_sigma`` (Trainer ``d_stats``: they are
+    summaries).  With both off all of this is unchanged."""
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         if isinstance(v, (tuple, list)):
             raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
@@ -1276,6 +1378,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     if ss is not None:
         options.update(sched_sampling=ss['kind'], ss_start=ss['start'], ss_final=ss['final'], ss_decay_steps=ss['decay_steps'],
                        ss_offset=ss['offset'], ss_seed=ss['seed'])
+    dn = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, 0, d_noise_seed, rollout_steps, arg_adv)
+    if dn is not None:                  # iterations -> D updates
+        options.update(d_noise=dn['start'], d_noise_final=dn['final'], d_noise_decay_steps=dn['decay_steps'] * D_per_G, d_noise_seed=dn['seed'])
+    if d_stats:
+        options['d_stats'] = True
     for key, value in (('ema_decay', check_ema_decay(ema_decay)), ('ssim_weight', check_ssim_weight(ssim_weight))):
         if value:
             options[key] = value
@@ -1532,6 +1639,20 @@ def add_sched_sampling_args(parser):
     parser.add_argument('--ss_seed', type=int, default=0, metavar='S', help='seed of the coins (0 <= S < 2^64)')
 
 
+def add_d_noise_args(parser):
+    """The flags of the instance noise on the discriminator's inputs, and of the statistics to choose its level by."""
+    parser.add_argument('--d_noise', type=float, default=0.0, metavar='S',
+                        help='add Gaussian noise of standard deviation S to every frame the discriminator judges, real and generated, '
+                             'drawn on the device inside the step (instance noise; 0 = off; needs --adv)')
+    parser.add_argument('--d_noise_final', type=float, default=0.0, metavar='F', help='the level at the end of the decay')
+    parser.add_argument('--d_noise_decay_iters', type=int, default=0, metavar='N',
+                        help='training iterations over which the level moves linearly from S to F (0: constant S)')
+    parser.add_argument('--d_noise_seed', type=int, default=0, metavar='SEED', help='seed of the instance noise (0 <= SEED < 2^64)')
+    parser.add_argument('--log_d_stats', nargs='?', const=True, default=False, type=_flag,
+                        help="record the discriminator's mean logits and accuracies on the generated and the real half in train.jsonl "
+                             '(d_fake_logit, d_real_logit, d_fake_acc, d_real_acc) and, with --d_noise, d_noise_sigma')
+
+
 def add_lr_args(parser):
     """The learning-rate flags: the rates of G and D, Adam's beta1 and the schedule."""
     parser.add_argument('--g_lr', type=float, default=None, metavar='LR', help='learning rate of the generator updates (default: 1e-3 for adam, 5e-5 for rmsprop)')
@@ -1601,6 +1722,7 @@ def main(argv=None):
     add_noise_args(parser)
     add_lr_args(parser)
     add_sched_sampling_args(parser)
+    add_d_noise_args(parser)
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
@@ -1616,7 +1738,9 @@ def main(argv=None):
             ('--g_clip_norm must be finite and >= 0, got %r' % args.g_clip_norm, lambda: check_clip_norm(args.g_clip_norm)),
             ('--d_clip_norm must be finite and >= 0, got %r' % args.d_clip_norm, lambda: check_clip_norm(args.d_clip_norm)),
             ('--sched_sampling / --ss_*: {}', lambda: check_sched_sampling(args.sched_sampling, args.ss_start, args.ss_final, args.ss_decay_iters,
-                                                                           0, args.ss_seed, args.rollout_steps, args.batch_size))):
+                                                                           0, args.ss_seed, args.rollout_steps, args.batch_size)),
+            ('--d_noise / --d_noise_*: {}', lambda: check_d_noise(args.d_noise, args.d_noise_final, args.d_noise_decay_iters, 0,
+                                                                   args.d_noise_seed, args.rollout_steps, args.adv))):
         try:
             check()
         except ValueError as e:
@@ -1635,7 +1759,7 @@ def main(argv=None):
     # every other flag is a keyword of train() under its own name, but for these four
     options = {k: v for k, v in vars(args).items() if k not in ('input_path', 'output_path', 'adv', 'loss', 'opt', 'dna', 'cdna')}
     for flag, keyword in (('g_ema', 'ema_decay'), ('log_grad_norms', 'grad_norms'), ('lr_decay_iters', 'lr_decay_steps'),
-                          ('ss_decay_iters', 'ss_decay_steps')):
+                          ('ss_decay_iters', 'ss_decay_steps'), ('d_noise_decay_iters', 'd_noise_decay_steps'), ('log_d_stats', 'd_stats')):
         options[keyword] = options.pop(flag)
     trainer = train(args.input_path, os.path.join(args.output_path, 'train_output'), os.path.join(args.output_path, 'test_output'),
                     log_dir, model_dir, args.adv, args.loss, args.opt, transform, device='cuda:%d' % local_rank, world_size=world_size,

@@ -30,6 +30,10 @@
  * of a cross-entropy-method planner around the generator forwards (acg_plan_sample / acg_plan_cost / acg_plan_refit), the draw by
  * the same generator from a state of its own.  Same conventions, same table, no atomics.  acg_plan_pixel_cost, the last entry,
  * is the planner's second cost: the expected distance of designated pixels' probability maps to their goal positions.
+ *
+ * The fourth draw of that generator is the one on the other network: instance noise on every frame the discriminator judges
+ * (acg_inst_noise_prepare / acg_inst_noise_add), and, to choose its level by, the statistics of D's logits (acg_logit_stats).
+ * Same conventions, same table, no atomics.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -274,6 +278,46 @@ int32_t acg_plan_refit(const float* cost, const float* actions, float* mean, flo
 #define ACG_PLAN_MAP_SIDE_MAX 1024
 int32_t acg_plan_pixel_cost(float* maps, const float* goals, float pixel_weight, float* cost, int32_t accumulate, float* expected,
                             float* mass, int32_t candidates, int32_t h, int32_t w, int32_t d, acg_stream_t stream);
+
+/* Instance noise (Sonderby et al. 2016; Arjovsky & Bottou 2017): Gaussian noise of a decaying level sigma on every frame the
+ * discriminator judges, real and generated.  The draws above are one block each and advance their own counter; this one covers
+ * every pixel of D's input, a multi-block launch that cannot, so the counter protocol is a launch of its own.
+ *
+ * acg_inst_noise_prepare: one launch of one block.  state uint64 [2] = {seed, counter} (laid out as the noise state above),
+ * updates uint64 [1] = the schedule position, key_out uint64 [2], sigma_out float32 [1], all in device memory and distinct.  With
+ * k = updates[0] as the launch finds it, j = max(k - offset, 0), S = sigma_start, F = sigma_final, everything in double and every
+ * operation rounded on its own:
+ *   sigma = S + (F - S) * min(j / decay_steps, 1)        (decay_steps == 0: sigma = S)
+ *   sigma_out[0] = (float)sigma
+ *   key_out[0..1] = {seed, counter} as found             (the snapshot acg_inst_noise_add reads)
+ * and then state[1] = counter + 1 and, if advance_schedule != 0, updates[0] = k + 1: a replayed graph draws fresh noise and - where
+ * it is the program that should - moves along the schedule with no host in the loop.  Checked on the host before anything is
+ * launched: pointers not NULL; sigma_start and sigma_final finite and >= 0; offset >= 0; decay_steps >= 0.  Calls that share a
+ * state must be stream-ordered.
+ *
+ * acg_inst_noise_add: in and out [pixels, pitch] of storage dtype = ACG_F32 or ACG_BF16, in != out (no overlap).  For a channel
+ * ch in [c0, c0 + cn):  out[p, ch] = in[p, ch] + sigma[0] * z(p, ch - c0) - one fused multiply-add in float32, rounded once to
+ * the storage type; every other channel ch < pitch, the pad channels [c, pitch) included, is a copy of bits.  z(p, l) is lane l
+ * of Philox4x32-10 block p with the counter words (lo32(key[1]), hi32(key[1]), p, stream_id ^ ACG_DN_STREAM_TAG) and the key
+ * (lo32(key[0]), hi32(key[0])), turned into normals as acg_noise_concat's are (the same uniform and Box-Muller pairing); the tag
+ * keeps this stream apart from the other draws of the same seed and stream id.  sigma[0] == 0 copies every channel bit for bit
+ * (-0.0 stays -0.0).  key uint64 [2] and sigma float32 [1] are read, never written: the result is a pure function of the
+ * arguments - no atomics, no workspace, the same bits on every run.  One multi-block, grid-strided launch, one thread per pixel;
+ * 16-byte accesses where pitch * element size is a multiple of 16 and both bases are 16-byte aligned, element accesses
+ * otherwise, the same bits either way.  1 <= cn <= 4 (a Philox block has four lanes), c0 >= 0, c0 + cn <= c <= pitch,
+ * 1 <= pixels < 2^32; a NULL pointer, in == out or a value outside these is ACG_ERR_INVALID_ARG (cn > 4, pixels >= 2^32 and an
+ * unknown dtype: ACG_ERR_UNSUPPORTED) and nothing is launched.
+ *
+ * acg_logit_stats: out4 = {mean of fake, mean of real, share of fake[i] < 0, share of real[i] > 0} - the discriminator's mean
+ * logits and its accuracy on either half - over fake and real float32 [n], n >= 1; sums in double in a fixed order (per-thread
+ * partials over a strided share, the lanes of a wave by shuffles, the waves in order), each result rounded to float32 once.  One
+ * launch of one block. */
+#define ACG_DN_STREAM_TAG 0x444E4F49u
+int32_t acg_inst_noise_prepare(uint64_t* state, uint64_t* updates, uint64_t* key_out, float* sigma_out, float sigma_start,
+                               float sigma_final, int64_t offset, int64_t decay_steps, int32_t advance_schedule, acg_stream_t stream);
+int32_t acg_inst_noise_add(const void* in, void* out, const uint64_t* key, const float* sigma, int64_t pixels, int32_t c, int32_t pitch,
+                           int32_t c0, int32_t cn, int32_t dtype, int32_t stream_id, acg_stream_t stream);
+int32_t acg_logit_stats(const float* fake, const float* real, int32_t n, float* out4, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
