@@ -1,8 +1,11 @@
-// Tile geometry and LDS staging of cdna_composite.hip (the fused transform-and-composite): one sample's normalised
-// kernels and an image window at a channel pitch.  The same arithmetic as cdna.hip's helpers, whose kernels keep their own
-// copy (dense images only).
+// What cdna.hip (the unfused transformation, M pieces in HBM) and cdna_composite.hip (the fused transform-and-composite)
+// share, in its one copy: the tile geometry and its argument checks, the LDS staging of a sample's normalised kernels and
+// of an image window at a channel pitch, and the two halves of the kernel gradient - the per-tile partials and the final
+// pass through the normalisation and the relu.  The per-pixel correlation loops stay in the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "common.h"
 
 namespace acg_cdna {
 
@@ -14,6 +17,24 @@ struct Geo {
   int tiles_x, tiles_y;
   int pitch;                    // channel pitch of the image (C: dense)
 };
+
+// odd_k: the entry runs kernels compiled per kernel size (3, 5 or 7); otherwise any 1 <= K <= kMaxK.  pitch 0 means dense.
+inline int make_geo(const char* who, int B, int H, int W, int C, int M, int K, int pitch, bool odd_k, Geo* g) {
+  ACG_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && M > 0 && K > 0, ACG_ERR_INVALID_ARG, "%s: non-positive size", who);
+  ACG_REQUIRE(C <= kMaxC && M <= kMaxM, ACG_ERR_UNSUPPORTED, "%s: supports C <= %d, masks <= %d", who, kMaxC, kMaxM);
+  ACG_REQUIRE(odd_k ? (K == 3 || K == 5 || K == 7) : K <= kMaxK, ACG_ERR_UNSUPPORTED, "%s: kernel size %d (%s)", who, K,
+              odd_k ? "3, 5 or 7" : "1 to 7");
+  ACG_REQUIRE(B <= 65535, ACG_ERR_UNSUPPORTED, "%s: batch too large", who);
+  ACG_REQUIRE(pitch == 0 || (pitch >= C && pitch <= 64), ACG_ERR_INVALID_ARG, "%s: image pitch %d for %d channels", who, pitch, C);
+  g->B = B; g->H = H; g->W = W; g->C = C; g->M = M; g->K = K;
+  g->pad = (K - 1) / 2;                              // SAME, stride 1: pad_before = (k-1)//2
+  g->tiles_x = (W + kTile - 1) / kTile; g->tiles_y = (H + kTile - 1) / kTile;
+  g->pitch = pitch ? pitch : C;
+  return ACG_OK;
+}
+
+// floats of the kernel-gradient partials in the workspace: [b][tile][(u*K+v)*M + m]
+inline size_t partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.K * g.K * g.M; }
 
 // normalised kernels of sample b into LDS: kn[(u*K+v)*M + m]; also the per-mask sums S[m]
 __device__ __forceinline__ void stage_kernels(const float* __restrict__ params, int b, const Geo& g, float shift,
@@ -42,6 +63,64 @@ __device__ __forceinline__ void stage_window(const float* __restrict__ src, int 
     const int c = i % Cs, p = i / Cs, x = p % ww, y = p / ww;
     const int gy = y0 + y - g.pad, gx = x0 + x - g.pad;
     win[i] = (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) ? src[((long long)gy * g.W + gx) * pitch + c] : 0.f;
+  }
+}
+
+// Kernel-gradient partials of one tile for the nm masks from m0 on: o[(u*K+v)*M + m0 + mm] = sum over the tile's pixels p
+// and the colours of dd[(p*nm + mm)*C + c] * win(p + (u,v), c).  4 pixel groups x 64 tap slots: a thread sums its tap over
+// 64 pixels, then the 4 groups are folded through red[256] in a fixed order.  win and dd must be complete (a barrier
+// behind their last write) on entry.
+__device__ __forceinline__ void tile_kernel_partials(const float* win, const float* dd, float* red, float* __restrict__ o,
+                                                     int K, int C, int M, int m0, int nm) {
+  static_assert(kMaxK * kMaxK <= 64, "one wave-slot per tap");
+  const int kk = K * K, ww = kTile + K - 1, tid = threadIdx.x;
+  const int t = tid & 63, pg = tid >> 6, u = t / K, v = t % K;
+  for (int mm = 0; mm < nm; ++mm) {
+    float acc = 0.f;
+    if (t < kk) {
+      for (int p = pg * 64; p < pg * 64 + 64; ++p) {
+        const float* wsrc = win + ((p / kTile + u) * ww + p % kTile + v) * C;
+        const float* dsrc = dd + (p * nm + mm) * C;
+#pragma unroll
+        for (int c = 0; c < kMaxC; ++c)
+          if (c < C) acc += dsrc[c] * wsrc[c];
+      }
+    }
+    __syncthreads();                                 // red[] of the previous mask has been consumed
+    red[tid] = acc;
+    __syncthreads();
+    if (tid < kk) o[tid * M + m0 + mm] = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
+  }
+}
+
+// dparams of sample b by one block: dn = sum of the sample's tile partials in tile order; through the normalisation,
+// dk = (dn - sum_uv(dn * n)) / S, and the relu, dp = dk * [p - shift > 0]
+__device__ __forceinline__ void finish_dparams(const float* __restrict__ params, const float* __restrict__ kern_norm,
+                                               const float* __restrict__ part, float* __restrict__ dparams, int b,
+                                               const Geo& g, float shift) {
+  __shared__ float dn[kMaxK * kMaxK * kMaxM];
+  __shared__ float dot[kMaxM], S[kMaxM];
+  const int kk = g.K * g.K, n = kk * g.M, ntile = g.tiles_x * g.tiles_y;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    double s = 0.0;
+    for (int t = 0; t < ntile; ++t) s += part[((long long)b * ntile + t) * n + i];
+    dn[i] = (float)s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < g.M) {
+    const int m = threadIdx.x;
+    float d = 0.f, s = 0.f;
+    for (int t = 0; t < kk; ++t) {
+      d += dn[t * g.M + m] * kern_norm[(long long)b * n + t * g.M + m];
+      s += fmaxf(params[(long long)b * n + t * g.M + m] - shift, 0.f) + shift;
+    }
+    dot[m] = d; S[m] = s;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int m = i % g.M;
+    const float dk = (dn[i] - dot[m]) / S[m];
+    dparams[(long long)b * n + i] = params[(long long)b * n + i] - shift > 0.f ? dk : 0.f;
   }
 }
 

@@ -162,11 +162,10 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_tile_k(const float* __restr
   if (tid < nz) part_b[tile * nz + tid] = red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3];
 
   // ---- phase 2: kernel-gradient partials.  dd[(p*nm + mm)*C + c] = dT_q of pixel p, q = c*M + m0 + mm, for as many masks
-  // as fit `big`; then 4 pixel groups x 64 tap slots: a thread sums its tap over 64 pixels, the groups fold through LDS
+  // as fit `big`, then the tap sums shared with cdna_bwd_kern_partial_k
   float* dd = big;
   float* o = part_n + tile * n;
   const int mc = min(g.M, kBig / (kPix * g.C));
-  const int t = tid & 63, pg = tid >> 6, u = t / K, v = t % K;
   for (int m0 = 0; m0 < g.M; m0 += mc) {
     const int nm = min(mc, g.M - m0);
     __syncthreads();                                 // every read of big (dz sums, previous chunk) is done
@@ -180,37 +179,20 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_tile_k(const float* __restr
         dd[(tid * nm + mm) * g.C + c] = di * weight(zp, zb, j + 1, zmax, inv);
       }
     __syncthreads();
-    for (int mm = 0; mm < nm; ++mm) {
-      float acc = 0.f;
-      if (t < kk) {
-        for (int p = pg * 64; p < pg * 64 + 64; ++p) {
-          const float* wsrc = win + ((p / kTile + u) * ww + p % kTile + v) * g.C;
-          const float* dsrc = dd + (p * nm + mm) * g.C;
-#pragma unroll
-          for (int c = 0; c < kMaxC; ++c)
-            if (c < g.C) acc += dsrc[c] * wsrc[c];
-        }
-      }
-      __syncthreads();                               // red[] of the previous mask has been consumed
-      red[tid] = acc;
-      __syncthreads();
-      if (tid < kk) o[tid * g.M + m0 + mm] = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid];
-    }
+    tile_kernel_partials(win, dd, red, o, K, g.C, g.M, m0, nm);
   }
 }
 
-// blocks 0..B-1: dn = sum of the sample's tile partials; through the normalisation dk = (dn - sum_uv(dn * n)) / S and the
-// relu, dp = dk * [p - shift > 0] (cdna_bwd_kern_final_k).  Block B (when dbias is wanted): dbias over all the partials.
+// blocks 0..B-1: the sample's tile partials summed and taken through the normalisation and the relu.  Block B (when dbias
+// is wanted): dbias over all the partials.
 __global__ __launch_bounds__(256) void cdna_comp_bwd_final_k(const float* __restrict__ params, const float* __restrict__ kern_norm,
                                                              const float* __restrict__ part_n, const float* __restrict__ part_b,
                                                              float* __restrict__ dparams, float* __restrict__ dbias, float dbias_acc,
                                                              Geo g, float shift) {
-  __shared__ float dn[kMaxK * kMaxK * kMaxM];
-  __shared__ float dot[kMaxM], S[kMaxM];
   __shared__ double scratch[16];
-  const int b = blockIdx.x, kk = g.K * g.K, n = kk * g.M, ntile = g.tiles_x * g.tiles_y, nz = g.M + 1;
+  const int b = blockIdx.x;
   if (b == g.B) {
-    const int rows = g.B * ntile;
+    const int rows = g.B * g.tiles_x * g.tiles_y, nz = g.M + 1;
     for (int j = 0; j < nz; ++j) {
       double s = 0.0;
       for (int r = threadIdx.x; r < rows; r += blockDim.x) s += part_b[(long long)r * nz + j];
@@ -219,43 +201,8 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_final_k(const float* __rest
     }
     return;
   }
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    double s = 0.0;
-    for (int t = 0; t < ntile; ++t) s += part_n[((long long)b * ntile + t) * n + i];
-    dn[i] = (float)s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < g.M) {
-    const int m = threadIdx.x;
-    float d = 0.f, s = 0.f;
-    for (int t = 0; t < kk; ++t) {
-      d += dn[t * g.M + m] * kern_norm[(long long)b * n + t * g.M + m];
-      s += fmaxf(params[(long long)b * n + t * g.M + m] - shift, 0.f) + shift;
-    }
-    dot[m] = d; S[m] = s;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const int m = i % g.M;
-    const float dk = (dn[i] - dot[m]) / S[m];
-    dparams[(long long)b * n + i] = params[(long long)b * n + i] - shift > 0.f ? dk : 0.f;
-  }
+  finish_dparams(params, kern_norm, part_n, dparams, b, g, shift);
 }
-
-int make_geo(const char* who, int B, int H, int W, int C, int M, int K, int pitch, Geo* g) {
-  ACG_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && M > 0 && K > 0, ACG_ERR_INVALID_ARG, "%s: non-positive size", who);
-  ACG_REQUIRE(C <= kMaxC && M <= kMaxM, ACG_ERR_UNSUPPORTED, "%s: supports C <= %d, masks <= %d", who, kMaxC, kMaxM);
-  ACG_REQUIRE(K == 3 || K == 5 || K == 7, ACG_ERR_UNSUPPORTED, "%s: kernel size %d (3, 5 or 7)", who, K);
-  ACG_REQUIRE(B <= 65535, ACG_ERR_UNSUPPORTED, "%s: batch too large", who);
-  ACG_REQUIRE(pitch == 0 || (pitch >= C && pitch <= 64), ACG_ERR_INVALID_ARG, "%s: image pitch %d for %d channels", who, pitch, C);
-  g->B = B; g->H = H; g->W = W; g->C = C; g->M = M; g->K = K;
-  g->pad = (K - 1) / 2;                              // SAME, stride 1: pad_before = (k-1)//2
-  g->tiles_x = (W + kTile - 1) / kTile; g->tiles_y = (H + kTile - 1) / kTile;
-  g->pitch = pitch ? pitch : C;
-  return ACG_OK;
-}
-
-size_t partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.K * g.K * g.M; }     // floats of part_n
 
 }  // namespace
 
@@ -263,7 +210,7 @@ extern "C" {
 
 size_t acg_cdna_composite_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t M, int32_t K) {
   Geo g;
-  if (make_geo("cdna_composite_workspace_bytes", B, H, W, C, M, K, 0, &g) != ACG_OK) return 0;
+  if (make_geo("cdna_composite_workspace_bytes", B, H, W, C, M, K, 0, true, &g) != ACG_OK) return 0;
   return (partials(g) + (size_t)B * g.tiles_x * g.tiles_y * (M + 1)) * sizeof(float);
 }
 
@@ -271,7 +218,7 @@ int32_t acg_cdna_composite_fwd(const float* params, const float* mask_logits, co
                                int32_t image_pitch, float* out, float* kern_norm, int32_t B, int32_t H, int32_t W, int32_t C,
                                int32_t M, int32_t K, float relu_shift, acg_stream_t stream) {
   Geo g;
-  if (int rc = make_geo("cdna_composite_fwd", B, H, W, C, M, K, image_pitch, &g)) return rc;
+  if (int rc = make_geo("cdna_composite_fwd", B, H, W, C, M, K, image_pitch, true, &g)) return rc;
   ACG_REQUIRE(params && mask_logits && image && out, ACG_ERR_INVALID_ARG, "cdna_composite_fwd: null pointer");
   const dim3 grid(g.tiles_x, g.tiles_y, B);
   hipStream_t st = acg::to_stream(stream);
@@ -286,7 +233,7 @@ int32_t acg_cdna_composite_bwd(const float* params, const float* kern_norm, cons
                                float* dmask_bias, float dmask_bias_accumulate, int32_t B, int32_t H, int32_t W, int32_t C,
                                int32_t M, int32_t K, float relu_shift, void* ws, size_t wsb, acg_stream_t stream) {
   Geo g;
-  if (int rc = make_geo("cdna_composite_bwd", B, H, W, C, M, K, image_pitch, &g)) return rc;
+  if (int rc = make_geo("cdna_composite_bwd", B, H, W, C, M, K, image_pitch, true, &g)) return rc;
   ACG_REQUIRE(params && kern_norm && mask_logits && image && dout && dparams && dmask_logits, ACG_ERR_INVALID_ARG,
               "cdna_composite_bwd: null pointer");
   ACG_REQUIRE(ws && wsb >= acg_cdna_composite_workspace_bytes(B, H, W, C, M, K), ACG_ERR_WORKSPACE,

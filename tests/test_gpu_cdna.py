@@ -88,7 +88,8 @@ def test_composite_forward_matches_float64(hip_abi, shape):
     kern = (kern / kern.sum(dim=1, keepdim=True)).view(b, -1)
     assert ((kn.cpu().double() - kern).abs() <= 1e-6 * kern.abs()).all()
     # the unfused path: acg_cdna_fwd's M pieces, composited in float32 by torch
-    pieces, _ = hip_abi.cdna_fwd(d(params), d(img), m, k)
+    pieces, kn_unfused = hip_abi.cdna_fwd(d(params), d(img), m, k)
+    assert torch.equal(kn_unfused, kn), 'both entries normalise the kernels through the one stage_kernels'
     s = torch.softmax(d(z) + d(bias), dim=-1)
     ref = s[..., :1] * d(img) + sum(s[..., j + 1:j + 2] * pieces[j] for j in range(m))
     assert (out - ref).abs().max().item() <= 1e-5
