@@ -205,12 +205,16 @@ EXTENSIONS = {
         'acg_frame_metrics': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float,
                                        _P, c_size_t, _P]),
     }),
-    # the CDNA generator's fused transform-and-composite (ops.CdnaCompositeOp)
-    'cdna': Extension('include/acgan_cdna.h', 'the CDNA generator runs on the HIP library only', {
+    # the CDNA generator's fused transform-and-composite (ops.CdnaCompositeOp) and the affine generator's warp-and-composite
+    'cdna': Extension('include/acgan_cdna.h', 'the CDNA and the affine generators run on the HIP library only', {
         'acg_cdna_composite_workspace_bytes': (c_size_t, [c_int32] * 6),
         'acg_cdna_composite_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P] + [c_int32] * 6 + [c_float, _P]),
         'acg_cdna_composite_bwd': (STATUS, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 6
                                    + [c_float, _P, c_size_t, _P]),
+        # the affine (STP) generator's fused warp-and-composite (ops.AffineCompositeOp)
+        'acg_affine_composite_workspace_bytes': (c_size_t, [c_int32] * 5),
+        'acg_affine_composite_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P] + [c_int32] * 5 + [_P]),
+        'acg_affine_composite_bwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 5 + [_P, c_size_t, _P]),
     }),
     # the image gradient of the DNA tail and the gradient of a tiled action vector, which training through the generator's own
     # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp), and the global-norm clip of a flat

@@ -1,7 +1,9 @@
 // What cdna.hip (the unfused transformation, M pieces in HBM) and cdna_composite.hip (the fused transform-and-composite)
 // share, in its one copy: the tile geometry and its argument checks, the LDS staging of a sample's normalised kernels and
 // of an image window at a channel pitch, and the two halves of the kernel gradient - the per-tile partials and the final
-// pass through the normalisation and the relu.  The per-pixel correlation loops stay in the kernels.
+// pass through the normalisation and the relu.  The per-pixel correlation loops stay in the kernels.  The two composites
+// (cdna_composite.hip, affine_composite.hip) also share the mask stage: the per-pixel softmax weight, the per-tile partial of
+// the bias gradient and its final sum.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +34,9 @@ inline int make_geo(const char* who, int B, int H, int W, int C, int M, int K, i
   g->pitch = pitch ? pitch : C;
   return ACG_OK;
 }
+
+constexpr int kPix = kTile * kTile;
+constexpr int kMaxZ = kMaxM + 1;                                   // mask channels: the image and the M transforms
 
 // floats of the kernel-gradient partials in the workspace: [b][tile][(u*K+v)*M + m]
 inline size_t partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.K * g.K * g.M; }
@@ -121,6 +126,46 @@ __device__ __forceinline__ void finish_dparams(const float* __restrict__ params,
     const int m = i % g.M;
     const float dk = (dn[i] - dot[m]) / S[m];
     dparams[(long long)b * n + i] = params[(long long)b * n + i] - shift > 0.f ? dk : 0.f;
+  }
+}
+
+// ---- the mask stage of the two composites ---------------------------------------------------------------------------
+// softmax weight of channel j of a pixel (zp its logits, zb the bias in LDS) given its max and 1 / sum
+__device__ __forceinline__ float weight(const float* zp, const float* zb, int j, float zmax, float inv) {
+  return expf(zp[j] + zb[j] - zmax) * inv;
+}
+
+// max and 1 / sum of exp of a pixel's nz biased logits
+__device__ __forceinline__ void softmax_stats(const float* zp, const float* zb, int nz, float* zmax_out, float* inv_out) {
+  float zmax = -INFINITY, sum = 0.f;
+  for (int j = 0; j < nz; ++j) zmax = fmaxf(zmax, zp[j] + zb[j]);
+  for (int j = 0; j < nz; ++j) sum += expf(zp[j] + zb[j] - zmax);
+  *zmax_out = zmax;
+  *inv_out = 1.f / sum;
+}
+
+// bias-gradient partial of a tile from dz_j of pixel p at big[j * kPix + p] (complete: a barrier behind the last write):
+// 4 lanes per channel, 64 pixels each, then the 4 in order.  o[j], j < nz.  red holds kPix floats.
+__device__ __forceinline__ void tile_bias_partial(const float* big, float* red, float* __restrict__ o, int nz) {
+  const int tid = threadIdx.x;
+  if (tid < nz * 4) {
+    const int j = tid >> 2, r = tid & 3;
+    float s = 0.f;
+    for (int p = r * 64; p < r * 64 + 64; ++p) s += big[j * kPix + p];
+    red[tid] = s;
+  }
+  __syncthreads();
+  if (tid < nz) o[tid] = red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3];
+}
+
+// dbias[j] = (acc != 0 ? acc * dbias[j] : 0) + the sum of the `rows` tile partials, by one block.  scratch holds 16 doubles.
+__device__ __forceinline__ void final_bias_sum(const float* __restrict__ part_b, float* __restrict__ dbias, float dbias_acc,
+                                               int rows, int nz, double* scratch) {
+  for (int j = 0; j < nz; ++j) {
+    double s = 0.0;
+    for (int r = threadIdx.x; r < rows; r += blockDim.x) s += part_b[(long long)r * nz + j];
+    s = acg::block_sum(s, scratch);
+    if (threadIdx.x == 0) dbias[j] = (dbias_acc != 0.f ? dbias_acc * dbias[j] : 0.f) + (float)s;
   }
 }
 

@@ -19,15 +19,8 @@ namespace {
 
 using namespace acg_cdna;
 
-constexpr int kPix = kTile * kTile;
-constexpr int kMaxZ = kMaxM + 1;                                   // mask channels: the image and the M transforms
 constexpr int kWin = (kTile + kMaxK - 1) * (kTile + kMaxK - 1) * kMaxC;
 constexpr int kBig = kMaxZ * kPix;                                 // bwd: g_j / dz_j per pixel, then the dd chunks
-
-// softmax weight of channel j of a pixel (zp its logits, zb the bias in LDS) given its max and 1 / sum
-__device__ __forceinline__ float weight(const float* zp, const float* zb, int j, float zmax, float inv) {
-  return expf(zp[j] + zb[j] - zmax) * inv;
-}
 
 template <int K>
 __global__ __launch_bounds__(256) void cdna_comp_fwd_k(const float* __restrict__ params, const float* __restrict__ z,
@@ -51,10 +44,8 @@ __global__ __launch_bounds__(256) void cdna_comp_fwd_k(const float* __restrict__
   if (y >= g.H || x >= g.W) return;
   const long long pix = ((long long)b * g.H + y) * g.W + x;
   const float* zp = z + pix * nz;
-  float zmax = -INFINITY, sum = 0.f;
-  for (int j = 0; j < nz; ++j) zmax = fmaxf(zmax, zp[j] + zb[j]);
-  for (int j = 0; j < nz; ++j) sum += expf(zp[j] + zb[j] - zmax);
-  const float inv = 1.f / sum;
+  float zmax, inv;
+  softmax_stats(zp, zb, nz, &zmax, &inv);
   const float* centre = win + ((ly + g.pad) * ww + lx + g.pad) * g.C;           // the pixel itself
   const float s0 = weight(zp, zb, 0, zmax, inv);
   float f[kMaxC];
@@ -110,10 +101,8 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_tile_k(const float* __restr
   float d[kMaxC];
 #pragma unroll
   for (int i = 0; i < kMaxC; ++i) d[i] = (inside && i < g.C) ? dout[pix * g.C + i] : 0.f;
-  float zmax = -INFINITY, sum = 0.f;
-  for (int j = 0; j < nz; ++j) zmax = fmaxf(zmax, zp[j] + zb[j]);
-  for (int j = 0; j < nz; ++j) sum += expf(zp[j] + zb[j] - zmax);
-  const float inv = 1.f / sum;
+  float zmax, inv;
+  softmax_stats(zp, zb, nz, &zmax, &inv);
 
   // ---- phase 1: g_j in big[j][pixel], then dz_j
   const float* centre = win + ((ly + g.pad) * ww + lx + g.pad) * g.C;
@@ -150,16 +139,8 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_tile_k(const float* __restr
     if (inside) dzp[j] = v;
   }
   __syncthreads();
-  // bias-gradient partial of the tile: 4 lanes per channel, 64 pixels each, then the 4 in order
-  if (tid < nz * 4) {
-    const int j = tid >> 2, r = tid & 3;
-    float s = 0.f;
-    for (int p = r * 64; p < r * 64 + 64; ++p) s += big[j * kPix + p];
-    red[tid] = s;
-  }
-  __syncthreads();
   const long long tile = ((long long)b * g.tiles_y + ty) * g.tiles_x + tx;
-  if (tid < nz) part_b[tile * nz + tid] = red[tid * 4] + red[tid * 4 + 1] + red[tid * 4 + 2] + red[tid * 4 + 3];
+  tile_bias_partial(big, red, part_b + tile * nz, nz);
 
   // ---- phase 2: kernel-gradient partials.  dd[(p*nm + mm)*C + c] = dT_q of pixel p, q = c*M + m0 + mm, for as many masks
   // as fit `big`, then the tap sums shared with cdna_bwd_kern_partial_k
@@ -192,13 +173,7 @@ __global__ __launch_bounds__(256) void cdna_comp_bwd_final_k(const float* __rest
   __shared__ double scratch[16];
   const int b = blockIdx.x;
   if (b == g.B) {
-    const int rows = g.B * g.tiles_x * g.tiles_y, nz = g.M + 1;
-    for (int j = 0; j < nz; ++j) {
-      double s = 0.0;
-      for (int r = threadIdx.x; r < rows; r += blockDim.x) s += part_b[(long long)r * nz + j];
-      s = acg::block_sum(s, scratch);
-      if (threadIdx.x == 0) dbias[j] = (dbias_acc != 0.f ? dbias_acc * dbias[j] : 0.f) + (float)s;
-    }
+    final_bias_sum(part_b, dbias, dbias_acc, g.B * g.tiles_x * g.tiles_y, g.M + 1, scratch);
     return;
   }
   finish_dparams(params, kern_norm, part_n, dparams, b, g, shift);

@@ -197,9 +197,9 @@ def set_psnr(sqerr, valid, count_per_frame):
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
              seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
              calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw', noise_dim=0,
-             noise='zero', noise_samples=1, noise_seed=0):
+             noise='zero', noise_samples=1, noise_seed=0, affine=False):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
-    ``dna`` / ``cdna`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
+    ``dna`` / ``cdna`` / ``affine`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
     with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  ``bn_stats`` 'batch', 'stored' or 'calibrate' and the
     ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
@@ -208,6 +208,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     -> the metrics dict."""
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
+    if affine and (dna or cdna):
+        raise ValueError('affine and %s name two different generators' % ('dna' if dna else 'cdna'))
     if bn_stats not in ('batch', 'stored', 'calibrate'):
         raise ValueError("bn_stats must be 'batch', 'stored' or 'calibrate', got %r" % (bn_stats,))
     if weights not in ('raw', 'ema'):
@@ -223,7 +225,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     if int(noise_samples) < 1 or (noise == 'zero' and int(noise_samples) != 1):
         raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' (got %r)" % (noise_samples,))
     n_draws = int(noise_samples)
-    transform = 'cdna' if cdna else dna
+    transform = 'affine' if affine else 'cdna' if cdna else dna
     from .metrics import SSIM_DEFINITION
     from .saver import latest_checkpoint
     from .util import save_samples
@@ -284,8 +286,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            'num_masks': num_masks if trainer.model == 'cdna' else None,
-            'ksize': ksize if trainer.model != 'plain' else None,
+            'num_masks': num_masks if trainer.model in ('cdna', 'affine') else None,
+            'ksize': ksize if trainer.model in ('dna', 'cdna') else None,
             'sequences': n_seq,
             'steps': int(steps),
             'ssim_definition': SSIM_DEFINITION + ' (data_range 2 for frames in [-1, 1])',
@@ -424,7 +426,7 @@ def main(argv=None):
                     num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
                     cdna=args.cdna, num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
                     calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions,
-                    **({'weights': args.weights} if args.weights != 'raw' else {}),
+                    **({'weights': args.weights} if args.weights != 'raw' else {}), **({'affine': True} if args.affine else {}),
                     **({'noise_dim': args.noise_dim, 'noise': args.noise, 'noise_samples': args.noise_samples, 'noise_seed': args.noise_seed}
                        if args.noise_dim else {}))
 

@@ -110,15 +110,21 @@ def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_ch
         raise ValueError('CDNA generator: image size %s is not a multiple of 16' % (images.shape[1:3],))
     if O.half_mode():
         raise NotImplementedError('the CDNA generator is float32 only')
+    return _mask_generator(images, actions, reuse, 'cdna_params', ksize * ksize * num_masks, num_masks,
+                           lambda logits, params: O.cdna_composite(logits, images, params, num_masks, ksize))
+
+
+def _mask_generator(images, actions, reuse, scope, width, num_masks, composite):
+    """The trunk the CDNA and the affine generators share: the DNA generator's layers, a linear layer ``scope`` of ``width``
+    outputs per sample on the action-conditioned bottleneck, tconv4 to M+1 mask logits and ``composite(logits, params)``."""
     with O.variable_scope('g', reuse=reuse), \
             O.arg_scope([O.conv2d, O.deconv2d], activation_fn=O.relu, stride=2, padding='SAME',
                         normalizer_fn=O.batch_norm, reuse=reuse):
         net = _stack(getattr(images, 'padded', images), G_DNA['encoder'], O.conv2d)
         net = _with_actions(net, actions, 'actions')
-        nk = ksize * ksize * num_masks
-        params = O.conv2d(net, nk, [net.shape[1], net.shape[2]], activation_fn=None, stride=1, padding='VALID',
-                          normalizer_fn=None, scope='cdna_params')
-        params = params.reshape((images.shape[0], nk))
+        params = O.conv2d(net, width, [net.shape[1], net.shape[2]], activation_fn=None, stride=1, padding='VALID',
+                          normalizer_fn=None, scope=scope)
+        params = params.reshape((images.shape[0], width))
         net = _stack(net, G_DNA['decoder_a'], O.deconv2d)
         with G.get_default_graph().side_branch():
             state = _stack(net, G_DNA['state'], O.conv2d, size=3)
@@ -128,8 +134,32 @@ def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_ch
             state = O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
         logits = O.deconv2d(net, num_masks + 1, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
-        frame = O.cdna_composite(logits, images, params, num_masks, ksize)
-        return frame, state
+        return composite(logits, params), state
+
+
+def build_generator_affine(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10):
+    """Affine (STP) generator: ``build_generator_cdna`` with a 2x3 affine transform per mask in place of a k x k kernel.
+    Returns ``(frame, state)``.
+
+    ``g/affine_params`` (weights [S/16, S/16, 266, 6*M], biases, default initialisers) stands where ``g/cdna_params`` does and
+    predicts M = ``num_masks`` transforms per sample, read as theta = params + (1, 0, 0, 0, 1, 0): zero parameters are the
+    identity.  The frame is s_0 * images + sum_m s_{m+1} * T_m with T_m the image warped by theta_m, bilinear with zeros
+    outside (include/acgan_cdna.h has the formula), in one fused kernel (ops.affine_composite).  Rotation, scale and shear of
+    an object take 6 numbers here; the k x k kernels of DNA / CDNA cannot move anything further than (k-1)/2 pixels.
+    As for CDNA there is no image generated from scratch among the candidates and the masks come from the 5x5/2 ``tconv4``.
+    float32 only; 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
+    if batch_size is not None and batch_size != images.shape[0]:
+        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
+    if images.shape[3] != color_channels:
+        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
+    if not 1 <= num_masks <= 32:
+        raise ValueError('affine generator: num_masks must be in 1..32 (got %r)' % (num_masks,))
+    if images.shape[1] % 16 or images.shape[2] % 16:
+        raise ValueError('affine generator: image size %s is not a multiple of 16' % (images.shape[1:3],))
+    if O.half_mode():
+        raise NotImplementedError('the affine generator is float32 only')
+    return _mask_generator(images, actions, reuse, 'affine_params', 6 * num_masks, num_masks,
+                           lambda logits, params: O.affine_composite(logits, images, params, num_masks))
 
 
 def build_discriminator(inputs, actions, reuse=False):

@@ -1079,6 +1079,65 @@ class CdnaCompositeBwdOp(G.Op):
         return lambda s: fn(*args, s)
 
 
+class AffineCompositeOp(G.Op):
+    """The affine (STP) generator's output stage in one kernel (acg_affine_composite_fwd): each of the M masks moves the image
+    by the 2x3 affine transform ``params`` [B, M*6] + identity, sampled bilinearly with zeros outside (the M warped images stay
+    in registers), and the composite is s_0 * image + sum_m s_{m+1} * T_m under s = softmax(logits + bias) over the M + 1 mask
+    channels.  ``bias`` (may be None) is the bias variable of the layer that produced the logits, folded in as DnaOp does."""
+
+    def __init__(self, logits, image, params, masks, name, bias=None):
+        self.masks = int(masks)
+        self.has_bias = bias is not None
+        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
+                         [_new(image.shape, name + ':0')])
+
+    def bind(self, rt):
+        lg, img, par = self.inputs[:3]
+        b, h, w, c = img.shape
+        fn = _lib.entry(rt.lib, 'affine_composite_fwd')
+        pb = _p(self.inputs[3].buf) if self.has_bias else None
+        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), b, h, w, c, self.masks)
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        if needs[1]:
+            raise NotImplementedError('affine_composite: gradient w.r.t. the image is not implemented (the image is a network '
+                                      'input, train.py:53-54)')
+        dst, acc = (None, 0.0)
+        if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
+            dst, acc = ctx.slot(self.inputs[3])
+        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
+            return [None] * len(self.inputs)
+        op = AffineCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
+        if dst is not None:
+            ctx.wrote(self.inputs[3], op)
+        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
+
+
+class AffineCompositeBwdOp(G.Op):
+    """acg_affine_composite_bwd: d logits, d params (the 6 numbers of every mask) and, into the bias variable's gradient
+    window, d bias."""
+
+    def __init__(self, fwd, dout, dbias_dst, accumulate, name):
+        self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
+        lg, img, par = fwd.inputs[:3]
+        super().__init__(G.get_default_graph(), name, [lg, img, par, dout] + list(fwd.inputs[3:]),
+                         [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
+                         + ([dbias_dst] if dbias_dst is not None else []))
+
+    def bind(self, rt):
+        lg, img, par, dout = self.inputs[:4]
+        f = self.fwd
+        b, h, w, c = img.shape
+        fn = _lib.entry(rt.lib, 'affine_composite_bwd')
+        ws, n = rt.workspace(_lib.entry(rt.lib, 'affine_composite_workspace_bytes')(b, h, w, c, f.masks))
+        self._keep = ws
+        pb = _p(self.inputs[4].buf) if f.has_bias else None
+        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf), _p(self.outputs[0].buf),
+                _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c, f.masks, _p(ws), n)
+        return lambda s: fn(*args, s)
+
+
 DGRAD_CHANNEL_LIMIT = True     # A/B switch (bench.py --no-dgrad-limit): input gradients skip the columns of tiled action channels
 
 
@@ -1832,6 +1891,32 @@ def cdna_composite(mask_logits, image, params, num_masks, ksize=DNA_KERN_SIZE, n
     if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
         mask_logits, bias = prod.inputs[0], prod.inputs[1]
     return CdnaCompositeOp(mask_logits, image, params, num_masks, ksize, RELU_SHIFT, _scope_name(name), bias=bias).outputs[0]
+
+
+def affine_composite(mask_logits, image, params, num_masks, name='affine'):
+    """The affine (STP) generator's frame in one op (AffineCompositeOp): the ``num_masks`` 2x3 transforms ``params`` [B, M*6]
+    (+ identity) warp ``image`` [B,H,W,C] bilinearly, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
+    the M warped images through a per-pixel softmax.  When the logits come from a layer with a bias and neither BatchNorm nor
+    activation, that bias is folded into the kernel (as dna_gather does)."""
+    _check_nhwc(mask_logits, 'affine_composite')
+    _check_nhwc(image, 'affine_composite')
+    if not 1 <= num_masks <= 32:
+        raise ValueError('affine_composite: supports 1..32 masks, got %r' % (num_masks,))
+    if not 1 <= image.shape[3] <= 4:
+        raise ValueError('affine_composite: image channels outside 1..4')
+    if image.shape[1] < 2 or image.shape[2] < 2:
+        raise ValueError('affine_composite: image %s, needs H, W >= 2' % (image.shape,))
+    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
+        raise ValueError('affine_composite: mask logits %s do not match image %s with %d masks' % (mask_logits.shape, image.shape, num_masks))
+    if params.shape != (image.shape[0], 6 * num_masks):
+        raise ValueError('affine_composite: params %s, expected [%d, %d]' % (params.shape, image.shape[0], 6 * num_masks))
+    if half_mode() or image.dtype != torch.float32:
+        raise NotImplementedError('affine_composite is float32 only')
+    bias = None
+    prod = mask_logits.op
+    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
+        mask_logits, bias = prod.inputs[0], prod.inputs[1]
+    return AffineCompositeOp(mask_logits, image, params, num_masks, _scope_name(name), bias=bias).outputs[0]
 
 
 def concat_actions(x, actions, name='concat_actions'):

@@ -531,7 +531,7 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
                    dtype='f32', device='cuda:0', bn_stats='batch', weights='raw', candidates=64, elites=8, iterations=3, horizon=5,
                    goal_step=None, init_std=DEFAULTS['init_std'], min_std=DEFAULTS['min_std'], alpha=DEFAULTS['alpha'], state_weight=0.0,
                    cost_steps='all', seed=0, num_sequences=None, seq_len=8, dump=False, pixels=None, goal_pixels=None, pixel_weight=None,
-                   frame_weight=1.0):
+                   frame_weight=1.0, affine=False):
     """Restore ``model_path`` as evaluate.evaluate does and plan for the sequences of ``input_path`` (module docstring).
     ``pixels`` (int) / ``goal_pixels`` (float): [D, 2] for every sequence or [n, D, 2], one set per sequence - the designated-pixel
     cost, weighted ``pixel_weight`` (None: 1.0 with pixels, 0 without); ``frame_weight`` 0 with ``state_weight`` 0: the goal frame
@@ -541,11 +541,13 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
     from .train import model_kind
     if dna and cdna:
         raise ValueError('dna and cdna name two different generators')
+    if affine and (dna or cdna):
+        raise ValueError('affine and %s name two different generators' % ('dna' if dna else 'cdna'))
     if bn_stats not in ('batch', 'stored'):
         raise ValueError("bn_stats must be 'batch' or 'stored', got %r" % (bn_stats,))
     if weights not in ('raw', 'ema'):
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
-    transform = 'cdna' if cdna else dna
+    transform = 'affine' if affine else 'cdna' if cdna else dna
     goal_step = horizon if goal_step is None else goal_step
     pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, pixel_weight, model_kind(transform), img_size)
     checked = check_plan(candidates, horizon, elites, iterations, init_std, min_std, alpha, frame_weight=frame_weight,
@@ -617,8 +619,8 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            'num_masks': num_masks if trainer.model == 'cdna' else None,
-            'ksize': ksize if trainer.model != 'plain' else None,
+            'num_masks': num_masks if trainer.model in ('cdna', 'affine') else None,
+            'ksize': ksize if trainer.model in ('dna', 'cdna') else None,
             'sequences': len(per_seq),
             'share_not_worse_than_recorded': float(np.mean([s['cost'] <= s['recorded_cost'] for s in per_seq])),
             'settings': {'candidates': candidates, 'elites': elites, 'iterations': iterations, 'horizon': horizon, 'goal_step': int(goal_step),
@@ -743,7 +745,8 @@ def main(argv=None):
                           iterations=args.iterations, horizon=args.horizon, goal_step=goal_step, init_std=args.init_std,
                           min_std=args.min_std, alpha=args.alpha, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
                           num_sequences=args.num_sequences, seq_len=args.seq_len, dump=args.dump, pixels=pixels, goal_pixels=goal_pixels,
-                          pixel_weight=pixel_weight if pixels is not None else None, frame_weight=args.frame_weight)
+                          pixel_weight=pixel_weight if pixels is not None else None, frame_weight=args.frame_weight,
+                          **({'affine': True} if args.affine else {}))
 
 
 if __name__ == '__main__':

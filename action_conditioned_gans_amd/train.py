@@ -53,7 +53,10 @@ class Trainer:
         touch them), so this is the reference's arithmetic - one D step, then one G step (train.py:241-263) - with the two
         generator forward passes of an iteration sharing their launches at twice the GEMM height.
         ``arg_transform``: False - the plain generator; True or 'dna' - the DNA generator (the reference's ``--dna``); 'cdna' -
-        the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses.
+        the CDNA generator (models.build_generator_cdna, ``num_masks`` kernels of ``ksize``), trained with the DNA losses;
+        'affine' - the affine (STP) generator (models.build_generator_affine, ``num_masks`` 2x3 transforms; ``ksize`` is not
+        read), trained with the DNA losses as well.  What declines the CDNA generator declines it too: ``rollout_steps`` > 1 (no
+        image gradient) and ``pixel_maps`` (no map advection through the warps).
         ``rollout_steps`` K > 1 (no reference counterpart): also builds the K-step G programs of ``train_g_rollout`` /
         ``pretrain_g_rollout`` - the generator trained through its own rollout (see there).  DNA or plain generator, float32,
         one rank; K = 1 builds nothing more.
@@ -90,7 +93,7 @@ class Trainer:
         the argument; else 1 <= Z <= 64): the generator reads [action, z] with z ~ N(0, 1) [B, Z] drawn on the device inside the
         step's program (ops.append_noise, acg_noise_concat: Philox4x32-10 + Box-Muller from the graph state ``g/noise/state`` =
         {``noise_seed``, counter}, which the kernel advances - a replayed HIP graph draws fresh values with no host in the loop).
-        ``g/tconv1`` (and ``g/cdna_params`` of the CDNA generator) get Z more input channels, drawn by their own initialiser; the
+        ``g/tconv1`` (and ``g/cdna_params`` / ``g/affine_params`` of the CDNA / affine generator) get Z more input channels, drawn by their own initialiser; the
         discriminator keeps the 10-dim action.  Every generator pass draws a fresh z: ``pretrain_g``, ``train_g``, the G pass
         inside ``train_d`` and ``test``; ``last_noise()`` returns the values of the last one.  ``test`` / ``test_sequence`` /
         ``rollout_metrics`` take ``noise='zero'`` (default: z = 0, a deterministic prediction; the counter advances all the same)
@@ -211,6 +214,8 @@ class Trainer:
             if self.noise_dim:
                 O.noise_state(noise_seed)
                 actions = self._noise = O.append_noise(actions, self.noise_dim)
+            if self.model == 'affine':
+                return M.build_generator_affine(images, actions, batch_size=batch, num_masks=num_masks, reuse=reuse)
             if self.model == 'cdna':
                 return M.build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse)
             if arg_transform:
@@ -934,11 +939,11 @@ class Trainer:
 
 
 def model_kind(arg_transform):
-    """The generator an ``arg_transform`` names: 'plain' (False), 'dna' (True or 'dna') or 'cdna'."""
+    """The generator an ``arg_transform`` names: 'plain' (False), 'dna' (True or 'dna'), 'cdna' or 'affine'."""
     if isinstance(arg_transform, str):
-        if arg_transform in ('dna', 'cdna'):
+        if arg_transform in ('dna', 'cdna', 'affine'):
             return arg_transform
-        raise ValueError("unexpected transform argument %r (False, True / 'dna' or 'cdna')" % arg_transform)
+        raise ValueError("unexpected transform argument %r (False, True / 'dna', 'cdna' or 'affine')" % arg_transform)
     return 'dna' if arg_transform else 'plain'
 
 
@@ -1112,6 +1117,9 @@ def check_pixel_maps(pixel_maps, model):
         raise ValueError('pixel_maps %d: the CDNA generator is declined - its channel split, kept as written from the reference, '
                          'transforms the colour channels of one mask with different kernels, so there is no single flow that a map '
                          'could follow consistently with the frame (DNA generator only)' % pixel_maps)
+    if pixel_maps and model == 'affine':
+        raise ValueError('pixel_maps %d: the affine generator is declined - there is no map advection through its warps (DNA '
+                         'generator only)' % pixel_maps)
     return int(pixel_maps)
 
 
@@ -1124,6 +1132,8 @@ def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
     if k > 1:
         if model == 'cdna':
             raise ValueError('rollout_steps > 1: the CDNA composite has no image gradient (train the DNA or the plain generator)')
+        if model == 'affine':
+            raise ValueError('rollout_steps > 1: the affine composite has no image gradient (train the DNA or the plain generator)')
         if bf16:
             raise ValueError('rollout_steps > 1 is float32 only (dtype bf16)')
         if data_parallel:
@@ -1567,19 +1577,27 @@ def _flag(v):
 
 
 def add_model_args(parser):
-    """The generator flags shared by this CLI and evaluate's: --dna (the reference's), --cdna and --num_masks."""
+    """The generator flags shared by this CLI and evaluate's: --dna (the reference's), --cdna, --affine and --num_masks."""
     parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
     parser.add_argument('--cdna', nargs='?', const=True, default=False, type=_flag,
                         help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7')
-    parser.add_argument('--num_masks', type=int, default=10, help='CDNA kernels / masks (1..32)')
+    parser.add_argument('--affine', nargs='?', const=True, default=False, type=_flag,
+                        help='the affine (STP) generator (models.build_generator_affine): float32, --ksize is not read')
+    parser.add_argument('--num_masks', type=int, default=10, help='CDNA kernels / affine transforms, and their masks (1..32)')
 
 
 def check_model_args(parser, args):
     """parser.error for generator flags that do not go together (before anything is created); -> Trainer's arg_transform."""
     if args.dna and args.cdna:
         parser.error('--dna and --cdna name two different generators')
+    if args.affine and (args.dna or args.cdna):
+        parser.error('--affine and --%s name two different generators' % ('dna' if args.dna else 'cdna'))
     if not 1 <= args.num_masks <= 32:
         parser.error('--num_masks must be in 1..32')
+    if args.affine:
+        if args.dtype == 'bf16':
+            parser.error('the affine generator is float32 only (--dtype bf16)')
+        return 'affine'
     if args.cdna:
         if args.dtype == 'bf16':
             parser.error('the CDNA generator is float32 only (--dtype bf16)')
@@ -1600,6 +1618,8 @@ def check_rollout_args(parser, args):
         parser.error('--rollout_steps %d needs sequences of more than %d frames (--seq_len %d)' % (k, k, args.seq_len))
     if args.cdna:
         parser.error('--rollout_steps > 1 does not train the CDNA generator (its composite has no image gradient)')
+    if args.affine:
+        parser.error('--rollout_steps > 1 does not train the affine generator (its composite has no image gradient)')
     if args.dtype == 'bf16':
         parser.error('--rollout_steps > 1 is float32 only (--dtype bf16)')
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -1757,7 +1777,7 @@ def main(argv=None):
         torch.cuda.set_device(local_rank)
         torch.distributed.init_process_group('gloo')
     # every other flag is a keyword of train() under its own name, but for these four
-    options = {k: v for k, v in vars(args).items() if k not in ('input_path', 'output_path', 'adv', 'loss', 'opt', 'dna', 'cdna')}
+    options = {k: v for k, v in vars(args).items() if k not in ('input_path', 'output_path', 'adv', 'loss', 'opt', 'dna', 'cdna', 'affine')}
     for flag, keyword in (('g_ema', 'ema_decay'), ('log_grad_norms', 'grad_norms'), ('lr_decay_iters', 'lr_decay_steps'),
                           ('ss_decay_iters', 'ss_decay_steps'), ('d_noise_decay_iters', 'd_noise_decay_steps'), ('log_d_stats', 'd_stats')):
         options[keyword] = options.pop(flag)

@@ -48,6 +48,49 @@ int32_t acg_cdna_composite_bwd(const float* params, const float* kern_norm, cons
                                int32_t masks, int32_t ksize, float relu_shift, void* workspace, size_t workspace_bytes,
                                acg_stream_t stream);
 
+/*
+ * The affine composite: the output stage of the affine (STP) generator.  Each of the M masks moves the image by a 2x3 affine
+ * transform, sampled bilinearly (a "spatial transformer"); the composite and the mask stage are those above.
+ *
+ * Definitions (B samples of H x W, C colours, M masks; 1 <= C <= 4, 1 <= M <= 32, H, W >= 2; float32, NHWC):
+ *   params [B, M*6]   read as [B, M, 6]; theta = params + (1, 0, 0, 0, 1, 0), so zero parameters are the identity;
+ *   for output pixel (y, x):  u = 2x/(W-1) - 1, v = 2y/(H-1) - 1;
+ *                             xs = t0*u + t1*v + t2, ys = t3*u + t4*v + t5;
+ *                             px = (xs+1)(W-1)/2, py = (ys+1)(H-1)/2;
+ *                             x0 = floor(px), fx = px - x0; y0 = floor(py), fy = py - y0;
+ *   T_m(y, x, c)      = sum over the 4 taps (x0+dx, y0+dy), dx, dy in {0, 1}, of wx*wy*image(tap, c), wx = fx for dx = 1 and
+ *                       1-fx for dx = 0, wy likewise from fy; a tap outside [0, W-1] x [0, H-1] contributes 0 (the zeros
+ *                       that SAME padding gives the kernels above).  This is grid_sample(image, affine_grid(theta,
+ *                       align_corners), bilinear, zeros, align_corners);
+ *   s                 = softmax(mask_logits + mask_bias) over the M+1 channels;
+ *   out [B, H, W, C]  = s_0 * image + sum_m s_{m+1} * T_m.
+ * Gradients: dmask_logits and dmask_bias as above with g_0 = <dout, image>, g_{m+1} = <dout, T_m>;
+ *   dparams[b, m, :]  = sum over pixels of s_{m+1} * (a*u, a*v, a, b*u, b*v, b), a = <dout, dT_m/dpx>*(W-1)/2,
+ *                       b = <dout, dT_m/dpy>*(H-1)/2, the derivative taken in the cell floor selects (one-sided at a
+ *                       coordinate that is exactly an integer).  No image gradient.
+ * px, py are range-checked in float before any conversion to int: unless -1 < px < W and -1 < py < H the piece and its
+ * gradient are 0, for NaN / Inf parameters too.
+ * Conventions as for acg_cdna_composite_*: NULL mask_bias = zero, dmask_bias may be NULL, the same accumulate, image_pitch 0
+ * or C..64, ACG_ERR_UNSUPPORTED and a workspace of 0 for an unsupported geometry.
+ */
+
+/* Bytes of workspace acg_affine_composite_bwd needs (0 for an unsupported geometry). */
+size_t acg_affine_composite_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks);
+
+/* out as defined above.  One launch. */
+int32_t acg_affine_composite_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                 int32_t image_pitch, float* out, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks,
+                                 acg_stream_t stream);
+
+/* dparams [B, M*6], dmask_logits [B, H, W, M+1] and dmask_bias [M+1] (may be NULL; = (accumulate != 0 ? accumulate *
+ * dmask_bias : 0) + sum over pixels of dz) from dout [B, H, W, C].  The warps are recomputed.  Two launches: a per-tile pass
+ * that writes dmask_logits and per-(sample, tile) partials into the workspace, and a final pass that sums the partials in
+ * tile order.  No atomics: the same call gives the same bits. */
+int32_t acg_affine_composite_bwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                 int32_t image_pitch, const float* dout, float* dparams, float* dmask_logits, float* dmask_bias,
+                                 float dmask_bias_accumulate, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks,
+                                 void* workspace, size_t workspace_bytes, acg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
