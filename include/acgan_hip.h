@@ -383,7 +383,9 @@ int32_t acg_bias_act_bwd(const void* y, const void* dy, void* dx, float* dbias, 
  * `bias` (float32 [k*k], may be NULL) folds in the bias of the layer that produces the logits - g/tconv4 has neither
  * BatchNorm nor activation (models.py:54-59) - i.e. the kernels take softmax(logits + bias) and backward also yields
  *   dbias = dbias_accumulate * dbias + sum over pixels of dlogits      (dbias may be NULL; workspace needed otherwise).
- * dtype: storage of logits / dlogits; ACG_BF16 rows are round8(k*k) elements apart (pad taps are not written).
+ * dtype: storage of logits / dlogits; ACG_BF16 rows are round8(k*k) elements apart.  A
+ * pad tap of dlogits is either left alone or set to zero (k < 6: the rest of the last group of 4 taps; k >= 6: tap k*k when k*k is
+ * odd), never anything else - a caller that wants them zero zero-initialises dlogits once.
  * image, out and dout are float32.
  * out2 / dout2 (may be NULL): the frame's second home.  train.py:63-66 feeds D concat(current frame, generated frame):
  * forward ALSO writes the frame into channels [out2_offset, out2_offset + c) of out2 - a tensor of out2_dtype (ACG_F32 /

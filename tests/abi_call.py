@@ -648,20 +648,23 @@ class Abi:
         return dpar, dimg
 
     # ---- dna
-    def dna_fwd(self, logits, img, k, bias=None, out2=None, out2_off=0):
+    def dna_fwd(self, logits, img, k, bias=None, out2=None, out2_off=0, out=None):
         """logits float32 [B,H,W,k*k] or bfloat16 [B,H,W,round8(k*k)].  ``out2`` [B,H,W,pitch] (float32 / bfloat16): the frame is
-        also written into its channels [out2_off, out2_off + C)."""
+        also written into its channels [out2_off, out2_off + C).  ``out``: the frame's tensor as the caller prepared it (else a
+        fresh one)."""
         b, h, w, c = img.shape
-        out = torch.empty_like(img)
+        if out is None:
+            out = torch.empty_like(img)
         self.lib.dna_fwd(_p(logits), _p(bias), _p(img), _p(out), _p(out2), out2.shape[-1] if out2 is not None else 0, out2_off,
                          L.code(out2.dtype) if out2 is not None else 0, b, h, w, c, k, L.code(logits.dtype), self.stream())
         return out
 
-    def dna_bwd(self, logits, img, dout, k, bias=None, want_dbias=False, dout2=None, dout2_off=0, dbias=None, accumulate=0.0):
+    def dna_bwd(self, logits, img, dout, k, bias=None, want_dbias=False, dout2=None, dout2_off=0, dbias=None, accumulate=0.0, dlogits=None):
         """``dout2`` [B,H,W,pitch]: its channels [dout2_off, dout2_off + C) are added to dout.  ``dbias`` with ``accumulate``:
-        dbias = accumulate * dbias + the tap sums (in place; implies want_dbias)."""
+        dbias = accumulate * dbias + the tap sums (in place; implies want_dbias).  ``dlogits``: the gradient's tensor as the
+        caller prepared it (else zeros shaped like logits)."""
         b, h, w, c = img.shape
-        dl = torch.zeros_like(logits)
+        dl = torch.zeros_like(logits) if dlogits is None else dlogits
         want_dbias = want_dbias or dbias is not None
         if want_dbias and dbias is None:
             dbias = self.empty(k * k)

@@ -520,8 +520,10 @@ def case_bias_accumulate(abi, tol):
 
 
 # (B, H, W, C, k, partial rows): both kernel families (k < 6: 64 x 4 pixel tiles; k >= 6: one block per 64 pixels of a row) on both
-# sides of the 1024 partial rows from which dna_bwd sums dbias in two stages
-DNA_ACC_SHAPES = [(2, 7, 5, 3, 5, 4), (130, 32, 3, 3, 5, 1040), (1, 9, 70, 3, 7, 18), (50, 21, 5, 1, 6, 1050)]
+# sides of the 1024 partial rows from which dna_bwd sums dbias in two stages, and the switch point itself: 1024 rows are the last
+# one-stage launch, 1025 the first two-stage one (33 rows per segment: the last of the 32 segments holds 2)
+DNA_ACC_SHAPES = [(2, 7, 5, 3, 5, 4), (130, 32, 3, 3, 5, 1040), (1, 9, 70, 3, 7, 18), (50, 21, 5, 1, 6, 1050),
+                  (16, 64, 3, 1, 6, 1024), (25, 41, 2, 1, 7, 1025)]
 
 
 def case_dna_accumulate(abi, shape, tol, half):
