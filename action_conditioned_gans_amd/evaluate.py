@@ -206,10 +206,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     ``weights``: 'raw' or 'ema' (module docstring); 'ema' on a checkpoint without an average is a ValueError.
     ``noise_dim`` / ``noise`` ('zero' or 'sample') / ``noise_samples`` / ``noise_seed``: the module docstring.
     -> the metrics dict."""
-    if dna and cdna:
-        raise ValueError('dna and cdna name two different generators')
-    if affine and (dna or cdna):
-        raise ValueError('affine and %s name two different generators' % ('dna' if dna else 'cdna'))
+    from . import models as M
+    transform = M.transform_argument(dict(dna=dna, cdna=cdna, affine=affine))
     if bn_stats not in ('batch', 'stored', 'calibrate'):
         raise ValueError("bn_stats must be 'batch', 'stored' or 'calibrate', got %r" % (bn_stats,))
     if weights not in ('raw', 'ema'):
@@ -225,7 +223,6 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     if int(noise_samples) < 1 or (noise == 'zero' and int(noise_samples) != 1):
         raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' (got %r)" % (noise_samples,))
     n_draws = int(noise_samples)
-    transform = 'affine' if affine else 'cdna' if cdna else dna
     from .metrics import SSIM_DEFINITION
     from .saver import latest_checkpoint
     from .util import save_samples
@@ -286,8 +283,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            'num_masks': num_masks if trainer.model in ('cdna', 'affine') else None,
-            'ksize': ksize if trainer.model in ('dna', 'cdna') else None,
+            **M.KINDS[trainer.model].result_fields(ksize, num_masks),
             'sequences': n_seq,
             'steps': int(steps),
             'ssim_definition': SSIM_DEFINITION + ' (data_range 2 for frames in [-1, 1])',
@@ -365,6 +361,7 @@ def main(argv=None):
     parser.add_argument('input', type=str, help="frames .npy [N,T,H,W,3], push TFRecord directory, or 'synthetic'")
     parser.add_argument('output', type=str)
     parser.add_argument('--actions', type=str, default=None, help='actions .npy [N,T,10] (with a frames .npy)')
+    from . import models as M
     from .train import add_model_args, check_model_args
     add_model_args(parser)
     parser.add_argument('--ksize', type=int, default=5)
@@ -421,12 +418,12 @@ def main(argv=None):
             parser.error('%s: expected actions [N, T, %d], got %s' % (args.actions, ACTION_DIM, actions.shape))
         if actions.shape[:2] != frames.shape[:2]:
             parser.error('frames %s and actions %s disagree in N or T' % (frames.shape[:2], actions.shape[:2]))
-    return evaluate(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, ksize=args.ksize,
+    return evaluate(args.model_path, args.input, args.output, actions_path=args.actions, ksize=args.ksize,
                     img_size=args.img_size, dtype=args.dtype, batch_size=args.batch_size, seq_len=args.seq_len,
                     num_sequences=args.num_sequences, samples=args.samples, gif=args.gif, dump=args.dump, device=args.device,
-                    cdna=args.cdna, num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
+                    num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
                     calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions,
-                    **({'weights': args.weights} if args.weights != 'raw' else {}), **({'affine': True} if args.affine else {}),
+                    **({'weights': args.weights} if args.weights != 'raw' else {}), **{flag: getattr(args, flag) for flag in M.flags()},
                     **({'noise_dim': args.noise_dim, 'noise': args.noise, 'noise_samples': args.noise_samples, 'noise_seed': args.noise_seed}
                        if args.noise_dim else {}))
 

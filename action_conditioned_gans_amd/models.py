@@ -14,6 +14,8 @@ Deviations from the reference text, which does not run as committed (SURVEY sect
 with 16-byte loads.  Actions may be given as ``[B, A]`` (tiled and concatenated in one fused op) or already tiled
 ``[B, h, w, A]`` as the reference Trainer passes them (train.py:48-50).
 """
+import typing
+
 from . import graph as G
 from . import ops as O
 
@@ -54,32 +56,39 @@ def build_generator(images, actions, reuse=False):
         return O.deconv2d(net, images.shape[3], [5, 5], activation_fn=O.tanh, normalizer_fn=None, scope='tconv4')
 
 
+def _check_images(images, batch_size, color_channels):
+    if batch_size is not None and batch_size != images.shape[0]:
+        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
+    if images.shape[3] != color_channels:
+        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
+
+
+def _state_head(net):
+    """The 5-d next state from the decoder's 16x16 features.  It reads nothing of what the frame decoder does next: a side chain
+    (five tiny latency-bound layers that hide behind tconv3 / tconv4 / the frame's last op, forward and backward)."""
+    with G.get_default_graph().side_branch():
+        state = _stack(net, G_DNA['state'], O.conv2d, size=3)
+        sk = state.shape[1]           # 4 at 64x64: the reference's 4x4 VALID head (models.py:44-51)
+        state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
+                         scope='sconv5')
+        return O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
+
+
 def build_generator_transform(images, actions, batch_size=None, reuse=False, color_channels=3, ksize=5):
     """DNA generator (models.py:24-74): predicts k*k per-pixel kernel logits and a 5-d next state.
 
     Returns ``(frame, state)``; ``batch_size`` is accepted for signature compatibility (the static
     shape already carries it).
     """
-    if batch_size is not None and batch_size != images.shape[0]:
-        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
-    if images.shape[3] != color_channels:
-        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
+    _check_images(images, batch_size, color_channels)
+    KINDS['dna'].check_args(ksize, None)
     with O.variable_scope('g', reuse=reuse), \
             O.arg_scope([O.conv2d, O.deconv2d], activation_fn=O.relu, stride=2, padding='SAME',
                         normalizer_fn=O.batch_norm, reuse=reuse):
         net = _stack(getattr(images, 'padded', images), G_DNA['encoder'], O.conv2d)
         net = _with_actions(net, actions, 'actions')
         net = _stack(net, G_DNA['decoder_a'], O.deconv2d)
-
-        # the state head reads the decoder's 16x16 features and nothing of what the frame decoder does next: a side chain
-        # (five tiny latency-bound layers that hide behind tconv3 / tconv4 / the DNA gather, forward and backward)
-        with G.get_default_graph().side_branch():
-            state = _stack(net, G_DNA['state'], O.conv2d, size=3)
-            sk = state.shape[1]           # 4 at 64x64: the reference's 4x4 VALID head (models.py:44-51)
-            state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
-                             scope='sconv5')
-            state = O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
-
+        state = _state_head(net)
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
         logits = O.deconv2d(net, ksize * ksize, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
         frame = O.dna_gather(logits, images, ksize)
@@ -100,23 +109,21 @@ def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_ch
     Two differences from the CDNA model of the paper the push dataset comes from: there is no image generated from
     scratch among the composited candidates, and the masks come from the 5x5/2 ``tconv4`` instead of a 1x1 layer.
     float32 only; ``ksize`` 3, 5 or 7, 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
-    if batch_size is not None and batch_size != images.shape[0]:
-        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
-    if images.shape[3] != color_channels:
-        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
-    if ksize not in (3, 5, 7) or not 1 <= num_masks <= 32:
-        raise ValueError('CDNA generator: ksize must be 3, 5 or 7 and num_masks 1..32 (got %r, %r)' % (ksize, num_masks))
-    if images.shape[1] % 16 or images.shape[2] % 16:
-        raise ValueError('CDNA generator: image size %s is not a multiple of 16' % (images.shape[1:3],))
-    if O.half_mode():
-        raise NotImplementedError('the CDNA generator is float32 only')
-    return _mask_generator(images, actions, reuse, 'cdna_params', ksize * ksize * num_masks, num_masks,
+    return _mask_generator(KINDS['cdna'], images, actions, batch_size, reuse, color_channels, ksize, num_masks,
+                           'cdna_params', ksize * ksize * num_masks,
                            lambda logits, params: O.cdna_composite(logits, images, params, num_masks, ksize))
 
 
-def _mask_generator(images, actions, reuse, scope, width, num_masks, composite):
-    """The trunk the CDNA and the affine generators share: the DNA generator's layers, a linear layer ``scope`` of ``width``
-    outputs per sample on the action-conditioned bottleneck, tconv4 to M+1 mask logits and ``composite(logits, params)``."""
+def _mask_generator(kind, images, actions, batch_size, reuse, color_channels, ksize, num_masks, scope, width, composite):
+    """The CDNA and the affine generators: what generator ``kind`` does not take is refused before anything is created; then
+    the DNA generator's layers, a linear layer ``scope`` of ``width`` outputs per sample on the action-conditioned bottleneck,
+    tconv4 to M+1 mask logits and ``composite(logits, params)``."""
+    _check_images(images, batch_size, color_channels)
+    kind.check_args(ksize, num_masks)
+    if images.shape[1] % 16 or images.shape[2] % 16:
+        raise ValueError('%s generator: image size %s is not a multiple of 16' % (kind.label, images.shape[1:3]))
+    if kind.float32_only and O.half_mode():
+        raise NotImplementedError('the %s generator is float32 only' % kind.label)
     with O.variable_scope('g', reuse=reuse), \
             O.arg_scope([O.conv2d, O.deconv2d], activation_fn=O.relu, stride=2, padding='SAME',
                         normalizer_fn=O.batch_norm, reuse=reuse):
@@ -126,12 +133,7 @@ def _mask_generator(images, actions, reuse, scope, width, num_masks, composite):
                           normalizer_fn=None, scope=scope)
         params = params.reshape((images.shape[0], width))
         net = _stack(net, G_DNA['decoder_a'], O.deconv2d)
-        with G.get_default_graph().side_branch():
-            state = _stack(net, G_DNA['state'], O.conv2d, size=3)
-            sk = state.shape[1]
-            state = O.conv2d(state, 5, [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None,
-                             scope='sconv5')
-            state = O.squeeze(state, axis=(1, 2))       # [B, 1, 1, 5] -> [B, 5], also at B = 1
+        state = _state_head(net)
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
         logits = O.deconv2d(net, num_masks + 1, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
         return composite(logits, params), state
@@ -148,17 +150,8 @@ def build_generator_affine(images, actions, batch_size=None, reuse=False, color_
     an object take 6 numbers here; the k x k kernels of DNA / CDNA cannot move anything further than (k-1)/2 pixels.
     As for CDNA there is no image generated from scratch among the candidates and the masks come from the 5x5/2 ``tconv4``.
     float32 only; 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
-    if batch_size is not None and batch_size != images.shape[0]:
-        raise ValueError('batch_size %r does not match images %s' % (batch_size, images.shape))
-    if images.shape[3] != color_channels:
-        raise ValueError('color_channels %r does not match images %s' % (color_channels, images.shape))
-    if not 1 <= num_masks <= 32:
-        raise ValueError('affine generator: num_masks must be in 1..32 (got %r)' % (num_masks,))
-    if images.shape[1] % 16 or images.shape[2] % 16:
-        raise ValueError('affine generator: image size %s is not a multiple of 16' % (images.shape[1:3],))
-    if O.half_mode():
-        raise NotImplementedError('the affine generator is float32 only')
-    return _mask_generator(images, actions, reuse, 'affine_params', 6 * num_masks, num_masks,
+    return _mask_generator(KINDS['affine'], images, actions, batch_size, reuse, color_channels, None, num_masks,
+                           'affine_params', 6 * num_masks,
                            lambda logits, params: O.affine_composite(logits, images, params, num_masks))
 
 
@@ -174,3 +167,87 @@ def build_discriminator(inputs, actions, reuse=False):
         net = _with_actions(net, actions, 'actions')
         net = _stack(net, D_NET['post'], O.conv2d)
         return O.conv2d(net, 1, [2, 2], activation_fn=None, stride=1, scope='conv6')
+
+
+# ================================================================================================
+# the generator kinds
+# ================================================================================================
+NUM_MASKS = range(1, 33)
+
+
+class Kind(typing.NamedTuple):
+    """What the layers above the builders know about one generator.  train.Trainer, the checks of train / evaluate / plan and
+    their CLIs read these records and compare no names: a new generator is one more record in KINDS, a new capability of an
+    existing one is a changed field."""
+    name: str                    # what Trainer.model, metrics.json and plan.json call it, and the string arg_transform that names it
+    label: str                   # what messages call it
+    build: object                # (images, actions, batch, reuse, ksize, num_masks) -> (frame, state or None)
+    ksizes: tuple = None         # the ``ksize`` values it takes (None: it does not read ksize) ...
+    ksize_text: str = None       # ... and the same in words
+    num_masks: bool = False      # whether it reads ``num_masks`` (one of NUM_MASKS)
+    float32_only: bool = False
+    state_head: bool = True      # whether it predicts the next state beside the frame
+    no_rollout: str = None       # why rollout_steps > 1 cannot train it (None: it can)
+    no_maps: str = None          # why designated-pixel maps (pixel_maps) cannot follow it (None: they can)
+    flag: str = None             # its CLI flag, which is also its keyword of evaluate.evaluate / plan.plan_sequences (None: the default)
+    help: str = None
+
+    def check_args(self, ksize, num_masks):
+        """ValueError for a ``ksize`` / ``num_masks`` that this generator reads and does not take."""
+        if self.ksizes is not None and ksize not in self.ksizes:
+            raise ValueError('%s generator: ksize must be %s (got %r)' % (self.label, self.ksize_text, ksize))
+        if self.num_masks and num_masks not in NUM_MASKS:
+            raise ValueError('%s generator: num_masks must be in 1..32 (got %r)' % (self.label, num_masks))
+
+    def result_fields(self, ksize, num_masks):
+        """The 'num_masks' / 'ksize' entries of metrics.json and plan.json: None for what this generator does not read."""
+        return {'num_masks': num_masks if self.num_masks else None, 'ksize': ksize if self.ksizes is not None else None}
+
+
+_NO_IMAGE_GRADIENT = 'its composite has no image gradient: train the DNA or the plain generator'
+KINDS = {kind.name: kind for kind in (
+    Kind('plain', 'plain', lambda images, actions, batch, reuse, ksize, num_masks: (build_generator(images, actions, reuse=reuse), None),
+         state_head=False, no_maps='the plain generator predicts no flow a map could follow (DNA generator only)'),
+    Kind('dna', 'DNA', lambda images, actions, batch, reuse, ksize, num_masks:
+         build_generator_transform(images, actions, batch_size=batch, ksize=ksize, reuse=reuse),
+         ksizes=tuple(range(1, 12)), ksize_text='in 1..11', flag='dna'),
+    Kind('cdna', 'CDNA', lambda images, actions, batch, reuse, ksize, num_masks:
+         build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse),
+         ksizes=(3, 5, 7), ksize_text='3, 5 or 7', num_masks=True, float32_only=True, no_rollout=_NO_IMAGE_GRADIENT,
+         no_maps='the CDNA generator is declined - its channel split, kept as written from the reference, transforms the colour '
+                 'channels of one mask with different kernels, so there is no single flow that a map could follow consistently '
+                 'with the frame (DNA generator only)',
+         flag='cdna', help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7'),
+    Kind('affine', 'affine', lambda images, actions, batch, reuse, ksize, num_masks:
+         build_generator_affine(images, actions, batch_size=batch, num_masks=num_masks, reuse=reuse),
+         num_masks=True, float32_only=True, no_rollout=_NO_IMAGE_GRADIENT,
+         no_maps='the affine generator is declined - there is no map advection through its warps (DNA generator only)',
+         flag='affine', help='the affine (STP) generator (models.build_generator_affine): float32, --ksize is not read'),
+)}
+BOOLEAN = {False: 'plain', True: 'dna'}        # the reference's arg_transform is its boolean --dna: these two kinds keep it
+
+
+def model_kind(arg_transform):
+    """The name in KINDS of the generator an ``arg_transform`` names: that name itself, or the reference's boolean ``--dna``
+    (False: 'plain', True: 'dna')."""
+    if isinstance(arg_transform, str):
+        if arg_transform in KINDS:
+            return arg_transform
+        raise ValueError('unexpected transform argument %r (False, True or one of %s)' % (arg_transform, ', '.join(map(repr, KINDS))))
+    return BOOLEAN[bool(arg_transform)]
+
+
+def flags():
+    """The CLI flags that name a generator (the keywords of evaluate.evaluate / plan.plan_sequences that do)."""
+    return [kind.flag for kind in KINDS.values() if kind.flag]
+
+
+def transform_argument(given, fmt='%s'):
+    """The Trainer's arg_transform for the generator flags ``given`` {flag: value, ...; other keys are ignored}: the name of the
+    generator whose flag is set, the boolean for the reference's ``--dna``, False without one.  Two set flags are a ValueError
+    that names them through ``fmt`` ('--%s' for a CLI)."""
+    named = [kind for kind in KINDS.values() if kind.flag and given.get(kind.flag)]
+    if len(named) > 1:
+        raise ValueError('%s and %s name two different generators' % (fmt % named[0].flag, fmt % named[1].flag))
+    name = named[0].name if named else BOOLEAN[False]
+    return next((b for b, n in BOOLEAN.items() if n == name), name)

@@ -852,6 +852,15 @@ class BiasActBwdOp(G.Op):
         return lambda s: fn(*args, s)
 
 
+def _window_args(window):
+    """The (pointer, channel pitch, channel offset, dtype code) a DNA entry takes for a second, pitched tensor it writes the frame
+    into or reads more of ``dout`` from: ``window`` is (tensor, channel offset), or None - the entry's "no such tensor"."""
+    if window is None:
+        return None, 0, 0, 0
+    t, off = window
+    return _p(t.buf), t.shape[-1], off, _code(t)
+
+
 class DnaOp(G.Op):
     """softmax(logits + bias) and the k x k gather in one kernel; ``bias`` (may be None) is the bias variable of the
     layer that produced the logits, folded in here instead of a pass of its own over the logits tensor."""
@@ -868,11 +877,9 @@ class DnaOp(G.Op):
         lg, img = self.inputs[:2]
         b, h, w, c = img.shape
         pb = _p(self.inputs[2].buf) if self.has_bias else None
-        p2, pitch2, off2, dt2 = None, 0, 0, 0
-        if self.second is not None and id(self.second[0]) in rt.program_ops:      # only where someone reads that tensor
-            _, y2, off2 = self.second
-            p2, pitch2, dt2 = _p(y2.buf), y2.shape[-1], _code(y2)
-        args = (_p(lg.buf), pb, _p(img.buf), _p(self.outputs[0].buf), p2, pitch2, off2, dt2, b, h, w, c, self.ksize, _code(lg))
+        home2 = self.second is not None and id(self.second[0]) in rt.program_ops      # only where someone reads that tensor
+        args = (_p(lg.buf), pb, _p(img.buf), _p(self.outputs[0].buf), *_window_args(self.second[1:] if home2 else None),
+                b, h, w, c, self.ksize, _code(lg))
         fn = rt.lib.dna_fwd
         return lambda s: fn(*args, s)
 
@@ -920,11 +927,7 @@ class DnaBwdOp(G.Op):
         pb = _p(self.inputs[3].buf) if self.fwd.has_bias else None
         ws, n = rt.workspace(rt.lib.dna_workspace_bytes(b, h, w, self.fwd.ksize)) if self.dbias is not None else (None, 0)
         self._keep = ws
-        p2, pitch2, off2, dt2 = None, 0, 0, 0
-        if self.dout2 is not None:
-            t2, off2 = self.dout2
-            p2, pitch2, dt2 = _p(t2.buf), t2.shape[-1], _code(t2)
-        args = (_p(lg.buf), pb, _p(img.buf), _p(dout.buf), p2, pitch2, off2, dt2, _p(self.outputs[0].buf),
+        args = (_p(lg.buf), pb, _p(img.buf), _p(dout.buf), *_window_args(self.dout2), _p(self.outputs[0].buf),
                 _p(self.dbias.buf) if self.dbias is not None else None,
                 self.accumulate, b, h, w, c, self.fwd.ksize, _code(lg), _p(ws) if ws is not None else None, n)
         fn = rt.lib.dna_bwd
@@ -947,11 +950,7 @@ class DnaImageGradOp(G.Op):
         b, h, w, c = self.outputs[0].shape
         fn = _lib.entry(rt.lib, 'dna_bwd_image')
         pb = _p(self.inputs[2].buf) if self.fwd.has_bias else None
-        p2, pitch2, off2, dt2 = None, 0, 0, 0
-        if self.dout2 is not None:
-            t2, off2 = self.dout2
-            p2, pitch2, dt2 = _p(t2.buf), t2.shape[-1], _code(t2)
-        args = (_p(lg.buf), pb, _p(dout.buf), p2, pitch2, off2, dt2, _p(self.outputs[0].buf), 0.0, b, h, w, c, self.fwd.ksize, _code(lg))
+        args = (_p(lg.buf), pb, _p(dout.buf), *_window_args(self.dout2), _p(self.outputs[0].buf), 0.0, b, h, w, c, self.fwd.ksize, _code(lg))
         return lambda s: fn(*args, s)
 
 
@@ -1015,127 +1014,87 @@ class CdnaBwdOp(G.Op):
         return launch
 
 
-class CdnaCompositeOp(G.Op):
-    """The CDNA generator's output stage in one kernel (acg_cdna_composite_fwd): normalise the per-sample kernels ``params``,
-    transform the image with each (cdna_transformation's M pieces, kept in registers) and composite s_0 * image +
-    sum_j s_{j+1} * T_j under s = softmax(logits + bias) over the M + 1 mask channels.  ``bias`` (may be None) is the bias
-    variable of the layer that produced the logits, folded in as DnaOp does.  Outputs: the frame, and the normalised kernels
-    the backward pass reads."""
+class MaskCompositeOp(G.Op):
+    """The output stage of a generator that moves the image M ways, in one kernel (acg_<entry>_fwd): s_0 * image +
+    sum_m s_{m+1} * T_m under s = softmax(logits + bias) over the M + 1 mask channels, T_m the image moved as the m-th part of
+    ``params`` says (the M moved images stay in registers).  ``bias`` (may be None) is the bias variable of the layer that
+    produced the logits, folded in as DnaOp does.  A variant names its ``entry`` prefix and passes the ``scalars`` its entries
+    take behind the mask count (the first ``ws_scalars`` of them size the backward's workspace) and, as ``saved``, the
+    (name suffix, width per sample) of what its forward leaves for its backward.  Outputs: the frame, then the saved ones."""
+    entry, ws_scalars = None, 0
+
+    def __init__(self, logits, image, params, masks, name, scalars=(), saved=(), bias=None):
+        self.masks, self.scalars = int(masks), tuple(scalars)
+        self.has_bias = bias is not None
+        self.saved = [_new((image.shape[0], width), name + suffix) for suffix, width in saved]
+        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
+                         [_new(image.shape, name + ':0')] + self.saved)
+
+    def bind(self, rt):
+        lg, img, par = self.inputs[:3]
+        b, h, w, c = img.shape
+        fn = _lib.entry(rt.lib, self.entry + '_fwd')
+        pb = _p(self.inputs[3].buf) if self.has_bias else None
+        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), *[_p(t.buf) for t in self.saved], b, h, w, c,
+                self.masks, *self.scalars)
+        return lambda s: fn(*args, s)
+
+    def grad(self, gouts, needs, ctx):
+        if needs[1]:
+            raise NotImplementedError('%s: gradient w.r.t. the image is not implemented (the image is a network '
+                                      'input, train.py:53-54)' % self.entry)
+        dst, acc = (None, 0.0)
+        if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
+            dst, acc = ctx.slot(self.inputs[3])
+        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
+            return [None] * len(self.inputs)
+        op = MaskCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
+        if dst is not None:
+            ctx.wrote(self.inputs[3], op)
+        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
+
+
+class MaskCompositeBwdOp(G.Op):
+    """acg_<entry>_bwd: d logits, d params and, into the bias variable's gradient window, d bias."""
+
+    def __init__(self, fwd, dout, dbias_dst, accumulate, name):
+        self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
+        lg, img, par = fwd.inputs[:3]
+        super().__init__(G.get_default_graph(), name, [lg, img, par] + fwd.saved + [dout] + list(fwd.inputs[3:]),
+                         [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
+                         + ([dbias_dst] if dbias_dst is not None else []))
+
+    def bind(self, rt):
+        f = self.fwd
+        lg, img, par = self.inputs[:3]
+        dout = self.inputs[3 + len(f.saved)]
+        b, h, w, c = img.shape
+        fn = _lib.entry(rt.lib, f.entry + '_bwd')
+        ws, n = rt.workspace(_lib.entry(rt.lib, f.entry + '_workspace_bytes')(b, h, w, c, f.masks, *f.scalars[:f.ws_scalars]))
+        self._keep = ws
+        pb = _p(f.inputs[3].buf) if f.has_bias else None
+        args = (_p(par.buf), *[_p(t.buf) for t in f.saved], _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf),
+                _p(self.outputs[0].buf), _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c,
+                f.masks, *f.scalars, _p(ws), n)
+        return lambda s: fn(*args, s)
+
+
+class CdnaCompositeOp(MaskCompositeOp):
+    """The CDNA generator's output stage (acg_cdna_composite_*): ``params`` [B, k*k*M] are normalised to M kernels per sample -
+    saved as ``kern_norm`` for the backward pass, which goes through the normalisation and the relu - and T_m is the m-th piece
+    of cdna_transformation."""
+    entry, ws_scalars = 'cdna_composite', 1            # (ksize sizes the workspace, relu_shift does not)
 
     def __init__(self, logits, image, params, masks, ksize, relu_shift, name, bias=None):
-        b, h, w, c = image.shape
-        self.masks, self.ksize, self.relu_shift = int(masks), int(ksize), float(relu_shift)
-        self.has_bias = bias is not None
-        self.kern_norm = _new((b, self.ksize * self.ksize * self.masks), name + ':kern_norm')
-        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
-                         [_new(image.shape, name + ':0'), self.kern_norm])
-
-    def bind(self, rt):
-        lg, img, par = self.inputs[:3]
-        b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, 'cdna_composite_fwd')
-        pb = _p(self.inputs[3].buf) if self.has_bias else None
-        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), _p(self.kern_norm.buf), b, h, w, c,
-                self.masks, self.ksize, self.relu_shift)
-        return lambda s: fn(*args, s)
-
-    def grad(self, gouts, needs, ctx):
-        if needs[1]:
-            raise NotImplementedError('cdna_composite: gradient w.r.t. the image is not implemented (the image is a network '
-                                      'input, train.py:53-54)')
-        dst, acc = (None, 0.0)
-        if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
-            dst, acc = ctx.slot(self.inputs[3])
-        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
-            return [None] * len(self.inputs)
-        op = CdnaCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
-        if dst is not None:
-            ctx.wrote(self.inputs[3], op)
-        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
+        super().__init__(logits, image, params, masks, name, (int(ksize), float(relu_shift)),
+                         [(':kern_norm', int(ksize) * int(ksize) * int(masks))], bias)
+        self.ksize, self.relu_shift, self.kern_norm = *self.scalars, self.saved[0]
 
 
-class CdnaCompositeBwdOp(G.Op):
-    """acg_cdna_composite_bwd: d logits, d params (through the normalisation and the relu) and, into the bias variable's
-    gradient window, d bias."""
-
-    def __init__(self, fwd, dout, dbias_dst, accumulate, name):
-        self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
-        lg, img, par = fwd.inputs[:3]
-        super().__init__(G.get_default_graph(), name, [lg, img, par, fwd.kern_norm, dout] + list(fwd.inputs[3:]),
-                         [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
-                         + ([dbias_dst] if dbias_dst is not None else []))
-
-    def bind(self, rt):
-        lg, img, par, kn, dout = self.inputs[:5]
-        f = self.fwd
-        b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, 'cdna_composite_bwd')
-        ws, n = rt.workspace(_lib.entry(rt.lib, 'cdna_composite_workspace_bytes')(b, h, w, c, f.masks, f.ksize))
-        self._keep = ws
-        pb = _p(self.inputs[5].buf) if f.has_bias else None
-        args = (_p(par.buf), _p(kn.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf), _p(self.outputs[0].buf),
-                _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c, f.masks, f.ksize, f.relu_shift,
-                _p(ws), n)
-        return lambda s: fn(*args, s)
-
-
-class AffineCompositeOp(G.Op):
-    """The affine (STP) generator's output stage in one kernel (acg_affine_composite_fwd): each of the M masks moves the image
-    by the 2x3 affine transform ``params`` [B, M*6] + identity, sampled bilinearly with zeros outside (the M warped images stay
-    in registers), and the composite is s_0 * image + sum_m s_{m+1} * T_m under s = softmax(logits + bias) over the M + 1 mask
-    channels.  ``bias`` (may be None) is the bias variable of the layer that produced the logits, folded in as DnaOp does."""
-
-    def __init__(self, logits, image, params, masks, name, bias=None):
-        self.masks = int(masks)
-        self.has_bias = bias is not None
-        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
-                         [_new(image.shape, name + ':0')])
-
-    def bind(self, rt):
-        lg, img, par = self.inputs[:3]
-        b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, 'affine_composite_fwd')
-        pb = _p(self.inputs[3].buf) if self.has_bias else None
-        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), b, h, w, c, self.masks)
-        return lambda s: fn(*args, s)
-
-    def grad(self, gouts, needs, ctx):
-        if needs[1]:
-            raise NotImplementedError('affine_composite: gradient w.r.t. the image is not implemented (the image is a network '
-                                      'input, train.py:53-54)')
-        dst, acc = (None, 0.0)
-        if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
-            dst, acc = ctx.slot(self.inputs[3])
-        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
-            return [None] * len(self.inputs)
-        op = AffineCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
-        if dst is not None:
-            ctx.wrote(self.inputs[3], op)
-        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
-
-
-class AffineCompositeBwdOp(G.Op):
-    """acg_affine_composite_bwd: d logits, d params (the 6 numbers of every mask) and, into the bias variable's gradient
-    window, d bias."""
-
-    def __init__(self, fwd, dout, dbias_dst, accumulate, name):
-        self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
-        lg, img, par = fwd.inputs[:3]
-        super().__init__(G.get_default_graph(), name, [lg, img, par, dout] + list(fwd.inputs[3:]),
-                         [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
-                         + ([dbias_dst] if dbias_dst is not None else []))
-
-    def bind(self, rt):
-        lg, img, par, dout = self.inputs[:4]
-        f = self.fwd
-        b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, 'affine_composite_bwd')
-        ws, n = rt.workspace(_lib.entry(rt.lib, 'affine_composite_workspace_bytes')(b, h, w, c, f.masks))
-        self._keep = ws
-        pb = _p(self.inputs[4].buf) if f.has_bias else None
-        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf), _p(self.outputs[0].buf),
-                _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c, f.masks, _p(ws), n)
-        return lambda s: fn(*args, s)
+class AffineCompositeOp(MaskCompositeOp):
+    """The affine (STP) generator's output stage (acg_affine_composite_*): T_m is the image under the 2x3 affine transform
+    ``params`` [B, M*6] + identity, sampled bilinearly with zeros outside."""
+    entry = 'affine_composite'
 
 
 DGRAD_CHANNEL_LIMIT = True     # A/B switch (bench.py --no-dgrad-limit): input gradients skip the columns of tiled action channels
@@ -1800,6 +1759,16 @@ def deconv2d(inputs, num_outputs, kernel_size, stride=1, padding='SAME', activat
 conv2d_transpose = deconv2d
 
 
+def _fold_bias(logits):
+    """models.py:54-72: when ``logits`` come from a layer with a bias and neither BatchNorm nor activation, -> (its pre-bias
+    output, the bias variable) for a softmax kernel that adds the bias itself - the bias op is then never fetched and gets
+    pruned; else -> (logits, None)."""
+    prod = logits.op
+    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
+        return prod.inputs[0], prod.inputs[1]
+    return logits, None
+
+
 def dna_gather(logits, image, ksize=DNA_KERN_SIZE, name='dna'):
     """models.py:60-72 in one op: softmax over the k*k logits, then the per-pixel k x k gather of ``image``."""
     _check_nhwc(logits, 'dna_gather')
@@ -1810,12 +1779,7 @@ def dna_gather(logits, image, ksize=DNA_KERN_SIZE, name='dna'):
         raise ValueError('dna_gather: ksize outside 1..11')
     if not 1 <= image.shape[3] <= 4:
         raise ValueError('dna_gather: image channels outside 1..4')
-    bias = None
-    prod = logits.op
-    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
-        # models.py:54-72: the logits come from a layer with a bias and neither BatchNorm nor activation - take its
-        # pre-bias output and fold the bias into the softmax kernel; the bias op itself is never fetched and gets pruned
-        logits, bias = prod.inputs[0], prod.inputs[1]
+    logits, bias = _fold_bias(logits)
     if half_mode() != (logits.dtype == torch.bfloat16):
         raise ValueError('dna_gather: logits are %s in a %s graph' % (logits.dtype, act_dtype()))
     return DnaOp(logits, image, ksize, _scope_name(name), bias=bias).outputs[0]
@@ -1874,23 +1838,27 @@ def cdna_composite(mask_logits, image, params, num_masks, ksize=DNA_KERN_SIZE, n
     ``image`` [B,H,W,C] as cdna_transformation does, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
     the M transformed images through a per-pixel softmax.  When the logits come from a layer with a bias and neither
     BatchNorm nor activation, that bias is folded into the kernel (as dna_gather does)."""
-    _check_nhwc(mask_logits, 'cdna_composite')
-    _check_nhwc(image, 'cdna_composite')
-    if ksize not in (3, 5, 7) or not 1 <= num_masks <= 32:
-        raise ValueError('cdna_composite: supports ksize 3/5/7 and 1..32 masks, got ksize %r, %r masks' % (ksize, num_masks))
-    if not 1 <= image.shape[3] <= 4:
-        raise ValueError('cdna_composite: image channels outside 1..4')
-    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
-        raise ValueError('cdna_composite: mask logits %s do not match image %s with %d masks' % (mask_logits.shape, image.shape, num_masks))
-    if params.shape != (image.shape[0], ksize * ksize * num_masks):
-        raise ValueError('cdna_composite: params %s, expected [%d, %d]' % (params.shape, image.shape[0], ksize * ksize * num_masks))
-    if half_mode() or image.dtype != torch.float32:
-        raise NotImplementedError('cdna_composite is float32 only')
-    bias = None
-    prod = mask_logits.op
-    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
-        mask_logits, bias = prod.inputs[0], prod.inputs[1]
+    if ksize not in (3, 5, 7):
+        raise ValueError('cdna_composite: supports ksize 3/5/7, got %r' % (ksize,))
+    _check_composite('cdna_composite', mask_logits, image, params, num_masks, ksize * ksize)
+    mask_logits, bias = _fold_bias(mask_logits)
     return CdnaCompositeOp(mask_logits, image, params, num_masks, ksize, RELU_SHIFT, _scope_name(name), bias=bias).outputs[0]
+
+
+def _check_composite(what, mask_logits, image, params, num_masks, per_mask):
+    """What cdna_composite and affine_composite ask of their arguments alike; ``params`` hold ``per_mask`` numbers per mask."""
+    _check_nhwc(mask_logits, what)
+    _check_nhwc(image, what)
+    if not 1 <= num_masks <= 32:
+        raise ValueError('%s: supports 1..32 masks, got %r' % (what, num_masks))
+    if not 1 <= image.shape[3] <= 4:
+        raise ValueError('%s: image channels outside 1..4' % what)
+    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
+        raise ValueError('%s: mask logits %s do not match image %s with %d masks' % (what, mask_logits.shape, image.shape, num_masks))
+    if params.shape != (image.shape[0], per_mask * num_masks):
+        raise ValueError('%s: params %s, expected [%d, %d]' % (what, params.shape, image.shape[0], per_mask * num_masks))
+    if half_mode() or image.dtype != torch.float32:
+        raise NotImplementedError('%s is float32 only' % what)
 
 
 def affine_composite(mask_logits, image, params, num_masks, name='affine'):
@@ -1898,24 +1866,10 @@ def affine_composite(mask_logits, image, params, num_masks, name='affine'):
     (+ identity) warp ``image`` [B,H,W,C] bilinearly, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
     the M warped images through a per-pixel softmax.  When the logits come from a layer with a bias and neither BatchNorm nor
     activation, that bias is folded into the kernel (as dna_gather does)."""
-    _check_nhwc(mask_logits, 'affine_composite')
-    _check_nhwc(image, 'affine_composite')
-    if not 1 <= num_masks <= 32:
-        raise ValueError('affine_composite: supports 1..32 masks, got %r' % (num_masks,))
-    if not 1 <= image.shape[3] <= 4:
-        raise ValueError('affine_composite: image channels outside 1..4')
+    _check_composite('affine_composite', mask_logits, image, params, num_masks, 6)
     if image.shape[1] < 2 or image.shape[2] < 2:
         raise ValueError('affine_composite: image %s, needs H, W >= 2' % (image.shape,))
-    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
-        raise ValueError('affine_composite: mask logits %s do not match image %s with %d masks' % (mask_logits.shape, image.shape, num_masks))
-    if params.shape != (image.shape[0], 6 * num_masks):
-        raise ValueError('affine_composite: params %s, expected [%d, %d]' % (params.shape, image.shape[0], 6 * num_masks))
-    if half_mode() or image.dtype != torch.float32:
-        raise NotImplementedError('affine_composite is float32 only')
-    bias = None
-    prod = mask_logits.op
-    if isinstance(prod, BiasActOp) and prod.act is None and prod.has_bias:
-        mask_logits, bias = prod.inputs[0], prod.inputs[1]
+    mask_logits, bias = _fold_bias(mask_logits)
     return AffineCompositeOp(mask_logits, image, params, num_masks, _scope_name(name), bias=bias).outputs[0]
 
 

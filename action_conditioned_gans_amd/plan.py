@@ -55,6 +55,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import models as M
 from .metrics import _stream_handle
 from .ops import read_draw_state, write_draw_state
 
@@ -253,7 +254,7 @@ class Planner:
                  alpha=DEFAULTS['alpha'], lo=DEFAULTS['lo'], hi=DEFAULTS['hi'], frame_weight=1.0, state_weight=0.0, cost_steps='all',
                  seed=0, bn='batch', weights='raw', pixel_weight=0.0):
         self.args = check_plan(trainer.batch_size, horizon, elites, iterations, init_std, min_std, alpha, lo, hi, frame_weight,
-                               state_weight, cost_steps, seed, has_state_head=trainer.model != 'plain', pixel_weight=pixel_weight)
+                               state_weight, cost_steps, seed, has_state_head=M.KINDS[trainer.model].state_head, pixel_weight=pixel_weight)
         pixel = self.args['pixel_weight'] > 0
         if pixel and not getattr(trainer, 'pixel_maps', 0):
             raise ValueError('pixel_weight %r needs a Trainer built with pixel_maps >= 1 (the DNA generator\'s map path)' % (pixel_weight,))
@@ -503,9 +504,8 @@ def check_pixel_args(pixels, goal_pixels, pixel_weight, model, img_size):
         return None, None, 0.0
     if pixels is None or goal_pixels is None:
         raise ValueError('pixels and goal_pixels go together')
-    if model != 'dna':
-        from .train import check_pixel_maps
-        check_pixel_maps(1, model)                       # (the Trainer's own refusal, with its reason)
+    from .train import check_pixel_maps
+    check_pixel_maps(1, model)                           # (the Trainer's own refusal, with its reason)
     px, gp = np.asarray(pixels), np.asarray(goal_pixels)
     if px.dtype.kind not in 'iu' or px.ndim not in (2, 3) or px.shape[-1] != 2:
         raise ValueError('pixels must be integer (y, x) pairs, [D, 2] or [n, D, 2], got %s %s' % (px.dtype, px.shape))
@@ -538,20 +538,16 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
     is not scored.  -> the dict written to ``output_path``/plan.json."""
     from .evaluate import _batches, predicting_trainer
     from .saver import latest_checkpoint
-    from .train import model_kind
-    if dna and cdna:
-        raise ValueError('dna and cdna name two different generators')
-    if affine and (dna or cdna):
-        raise ValueError('affine and %s name two different generators' % ('dna' if dna else 'cdna'))
+    transform = M.transform_argument(dict(dna=dna, cdna=cdna, affine=affine))
+    kind = M.KINDS[M.model_kind(transform)]
     if bn_stats not in ('batch', 'stored'):
         raise ValueError("bn_stats must be 'batch' or 'stored', got %r" % (bn_stats,))
     if weights not in ('raw', 'ema'):
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
-    transform = 'affine' if affine else 'cdna' if cdna else dna
     goal_step = horizon if goal_step is None else goal_step
-    pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, pixel_weight, model_kind(transform), img_size)
+    pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, pixel_weight, kind.name, img_size)
     checked = check_plan(candidates, horizon, elites, iterations, init_std, min_std, alpha, frame_weight=frame_weight,
-                         state_weight=state_weight, cost_steps=cost_steps, seed=seed, has_state_head=model_kind(transform) != 'plain',
+                         state_weight=state_weight, cost_steps=cost_steps, seed=seed, has_state_head=kind.state_head,
                          pixel_weight=pixel_weight)
     if pixels is None and checked['frame_weight'] == 0 and checked['state_weight'] == 0:
         raise ValueError('frame_weight 0 and state_weight 0 without pixels: nothing is scored')
@@ -619,8 +615,7 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            'num_masks': num_masks if trainer.model in ('cdna', 'affine') else None,
-            'ksize': ksize if trainer.model in ('dna', 'cdna') else None,
+            **kind.result_fields(ksize, num_masks),
             'sequences': len(per_seq),
             'share_not_worse_than_recorded': float(np.mean([s['cost'] <= s['recorded_cost'] for s in per_seq])),
             'settings': {'candidates': candidates, 'elites': elites, 'iterations': iterations, 'horizon': horizon, 'goal_step': int(goal_step),
@@ -688,8 +683,7 @@ def main(argv=None):
     parser.add_argument('--pixel_weight', type=float, default=None, help='weight of the designated-pixel cost (default 1.0 once pixels are given)')
     parser.add_argument('--frame_weight', type=float, default=1.0, help='weight of the frame cost; 0 (with --state_weight 0): the goal frame is not scored')
     args = parser.parse_args(argv)
-    transform = check_model_args(parser, args)
-    from .train import model_kind
+    kind = M.KINDS[M.model_kind(check_model_args(parser, args))]
     goal_step = args.horizon if args.goal_step is None else args.goal_step
     pixels = goal_pixels = None
     if (args.pixel or args.goal_pixel) and (args.pixels or args.goal_pixels):
@@ -706,10 +700,10 @@ def main(argv=None):
             pixels, goal_pixels = np.load(args.pixels), np.load(args.goal_pixels)
             if pixels.ndim != 3:
                 parser.error('%s: expected pixels [n, D, 2], got %s' % (args.pixels, pixels.shape))
-        pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, args.pixel_weight, model_kind(transform), args.img_size)
+        pixels, goal_pixels, pixel_weight = check_pixel_args(pixels, goal_pixels, args.pixel_weight, kind.name, args.img_size)
         checked = check_plan(args.candidates, args.horizon, args.elites, args.iterations, args.init_std, args.min_std, args.alpha,
                              frame_weight=args.frame_weight, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
-                             has_state_head=model_kind(transform) != 'plain', pixel_weight=pixel_weight)
+                             has_state_head=kind.state_head, pixel_weight=pixel_weight)
     except (OSError, ValueError) as e:
         parser.error(str(e))
     if pixels is None and checked['frame_weight'] == 0 and checked['state_weight'] == 0:
@@ -739,14 +733,14 @@ def main(argv=None):
             parser.error('%s holds pixels for %d sequences, %d are planned' % (args.pixels, len(pixels), frames.shape[0]))
     if pixels is not None and pixels.ndim == 3 and args.num_sequences is not None and len(pixels) < args.num_sequences:
         parser.error('%s holds pixels for %d sequences, %d are planned' % (args.pixels, len(pixels), args.num_sequences))
-    return plan_sequences(args.model_path, args.input, args.output, actions_path=args.actions, dna=args.dna, cdna=args.cdna,
+    return plan_sequences(args.model_path, args.input, args.output, actions_path=args.actions,
                           num_masks=args.num_masks, ksize=args.ksize, img_size=args.img_size, dtype=args.dtype, device=args.device,
                           bn_stats=args.bn_stats, weights=args.weights, candidates=args.candidates, elites=args.elites,
                           iterations=args.iterations, horizon=args.horizon, goal_step=goal_step, init_std=args.init_std,
                           min_std=args.min_std, alpha=args.alpha, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
                           num_sequences=args.num_sequences, seq_len=args.seq_len, dump=args.dump, pixels=pixels, goal_pixels=goal_pixels,
                           pixel_weight=pixel_weight if pixels is not None else None, frame_weight=args.frame_weight,
-                          **({'affine': True} if args.affine else {}))
+                          **{flag: getattr(args, flag) for flag in M.flags()})
 
 
 if __name__ == '__main__':

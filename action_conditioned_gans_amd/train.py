@@ -214,13 +214,7 @@ class Trainer:
             if self.noise_dim:
                 O.noise_state(noise_seed)
                 actions = self._noise = O.append_noise(actions, self.noise_dim)
-            if self.model == 'affine':
-                return M.build_generator_affine(images, actions, batch_size=batch, num_masks=num_masks, reuse=reuse)
-            if self.model == 'cdna':
-                return M.build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse)
-            if arg_transform:
-                return M.build_generator_transform(images, actions, batch_size=batch, ksize=ksize, reuse=reuse)
-            return M.build_generator(images, actions, reuse=reuse), None
+            return M.KINDS[self.model].build(images, actions, batch, reuse, ksize, num_masks)
         n0 = len(graph.ops)
         self.g_out, self.g_state_out = build_g(self.img_ph, self.action_ph, B, False)
         n1 = len(graph.ops)
@@ -679,7 +673,7 @@ class Trainer:
         The G loss is the mean of the K step losses, the pretraining loss the mean of their l2 parts; both updates continue the
         one-step optimizers' state (optim minimize slots_of)."""
         K, B, S = self.rollout_steps, self.batch_size, self.img_size
-        dna = self.model == 'dna'
+        dna = M.KINDS[self.model].state_head
         self.roll_img_ph = G.placeholder((B, S, S, 3), name='rollout/frame0')
         self.roll_img_ph.padded = self._roll_img_pad = G.placeholder((B, S, S, 3), name='rollout/frame0_conv', channel_pitch=O.cpad(3), act=True)
         self.roll_next_ph = [G.placeholder((B, S, S, 3), name='rollout/next_frame%d' % j) for j in range(K)]
@@ -938,13 +932,7 @@ class Trainer:
         return {k: float(np.asarray(v).reshape(-1)[0]) for k, v in zip(self._summary_names, values)}
 
 
-def model_kind(arg_transform):
-    """The generator an ``arg_transform`` names: 'plain' (False), 'dna' (True or 'dna'), 'cdna' or 'affine'."""
-    if isinstance(arg_transform, str):
-        if arg_transform in ('dna', 'cdna', 'affine'):
-            return arg_transform
-        raise ValueError("unexpected transform argument %r (False, True / 'dna', 'cdna' or 'affine')" % arg_transform)
-    return 'dna' if arg_transform else 'plain'
+model_kind = M.model_kind        # (the generator an ``arg_transform`` names: a key of models.KINDS)
 
 
 F32_MAX = float(np.finfo(np.float32).max)
@@ -1111,15 +1099,8 @@ def check_pixel_maps(pixel_maps, model):
     """ValueError for a ``pixel_maps`` the Trainer does not take with the generator ``model``; -> D (0: no map path)."""
     if isinstance(pixel_maps, bool) or not isinstance(pixel_maps, (int, np.integer)) or not 0 <= pixel_maps <= _lib.PLAN_PIXEL_MAPS_MAX:
         raise ValueError('pixel_maps must be an integer in 0..%d, got %r' % (_lib.PLAN_PIXEL_MAPS_MAX, pixel_maps))
-    if pixel_maps and model == 'plain':
-        raise ValueError('pixel_maps %d: the plain generator predicts no flow a map could follow (DNA generator only)' % pixel_maps)
-    if pixel_maps and model == 'cdna':
-        raise ValueError('pixel_maps %d: the CDNA generator is declined - its channel split, kept as written from the reference, '
-                         'transforms the colour channels of one mask with different kernels, so there is no single flow that a map '
-                         'could follow consistently with the frame (DNA generator only)' % pixel_maps)
-    if pixel_maps and model == 'affine':
-        raise ValueError('pixel_maps %d: the affine generator is declined - there is no map advection through its warps (DNA '
-                         'generator only)' % pixel_maps)
+    if pixel_maps and M.KINDS[model].no_maps:
+        raise ValueError('pixel_maps %d: %s' % (pixel_maps, M.KINDS[model].no_maps))
     return int(pixel_maps)
 
 
@@ -1130,10 +1111,8 @@ def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
     if k < 1:
         raise ValueError('rollout_steps must be >= 1, got %d' % k)
     if k > 1:
-        if model == 'cdna':
-            raise ValueError('rollout_steps > 1: the CDNA composite has no image gradient (train the DNA or the plain generator)')
-        if model == 'affine':
-            raise ValueError('rollout_steps > 1: the affine composite has no image gradient (train the DNA or the plain generator)')
+        if M.KINDS[model].no_rollout:
+            raise ValueError('rollout_steps > 1 does not train the %s generator (%s)' % (M.KINDS[model].label, M.KINDS[model].no_rollout))
         if bf16:
             raise ValueError('rollout_steps > 1 is float32 only (dtype bf16)')
         if data_parallel:
@@ -1578,33 +1557,26 @@ def _flag(v):
 
 def add_model_args(parser):
     """The generator flags shared by this CLI and evaluate's: --dna (the reference's), --cdna, --affine and --num_masks."""
-    parser.add_argument('--dna', nargs='?', const=True, default=False, type=_flag)
-    parser.add_argument('--cdna', nargs='?', const=True, default=False, type=_flag,
-                        help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7')
-    parser.add_argument('--affine', nargs='?', const=True, default=False, type=_flag,
-                        help='the affine (STP) generator (models.build_generator_affine): float32, --ksize is not read')
+    for kind in M.KINDS.values():
+        if kind.flag:
+            parser.add_argument('--' + kind.flag, nargs='?', const=True, default=False, type=_flag, help=kind.help)
     parser.add_argument('--num_masks', type=int, default=10, help='CDNA kernels / affine transforms, and their masks (1..32)')
 
 
 def check_model_args(parser, args):
-    """parser.error for generator flags that do not go together (before anything is created); -> Trainer's arg_transform."""
-    if args.dna and args.cdna:
-        parser.error('--dna and --cdna name two different generators')
-    if args.affine and (args.dna or args.cdna):
-        parser.error('--affine and --%s name two different generators' % ('dna' if args.dna else 'cdna'))
-    if not 1 <= args.num_masks <= 32:
+    """parser.error for generator flags that do not go together, and for what the generator they name does not take (before
+    anything is created); -> Trainer's arg_transform."""
+    if args.num_masks not in M.NUM_MASKS:
         parser.error('--num_masks must be in 1..32')
-    if args.affine:
-        if args.dtype == 'bf16':
-            parser.error('the affine generator is float32 only (--dtype bf16)')
-        return 'affine'
-    if args.cdna:
-        if args.dtype == 'bf16':
-            parser.error('the CDNA generator is float32 only (--dtype bf16)')
-        if args.ksize not in (3, 5, 7):
-            parser.error('--cdna takes --ksize 3, 5 or 7')
-        return 'cdna'
-    return args.dna
+    try:
+        transform = M.transform_argument(vars(args), '--%s')
+        kind = M.KINDS[model_kind(transform)]
+        kind.check_args(args.ksize, args.num_masks)
+    except ValueError as e:
+        parser.error(str(e))
+    if kind.float32_only and args.dtype == 'bf16':
+        parser.error('the %s generator is float32 only (--dtype bf16)' % kind.label)
+    return transform
 
 
 def check_rollout_args(parser, args):
@@ -1616,10 +1588,10 @@ def check_rollout_args(parser, args):
         return
     if k > args.seq_len - 1:
         parser.error('--rollout_steps %d needs sequences of more than %d frames (--seq_len %d)' % (k, k, args.seq_len))
-    if args.cdna:
-        parser.error('--rollout_steps > 1 does not train the CDNA generator (its composite has no image gradient)')
-    if args.affine:
-        parser.error('--rollout_steps > 1 does not train the affine generator (its composite has no image gradient)')
+    try:
+        check_rollout(k, model_kind(M.transform_argument(vars(args))))      # (the Trainer's own refusal of a generator)
+    except ValueError as e:
+        parser.error('--%s' % e)
     if args.dtype == 'bf16':
         parser.error('--rollout_steps > 1 is float32 only (--dtype bf16)')
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -1777,7 +1749,7 @@ def main(argv=None):
         torch.cuda.set_device(local_rank)
         torch.distributed.init_process_group('gloo')
     # every other flag is a keyword of train() under its own name, but for these four
-    options = {k: v for k, v in vars(args).items() if k not in ('input_path', 'output_path', 'adv', 'loss', 'opt', 'dna', 'cdna', 'affine')}
+    options = {k: v for k, v in vars(args).items() if k not in ['input_path', 'output_path', 'adv', 'loss', 'opt'] + M.flags()}
     for flag, keyword in (('g_ema', 'ema_decay'), ('log_grad_norms', 'grad_norms'), ('lr_decay_iters', 'lr_decay_steps'),
                           ('ss_decay_iters', 'ss_decay_steps'), ('d_noise_decay_iters', 'd_noise_decay_steps'), ('log_d_stats', 'd_stats')):
         options[keyword] = options.pop(flag)
