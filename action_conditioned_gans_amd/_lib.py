@@ -215,6 +215,16 @@ EXTENSIONS = {
         'acg_affine_composite_workspace_bytes': (c_size_t, [c_int32] * 5),
         'acg_affine_composite_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P] + [c_int32] * 5 + [_P]),
         'acg_affine_composite_bwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_float] + [c_int32] * 5 + [_P, c_size_t, _P]),
+        # the same two with a painted canvas among the candidates (ops.MaskCompositeOp canvas=): ``canvas`` behind the image
+        # pitch, ``dcanvas`` behind the accumulate factor
+        'acg_cdna_composite_canvas_workspace_bytes': (c_size_t, [c_int32] * 6),
+        'acg_cdna_composite_canvas_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P, _P] + [c_int32] * 6 + [c_float, _P]),
+        'acg_cdna_composite_canvas_bwd': (STATUS, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, c_float, _P] + [c_int32] * 6
+                                          + [c_float, _P, c_size_t, _P]),
+        'acg_affine_composite_canvas_workspace_bytes': (c_size_t, [c_int32] * 5),
+        'acg_affine_composite_canvas_fwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P] + [c_int32] * 5 + [_P]),
+        'acg_affine_composite_canvas_bwd': (STATUS, [_P, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, c_float, _P] + [c_int32] * 5
+                                            + [_P, c_size_t, _P]),
     }),
     # the image gradient of the DNA tail and the gradient of a tiled action vector, which training through the generator's own
     # rollouts needs (train.Trainer rollout_steps > 1; ops.DnaImageGradOp / ActionGradOp), and the global-norm clip of a flat

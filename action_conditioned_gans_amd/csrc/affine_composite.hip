@@ -16,7 +16,13 @@
 // Backward: the warps are recomputed.  The tile pass writes dmask_logits and leaves per-(sample, tile) partials of dparams
 // (6 values per mask: wave shuffles, then the 4 waves in order) and of the bias gradient (cdna_common.h) in the workspace;
 // the final pass sums them in tile order.  No atomics.
+//
+// kCanvas (the acg_affine_composite_canvas_* entries): one more candidate behind the M warped images, a canvas [B,H,W,C]
+// under mask channel M+1, read once per pixel and folded where s_0 * image is; backward, g_{M+1} = <dout, canvas> and
+// dcanvas = s_{M+1} dout by the pixel's thread.  The instantiations without it are the kernels as they were.
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "../../include/acgan_cdna.h"
 #include "cdna_common.h"
@@ -82,12 +88,13 @@ __device__ __forceinline__ void sample(const float* __restrict__ src, const Geo&
   }
 }
 
+template <bool kCanvas>
 __global__ __launch_bounds__(256) void affine_comp_fwd_k(const float* __restrict__ params, const float* __restrict__ z,
                                                          const float* __restrict__ zbias, const float* __restrict__ img,
-                                                         float* __restrict__ out, Geo g) {
+                                                         const float* __restrict__ canvas, float* __restrict__ out, Geo g) {
   __shared__ float th[kMaxM * kTheta];
   __shared__ float zb[kMaxZ];
-  const int b = blockIdx.z, y0 = blockIdx.y * kTile, x0 = blockIdx.x * kTile, nz = g.M + 1, tid = threadIdx.x;
+  const int b = blockIdx.z, y0 = blockIdx.y * kTile, x0 = blockIdx.x * kTile, nz = g.M + 1 + kCanvas, tid = threadIdx.x;
   if (tid < nz) zb[tid] = zbias ? zbias[tid] : 0.f;
   stage_theta(params, b, g.M, th);
   __syncthreads();
@@ -105,6 +112,12 @@ __global__ __launch_bounds__(256) void affine_comp_fwd_k(const float* __restrict
   float f[kMaxC];
 #pragma unroll
   for (int i = 0; i < kMaxC; ++i) f[i] = i < g.C ? s0 * centre[i] : 0.f;
+  if (kCanvas) {
+    const float sc = weight(zp, zb, g.M + 1, zmax, inv);
+#pragma unroll
+    for (int i = 0; i < kMaxC; ++i)
+      if (i < g.C) f[i] += sc * canvas[pix * g.C + i];
+  }
   for (int m = 0; m < g.M; ++m) {
     float px, py, T[kMaxC], Tx[kMaxC], Ty[kMaxC];
     affine_map(th + m * kTheta, (float)x, (float)y, g.H, g.W, &px, &py);
@@ -121,10 +134,13 @@ __global__ __launch_bounds__(256) void affine_comp_fwd_k(const float* __restrict
 }
 
 // The tile pass of the backward: dz for every pixel; part_p[b][tile][m*6 + i] = the tile's sum of s_{m+1} * (a u, a v, a,
-// b u, b v, b); part_b[b][tile][j] = the tile's sum of dz_j.  Dynamic LDS: big[(M + 1) * 256].
+// b u, b v, b); part_b[b][tile][j] = the tile's sum of dz_j.  Dynamic LDS: big[nz * 256], nz = M + 1 mask channels.
+// kCanvas: nz = M + 2, g_{M+1} = <dout, canvas> and dcanvas = s_{M+1} dout, one thread per pixel.
+template <bool kCanvas>
 __global__ __launch_bounds__(256) void affine_comp_bwd_tile_k(const float* __restrict__ params, const float* __restrict__ z,
                                                               const float* __restrict__ zbias, const float* __restrict__ img,
-                                                              const float* __restrict__ dout, float* __restrict__ dz,
+                                                              const float* __restrict__ canvas, const float* __restrict__ dout,
+                                                              float* __restrict__ dz, float* __restrict__ dcanvas,
                                                               float* __restrict__ part_p, float* __restrict__ part_b, Geo g) {
   __shared__ float th[kMaxM * kTheta];
   __shared__ float zb[kMaxZ];
@@ -132,7 +148,7 @@ __global__ __launch_bounds__(256) void affine_comp_bwd_tile_k(const float* __res
   __shared__ float wred[4 * kMaxM * kTheta];      // per wave: the 6 sums of every mask
   extern __shared__ float big[];                  // g_j, then dz_j, of pixel p at big[j * kPix + p]
   const int b = blockIdx.z, ty = blockIdx.y, tx = blockIdx.x, y0 = ty * kTile, x0 = tx * kTile;
-  const int nz = g.M + 1, n = g.M * kTheta, tid = threadIdx.x;
+  const int nz = g.M + 1 + kCanvas, n = g.M * kTheta, tid = threadIdx.x;
   if (tid < nz) zb[tid] = zbias ? zbias[tid] : 0.f;
   stage_theta(params, b, g.M, th);
   __syncthreads();
@@ -154,6 +170,17 @@ __global__ __launch_bounds__(256) void affine_comp_bwd_tile_k(const float* __res
   for (int i = 0; i < kMaxC; ++i)
     if (i < g.C) g0 += d[i] * centre[i];
   big[tid] = g0;
+  if (kCanvas) {
+    const float sc = inside ? weight(zp, zb, g.M + 1, zmax, inv) : 0.f;
+    float gc = 0.f;
+#pragma unroll
+    for (int i = 0; i < kMaxC; ++i)
+      if (i < g.C) {
+        gc += d[i] * canvas[pix * g.C + i];
+        if (inside) dcanvas[pix * g.C + i] = sc * d[i];
+      }
+    big[(g.M + 1) * kPix + tid] = gc;
+  }
   const float u = 2.f * (float)x / (float)(g.W - 1) - 1.f, v = 2.f * (float)y / (float)(g.H - 1) - 1.f;
   const float half_w = 0.5f * (float)(g.W - 1), half_h = 0.5f * (float)(g.H - 1);
   const int lane = tid & 63, wave = tid >> 6;
@@ -199,11 +226,11 @@ __global__ __launch_bounds__(256) void affine_comp_bwd_tile_k(const float* __res
 // the partials.
 __global__ __launch_bounds__(256) void affine_comp_bwd_final_k(const float* __restrict__ part_p, const float* __restrict__ part_b,
                                                                float* __restrict__ dparams, float* __restrict__ dbias,
-                                                               float dbias_acc, Geo g) {
+                                                               float dbias_acc, Geo g, int nz) {
   __shared__ double scratch[16];
   const int b = blockIdx.x, ntile = g.tiles_x * g.tiles_y, n = g.M * kTheta;
   if (b == g.B) {
-    final_bias_sum(part_b, dbias, dbias_acc, g.B * ntile, g.M + 1, scratch);
+    final_bias_sum(part_b, dbias, dbias_acc, g.B * ntile, nz, scratch);
     return;
   }
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
@@ -213,54 +240,95 @@ __global__ __launch_bounds__(256) void affine_comp_bwd_final_k(const float* __re
   }
 }
 
+// (a canvas takes one of the kMaxZ mask channels: M <= kMaxM - 1)
+template <bool kCanvas>
 int affine_geo(const char* who, int B, int H, int W, int C, int M, int pitch, Geo* g) {
   if (int rc = make_geo(who, B, H, W, C, M, 1, pitch, false, g)) return rc;          // (K = 1: no halo)
   ACG_REQUIRE(H >= 2 && W >= 2, ACG_ERR_UNSUPPORTED, "%s: needs H, W >= 2 (got %d x %d)", who, H, W);
+  ACG_REQUIRE(!kCanvas || M + 2 <= kMaxZ, ACG_ERR_UNSUPPORTED, "%s: supports masks <= %d beside a canvas", who, kMaxZ - 2);
   return ACG_OK;
 }
 
 size_t dparam_partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.M * kTheta; }
+
+// ---- the entries, with and without a canvas -------------------------------------------------------------------------
+template <bool kCanvas>
+size_t comp_workspace(const char* who, int B, int H, int W, int C, int M) {
+  Geo g;
+  if (affine_geo<kCanvas>(who, B, H, W, C, M, 0, &g) != ACG_OK) return 0;
+  return (dparam_partials(g) + (size_t)B * g.tiles_x * g.tiles_y * (M + 1 + kCanvas)) * sizeof(float);
+}
+
+template <bool kCanvas>
+int comp_fwd(const char* who, const float* params, const float* z, const float* zbias, const float* image, int pitch,
+             const float* canvas, float* out, int B, int H, int W, int C, int M, acg_stream_t stream) {
+  Geo g;
+  if (int rc = affine_geo<kCanvas>(who, B, H, W, C, M, pitch, &g)) return rc;
+  ACG_REQUIRE(params && z && image && out && (!kCanvas || canvas), ACG_ERR_INVALID_ARG, "%s: null pointer", who);
+  ACG_LAUNCH(affine_comp_fwd_k<kCanvas>, dim3(g.tiles_x, g.tiles_y, B), dim3(256), 0, acg::to_stream(stream), params, z, zbias, image,
+             canvas, out, g);
+  return acg::check_launch(who);
+}
+
+template <bool kCanvas>
+int comp_bwd(const char* who, const float* params, const float* z, const float* zbias, const float* image, int pitch,
+             const float* canvas, const float* dout, float* dparams, float* dz, float* dbias, float dbias_acc, float* dcanvas, int B,
+             int H, int W, int C, int M, void* ws, size_t wsb, acg_stream_t stream) {
+  Geo g;
+  if (int rc = affine_geo<kCanvas>(who, B, H, W, C, M, pitch, &g)) return rc;
+  ACG_REQUIRE(params && z && image && dout && dparams && dz && (!kCanvas || (canvas && dcanvas)), ACG_ERR_INVALID_ARG,
+              "%s: null pointer", who);
+  ACG_REQUIRE(ws && wsb >= comp_workspace<kCanvas>(who, B, H, W, C, M), ACG_ERR_WORKSPACE, "%s: workspace too small", who);
+  hipStream_t st = acg::to_stream(stream);
+  float* part_p = (float*)ws;
+  float* part_b = part_p + dparam_partials(g);
+  ACG_LAUNCH(affine_comp_bwd_tile_k<kCanvas>, dim3(g.tiles_x, g.tiles_y, B), dim3(256), (size_t)(M + 1 + kCanvas) * kPix * sizeof(float),
+             st, params, z, zbias, image, canvas, dout, dz, dcanvas, part_p, part_b, g);
+  if (int rc = acg::check_launch((std::string(who) + " tile").c_str())) return rc;
+  ACG_LAUNCH(affine_comp_bwd_final_k, dim3(B + (dbias ? 1 : 0)), dim3(256), 0, st, (const float*)part_p, (const float*)part_b,
+             dparams, dbias, dbias_acc, g, M + 1 + kCanvas);
+  return acg::check_launch((std::string(who) + " final").c_str());
+}
 
 }  // namespace
 
 extern "C" {
 
 size_t acg_affine_composite_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t M) {
-  Geo g;
-  if (affine_geo("affine_composite_workspace_bytes", B, H, W, C, M, 0, &g) != ACG_OK) return 0;
-  return (dparam_partials(g) + (size_t)B * g.tiles_x * g.tiles_y * (M + 1)) * sizeof(float);
+  return comp_workspace<false>("affine_composite_workspace_bytes", B, H, W, C, M);
 }
 
 int32_t acg_affine_composite_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
                                  int32_t image_pitch, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t M,
                                  acg_stream_t stream) {
-  Geo g;
-  if (int rc = affine_geo("affine_composite_fwd", B, H, W, C, M, image_pitch, &g)) return rc;
-  ACG_REQUIRE(params && mask_logits && image && out, ACG_ERR_INVALID_ARG, "affine_composite_fwd: null pointer");
-  ACG_LAUNCH(affine_comp_fwd_k, dim3(g.tiles_x, g.tiles_y, B), dim3(256), 0, acg::to_stream(stream), params, mask_logits, mask_bias,
-             image, out, g);
-  return acg::check_launch("affine_composite_fwd");
+  return comp_fwd<false>("affine_composite_fwd", params, mask_logits, mask_bias, image, image_pitch, nullptr, out, B, H, W, C, M, stream);
 }
 
 int32_t acg_affine_composite_bwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
                                  int32_t image_pitch, const float* dout, float* dparams, float* dmask_logits, float* dmask_bias,
                                  float dmask_bias_accumulate, int32_t B, int32_t H, int32_t W, int32_t C, int32_t M, void* ws,
                                  size_t wsb, acg_stream_t stream) {
-  Geo g;
-  if (int rc = affine_geo("affine_composite_bwd", B, H, W, C, M, image_pitch, &g)) return rc;
-  ACG_REQUIRE(params && mask_logits && image && dout && dparams && dmask_logits, ACG_ERR_INVALID_ARG,
-              "affine_composite_bwd: null pointer");
-  ACG_REQUIRE(ws && wsb >= acg_affine_composite_workspace_bytes(B, H, W, C, M), ACG_ERR_WORKSPACE,
-              "affine_composite_bwd: workspace too small");
-  hipStream_t st = acg::to_stream(stream);
-  float* part_p = (float*)ws;
-  float* part_b = part_p + dparam_partials(g);
-  ACG_LAUNCH(affine_comp_bwd_tile_k, dim3(g.tiles_x, g.tiles_y, B), dim3(256), (size_t)(M + 1) * kPix * sizeof(float), st, params,
-             mask_logits, mask_bias, image, dout, dmask_logits, part_p, part_b, g);
-  if (int rc = acg::check_launch("affine_composite_bwd tile")) return rc;
-  ACG_LAUNCH(affine_comp_bwd_final_k, dim3(B + (dmask_bias ? 1 : 0)), dim3(256), 0, st, (const float*)part_p, (const float*)part_b,
-             dparams, dmask_bias, dmask_bias_accumulate, g);
-  return acg::check_launch("affine_composite_bwd final");
+  return comp_bwd<false>("affine_composite_bwd", params, mask_logits, mask_bias, image, image_pitch, nullptr, dout, dparams, dmask_logits,
+                         dmask_bias, dmask_bias_accumulate, nullptr, B, H, W, C, M, ws, wsb, stream);
+}
+
+size_t acg_affine_composite_canvas_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t M) {
+  return comp_workspace<true>("affine_composite_canvas_workspace_bytes", B, H, W, C, M);
+}
+
+int32_t acg_affine_composite_canvas_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                        int32_t image_pitch, const float* canvas, float* out, int32_t B, int32_t H, int32_t W,
+                                        int32_t C, int32_t M, acg_stream_t stream) {
+  return comp_fwd<true>("affine_composite_canvas_fwd", params, mask_logits, mask_bias, image, image_pitch, canvas, out, B, H, W, C, M,
+                        stream);
+}
+
+int32_t acg_affine_composite_canvas_bwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                        int32_t image_pitch, const float* canvas, const float* dout, float* dparams,
+                                        float* dmask_logits, float* dmask_bias, float dmask_bias_accumulate, float* dcanvas, int32_t B,
+                                        int32_t H, int32_t W, int32_t C, int32_t M, void* ws, size_t wsb, acg_stream_t stream) {
+  return comp_bwd<true>("affine_composite_canvas_bwd", params, mask_logits, mask_bias, image, image_pitch, canvas, dout, dparams,
+                        dmask_logits, dmask_bias, dmask_bias_accumulate, dcanvas, B, H, W, C, M, ws, wsb, stream);
 }
 
 }  // extern "C"

@@ -36,7 +36,7 @@ inline int make_geo(const char* who, int B, int H, int W, int C, int M, int K, i
 }
 
 constexpr int kPix = kTile * kTile;
-constexpr int kMaxZ = kMaxM + 1;                                   // mask channels: the image and the M transforms
+constexpr int kMaxZ = kMaxM + 1;                                   // mask channels: the image, the M transforms and, for M < kMaxM, a canvas
 
 // floats of the kernel-gradient partials in the workspace: [b][tile][(u*K+v)*M + m]
 inline size_t partials(const Geo& g) { return (size_t)g.B * g.tiles_x * g.tiles_y * g.K * g.K * g.M; }

@@ -120,13 +120,14 @@ def _use_ema_weights(trainer, ckpt):
 
 
 def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn_stats='batch', weights='raw',
-                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate', pixel_maps=0):
+                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate', pixel_maps=0, canvas=False):
     """A checkpoint as a Trainer that predicts: a fresh graph and session, the generator ``transform`` / ``ksize`` / ``num_masks`` at
     ``batch_size`` with what the modes need and nothing else - ``bn_stats`` 'stored' or 'calibrate': the stored-statistics instances;
     ``weights='ema'``: the average (then copied into the variables, _use_ema_weights); ``noise_dim`` > 0: the noise input, its stream
     restarted at ``noise_seed`` - initialised and restored from ``restore_from`` (default: ``ckpt``, which the messages name).  An int
     ``noise_dim`` also makes the Saver's shape refusal ask about --noise_dim.  'stored' needs calibrated rows in the checkpoint (the
     error names ``calibrate_with``).  ``pixel_maps`` > 0: the map path of plan.Planner's designated-pixel cost (DNA generator).
+    ``canvas``: the CDNA / affine generator with its painted candidate (Trainer ``canvas``).
     -> (trainer, updates of the average or None, calibrated rows or None); the caller closes
     ``trainer.sess``."""
     from . import graph as G
@@ -139,6 +140,8 @@ def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, devi
         extra.update(noise_dim=noise_dim, noise_seed=noise_seed)
     if pixel_maps:
         extra['pixel_maps'] = pixel_maps
+    if canvas:
+        extra['canvas'] = True
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
     try:
@@ -166,12 +169,13 @@ def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, devi
 
 
 def calibrate(ckpt, save_prefix, input_path, actions_path, transform, ksize, img_size, dtype, pair_batch, num_batches, seq_len, device,
-              num_masks, weights='raw'):
+              num_masks, weights='raw', canvas=False):
     """Restore ``ckpt`` into a generator built at batch ``pair_batch``, pool its BatchNorm statistics over ``num_batches`` batches
     of one-step pairs of ``input_path`` (Trainer.calibrate_bn) and save everything as ``save_prefix``.npz.  -> pairs pooled.
     ``weights='ema'``: calibrate (and save) the averaged weights (_use_ema_weights)."""
     from .saver import Saver
-    trainer, _, _ = predicting_trainer(ckpt, transform, pair_batch, ksize, img_size, dtype, device, num_masks, 'calibrate', weights)
+    trainer, _, _ = predicting_trainer(ckpt, transform, pair_batch, ksize, img_size, dtype, device, num_masks, 'calibrate', weights,
+                                       canvas=canvas)
     sess = trainer.sess
     try:
         trainer.reset_bn_statistics()
@@ -197,7 +201,7 @@ def set_psnr(sqerr, valid, count_per_frame):
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
              seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
              calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw', noise_dim=0,
-             noise='zero', noise_samples=1, noise_seed=0, affine=False):
+             noise='zero', noise_samples=1, noise_seed=0, affine=False, canvas=False):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
     ``dna`` / ``cdna`` / ``affine`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
@@ -205,6 +209,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
     ``weights``: 'raw' or 'ema' (module docstring); 'ema' on a checkpoint without an average is a ValueError.
     ``noise_dim`` / ``noise`` ('zero' or 'sample') / ``noise_samples`` / ``noise_seed``: the module docstring.
+    ``canvas``: the checkpoint is of a ``cdna`` / ``affine`` generator trained with its painted candidate (Trainer ``canvas``);
+    metrics.json then holds ``canvas: true``.
     -> the metrics dict."""
     from . import models as M
     transform = M.transform_argument(dict(dna=dna, cdna=cdna, affine=affine))
@@ -214,7 +220,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
     if bn_stats == 'calibrate' and (calibrate_batch_size < 1 or calibrate_batches < 1):
         raise ValueError('calibrate_batch_size and calibrate_batches must be >= 1')
-    from .train import check_noise
+    from .train import check_canvas, check_noise
+    canvas = check_canvas(canvas, M.model_kind(transform), ksize, num_masks)
     noise_dim = check_noise(noise_dim, noise_seed, 1, bn_stats != 'batch', batch_size)
     if noise not in ('zero', 'sample'):
         raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
@@ -237,11 +244,13 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             calibrate_input, calibrate_actions = input_path, actions_path
         restore_from = os.path.join(output_path, 'calibrated')
         calibrate(ckpt, restore_from, calibrate_input, calibrate_actions, transform, ksize, img_size, dtype, calibrate_batch_size,
-                  calibrate_batches, seq_len, device, num_masks, **({'weights': weights} if weights == 'ema' else {}))
+                  calibrate_batches, seq_len, device, num_masks, **({'weights': weights} if weights == 'ema' else {}),
+                  **({'canvas': True} if canvas else {}))
     stored = bn_stats != 'batch'
     bn = 'stored' if stored else 'batch'
     trainer, ema_updates, calibration_rows = predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn,
-                                                                weights, noise_dim, noise_seed, restore_from=restore_from)
+                                                                weights, noise_dim, noise_seed, restore_from=restore_from,
+                                                                **({'canvas': True} if canvas else {}))
     sess = trainer.sess
     try:
         keys =('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
@@ -283,7 +292,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            **M.KINDS[trainer.model].result_fields(ksize, num_masks),
+            **M.KINDS[trainer.model].result_fields(ksize, num_masks, trainer.canvas),
             'sequences': n_seq,
             'steps': int(steps),
             'ssim_definition': SSIM_DEFINITION + ' (data_range 2 for frames in [-1, 1])',
@@ -424,6 +433,7 @@ def main(argv=None):
                     num_masks=args.num_masks, bn_stats=args.bn_stats, calibrate_batch_size=args.calibrate_batch_size,
                     calibrate_batches=args.calibrate_batches, calibrate_input=args.calibrate_input, calibrate_actions=args.calibrate_actions,
                     **({'weights': args.weights} if args.weights != 'raw' else {}), **{flag: getattr(args, flag) for flag in M.flags()},
+                    **({'canvas': True} if args.canvas else {}),
                     **({'noise_dim': args.noise_dim, 'noise': args.noise, 'noise_samples': args.noise_samples, 'noise_seed': args.noise_seed}
                        if args.noise_dim else {}))
 

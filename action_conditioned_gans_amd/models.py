@@ -95,7 +95,7 @@ def build_generator_transform(images, actions, batch_size=None, reuse=False, col
         return frame, state
 
 
-def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10, ksize=5):
+def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10, ksize=5, canvas=False):
     """CDNA generator: the DNA generator's trunk with the reference's ``cdna_transformation`` (ops.py:52-98, which none of
     its models calls) as the motion model.  Returns ``(frame, state)``.
 
@@ -106,20 +106,26 @@ def build_generator_cdna(images, actions, batch_size=None, reuse=False, color_ch
     The frame is s_0 * images + sum_j s_{j+1} * T_j with s = softmax over the M+1 channels and T_j the pieces of
     cdna_transformation (its channel split kept as written), in one fused kernel (ops.cdna_composite).
 
-    Two differences from the CDNA model of the paper the push dataset comes from: there is no image generated from
-    scratch among the composited candidates, and the masks come from the 5x5/2 ``tconv4`` instead of a 1x1 layer.
+    Two differences from the CDNA model of the paper the push dataset comes from: without ``canvas`` there is no image
+    generated from scratch among the composited candidates, and the masks come from the 5x5/2 ``tconv4`` instead of a 1x1
+    layer.  ``canvas=True`` adds that image (see _mask_generator): ``tconv4`` then gives M+2 mask logits, a new layer
+    ``g/tconv4_canvas`` paints the candidate, and the frame gains s_{M+1} * canvas; 1 <= ``num_masks`` <= 31 then.
     float32 only; ``ksize`` 3, 5 or 7, 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
     return _mask_generator(KINDS['cdna'], images, actions, batch_size, reuse, color_channels, ksize, num_masks,
                            'cdna_params', ksize * ksize * num_masks,
-                           lambda logits, params: O.cdna_composite(logits, images, params, num_masks, ksize))
+                           lambda logits, params, **kw: O.cdna_composite(logits, images, params, num_masks, ksize, **kw), canvas)
 
 
-def _mask_generator(kind, images, actions, batch_size, reuse, color_channels, ksize, num_masks, scope, width, composite):
+def _mask_generator(kind, images, actions, batch_size, reuse, color_channels, ksize, num_masks, scope, width, composite,
+                    canvas=False):
     """The CDNA and the affine generators: what generator ``kind`` does not take is refused before anything is created; then
     the DNA generator's layers, a linear layer ``scope`` of ``width`` outputs per sample on the action-conditioned bottleneck,
-    tconv4 to M+1 mask logits and ``composite(logits, params)``."""
+    tconv4 to M+1 mask logits and ``composite(logits, params)``.
+    ``canvas``: tconv4 gives M+2 mask logits, and ``tconv4_canvas`` - a 5x5/2 deconvolution of the same ``tconv3`` output to
+    ``color_channels``, bias only, tanh, as the plain generator's tconv4 is - paints an image that the composite takes as one
+    more candidate, ``composite(logits, params, canvas=image)``, under mask channel M+1."""
     _check_images(images, batch_size, color_channels)
-    kind.check_args(ksize, num_masks)
+    kind.check_args(ksize, num_masks, canvas)
     if images.shape[1] % 16 or images.shape[2] % 16:
         raise ValueError('%s generator: image size %s is not a multiple of 16' % (kind.label, images.shape[1:3]))
     if kind.float32_only and O.half_mode():
@@ -135,11 +141,14 @@ def _mask_generator(kind, images, actions, batch_size, reuse, color_channels, ks
         net = _stack(net, G_DNA['decoder_a'], O.deconv2d)
         state = _state_head(net)
         net = _stack(net, G_DNA['decoder_b'], O.deconv2d)
-        logits = O.deconv2d(net, num_masks + 1, [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
-        return composite(logits, params), state
+        logits = O.deconv2d(net, num_masks + (2 if canvas else 1), [5, 5], activation_fn=None, normalizer_fn=None, scope='tconv4')
+        if not canvas:
+            return composite(logits, params), state
+        painted = O.deconv2d(net, color_channels, [5, 5], activation_fn=O.tanh, normalizer_fn=None, scope='tconv4_canvas')
+        return composite(logits, params, canvas=painted), state
 
 
-def build_generator_affine(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10):
+def build_generator_affine(images, actions, batch_size=None, reuse=False, color_channels=3, num_masks=10, canvas=False):
     """Affine (STP) generator: ``build_generator_cdna`` with a 2x3 affine transform per mask in place of a k x k kernel.
     Returns ``(frame, state)``.
 
@@ -148,11 +157,12 @@ def build_generator_affine(images, actions, batch_size=None, reuse=False, color_
     identity.  The frame is s_0 * images + sum_m s_{m+1} * T_m with T_m the image warped by theta_m, bilinear with zeros
     outside (include/acgan_cdna.h has the formula), in one fused kernel (ops.affine_composite).  Rotation, scale and shear of
     an object take 6 numbers here; the k x k kernels of DNA / CDNA cannot move anything further than (k-1)/2 pixels.
-    As for CDNA there is no image generated from scratch among the candidates and the masks come from the 5x5/2 ``tconv4``.
+    As for CDNA there is no image generated from scratch among the candidates unless ``canvas=True`` adds one (as
+    build_generator_cdna does; 1 <= ``num_masks`` <= 31 then), and the masks come from the 5x5/2 ``tconv4``.
     float32 only; 1 <= ``num_masks`` <= 32, image size a multiple of 16."""
     return _mask_generator(KINDS['affine'], images, actions, batch_size, reuse, color_channels, None, num_masks,
                            'affine_params', 6 * num_masks,
-                           lambda logits, params: O.affine_composite(logits, images, params, num_masks))
+                           lambda logits, params, **kw: O.affine_composite(logits, images, params, num_masks, **kw), canvas)
 
 
 def build_discriminator(inputs, actions, reuse=False):
@@ -175,13 +185,17 @@ def build_discriminator(inputs, actions, reuse=False):
 NUM_MASKS = range(1, 33)
 
 
+_NO_MASKS = 'it composites no masked candidates a canvas could join: --cdna or --affine'
+
+
 class Kind(typing.NamedTuple):
     """What the layers above the builders know about one generator.  train.Trainer, the checks of train / evaluate / plan and
     their CLIs read these records and compare no names: a new generator is one more record in KINDS, a new capability of an
     existing one is a changed field."""
     name: str                    # what Trainer.model, metrics.json and plan.json call it, and the string arg_transform that names it
     label: str                   # what messages call it
-    build: object                # (images, actions, batch, reuse, ksize, num_masks) -> (frame, state or None)
+    build: object                # (images, actions, batch, reuse, ksize, num_masks) -> (frame, state or None); one that takes a
+                                 # canvas is also called with the keyword canvas=True
     ksizes: tuple = None         # the ``ksize`` values it takes (None: it does not read ksize) ...
     ksize_text: str = None       # ... and the same in words
     num_masks: bool = False      # whether it reads ``num_masks`` (one of NUM_MASKS)
@@ -191,17 +205,30 @@ class Kind(typing.NamedTuple):
     no_maps: str = None          # why designated-pixel maps (pixel_maps) cannot follow it (None: they can)
     flag: str = None             # its CLI flag, which is also its keyword of evaluate.evaluate / plan.plan_sequences (None: the default)
     help: str = None
+    no_canvas: str = _NO_MASKS   # why it cannot composite a painted canvas (None: it can)
 
-    def check_args(self, ksize, num_masks):
-        """ValueError for a ``ksize`` / ``num_masks`` that this generator reads and does not take."""
+    def check_args(self, ksize, num_masks, canvas=False):
+        """ValueError for a ``ksize`` / ``num_masks`` that this generator reads and does not take, and for a ``canvas`` that
+        it does not take or that leaves no mask channel for ``num_masks``."""
         if self.ksizes is not None and ksize not in self.ksizes:
             raise ValueError('%s generator: ksize must be %s (got %r)' % (self.label, self.ksize_text, ksize))
         if self.num_masks and num_masks not in NUM_MASKS:
             raise ValueError('%s generator: num_masks must be in 1..32 (got %r)' % (self.label, num_masks))
+        if canvas and self.no_canvas:
+            raise ValueError('canvas does not go with the %s generator (%s)' % (self.label, self.no_canvas))
+        if canvas and num_masks > O.CANVAS_MAX_MASKS:
+            raise ValueError('%s generator: num_masks must be in 1..%d with a canvas, which takes one of the 33 mask channels '
+                             '(got %r)' % (self.label, O.CANVAS_MAX_MASKS, num_masks))
 
-    def result_fields(self, ksize, num_masks):
-        """The 'num_masks' / 'ksize' entries of metrics.json and plan.json: None for what this generator does not read."""
-        return {'num_masks': num_masks if self.num_masks else None, 'ksize': ksize if self.ksizes is not None else None}
+    def build_with(self, images, actions, batch, reuse, ksize, num_masks, canvas=False):
+        """``build``; the canvas is passed only when it is set, so a ``build`` of six arguments stays one."""
+        return self.build(images, actions, batch, reuse, ksize, num_masks, **({'canvas': True} if canvas else {}))
+
+    def result_fields(self, ksize, num_masks, canvas=False):
+        """The 'num_masks' / 'ksize' entries of metrics.json and plan.json: None for what this generator does not read; and
+        'canvas': True when it is on."""
+        return dict({'num_masks': num_masks if self.num_masks else None, 'ksize': ksize if self.ksizes is not None else None},
+                    **({'canvas': True} if canvas else {}))
 
 
 _NO_IMAGE_GRADIENT = 'its composite has no image gradient: train the DNA or the plain generator'
@@ -211,18 +238,19 @@ KINDS = {kind.name: kind for kind in (
     Kind('dna', 'DNA', lambda images, actions, batch, reuse, ksize, num_masks:
          build_generator_transform(images, actions, batch_size=batch, ksize=ksize, reuse=reuse),
          ksizes=tuple(range(1, 12)), ksize_text='in 1..11', flag='dna'),
-    Kind('cdna', 'CDNA', lambda images, actions, batch, reuse, ksize, num_masks:
-         build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse),
+    Kind('cdna', 'CDNA', lambda images, actions, batch, reuse, ksize, num_masks, canvas=False:
+         build_generator_cdna(images, actions, batch_size=batch, num_masks=num_masks, ksize=ksize, reuse=reuse, canvas=canvas),
          ksizes=(3, 5, 7), ksize_text='3, 5 or 7', num_masks=True, float32_only=True, no_rollout=_NO_IMAGE_GRADIENT,
          no_maps='the CDNA generator is declined - its channel split, kept as written from the reference, transforms the colour '
                  'channels of one mask with different kernels, so there is no single flow that a map could follow consistently '
                  'with the frame (DNA generator only)',
-         flag='cdna', help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7'),
-    Kind('affine', 'affine', lambda images, actions, batch, reuse, ksize, num_masks:
-         build_generator_affine(images, actions, batch_size=batch, num_masks=num_masks, reuse=reuse),
+         flag='cdna', help='the CDNA generator (models.build_generator_cdna): float32, --ksize 3, 5 or 7', no_canvas=None),
+    Kind('affine', 'affine', lambda images, actions, batch, reuse, ksize, num_masks, canvas=False:
+         build_generator_affine(images, actions, batch_size=batch, num_masks=num_masks, reuse=reuse, canvas=canvas),
          num_masks=True, float32_only=True, no_rollout=_NO_IMAGE_GRADIENT,
          no_maps='the affine generator is declined - there is no map advection through its warps (DNA generator only)',
-         flag='affine', help='the affine (STP) generator (models.build_generator_affine): float32, --ksize is not read'),
+         flag='affine', help='the affine (STP) generator (models.build_generator_affine): float32, --ksize is not read',
+         no_canvas=None),
 )}
 BOOLEAN = {False: 'plain', True: 'dna'}        # the reference's arg_transform is its boolean --dna: these two kinds keep it
 

@@ -1020,23 +1020,31 @@ class MaskCompositeOp(G.Op):
     ``params`` says (the M moved images stay in registers).  ``bias`` (may be None) is the bias variable of the layer that
     produced the logits, folded in as DnaOp does.  A variant names its ``entry`` prefix and passes the ``scalars`` its entries
     take behind the mask count (the first ``ws_scalars`` of them size the backward's workspace) and, as ``saved``, the
-    (name suffix, width per sample) of what its forward leaves for its backward.  Outputs: the frame, then the saved ones."""
+    (name suffix, width per sample) of what its forward leaves for its backward.  Outputs: the frame, then the saved ones.
+    ``canvas`` (may be None; the last input): an image the generator paints itself, one more candidate behind the M moved ones
+    under mask channel M + 1 - the logits and the bias then have M + 2 channels and the acg_<entry>_canvas_* entries run."""
     entry, ws_scalars = None, 0
 
-    def __init__(self, logits, image, params, masks, name, scalars=(), saved=(), bias=None):
+    def __init__(self, logits, image, params, masks, name, scalars=(), saved=(), bias=None, canvas=None):
         self.masks, self.scalars = int(masks), tuple(scalars)
-        self.has_bias = bias is not None
+        self.has_bias, self.has_canvas = bias is not None, canvas is not None
         self.saved = [_new((image.shape[0], width), name + suffix) for suffix, width in saved]
-        super().__init__(G.get_default_graph(), name, [logits, image, params] + ([bias] if bias is not None else []),
+        super().__init__(G.get_default_graph(), name,
+                         [logits, image, params] + ([bias] if self.has_bias else []) + ([canvas] if self.has_canvas else []),
                          [_new(image.shape, name + ':0')] + self.saved)
+
+    def prefix(self):
+        """The prefix of the entries this op and its backward bind."""
+        return self.entry + ('_canvas' if self.has_canvas else '')
 
     def bind(self, rt):
         lg, img, par = self.inputs[:3]
         b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, self.entry + '_fwd')
+        fn = _lib.entry(rt.lib, self.prefix() + '_fwd')
         pb = _p(self.inputs[3].buf) if self.has_bias else None
-        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, _p(self.outputs[0].buf), *[_p(t.buf) for t in self.saved], b, h, w, c,
-                self.masks, *self.scalars)
+        canvas = [_p(self.inputs[-1].buf)] if self.has_canvas else []
+        args = (_p(par.buf), _p(lg.buf), pb, _p(img.buf), 0, *canvas, _p(self.outputs[0].buf), *[_p(t.buf) for t in self.saved],
+                b, h, w, c, self.masks, *self.scalars)
         return lambda s: fn(*args, s)
 
     def grad(self, gouts, needs, ctx):
@@ -1046,22 +1054,25 @@ class MaskCompositeOp(G.Op):
         dst, acc = (None, 0.0)
         if self.has_bias and needs[3] and ctx.wants(self.inputs[3]):
             dst, acc = ctx.slot(self.inputs[3])
-        if (not needs[0] and not needs[2] and dst is None) or gouts[0] is None:
+        want_canvas = self.has_canvas and needs[-1]
+        if (not needs[0] and not needs[2] and dst is None and not want_canvas) or gouts[0] is None:
             return [None] * len(self.inputs)
         op = MaskCompositeBwdOp(self, gouts[0], dst, acc, self.name + '/bwd')
         if dst is not None:
             ctx.wrote(self.inputs[3], op)
-        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else [])
+        return [op.outputs[0] if needs[0] else None, None, op.outputs[1] if needs[2] else None] + ([None] if self.has_bias else []) \
+            + ([op.outputs[2] if want_canvas else None] if self.has_canvas else [])
 
 
 class MaskCompositeBwdOp(G.Op):
-    """acg_<entry>_bwd: d logits, d params and, into the bias variable's gradient window, d bias."""
+    """acg_<entry>_bwd: d logits, d params, with a canvas d canvas, and, into the bias variable's gradient window, d bias."""
 
     def __init__(self, fwd, dout, dbias_dst, accumulate, name):
         self.fwd, self.accumulate, self.dbias = fwd, float(accumulate), dbias_dst
         lg, img, par = fwd.inputs[:3]
         super().__init__(G.get_default_graph(), name, [lg, img, par] + fwd.saved + [dout] + list(fwd.inputs[3:]),
                          [_new(lg.shape, name + ':dlogits'), _new(par.shape, name + ':dparams')]
+                         + ([_new(fwd.inputs[-1].shape, name + ':dcanvas')] if fwd.has_canvas else [])
                          + ([dbias_dst] if dbias_dst is not None else []))
 
     def bind(self, rt):
@@ -1069,13 +1080,14 @@ class MaskCompositeBwdOp(G.Op):
         lg, img, par = self.inputs[:3]
         dout = self.inputs[3 + len(f.saved)]
         b, h, w, c = img.shape
-        fn = _lib.entry(rt.lib, f.entry + '_bwd')
-        ws, n = rt.workspace(_lib.entry(rt.lib, f.entry + '_workspace_bytes')(b, h, w, c, f.masks, *f.scalars[:f.ws_scalars]))
+        fn = _lib.entry(rt.lib, f.prefix() + '_bwd')
+        ws, n = rt.workspace(_lib.entry(rt.lib, f.prefix() + '_workspace_bytes')(b, h, w, c, f.masks, *f.scalars[:f.ws_scalars]))
         self._keep = ws
         pb = _p(f.inputs[3].buf) if f.has_bias else None
-        args = (_p(par.buf), *[_p(t.buf) for t in f.saved], _p(lg.buf), pb, _p(img.buf), 0, _p(dout.buf), _p(self.outputs[1].buf),
-                _p(self.outputs[0].buf), _p(self.dbias.buf) if self.dbias is not None else None, self.accumulate, b, h, w, c,
-                f.masks, *f.scalars, _p(ws), n)
+        canvas, dcanvas = ([_p(f.inputs[-1].buf)], [_p(self.outputs[2].buf)]) if f.has_canvas else ([], [])
+        args = (_p(par.buf), *[_p(t.buf) for t in f.saved], _p(lg.buf), pb, _p(img.buf), 0, *canvas, _p(dout.buf),
+                _p(self.outputs[1].buf), _p(self.outputs[0].buf), _p(self.dbias.buf) if self.dbias is not None else None,
+                self.accumulate, *dcanvas, b, h, w, c, f.masks, *f.scalars, _p(ws), n)
         return lambda s: fn(*args, s)
 
 
@@ -1085,9 +1097,9 @@ class CdnaCompositeOp(MaskCompositeOp):
     of cdna_transformation."""
     entry, ws_scalars = 'cdna_composite', 1            # (ksize sizes the workspace, relu_shift does not)
 
-    def __init__(self, logits, image, params, masks, ksize, relu_shift, name, bias=None):
+    def __init__(self, logits, image, params, masks, ksize, relu_shift, name, bias=None, canvas=None):
         super().__init__(logits, image, params, masks, name, (int(ksize), float(relu_shift)),
-                         [(':kern_norm', int(ksize) * int(ksize) * int(masks))], bias)
+                         [(':kern_norm', int(ksize) * int(ksize) * int(masks))], bias, canvas)
         self.ksize, self.relu_shift, self.kern_norm = *self.scalars, self.saved[0]
 
 
@@ -1833,19 +1845,25 @@ def cdna_transformation(prev_image, cdna_input, num_masks, color_channels, ksize
     return list(op.outputs[:num_masks])
 
 
-def cdna_composite(mask_logits, image, params, num_masks, ksize=DNA_KERN_SIZE, name='cdna'):
+def cdna_composite(mask_logits, image, params, num_masks, ksize=DNA_KERN_SIZE, name='cdna', canvas=None):
     """The CDNA generator's frame in one op (CdnaCompositeOp): the ``num_masks`` kernels ``params`` [B, k*k*M] transform
     ``image`` [B,H,W,C] as cdna_transformation does, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
     the M transformed images through a per-pixel softmax.  When the logits come from a layer with a bias and neither
-    BatchNorm nor activation, that bias is folded into the kernel (as dna_gather does)."""
+    BatchNorm nor activation, that bias is folded into the kernel (as dna_gather does).  ``canvas`` [B,H,W,C] (None: none): an
+    image composited as one more candidate behind the transformed ones, under channel M + 1 of then M + 2 mask logits
+    (1 <= ``num_masks`` <= 31)."""
     if ksize not in (3, 5, 7):
         raise ValueError('cdna_composite: supports ksize 3/5/7, got %r' % (ksize,))
-    _check_composite('cdna_composite', mask_logits, image, params, num_masks, ksize * ksize)
+    _check_composite('cdna_composite', mask_logits, image, params, num_masks, ksize * ksize, canvas)
     mask_logits, bias = _fold_bias(mask_logits)
-    return CdnaCompositeOp(mask_logits, image, params, num_masks, ksize, RELU_SHIFT, _scope_name(name), bias=bias).outputs[0]
+    return CdnaCompositeOp(mask_logits, image, params, num_masks, ksize, RELU_SHIFT, _scope_name(name), bias=bias,
+                           canvas=canvas).outputs[0]
 
 
-def _check_composite(what, mask_logits, image, params, num_masks, per_mask):
+CANVAS_MAX_MASKS = 31          # acgan_cdna.h: a canvas takes one of the 33 mask channels the composite kernels hold
+
+
+def _check_composite(what, mask_logits, image, params, num_masks, per_mask, canvas=None):
     """What cdna_composite and affine_composite ask of their arguments alike; ``params`` hold ``per_mask`` numbers per mask."""
     _check_nhwc(mask_logits, what)
     _check_nhwc(image, what)
@@ -1853,7 +1871,13 @@ def _check_composite(what, mask_logits, image, params, num_masks, per_mask):
         raise ValueError('%s: supports 1..32 masks, got %r' % (what, num_masks))
     if not 1 <= image.shape[3] <= 4:
         raise ValueError('%s: image channels outside 1..4' % what)
-    if mask_logits.shape != image.shape[:3] + (num_masks + 1,) or mask_logits.valid_c:
+    if canvas is not None:
+        _check_nhwc(canvas, what)
+        if num_masks > CANVAS_MAX_MASKS:
+            raise ValueError('%s: supports 1..%d masks beside a canvas, got %r' % (what, CANVAS_MAX_MASKS, num_masks))
+        if canvas.shape != image.shape or canvas.valid_c or canvas.dtype != torch.float32:
+            raise ValueError('%s: canvas %s %s does not match image %s (float32, dense)' % (what, canvas.shape, canvas.dtype, image.shape))
+    if mask_logits.shape != image.shape[:3] + (num_masks + (1 if canvas is None else 2),) or mask_logits.valid_c:
         raise ValueError('%s: mask logits %s do not match image %s with %d masks' % (what, mask_logits.shape, image.shape, num_masks))
     if params.shape != (image.shape[0], per_mask * num_masks):
         raise ValueError('%s: params %s, expected [%d, %d]' % (what, params.shape, image.shape[0], per_mask * num_masks))
@@ -1861,16 +1885,16 @@ def _check_composite(what, mask_logits, image, params, num_masks, per_mask):
         raise NotImplementedError('%s is float32 only' % what)
 
 
-def affine_composite(mask_logits, image, params, num_masks, name='affine'):
+def affine_composite(mask_logits, image, params, num_masks, name='affine', canvas=None):
     """The affine (STP) generator's frame in one op (AffineCompositeOp): the ``num_masks`` 2x3 transforms ``params`` [B, M*6]
     (+ identity) warp ``image`` [B,H,W,C] bilinearly, and the M + 1 channels of ``mask_logits`` [B,H,W,M+1] weigh the image and
     the M warped images through a per-pixel softmax.  When the logits come from a layer with a bias and neither BatchNorm nor
-    activation, that bias is folded into the kernel (as dna_gather does)."""
-    _check_composite('affine_composite', mask_logits, image, params, num_masks, 6)
+    activation, that bias is folded into the kernel (as dna_gather does).  ``canvas``: as cdna_composite takes it."""
+    _check_composite('affine_composite', mask_logits, image, params, num_masks, 6, canvas)
     if image.shape[1] < 2 or image.shape[2] < 2:
         raise ValueError('affine_composite: image %s, needs H, W >= 2' % (image.shape,))
     mask_logits, bias = _fold_bias(mask_logits)
-    return AffineCompositeOp(mask_logits, image, params, num_masks, _scope_name(name), bias=bias).outputs[0]
+    return AffineCompositeOp(mask_logits, image, params, num_masks, _scope_name(name), bias=bias, canvas=canvas).outputs[0]
 
 
 def concat_actions(x, actions, name='concat_actions'):

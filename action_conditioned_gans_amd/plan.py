@@ -531,15 +531,18 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
                    dtype='f32', device='cuda:0', bn_stats='batch', weights='raw', candidates=64, elites=8, iterations=3, horizon=5,
                    goal_step=None, init_std=DEFAULTS['init_std'], min_std=DEFAULTS['min_std'], alpha=DEFAULTS['alpha'], state_weight=0.0,
                    cost_steps='all', seed=0, num_sequences=None, seq_len=8, dump=False, pixels=None, goal_pixels=None, pixel_weight=None,
-                   frame_weight=1.0, affine=False):
+                   frame_weight=1.0, affine=False, canvas=False):
     """Restore ``model_path`` as evaluate.evaluate does and plan for the sequences of ``input_path`` (module docstring).
     ``pixels`` (int) / ``goal_pixels`` (float): [D, 2] for every sequence or [n, D, 2], one set per sequence - the designated-pixel
     cost, weighted ``pixel_weight`` (None: 1.0 with pixels, 0 without); ``frame_weight`` 0 with ``state_weight`` 0: the goal frame
-    is not scored.  -> the dict written to ``output_path``/plan.json."""
+    is not scored.  ``canvas``: as evaluate.evaluate takes it; plan.json then holds ``canvas: true``.
+    -> the dict written to ``output_path``/plan.json."""
     from .evaluate import _batches, predicting_trainer
     from .saver import latest_checkpoint
+    from .train import check_canvas
     transform = M.transform_argument(dict(dna=dna, cdna=cdna, affine=affine))
     kind = M.KINDS[M.model_kind(transform)]
+    canvas = check_canvas(canvas, kind.name, ksize, num_masks)
     if bn_stats not in ('batch', 'stored'):
         raise ValueError("bn_stats must be 'batch' or 'stored', got %r" % (bn_stats,))
     if weights not in ('raw', 'ema'):
@@ -563,7 +566,8 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
     os.makedirs(output_path, exist_ok=True)
     trainer, ema_updates, _ = predicting_trainer(ckpt, transform, candidates, ksize, img_size, dtype, device, num_masks, bn_stats, weights,
                                                  calibrate_with='evaluate --bn_stats calibrate',
-                                                 pixel_maps=0 if pixels is None else pixels.shape[-2])
+                                                 pixel_maps=0 if pixels is None else pixels.shape[-2],
+                                                 **({'canvas': True} if canvas else {}))
     sess = trainer.sess
     try:
         planner = Planner(trainer, horizon, elites, iterations, init_std=init_std, min_std=min_std, alpha=alpha, frame_weight=frame_weight,
@@ -615,7 +619,7 @@ def plan_sequences(model_path, input_path, output_path, actions_path=None, dna=F
         result = {
             'checkpoint': os.path.abspath(ckpt),
             'model': trainer.model,
-            **kind.result_fields(ksize, num_masks),
+            **kind.result_fields(ksize, num_masks, canvas),
             'sequences': len(per_seq),
             'share_not_worse_than_recorded': float(np.mean([s['cost'] <= s['recorded_cost'] for s in per_seq])),
             'settings': {'candidates': candidates, 'elites': elites, 'iterations': iterations, 'horizon': horizon, 'goal_step': int(goal_step),
@@ -740,7 +744,7 @@ def main(argv=None):
                           min_std=args.min_std, alpha=args.alpha, state_weight=args.state_weight, cost_steps=args.cost_steps, seed=args.seed,
                           num_sequences=args.num_sequences, seq_len=args.seq_len, dump=args.dump, pixels=pixels, goal_pixels=goal_pixels,
                           pixel_weight=pixel_weight if pixels is not None else None, frame_weight=args.frame_weight,
-                          **{flag: getattr(args, flag) for flag in M.flags()})
+                          **{flag: getattr(args, flag) for flag in M.flags()}, **({'canvas': True} if args.canvas else {}))
 
 
 if __name__ == '__main__':

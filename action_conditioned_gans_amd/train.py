@@ -45,7 +45,7 @@ class Trainer:
                  ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
                  g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
                  sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0,
-                 d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False):
+                 d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False, canvas=False):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -170,7 +170,17 @@ class Trainer:
         ``d_stats=True`` (False adds nothing): the summaries ``d_fake_logit`` / ``d_real_logit`` - the mean logit of D on the
         generated and on the real half - and ``d_fake_acc`` / ``d_real_acc`` - the share of fake logits < 0 and of real logits > 0 -
         computed on the device from the logits the D loss reads (ops.LogitStatsOp), and with ``d_noise`` > 0 ``d_noise_sigma``, the
-        level of the program that computed them."""
+        level of the program that computed them.
+        ``canvas=True`` (no reference counterpart; False builds nothing: ops, variables and checkpoint keys are those of a Trainer
+        without the argument; CDNA and affine generators, ``num_masks`` <= 31): every generator instance paints an image of its own
+        from its decoder (``g/tconv4_canvas``, 5x5/2 deconvolution + bias + tanh) and composites it as one more candidate behind the
+        M moved images, under channel M + 1 of then M + 2 mask logits (models._mask_generator; acg_*_composite_canvas_*) - a
+        pixel that no pixel of the input frame can colour has a candidate.  ``g/tconv4/*`` has M + 2 output channels and
+        ``g/tconv4_canvas/*`` is new, with their optimizer and average slots: a checkpoint of one setting does not restore into
+        the other.  Everything these generators take they take with it (the look-ahead pair pass, HIP-graph replay, noise_dim,
+        ema_decay, ssim_weight, the clip norms, the schedules, bn_inference), and what they decline stays declined.  A generator
+        without masks (plain, DNA) is a ValueError before anything is created."""
+        self.canvas = check_canvas(canvas, model_kind(arg_transform), ksize, num_masks)      # (before anything is created)
         self.d_noise = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, d_noise_offset, d_noise_seed, rollout_steps,
                                      arg_adv)         # (before anything is created; None: off)
         self.pixel_maps = check_pixel_maps(pixel_maps, model_kind(arg_transform))      # (before anything is created)
@@ -214,7 +224,7 @@ class Trainer:
             if self.noise_dim:
                 O.noise_state(noise_seed)
                 actions = self._noise = O.append_noise(actions, self.noise_dim)
-            return M.KINDS[self.model].build(images, actions, batch, reuse, ksize, num_masks)
+            return M.KINDS[self.model].build_with(images, actions, batch, reuse, ksize, num_masks, self.canvas)
         n0 = len(graph.ops)
         self.g_out, self.g_state_out = build_g(self.img_ph, self.action_ph, B, False)
         n1 = len(graph.ops)
@@ -1104,6 +1114,14 @@ def check_pixel_maps(pixel_maps, model):
     return int(pixel_maps)
 
 
+def check_canvas(canvas, model, ksize, num_masks):
+    """ValueError for a ``canvas`` the generator ``model`` does not take (it has no masks, or ``num_masks`` leaves it no mask
+    channel); -> bool."""
+    if canvas:
+        M.KINDS[model].check_args(ksize, num_masks, True)
+    return bool(canvas)
+
+
 def check_rollout(rollout_steps, model, bf16=False, data_parallel=False):
     """ValueError for a ``rollout_steps`` the K-step trainer does not take (with the generator ``model``, a bf16 graph, data
     parallelism / synchronised BatchNorm); -> K."""
@@ -1259,17 +1277,18 @@ class _PairSelections:
 
 
 def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0,
-                 rates=None, ss_prob=None):
+                 rates=None, ss_prob=None, canvas=False):
     """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
     the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
     ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0.
     ``rates``: Trainer.learning_rates() of a run with a learning-rate schedule (None: no field is added) -> ``g_lr`` / ``d_lr``, the
     rates the iteration's last updates used.  ``ss_prob``: the probability of truth of the iteration's K-step update in a run with
-    scheduled sampling (None: no field is added) -> ``ss_prob``."""
+    scheduled sampling (None: no field is added) -> ``ss_prob``.  ``canvas`` is recorded when on."""
     record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
                   **({'g_ema': ema_decay} if ema_decay else {}),
                   **({'ssim_weight': ssim_weight} if ssim_weight else {}),
-                  **({'noise_dim': noise_dim} if noise_dim else {}))
+                  **({'noise_dim': noise_dim} if noise_dim else {}),
+                  **({'canvas': True} if canvas else {}))
     for scope in sorted(grad_stats or {}, reverse=True):             # g, then d
         record[scope + '_grad_norm'] = grad_stats[scope]['norm']
         record[scope + '_clip_scale'] = grad_stats[scope]['scale']
@@ -1295,7 +1314,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
           noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
           lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0, d_noise=0.0, d_noise_final=0.0,
-          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False):
+          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False, canvas=False):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1344,7 +1363,9 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     offset).  The loop takes the plain call path (no look-ahead pass) and checkpoints hold ``d/inst_noise/state`` and
     ``d/inst_noise/updates``.  ``d_stats``: ``train.jsonl`` records ``d_fake_logit`` / ``d_real_logit`` / ``d_fake_acc`` /
     ``d_real_acc`` of the interval's last D step and, with ``d_noise`` > 0, its ``d_noise_sigma`` (Trainer ``d_stats``: they are
-    summaries).  With both off all of this is unchanged."""
+    summaries).  With both off all of this is unchanged.
+    ``canvas``: the CDNA / affine generator composites an image it paints itself (Trainer ``canvas``); ``train.jsonl`` records
+    ``canvas`` and checkpoints hold ``g/tconv4_canvas/*``.  Off, all of this is unchanged."""
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         if isinstance(v, (tuple, list)):
             raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
@@ -1359,6 +1380,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     if la['scheduled']:                 # iterations -> updates: D takes D_per_G of them per iteration
         options.update(lr_schedule=la['schedule'], lr_final=la['final'], lr_warmup=(la['warmup'][0], la['warmup'][0] * D_per_G),
                        lr_decay_steps=(la['decay_steps'][0], la['decay_steps'][0] * D_per_G))
+    if check_canvas(canvas, model_kind(arg_transform), ksize, num_masks):
+        options['canvas'] = True
     noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
     if noise_dim:
         options.update(noise_dim=noise_dim, noise_seed=noise_seed)
@@ -1502,7 +1525,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 bounds = None if bounds_logged or not stats else {'g': trainer.g_clip_norm, 'd': trainer.d_clip_norm}
                 _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, trainer.ema_decay, trainer.ssim_weight, stats, bounds,
                                                     trainer.noise_dim, trainer.learning_rates() if scheduled else None,
-                                                    ss_prob=trainer.sched_sampling_last()['prob'] if sampling else None))
+                                                    ss_prob=trainer.sched_sampling_last()['prob'] if sampling else None,
+                                                    canvas=trainer.canvas))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
@@ -1556,11 +1580,14 @@ def _flag(v):
 
 
 def add_model_args(parser):
-    """The generator flags shared by this CLI and evaluate's: --dna (the reference's), --cdna, --affine and --num_masks."""
+    """The generator flags shared by this CLI, evaluate's and plan's: --dna (the reference's), --cdna, --affine, --num_masks and
+    --canvas."""
     for kind in M.KINDS.values():
         if kind.flag:
             parser.add_argument('--' + kind.flag, nargs='?', const=True, default=False, type=_flag, help=kind.help)
     parser.add_argument('--num_masks', type=int, default=10, help='CDNA kernels / affine transforms, and their masks (1..32)')
+    parser.add_argument('--canvas', nargs='?', const=True, default=False, type=_flag,
+                        help='--cdna / --affine: composite an image the generator paints itself as one more candidate (--num_masks <= 31)')
 
 
 def check_model_args(parser, args):
@@ -1571,7 +1598,7 @@ def check_model_args(parser, args):
     try:
         transform = M.transform_argument(vars(args), '--%s')
         kind = M.KINDS[model_kind(transform)]
-        kind.check_args(args.ksize, args.num_masks)
+        kind.check_args(args.ksize, args.num_masks, args.canvas)
     except ValueError as e:
         parser.error(str(e))
     if kind.float32_only and args.dtype == 'bf16':

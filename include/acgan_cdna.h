@@ -91,6 +91,49 @@ int32_t acg_affine_composite_bwd(const float* params, const float* mask_logits, 
                                  float dmask_bias_accumulate, int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks,
                                  void* workspace, size_t workspace_bytes, acg_stream_t stream);
 
+/*
+ * A canvas among the candidates (both composites): a C-channel image the generator paints itself, composited behind the M
+ * moved images under a mask channel of its own.
+ *
+ * Definitions (as above, with 1 <= M <= 31: the canvas takes one of the 33 mask channels the kernels hold):
+ *   canvas      [B, H, W, C], dense;
+ *   mask_logits [B, H, W, M+2], mask_bias [M+2] (NULL = zero); channel M+1 is the canvas's;
+ *   s           softmax over the M+2 channels of z + b, per pixel;
+ *   out         = s_0 * image + sum_{j<M} s_{j+1} * T_j + s_{M+1} * canvas.
+ * Gradients: g_{M+1} = <dout, canvas> enters dz_j = s_j (g_j - sum_l s_l g_l) beside the other g; dmask_logits
+ * [B, H, W, M+2] and dmask_bias [M+2] as above; dparams keeps its definition (the s in it are those of the M+2 channels);
+ *   dcanvas [B, H, W, C], dense: s_{M+1} * dout, every element written by exactly one thread.
+ * The entries take the arguments of the entries they extend, `canvas` behind image_pitch and `dcanvas` behind
+ * dmask_bias_accumulate; both must not be NULL (ACG_ERR_INVALID_ARG).  M = 32 is ACG_ERR_UNSUPPORTED and a workspace of 0.
+ * The workspace holds the bias partials of M+2 channels: size it with the *_canvas_workspace_bytes query.  The same
+ * kernels as the entries above, compiled with the canvas term: the same two launches, no atomics, the same bits from the
+ * same call.
+ */
+size_t acg_cdna_composite_canvas_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks, int32_t ksize);
+
+int32_t acg_cdna_composite_canvas_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                      int32_t image_pitch, const float* canvas, float* out, float* kern_norm, int32_t batch,
+                                      int32_t h, int32_t w, int32_t c, int32_t masks, int32_t ksize, float relu_shift,
+                                      acg_stream_t stream);
+
+int32_t acg_cdna_composite_canvas_bwd(const float* params, const float* kern_norm, const float* mask_logits, const float* mask_bias,
+                                      const float* image, int32_t image_pitch, const float* canvas, const float* dout, float* dparams,
+                                      float* dmask_logits, float* dmask_bias, float dmask_bias_accumulate, float* dcanvas,
+                                      int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks, int32_t ksize, float relu_shift,
+                                      void* workspace, size_t workspace_bytes, acg_stream_t stream);
+
+size_t acg_affine_composite_canvas_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks);
+
+int32_t acg_affine_composite_canvas_fwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                        int32_t image_pitch, const float* canvas, float* out, int32_t batch, int32_t h, int32_t w,
+                                        int32_t c, int32_t masks, acg_stream_t stream);
+
+int32_t acg_affine_composite_canvas_bwd(const float* params, const float* mask_logits, const float* mask_bias, const float* image,
+                                        int32_t image_pitch, const float* canvas, const float* dout, float* dparams,
+                                        float* dmask_logits, float* dmask_bias, float dmask_bias_accumulate, float* dcanvas,
+                                        int32_t batch, int32_t h, int32_t w, int32_t c, int32_t masks, void* workspace,
+                                        size_t workspace_bytes, acg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
