@@ -31,6 +31,10 @@
 
 using namespace acgconv;
 
+// acg_conv2d_uniform_k: the one process-wide switch of the shipped library.  It picks between two loaders that compute the same
+// bits (conv_f32_kernel.h: uniform_k_variant) and is read by nothing else - no plan, no workspace size depends on it.
+int acgconv::g_uniform_k = 1;
+
 namespace {
 
 // out[i] = accumulate * out[i] + sum_z slabs[z][i]   (fixed summation order); `block` of `nblocks` 256-thread blocks
@@ -225,7 +229,7 @@ int validate(const acg_conv_desc* d, const char* who) {
 }
 
 // Tuning hooks exist in -DACG_TUNING builds only (libacgan_hip_tuning.so, `make tuning`, used by tools/): the shipped
-// library has no process-wide mutable state and reads no environment variable.
+// library has no process-wide mutable state beyond g_uniform_k above and reads no environment variable.
 #ifdef ACG_TUNING
 int g_force_cfg = -1, g_force_splits = -1;   // acg_debug_conv_plan: force a tile configuration / split-K factor; -1 = heuristic
 int env_int(const char* name, int dflt) {
@@ -811,12 +815,20 @@ int32_t acg_conv2d_path(const acg_conv_desc* d, int32_t which, int32_t dtype, in
   o.classes = pl.classes; o.nk = pl.nk; o.splits = pl.splits;
   if (o.family == ACG_PATH_MFMA_F32) {
     o.ragged = pl.ragged; o.nvec = pl.nvec; o.compact = j.a.compact;
-    o.lin = lin_variant(j.which == ACG_CONV_FWD ? MODE_FWD : j.which == ACG_CONV_DGRAD ? MODE_DGRAD : MODE_WGRAD, pl, j.a);
+    const int mode = j.which == ACG_CONV_FWD ? MODE_FWD : j.which == ACG_CONV_DGRAD ? MODE_DGRAD : MODE_WGRAD;
+    o.lin = lin_variant(mode, pl, j.a);
+    o.uniform_k = uniform_k_variant(mode, pl, j.a);
   }
   o.merged = merged;
   o.reduce = reduce_kind(j);
   o.direct_nb = pl.direct ? (j.a.K <= 1 ? 1 : 8) : 0;      // (launch_direct / launch_direct_pair, conv_direct.hip: NB = 1 for a.K <= 1, else 8)
   *out = o;
+  return ACG_OK;
+}
+
+int32_t acg_conv2d_uniform_k(int32_t on) {
+  ACG_REQUIRE(on == 0 || on == 1, ACG_ERR_INVALID_ARG, "conv2d_uniform_k: %d is neither 0 nor 1", on);
+  g_uniform_k = on;
   return ACG_OK;
 }
 

@@ -165,7 +165,13 @@ constexpr int conv_lds_bytes() {
 
 // LIN (FWD, !RAGGED, NVEC): the gathered channel count is a multiple of 4 (Cs == Cp), so filter row k of W[(tap, c)][n] is
 // row k of the [Kdim][N] matrix - the dense operand needs no (tap, channel) state (conv_body: run_boff).
-template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false>
+//
+// UK (FWD with LIN, or DGRAD; !RAGGED, NVEC): the gathered channel count is a multiple of BK, so a K-step lies inside ONE tap and
+// everything the loaders derive from k - tap, channel origin, tap-table entries, `live`, the dense row offset - is the same for
+// every lane of the block.  That state then lives in scalar registers and reaches the loads through the buffer descriptors (base
+// moved by the step's uniform offset, zero records for a dead step); a lane keeps loop-invariant byte offsets and spends its
+// VALU on the tap-mask test alone.  Same loads into the same LDS slots as the generic loaders: results are bit-identical.
+template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false>
 __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const int by, const int bz, const int gx, char* smem) {
   static_assert(WM * WN == 4, "4 waves per block");
   constexpr int TA = BM / (32 * WM), TB = BN / (32 * WN);
@@ -218,6 +224,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // pieces are written as 16-, 8- or 4-byte parts of the k-quads in LDS.
   constexpr int LPA = BM / 32, LPB = BN / 32;
   static_assert(!LIN || (MODE == MODE_FWD && NVEC && !RAGGED), "LIN: float4-able forward contraction");
+  static_assert(!UK || (NVEC && !RAGGED && (MODE == MODE_DGRAD || (MODE == MODE_FWD && LIN))), "UK: FWD LIN or DGRAD, 16-byte gathers");
   // (Filter rows as column quads - a thread owns one column and fetches the four k-rows of a quad with four dword loads off
   // one offset register, so the quad arrives in LDS order without a register transpose - was measured on top of LIN: 31.5
   // instead of 36.8 VALU instructions per K-step but 10 instead of 4 VMEM instructions, 404.4 vs 406.0 steps/s: dropped.)
@@ -283,6 +290,38 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
 #pragma unroll
     for (int u = 0; u < QB; ++u) { const int n = n0 + (tid >> 3) + 32 * u; nK[u] = n * p.K; nOk[u] = n < N; }
   }
+  // UK: (tap, channel origin) of the K-step in scalar registers - kernel arguments, block indices and the loop counter only -
+  // and per lane what never changes in the loop: the byte offset of each gathered row-quad and of each dense quad (kOob where
+  // the lane's column does not exist) and the complement of the row's tap mask.  The tap tables sit in one VGPR each, entry t
+  // in lane t (kMaxTaps = the 64 lanes of a wave), so a step fetches its entry with v_readlane instead of an LDS round trip.
+  // Nothing here relies on how the hardware treats soffset in its range check: the step's uniform offset moves the BASE of the
+  // descriptor (64-bit scalar adds) and shrinks its record count by the same bytes, so the check stays "voffset + 16 <=
+  // records" with soffset 0, exactly the test the generic loaders pass.  uk_shift makes every lane offset non-negative: FWD
+  // rows start up to (pt, pl) pixels in front of the tensor (RowInfo::base < 0), so the lane offsets are taken relative to
+  // that corner and the descriptor base moves back by as much; a descriptor base in front of the tensor is never
+  // dereferenced, because a lane whose tap reads inside the tensor lands inside it and every other lane is masked.
+  // (Host side, uniform_k_variant: both operands and the corner are at most 2^29 bytes, so a record count stays below 2^31,
+  // the byte arithmetic of a step fits 32 bits, and the masked offsets - kOob, or a lane offset with bit 31 set - are beyond it.)
+  static_assert(kMaxTaps == 64, "UK: a tap table per wave register");
+  int uk_t = 0, uk_c0 = 0, uk_shift = 0, uk_tabA = 0, uk_tabB = 0;
+  unsigned uk_va[UK ? QA : 1], uk_inv_lo[UK ? QA : 1], uk_inv_hi[UK ? QA : 1], uk_vb[UK ? RB : 1];
+  if constexpr (UK) {
+    const int k0 = ks_begin * BK;
+    uk_t = div_fast(k0, p.mg_cp, p.sh_cp); uk_c0 = k0 - uk_t * Cp;
+    uk_shift = MODE == MODE_FWD ? (p.pt * p.W + p.pl) * p.Cx : 0;
+    uk_tabA = tapA[lane];
+    if constexpr (MODE == MODE_DGRAD) uk_tabB = tapB[lane];
+#pragma unroll
+    for (int u = 0; u < QA; ++u) {
+      uk_va[u] = (unsigned)(myrow[u].base + uk_shift + 4 * (tid & 7)) * 4u;
+      uk_inv_lo[u] = ~myrow[u].mask_lo; uk_inv_hi[u] = ~myrow[u].mask_hi;
+    }
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+      if constexpr (MODE == MODE_DGRAD) uk_vb[u] = nOk[u] ? (unsigned)(nK[u] + 4 * (tid & 7)) * 4u : kOob;
+      else uk_vb[u] = nB < N ? (unsigned)((r0b + u) * NS + nB) * 4u : kOob;
+    }
+  }
 #ifdef ACG_NORM_PROBE
   // COST PROBE (tools only, `make probe`; never in the shipped library): what normalise-on-load would add to the loaders -
   // act((x - mean) * rstd + beta) on every GATHERED element on its way into LDS, zero padding applied after the activation.
@@ -305,9 +344,29 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     int t, kc, aoff, tb, bt, bc, boff, brow;
     bool kv;
     RowInfo wri[MODE == MODE_WGRAD ? LPA : 1];
+    const float* ug; const float* ud;      // UK: the step's descriptor bases and record counts (scalar registers)
+    unsigned ug_bytes, ud_bytes;
+  };
+  // UK: descriptor base `ptr + off` (elements; may lie in front of the tensor, see above) and what is left of `bytes` behind it
+  auto uk_window = [](const float* ptr, unsigned bytes, int off, bool on, const float*& base, unsigned& left) {
+    const int ob = off * 4, rem = (int)bytes - ob;      // 32-bit (uniform_k_variant: |ob| and bytes are at most 2^29): scalar compares only
+    base = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(ptr) + (uintptr_t)(long long)ob);
+    left = (on && rem > 0) ? (unsigned)rem : 0u;
   };
   auto load_prep = [&](int ks, bool live) {
     Prep q{};
+    if constexpr (UK) {
+      q.kv = live && uk_t < ntaps;
+      q.t = q.kv ? uk_t : 0;
+      const int ta = __builtin_amdgcn_readlane(uk_tabA, q.t);
+      uk_window(p.gsrc, p.g_bytes, ta + uk_c0 - uk_shift, q.kv, q.ug, q.ug_bytes);
+      if constexpr (MODE == MODE_DGRAD) uk_window(p.dense, p.d_bytes, __builtin_amdgcn_readlane(uk_tabB, q.t) + uk_c0, q.kv, q.ud, q.ud_bytes);
+      else uk_window(p.dense, p.d_bytes, ks * (BK * NS), live, q.ud, q.ud_bytes);      // LIN: filter row ks * BK; live => the step lies below Kdim (a multiple of BK)
+      uk_t += step_t; uk_c0 += step_c;
+      const bool wrap = uk_c0 >= Cp;
+      uk_c0 -= wrap ? Cp : 0; uk_t += wrap ? 1 : 0;
+      return q;
+    }
     if constexpr (MODE == MODE_WGRAD) {
 #pragma unroll
       for (int e = 0; e < LPA; ++e) q.wri[e] = rows[((ks - ks_begin) & 15) * BK + r0a + e];
@@ -340,7 +399,23 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   auto load_piece = [&](auto stage, int ks, bool live, const Prep& q, auto pc) {
     constexpr int ST = decltype(stage)::value;
     constexpr int I = decltype(pc)::value;
-    if constexpr (I < RA) {
+    if constexpr (UK) {
+      if constexpr (I < RA) {
+        // the one per-lane decision left: is the step's tap inside the tensor for this row?  bit t of the complemented mask,
+        // moved to bit 31, turns the lane offset of a dead tap into one of 2^31 or more: beyond any record count, and still
+        // 16 bytes short of wrapping
+        const unsigned inv = q.t < 32 ? uk_inv_lo[I] : uk_inv_hi[I];
+        const unsigned dead = (inv << (31u - ((unsigned)q.t & 31u))) & 0x80000000u;
+#ifdef ACG_NORM_PROBE
+        probe_ok[ST][I] = q.kv && dead == 0u;
+#endif
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.ug), 0, q.ug_bytes, 0x00020000);
+        ra[ST][I] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, uk_va[I] | dead, 0, 0));
+      } else {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.ud), 0, q.ud_bytes, 0x00020000);
+        rb[ST][I - RA] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, uk_vb[I - RA], 0, 0));
+      }
+    } else if constexpr (I < RA) {
       if constexpr (MODE == MODE_WGRAD) {   // raw rows now; the transpose happens at store time
         const RowInfo ri = q.wri[I];
         const bool ok = live && wg_nvalid > 0 && tap_ok(ri, wg_t);
@@ -600,7 +675,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   store_tile<MODE, BM, TA, TB, false>(acc, out_map<MODE, F32Tensors, COMPACT>(p, g), rows, outp, false, wm0, wn0, lrow, lk);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false>
+template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false>
 __global__ __launch_bounds__(256) void conv_mfma_f32(const ConvArgs p) {
   __shared__ __align__(16) char smem[conv_lds_bytes<MODE, BM, BN>()];
   if constexpr (MODE == MODE_WGRAD) {      // grid (tiles, 1, splits)
@@ -608,7 +683,7 @@ __global__ __launch_bounds__(256) void conv_mfma_f32(const ConvArgs p) {
     wgrad_xcd_map((int)(blockIdx.x + gridDim.x * blockIdx.z), (int)gridDim.x, (int)gridDim.z, tile, split);
     conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC>(p, tile, 0, split, (int)gridDim.x, smem);
   } else {
-    conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC, EPI, LIN>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, smem);
+    conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC, EPI, LIN, UK>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, smem);
   }
 }
 
@@ -622,14 +697,14 @@ __global__ __launch_bounds__(256) void conv_mfma_f32(const ConvArgs p) {
 // Blocks [0, nA) run contraction A with the grid (gxA, gyA, *), the rest run the weight gradient with (gxB, 1, *).
 struct PairGeom { int nA, gxA, gyA, gxB; };
 
-template <int MODE_A, int BMA, int BNA, int WMA, int WNA, int BMB, int BNB, int WMB, int WNB, bool RAGGED, bool LIN_A = false>
+template <int MODE_A, int BMA, int BNA, int WMA, int WNA, int BMB, int BNB, int WMB, int WNB, bool RAGGED, bool LIN_A = false, bool UK_A = false>
 __global__ __launch_bounds__(256) void conv_pair_f32(const ConvArgs a, const ConvArgs b, const PairGeom g) {
   constexpr int LA = conv_lds_bytes<MODE_A, BMA, BNA>(), LB = conv_lds_bytes<MODE_WGRAD, BMB, BNB>();
   __shared__ __align__(16) char smem[LA > LB ? LA : LB];      // one block runs one of the two programs
   const int L = (int)blockIdx.x;
   if (L < g.nA) {
     const int t = L / g.gxA;
-    conv_body<MODE_A, BMA, BNA, WMA, WNA, RAGGED, true, false, LIN_A>(a, L - t * g.gxA, t % g.gyA, t / g.gyA, g.gxA, smem);
+    conv_body<MODE_A, BMA, BNA, WMA, WNA, RAGGED, true, false, LIN_A, UK_A>(a, L - t * g.gxA, t % g.gyA, t / g.gyA, g.gxA, smem);
   } else {
     int tile, split;
     wgrad_xcd_map(L - g.nA, g.gxB, b.splits, tile, split);
@@ -673,9 +748,32 @@ static inline bool lin_variant(int mode, const Plan& pl, const ConvArgs& a) {
   return mode == MODE_FWD && !pl.ragged && pl.nvec && (a.C & 3) == 0 && !a.compact && !a.tap_classes;
 }
 
+// The UK variant (K-step state in scalar registers, conv_body): FWD where it is LIN, and DGRAD, with 16-byte gathers of a
+// channel count that is a multiple of the K-step - so a K-step lies inside one tap, also of a compacted tile or a stride class,
+// whose tables it reads like the generic loaders.  Weight gradients keep the generic loaders (their gathered rows change every
+// K-step).  Operands of at most 2^29 bytes and a padding corner of at most that: conv_body's masked offsets of 2^31 and more
+// are then beyond every record count.  g_uniform_k: acg_conv2d_uniform_k (acgan_conv_plan.h), the variant alone - never a plan.
+// One rule for launch_cfg, launch_pair, the bias + activation entry and the path query.
+extern int g_uniform_k;
+static inline bool uniform_k_variant(int mode, const Plan& pl, const ConvArgs& a) {
+  if (!g_uniform_k || pl.bf16 || pl.direct || pl.ragged) return false;
+  if (mode != MODE_DGRAD && !lin_variant(mode, pl, a)) return false;      // (FWD: LIN brings float4-able filter rows with it; DGRAD never reads NVEC)
+  const int cs = mode == MODE_DGRAD ? a.K : a.C;
+  const long long corner = mode == MODE_FWD ? (long long)(a.pt * (long long)a.W + a.pl) * a.Cx * 4 : 0;
+  return cs % BK == 0 && a.g_bytes <= (1u << 29) && a.d_bytes <= (1u << 29) && corner <= (1ll << 29);
+}
+
 template <int MODE, bool RAGGED, bool NVEC>
 static inline void launch_cfg(const Plan& pl, const ConvArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)(acg::ceil_div(pl.M, pl.bm) * acg::ceil_div(pl.N, pl.bn)), (unsigned)pl.classes, (unsigned)pl.splits);
+  if constexpr (MODE != MODE_WGRAD && !RAGGED) {
+    if (uniform_k_variant(MODE, pl, a)) {      // (one instantiation per tile: the DGRAD body is the same code for either NVEC)
+      constexpr bool LIN = MODE == MODE_FWD;
+      if (pl.cfg == 2) ACG_LAUNCH((conv_mfma_f32<MODE, 128, 32, 4, 1, false, true, false, LIN, true>), grid, dim3(256), 0, st, a);
+      else ACG_LAUNCH((conv_mfma_f32<MODE, 64, 64, 2, 2, false, true, false, LIN, true>), grid, dim3(256), 0, st, a);
+      return;
+    }
+  }
   // two tile shapes: 128x32 for narrow N, 64x64 otherwise.  128x128 / 128x64 variants existed through v4; with the
   // one-barrier pipeline they lost every layer of the tuning sweep (profiles/r1) and were dropped.
   if constexpr (MODE == MODE_FWD && !RAGGED && NVEC) {

@@ -34,6 +34,8 @@ typedef struct acg_conv_path {
                                     forward contraction it runs as */
   int32_t reduce;                /* ACG_REDUCE_*: the kernel that sums the slabs of the plain (not slabs-only) entry */
   int32_t direct_nb;             /* direct family: the NB template argument (1 or 8); 0 otherwise */
+  int32_t uniform_k;             /* fp32 MFMA: the loaders keep their K-step state in scalar registers (FWD where lin, and DGRAD,
+                                    with 16-byte gathers of a multiple of 32 channels); 0 for the other families */
 } acg_conv_path;
 
 /* The path of acg_conv2d_fwd / _dgrad / _wgrad (`which` = ACG_CONV_*) on `desc` with the storage `dtype` (ACG_F32, ACG_BF16 or
@@ -45,6 +47,11 @@ int32_t acg_conv2d_path(const acg_conv_desc* desc, int32_t which, int32_t dtype,
  * ACG_PAIR_*, or 0 where the entry would refuse the call.  The contractions of ACG_PAIR_F32 / _BF16 are
  * acg_conv2d_path(desc, A, dtype, 1) and acg_conv2d_path(desc, ACG_CONV_WGRAD, dtype, 0). */
 int32_t acg_conv2d_pair_path(const acg_conv_desc* desc, int32_t transposed, int32_t dtype, int32_t flags);
+
+/* Process-wide: on = 0 keeps every fp32 MFMA launch on the generic loaders, 1 (the default) lets the eligible ones take the
+ * uniform_k variant.  The two compute the same bits; no plan (tile, splits, reduction, workspace) depends on the switch.  It is
+ * there so that a test can run both in one process - not thread-safe against launches in flight on other threads. */
+int32_t acg_conv2d_uniform_k(int32_t on);
 
 #ifdef __cplusplus
 }
