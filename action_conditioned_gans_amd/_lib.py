@@ -46,7 +46,7 @@ class ConvPath(ctypes.Structure):
     REDUCES = ('none', 'plain', 'bf16', 'cols')
     _fields_ = [(n, c_int32) for n in (
         'family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce',
-        'direct_nb', 'uniform_k')]
+        'direct_nb', 'uniform_k', 'uniform_w')]
 
 
 PAIR_KINDS = ('refused', 'direct_pair', 'conv_pair_f32', 'conv_pair_bf16', 'two_launches', 'merged')      # ACG_PAIR_*
@@ -290,6 +290,7 @@ EXTENSIONS = {
         'acg_conv2d_pair_path': (c_int32, [_D, c_int32, c_int32, c_int32]),
         # the process-wide switch between the uniform_k loaders of the fp32 MFMA kernels and the generic ones (same bits either way)
         'acg_conv2d_uniform_k': (STATUS, [c_int32]),
+        'acg_conv2d_uniform_w': (STATUS, [c_int32]),      # the same for the weight gradients' uniform_w loaders
     }),
 }
 

@@ -34,6 +34,8 @@ using namespace acgconv;
 // acg_conv2d_uniform_k: the one process-wide switch of the shipped library.  It picks between two loaders that compute the same
 // bits (conv_f32_kernel.h: uniform_k_variant) and is read by nothing else - no plan, no workspace size depends on it.
 int acgconv::g_uniform_k = 1;
+// acg_conv2d_uniform_w: the same for the weight gradient's loaders (uniform_w_variant)
+int acgconv::g_uniform_w = 1;
 
 namespace {
 
@@ -229,7 +231,7 @@ int validate(const acg_conv_desc* d, const char* who) {
 }
 
 // Tuning hooks exist in -DACG_TUNING builds only (libacgan_hip_tuning.so, `make tuning`, used by tools/): the shipped
-// library has no process-wide mutable state beyond g_uniform_k above and reads no environment variable.
+// library has no process-wide mutable state beyond g_uniform_k / g_uniform_w above and reads no environment variable.
 #ifdef ACG_TUNING
 int g_force_cfg = -1, g_force_splits = -1;   // acg_debug_conv_plan: force a tile configuration / split-K factor; -1 = heuristic
 int env_int(const char* name, int dflt) {
@@ -818,6 +820,7 @@ int32_t acg_conv2d_path(const acg_conv_desc* d, int32_t which, int32_t dtype, in
     const int mode = j.which == ACG_CONV_FWD ? MODE_FWD : j.which == ACG_CONV_DGRAD ? MODE_DGRAD : MODE_WGRAD;
     o.lin = lin_variant(mode, pl, j.a);
     o.uniform_k = uniform_k_variant(mode, pl, j.a);
+    o.uniform_w = uniform_w_variant(mode, pl, j.a);
   }
   o.merged = merged;
   o.reduce = reduce_kind(j);
@@ -829,6 +832,12 @@ int32_t acg_conv2d_path(const acg_conv_desc* d, int32_t which, int32_t dtype, in
 int32_t acg_conv2d_uniform_k(int32_t on) {
   ACG_REQUIRE(on == 0 || on == 1, ACG_ERR_INVALID_ARG, "conv2d_uniform_k: %d is neither 0 nor 1", on);
   g_uniform_k = on;
+  return ACG_OK;
+}
+
+int32_t acg_conv2d_uniform_w(int32_t on) {
+  ACG_REQUIRE(on == 0 || on == 1, ACG_ERR_INVALID_ARG, "conv2d_uniform_w: %d is neither 0 nor 1", on);
+  g_uniform_w = on;
   return ACG_OK;
 }
 

@@ -157,9 +157,10 @@ __device__ __forceinline__ void tile_stats_epilogue(V&& value, float* red, float
 // The block program.  (bx, by, bz) / gx stand in for blockIdx / gridDim.x so that conv_pair_f32 below can run the blocks
 // of two contractions out of one 1-D grid.
 // LDS of one block program: two K-steps of both tiles, the row infos, the tap tables.
-template <int MODE, int BM, int BN>
+// (UW: the weight gradient's row table as three arrays of 2 x 256 words, see conv_body.)
+template <int MODE, int BM, int BN, bool UW = false>
 constexpr int conv_lds_bytes() {
-  return 2 * 8 * (BM + BN) * (int)sizeof(f4) + ((MODE == MODE_WGRAD) ? 2 * 256 : BM) * (int)sizeof(RowInfo) +
+  return 2 * 8 * (BM + BN) * (int)sizeof(f4) + (UW ? 3 * 2 * 256 * (int)sizeof(unsigned) : ((MODE == MODE_WGRAD) ? 2 * 256 : BM) * (int)sizeof(RowInfo)) +
          2 * kMaxTaps * (int)sizeof(int);
 }
 
@@ -171,24 +172,35 @@ constexpr int conv_lds_bytes() {
 // every lane of the block.  That state then lives in scalar registers and reaches the loads through the buffer descriptors (base
 // moved by the step's uniform offset, zero records for a dead step); a lane keeps loop-invariant byte offsets and spends its
 // VALU on the tap-mask test alone.  Same loads into the same LDS slots as the generic loaders: results are bit-identical.
-template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false>
+//
+// UW (WGRAD; !RAGGED, NVEC): the weight gradient's counterpart.  Its gathered ROWS change every K-step, so what goes to the scalar
+// side is the rest: `live` and the dense row origin reach the loads through the descriptors (dY rows at or beyond Kdim and dead steps
+// fall to the hardware range check), a lane keeps loop-invariant byte offsets, and a gathered row costs its offset plus the mask
+// test.  The row table holds byte offsets and complemented masks as three word arrays, written UNR K-steps at a time by
+// straight-line code in ONE fixed unrolled copy of the loop and read at compile-time slots.  Same loads, same LDS slots, same bits.
+#ifndef ACG_NST
+#define ACG_NST 3      // whole-step sweep: 2 -> 339.5, 3 -> 349, 4 -> 344, 5 -> 340 steps/s
+#endif
+template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false, bool UW = false>
 __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const int by, const int bz, const int gx, char* smem) {
   static_assert(WM * WN == 4, "4 waves per block");
   constexpr int TA = BM / (32 * WM), TB = BN / (32 * WN);
   constexpr int QA = BM / 32, QB = BN / 32;  // quads per thread per K-step
   constexpr int NROW = (MODE == MODE_WGRAD) ? 2 * 256 : BM;  // WGRAD: row infos of 2 x 8 K-steps (chunk parity)
-#ifndef ACG_NST
-#define ACG_NST 3      // whole-step sweep: 2 -> 339.5, 3 -> 349, 4 -> 344, 5 -> 340 steps/s
-#endif
   constexpr int NST = ACG_NST;           // register stages: global loads run NST K-steps ahead of their MFMAs
+  constexpr int UNR = (NST % 2 == 0) ? NST : 2 * NST;      // the K-loop's unroll: (stage, LDS buffer) repeat with period lcm(NST, 2)
 
   constexpr int KSLOTS = 8;              // 16-byte k-slots (quads) per tile column
   constexpr int ASZ = KSLOTS * BM, BSZ = KSLOTS * BN;
-  static_assert(conv_lds_bytes<MODE, BM, BN>() == (2 * ASZ + 2 * BSZ) * (int)sizeof(f4) + NROW * (int)sizeof(RowInfo) + 2 * kMaxTaps * (int)sizeof(int), "LDS layout");
+  constexpr int ROWB = UW ? 3 * 2 * 256 * (int)sizeof(unsigned) : NROW * (int)sizeof(RowInfo);
+  static_assert(conv_lds_bytes<MODE, BM, BN, UW>() == (2 * ASZ + 2 * BSZ) * (int)sizeof(f4) + ROWB + 2 * kMaxTaps * (int)sizeof(int), "LDS layout");
+  static_assert(!UW || BM != 64 || BN != 64 || conv_lds_bytes<MODE, BM, BN, UW>() + 8 <= 40960, "UW 64x64: four blocks per CU, also beside compact_taps' two words in conv_pair_f32");
   f4* const As_all = reinterpret_cast<f4*>(smem);                         // [2 * ASZ]
   f4* const Bs_all = As_all + 2 * ASZ;                                    // [2 * BSZ]
   RowInfo* const rows = reinterpret_cast<RowInfo*>(Bs_all + 2 * BSZ);     // [NROW]
-  int* const tapA = reinterpret_cast<int*>(rows + NROW);                  // [kMaxTaps]
+  // UW: [3][2][256] words - byte offset, ~mask_lo, ~mask_hi of the rows of two chunks of UNR K-steps (chunk parity)
+  char* const uw_tab = reinterpret_cast<char*>(Bs_all + 2 * BSZ);
+  int* const tapA = reinterpret_cast<int*>(uw_tab + ROWB);                // [kMaxTaps]
   int* const tapB = tapA + kMaxTaps;                                      // [kMaxTaps]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -225,6 +237,8 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   constexpr int LPA = BM / 32, LPB = BN / 32;
   static_assert(!LIN || (MODE == MODE_FWD && NVEC && !RAGGED), "LIN: float4-able forward contraction");
   static_assert(!UK || (NVEC && !RAGGED && (MODE == MODE_DGRAD || (MODE == MODE_FWD && LIN))), "UK: FWD LIN or DGRAD, 16-byte gathers");
+  static_assert(!UW || (MODE == MODE_WGRAD && NVEC && !RAGGED && !UK), "UW: weight gradient with 16-byte loads on both sides");
+  static_assert(!UW || (NST == 3 && UNR * BK <= 256), "UW: the row-table schedule below is written for three stages (a chunk of 6 K-steps, one row per thread)");
   // (Filter rows as column quads - a thread owns one column and fetches the four k-rows of a quad with four dword loads off
   // one offset register, so the quad arrives in LDS order without a register transpose - was measured on top of LIN: 31.5
   // instead of 36.8 VALU instructions per K-step but 10 instead of 4 VMEM instructions, 404.4 vs 406.0 steps/s: dropped.)
@@ -304,7 +318,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // the byte arithmetic of a step fits 32 bits, and the masked offsets - kOob, or a lane offset with bit 31 set - are beyond it.)
   static_assert(kMaxTaps == 64, "UK: a tap table per wave register");
   int uk_t = 0, uk_c0 = 0, uk_shift = 0, uk_tabA = 0, uk_tabB = 0;
-  unsigned uk_va[UK ? QA : 1], uk_inv_lo[UK ? QA : 1], uk_inv_hi[UK ? QA : 1], uk_vb[UK ? RB : 1];
+  unsigned uk_va[UK ? QA : 1], uk_inv_lo[UK ? QA : 1], uk_inv_hi[UK ? QA : 1], uk_vb[(UK || UW) ? RB : 1];
   if constexpr (UK) {
     const int k0 = ks_begin * BK;
     uk_t = div_fast(k0, p.mg_cp, p.sh_cp); uk_c0 = k0 - uk_t * Cp;
@@ -321,6 +335,28 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
       if constexpr (MODE == MODE_DGRAD) uk_vb[u] = nOk[u] ? (unsigned)(nK[u] + 4 * (tid & 7)) * 4u : kOob;
       else uk_vb[u] = nB < N ? (unsigned)((r0b + u) * NS + nB) * 4u : kOob;
     }
+  }
+  // UW.  Gathered side: a row's table entry is its byte offset from the padding corner (uk_shift, as in UK: never negative) and
+  // its complemented mask; the lane adds uw_lane = its (tap, channel quad) in bytes - 2^31 where its output rows do not exist, so
+  // it stays masked whatever the row - and ors in bit wg_t of the complement, moved to bit 31 (shift uw_sh; the lo / hi word is
+  // chosen once, by the table address uw_rm).  Offsets stay below 2^31 + 2^30 * 1.5: masked ones are beyond every record count
+  // and short of wrapping.  The gathered descriptor starts at the corner and has zero records in a dead step; the dense one starts
+  // at the step's first dY row and ends at row Kdim (uw_dlim).  uw_ro / uw_rm: byte positions in uw_tab of this thread's reads
+  // (offset array; its mask word's array) in the table half of the chunk a round of the unrolled loop starts in ([0]) and in the
+  // other half ([1]).  They are set at the top of a round from the round's number - no state is carried around the loop.
+  constexpr unsigned UW_ARR = 2 * 256 * sizeof(unsigned), UW_HALF = 256 * sizeof(unsigned);
+  unsigned uw_lane = 0, uw_sh = 0, uw_ro[2] = {0, 0}, uw_rm[2] = {0, 0}, uw_half = 0, uw_dlim = 0;
+  unsigned long long uw_rep = 0ull;
+  if constexpr (UW) {
+    uk_shift = (p.pt * p.W + p.pl) * p.Cx;
+    uw_lane = wg_nvalid > 0 ? (unsigned)wg_off * 4u : 0x80000000u;
+    uw_sh = 31u - ((unsigned)wg_t & 31u);
+    uw_ro[0] = (unsigned)r0a * 4u; uw_rm[0] = uw_ro[0] + (wg_t < 32 ? 1u : 2u) * UW_ARR;      // (prologue: chunk 0 in half 0)
+    uw_rep = tap_rep(p.KH, p.KW);
+    const unsigned long long dend = (unsigned long long)Kdim * (unsigned long long)p.Ky * 4ull;
+    uw_dlim = dend < (unsigned long long)p.d_bytes ? (unsigned)dend : p.d_bytes;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) uk_vb[u] = nB < N ? (unsigned)((r0b + u) * p.Ky + nB) * 4u : kOob;
   }
 #ifdef ACG_NORM_PROBE
   // COST PROBE (tools only, `make probe`; never in the shipped library): what normalise-on-load would add to the loaders -
@@ -346,6 +382,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     RowInfo wri[MODE == MODE_WGRAD ? LPA : 1];
     const float* ug; const float* ud;      // UK: the step's descriptor bases and record counts (scalar registers)
     unsigned ug_bytes, ud_bytes;
+    unsigned uoff[UW ? LPA : 1], uinv[UW ? LPA : 1];      // UW: table entries of the step's rows (this lane's mask word)
   };
   // UK: descriptor base `ptr + off` (elements; may lie in front of the tensor, see above) and what is left of `bytes` behind it
   auto uk_window = [](const float* ptr, unsigned bytes, int off, bool on, const float*& base, unsigned& left) {
@@ -353,8 +390,21 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     base = reinterpret_cast<const float*>(reinterpret_cast<uintptr_t>(ptr) + (uintptr_t)(long long)ob);
     left = (on && rem > 0) ? (unsigned)rem : 0u;
   };
-  auto load_prep = [&](int ks, bool live) {
+  // sc, wc (UW only): the step's slot in its row-table chunk, (ks - ks_begin) % UNR, and whether that chunk is the one behind
+  // the chunk the round started in - compile-time constants of the unrolled copy
+  auto load_prep = [&](int ks, bool live, auto sc, auto wc) {
     Prep q{};
+    if constexpr (UW) {
+      constexpr int S = decltype(sc)::value, W = decltype(wc)::value;
+      typedef unsigned urow __attribute__((ext_vector_type(LPA)));
+      const urow o = *reinterpret_cast<const urow*>(uw_tab + uw_ro[W] + S * BK * 4);
+      const urow m = *reinterpret_cast<const urow*>(uw_tab + uw_rm[W] + S * BK * 4);
+#pragma unroll
+      for (int e = 0; e < LPA; ++e) { q.uoff[e] = o[e]; q.uinv[e] = m[e]; }
+      uk_window(p.gsrc, p.g_bytes, -uk_shift, live, q.ug, q.ug_bytes);
+      uk_window(p.dense, uw_dlim, ks * (BK * p.Ky), live, q.ud, q.ud_bytes);      // rows at or beyond Kdim: beyond the record count
+      return q;
+    }
     if constexpr (UK) {
       q.kv = live && uk_t < ntaps;
       q.t = q.kv ? uk_t : 0;
@@ -399,7 +449,19 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   auto load_piece = [&](auto stage, int ks, bool live, const Prep& q, auto pc) {
     constexpr int ST = decltype(stage)::value;
     constexpr int I = decltype(pc)::value;
-    if constexpr (UK) {
+    if constexpr (UW) {
+      if constexpr (I < RA) {      // raw rows now; the transpose happens at store time
+        const unsigned dead = (q.uinv[I] << uw_sh) & 0x80000000u;
+#ifdef ACG_NORM_PROBE
+        probe_ok[ST][I] = live && dead == 0u && uw_lane < 0x80000000u;
+#endif
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.ug), 0, q.ug_bytes, 0x00020000);
+        ra[ST][I] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, (q.uoff[I] + uw_lane) | dead, 0, 0));
+      } else {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(q.ud), 0, q.ud_bytes, 0x00020000);
+        rb[ST][I - RA] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, uk_vb[I - RA], 0, 0));
+      }
+    } else if constexpr (UK) {
       if constexpr (I < RA) {
         // the one per-lane decision left: is the step's tap inside the tensor for this row?  bit t of the complemented mask,
         // moved to bit 31, turns the lane offset of a dead tap into one of 2^31 or more: beyond any record count, and still
@@ -465,7 +527,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     }
   };
   auto load_tiles = [&](auto stage, int ks, bool live) {
-    const Prep q = load_prep(ks, live);
+    const Prep q = load_prep(ks, live, stage, std::integral_constant<int, 0>{});      // (prologue: stage J holds step ks_begin + J = slot J of chunk 0)
     static_for<0, NLD>([&](auto pc) { load_piece(stage, ks, live, q, pc); });
   };
 
@@ -592,10 +654,21 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   auto wgrad_rows = [&](int chunk) {
     if constexpr (MODE == MODE_WGRAD) rows[(chunk & 1) * 256 + tid] = row_info<MODE, F32Tensors, false>(p, g, (ks_begin + 8 * chunk) * BK + tid, Kdim);
   };
+  // UW: a chunk is UNR K-steps (192 of the 256 rows the threads derive are read), so a step's slot in its chunk is the unrolled
+  // copy's own constant and the refill sits in ONE copy - the one whose successor issues the first loads of the next chunk -
+  // as straight-line code: no condition (rows at or beyond Kdim come out dead), no loop, nothing divergent.
+  auto uw_rows = [&](int row0, unsigned half) {
+    const WgradRow w = wgrad_row<F32Tensors>(p, row0 + tid, Kdim, uk_shift, uw_rep);
+    const unsigned at = ((unsigned)tid * 4u) ^ half;
+    *reinterpret_cast<unsigned*>(uw_tab + at) = w.off;
+    *reinterpret_cast<unsigned*>(uw_tab + UW_ARR + at) = w.inv_lo;
+    *reinterpret_cast<unsigned*>(uw_tab + 2 * UW_ARR + at) = w.inv_hi;
+  };
 
   // prologue: stages 0..NST-1 <- steps ks_begin..+NST-1; step ks_begin -> LDS buffer 0
   if (ks_begin < ks_end) {
-    if constexpr (MODE == MODE_WGRAD) { wgrad_rows(0); __syncthreads(); }
+    if constexpr (UW) { uw_rows(ks_begin * BK, 0u); __syncthreads(); }
+    else if constexpr (MODE == MODE_WGRAD) { wgrad_rows(0); __syncthreads(); }
     static_for<0, NST>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       load_tiles(jc, ks_begin + J, ks_begin + J < ks_end);
@@ -606,12 +679,20 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // iteration ks: LDS[buf] holds step ks; stage J (its source) is free; stage J+1 holds step ks+1.
   // The loads of the step NST ahead are dealt out between the MFMAs and the order is pinned with sched_barrier: it
   // keeps the fragment reads of group t+1 in front of the MFMAs of group t and spreads the VMEM issue over the K-step.
-  auto iterate = [&](auto jc, int ks, int buf) {
-    constexpr int J = decltype(jc)::value;
+  auto iterate = [&](auto uc, int ks) {
+    constexpr int C = decltype(uc)::value, J = C % NST;      // C: the unrolled copy = (ks - ks_begin) % UNR
+    const std::integral_constant<int, J> jc{};
+    const int buf = C & 1;
     using SN = std::integral_constant<int, (J + 1) % NST>;
     const bool live = ks + NST < ks_end;
+    if constexpr (UW && C == 0) {      // round (ks - ks_begin) / UNR starts in chunk half `round & 1`: derived, not carried (see the loop below)
+      uw_half = ((__umulhi((unsigned)(ks - ks_begin), 0xAAAAAAABu) >> 2) & 1u) * UW_HALF;
+      static_assert(!UW || UNR == 6, "UW: x / 6 = umulhi(x, 0xAAAAAAAB) >> 2");
+      uw_ro[0] = ((unsigned)r0a * 4u) ^ uw_half; uw_ro[1] = uw_ro[0] ^ UW_HALF;
+      uw_rm[0] = uw_ro[0] + (wg_t < 32 ? 1u : 2u) * UW_ARR; uw_rm[1] = uw_rm[0] ^ UW_HALF;
+    }
     frag_read(buf, std::integral_constant<int, 0>{});
-    const Prep q = load_prep(ks + NST, live);
+    const Prep q = load_prep(ks + NST, live, std::integral_constant<int, (C + NST) % UNR>{}, std::integral_constant<int, (C + NST) / UNR>{});
     store_tiles(SN{}, buf ^ 1);       // overlaps the LDS latency of the first fragments and of the lookups
     __builtin_amdgcn_sched_barrier(0);
     static_for<0, NM>([&](auto ic) {
@@ -624,7 +705,9 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
       });
       __builtin_amdgcn_sched_barrier(0);
     });
-    if constexpr (MODE == MODE_WGRAD) {
+    if constexpr (UW) {
+      if constexpr ((C + NST + 1) % UNR == 0) uw_rows((ks + NST + 1) * BK, uw_half ^ UW_HALF);      // the chunk whose loads start in the NEXT iteration
+    } else if constexpr (MODE == MODE_WGRAD) {
       const int rel = ks - ks_begin + NST + 1;      // first step whose loads are issued in the NEXT iteration
       if ((rel & 7) == 0 && ks + NST + 1 < ks_end) wgrad_rows(rel >> 3);
     }
@@ -634,11 +717,9 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   // besides the loop entry, so the compiler's outstanding-load bookkeeping stays exact (chained `if (ks+j < end)`
   // do not: each skipped iteration is a second path into the next one and the merge drains vmcnt to 0)
   if (ks_begin < ks_end) {
-    constexpr int UNR = (NST % 2 == 0) ? NST : 2 * NST;
     int ks = ks_begin;
     while (run_unrolled<0, UNR>([&](auto ic) {
-      constexpr int I = decltype(ic)::value;
-      iterate(std::integral_constant<int, I % NST>{}, ks, I & 1);
+      iterate(ic, ks);
       return ++ks < ks_end;
     })) {
     }
@@ -675,13 +756,13 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   store_tile<MODE, BM, TA, TB, false>(acc, out_map<MODE, F32Tensors, COMPACT>(p, g), rows, outp, false, wm0, wn0, lrow, lk);
 }
 
-template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false>
+template <int MODE, int BM, int BN, int WM, int WN, bool RAGGED, bool NVEC, bool EPI = false, bool LIN = false, bool UK = false, bool UW = false>
 __global__ __launch_bounds__(256) void conv_mfma_f32(const ConvArgs p) {
-  __shared__ __align__(16) char smem[conv_lds_bytes<MODE, BM, BN>()];
+  __shared__ __align__(16) char smem[conv_lds_bytes<MODE, BM, BN, UW>()];
   if constexpr (MODE == MODE_WGRAD) {      // grid (tiles, 1, splits)
     int tile, split;
     wgrad_xcd_map((int)(blockIdx.x + gridDim.x * blockIdx.z), (int)gridDim.x, (int)gridDim.z, tile, split);
-    conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC>(p, tile, 0, split, (int)gridDim.x, smem);
+    conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC, false, false, false, UW>(p, tile, 0, split, (int)gridDim.x, smem);
   } else {
     conv_body<MODE, BM, BN, WM, WN, RAGGED, NVEC, EPI, LIN, UK>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, (int)gridDim.x, smem);
   }
@@ -697,9 +778,9 @@ __global__ __launch_bounds__(256) void conv_mfma_f32(const ConvArgs p) {
 // Blocks [0, nA) run contraction A with the grid (gxA, gyA, *), the rest run the weight gradient with (gxB, 1, *).
 struct PairGeom { int nA, gxA, gyA, gxB; };
 
-template <int MODE_A, int BMA, int BNA, int WMA, int WNA, int BMB, int BNB, int WMB, int WNB, bool RAGGED, bool LIN_A = false, bool UK_A = false>
+template <int MODE_A, int BMA, int BNA, int WMA, int WNA, int BMB, int BNB, int WMB, int WNB, bool RAGGED, bool LIN_A = false, bool UK_A = false, bool UW_B = false>
 __global__ __launch_bounds__(256) void conv_pair_f32(const ConvArgs a, const ConvArgs b, const PairGeom g) {
-  constexpr int LA = conv_lds_bytes<MODE_A, BMA, BNA>(), LB = conv_lds_bytes<MODE_WGRAD, BMB, BNB>();
+  constexpr int LA = conv_lds_bytes<MODE_A, BMA, BNA>(), LB = conv_lds_bytes<MODE_WGRAD, BMB, BNB, UW_B>();
   __shared__ __align__(16) char smem[LA > LB ? LA : LB];      // one block runs one of the two programs
   const int L = (int)blockIdx.x;
   if (L < g.nA) {
@@ -708,7 +789,7 @@ __global__ __launch_bounds__(256) void conv_pair_f32(const ConvArgs a, const Con
   } else {
     int tile, split;
     wgrad_xcd_map(L - g.nA, g.gxB, b.splits, tile, split);
-    conv_body<MODE_WGRAD, BMB, BNB, WMB, WNB, RAGGED, true>(b, tile, 0, split, g.gxB, smem);
+    conv_body<MODE_WGRAD, BMB, BNB, WMB, WNB, RAGGED, true, false, false, false, UW_B>(b, tile, 0, split, g.gxB, smem);
   }
 }
 
@@ -750,8 +831,8 @@ static inline bool lin_variant(int mode, const Plan& pl, const ConvArgs& a) {
 
 // The UK variant (K-step state in scalar registers, conv_body): FWD where it is LIN, and DGRAD, with 16-byte gathers of a
 // channel count that is a multiple of the K-step - so a K-step lies inside one tap, also of a compacted tile or a stride class,
-// whose tables it reads like the generic loaders.  Weight gradients keep the generic loaders (their gathered rows change every
-// K-step).  Operands of at most 2^29 bytes and a padding corner of at most that: conv_body's masked offsets of 2^31 and more
+// whose tables it reads like the generic loaders.  Weight gradients never take it (their gathered rows change every K-step; they
+// have a variant of their own, uniform_w_variant below).  Operands of at most 2^29 bytes and a padding corner of at most that: conv_body's masked offsets of 2^31 and more
 // are then beyond every record count.  g_uniform_k: acg_conv2d_uniform_k (acgan_conv_plan.h), the variant alone - never a plan.
 // One rule for launch_cfg, launch_pair, the bias + activation entry and the path query.
 extern int g_uniform_k;
@@ -763,9 +844,27 @@ static inline bool uniform_k_variant(int mode, const Plan& pl, const ConvArgs& a
   return cs % BK == 0 && a.g_bytes <= (1u << 29) && a.d_bytes <= (1u << 29) && corner <= (1ll << 29);
 }
 
+// The UW variant (conv_body): a weight gradient with 16-byte loads on both sides - gathered channels a multiple of 4 (any such
+// count: nothing in it needs a K-step inside one tap), dY rows float4-able.  The same 2^29-byte bounds as UK on both operands and
+// the padding corner, for the same reason.  g_uniform_w: acg_conv2d_uniform_w (acgan_conv_plan.h), the variant alone - never a plan.
+// One rule for launch_cfg, launch_pair and the path query (launch_pair leaves one tile combination out: conv_f32_pair.hip, launch_b).
+extern int g_uniform_w;
+static inline bool uniform_w_variant(int mode, const Plan& pl, const ConvArgs& a) {
+  if (!g_uniform_w || mode != MODE_WGRAD || pl.bf16 || pl.direct || pl.ragged || !pl.nvec) return false;
+  const long long corner = (long long)(a.pt * (long long)a.W + a.pl) * a.Cx * 4;
+  return a.g_bytes <= (1u << 29) && a.d_bytes <= (1u << 29) && corner <= (1ll << 29);
+}
+
 template <int MODE, bool RAGGED, bool NVEC>
 static inline void launch_cfg(const Plan& pl, const ConvArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)(acg::ceil_div(pl.M, pl.bm) * acg::ceil_div(pl.N, pl.bn)), (unsigned)pl.classes, (unsigned)pl.splits);
+  if constexpr (MODE == MODE_WGRAD && !RAGGED && NVEC) {
+    if (uniform_w_variant(MODE, pl, a)) {
+      if (pl.cfg == 2) ACG_LAUNCH((conv_mfma_f32<MODE, 128, 32, 4, 1, false, true, false, false, false, true>), grid, dim3(256), 0, st, a);
+      else ACG_LAUNCH((conv_mfma_f32<MODE, 64, 64, 2, 2, false, true, false, false, false, true>), grid, dim3(256), 0, st, a);
+      return;
+    }
+  }
   if constexpr (MODE != MODE_WGRAD && !RAGGED) {
     if (uniform_k_variant(MODE, pl, a)) {      // (one instantiation per tile: the DGRAD body is the same code for either NVEC)
       constexpr bool LIN = MODE == MODE_FWD;

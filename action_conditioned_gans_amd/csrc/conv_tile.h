@@ -142,6 +142,35 @@ __device__ __forceinline__ bool tap_ok(const RowInfo& ri, int t) {
 
 constexpr unsigned kOob = 0xFFFFFF00u;   // >= any num_records (tensors are < 2^30 elements)
 
+// ---- row table of the weight gradient's UW loaders (conv_f32_kernel.h) ----------------------------------------------------------
+// tap_mask without its loop: the column range of one filter row, repeated into every filter row by a multiply with
+// rep = sum over a < KH of 2^(a * nb) (tap_rep; no carries, the range is narrower than nb bits), cut to the rows [lo_a, hi_a).
+__device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {      // bits [lo, hi) with 0 <= lo and hi <= 64; none where hi <= lo
+  const int n = hi - lo;
+  return n > 0 ? (~0ull >> ((64 - n) & 63)) << (lo & 63) : 0ull;
+}
+__device__ __forceinline__ unsigned long long tap_rep(int na, int nb) {
+  unsigned long long rep = 0ull;
+  for (int a = 0; a < na; ++a) rep |= 1ull << (a * nb);
+  return rep;
+}
+__device__ __forceinline__ unsigned long long tap_mask_closed(int lo_a, int hi_a, int lo_b, int hi_b, int nb, unsigned long long rep) {
+  return (bit_range(lo_b, hi_b) * rep) & bit_range(lo_a * nb, hi_a * nb);
+}
+// Output pixel r = (b, p, q) as a K position of the weight gradient: the BYTE offset of its (tap 0, channel 0) source element,
+// taken from the padding corner (`shift` elements in front of the tensor: never negative), and the COMPLEMENT of its tap mask.
+// Straight-line code: a row at or beyond `limit` is selected to (0, all taps dead), not branched around.
+struct WgradRow { unsigned off, inv_lo, inv_hi; };
+template <class TR>
+__device__ __forceinline__ WgradRow wgrad_row(const ConvArgs& p, const int r, const int limit, const int shift, const unsigned long long rep) {
+  const int t2 = div_fast(r, p.mg_ow, p.sh_ow), q = r - t2 * p.OW, b = div_fast(t2, p.mg_oh, p.sh_oh), pp = t2 - b * p.OH;
+  const int y0 = pp * p.sh - p.pt, x0 = q * p.sw - p.pl;
+  const unsigned long long m = tap_mask_closed(max(0, -y0), min(p.KH, p.H - y0), max(0, -x0), min(p.KW, p.W - x0), p.KW, rep);
+  const bool in = r < limit;
+  const unsigned off = (unsigned)(((b * p.H + y0) * p.W + x0) * TR::x_pitch(p) + shift) * 4u;
+  return WgradRow{in ? off : 0u, in ? ~(unsigned)m : ~0u, in ? ~(unsigned)(m >> 32) : ~0u};
+}
+
 // ---- storage traits: what the element type of the tensors changes in the addressing -----------------------------------------
 // unit: channels per 16-byte load, every gathered channel count is padded to it per tap; x_pitch / y_pitch: channels between two
 // pixels of x (dx) / y (dy) in memory; tap_fwd / tap_dgrad: elements between two taps of the filter copy FWD / DGRAD reads;

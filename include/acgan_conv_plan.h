@@ -36,6 +36,11 @@ typedef struct acg_conv_path {
   int32_t direct_nb;             /* direct family: the NB template argument (1 or 8); 0 otherwise */
   int32_t uniform_k;             /* fp32 MFMA: the loaders keep their K-step state in scalar registers (FWD where lin, and DGRAD,
                                     with 16-byte gathers of a multiple of 32 channels); 0 for the other families */
+  int32_t uniform_w;             /* fp32 MFMA weight gradient: `live`, the dY row origin and the range tests ride in the buffer
+                                    descriptors, the row table holds byte offsets (16-byte loads on both sides: not ragged, nvec);
+                                    0 for the other contractions and families.  As B of conv_pair_f32 the weight gradient
+                                    follows this answer except for a 64 x 64 tile beside a 128 x 32 contraction A, which
+                                    keeps the generic loaders (same bits) */
 } acg_conv_path;
 
 /* The path of acg_conv2d_fwd / _dgrad / _wgrad (`which` = ACG_CONV_*) on `desc` with the storage `dtype` (ACG_F32, ACG_BF16 or
@@ -52,6 +57,10 @@ int32_t acg_conv2d_pair_path(const acg_conv_desc* desc, int32_t transposed, int3
  * uniform_k variant.  The two compute the same bits; no plan (tile, splits, reduction, workspace) depends on the switch.  It is
  * there so that a test can run both in one process - not thread-safe against launches in flight on other threads. */
 int32_t acg_conv2d_uniform_k(int32_t on);
+
+/* The same switch for the uniform_w variant of the weight gradients: 0 or 1 (the default), the variant alone, never a plan; the two
+ * loaders compute the same bits.  Independent of acg_conv2d_uniform_k, which never touches a weight gradient. */
+int32_t acg_conv2d_uniform_w(int32_t on);
 
 #ifdef __cplusplus
 }

@@ -84,9 +84,9 @@ int main() {
       const int w = atoi(tok[2]);
       const int rc = acg_conv2d_path(&d, w, atoi(tok[3]), atoi(tok[4]), &p);
       if (rc != ACG_OK) { printf("path %s %s error=%d\n", tok[1], w >= 0 && w <= 2 ? which[w] : "?", rc); continue; }
-      printf("path %s %s family=%s tile=%dx%d tiles=%d classes=%d nk=%d splits=%d ragged=%d nvec=%d lin=%d compact=%d merged=%d reduce=%s nb=%d\n",
+      printf("path %s %s family=%s tile=%dx%d tiles=%d classes=%d nk=%d splits=%d ragged=%d nvec=%d lin=%d compact=%d merged=%d reduce=%s nb=%d uk=%d uw=%d\n",
              tok[1], which[w], fam[p.family], p.tile_rows, p.tile_cols, p.tiles, p.classes, p.nk, p.splits, p.ragged, p.nvec, p.lin, p.compact,
-             p.merged, red[p.reduce], p.direct_nb);
+             p.merged, red[p.reduce], p.direct_nb, p.uniform_k, p.uniform_w);
     } else if (!strcmp(tok[0], "pair") && n == 5 + 17 && read_desc(tok + 5, &d)) {
       printf("pair %s flags=%d kind=%s\n", tok[1], atoi(tok[4]), pairs[acg_conv2d_pair_path(&d, atoi(tok[2]), atoi(tok[3]), atoi(tok[4]))]);
     } else if (!strcmp(tok[0], "epi") && n == 3 + 17 && read_desc(tok + 3, &d)) {
