@@ -234,8 +234,9 @@ EXTENSIONS = {
     # from an update counter they advance themselves (optim.LrSchedule); and scheduled sampling of the rollout's fed-back inputs;
     # and the launches of the planner around the generator forwards (plan.Planner)
     # and instance noise on the discriminator's inputs with the statistics of its logits (train.Trainer d_noise / d_stats)
+    # and the learned posterior of the noise input, which draws from the noise input's state (train.Trainer posterior)
     'rollout': Extension('include/acgan_rollout.h', 'training through rollouts, scheduled sampling, the gradient clip, the noise input, '
-                         'learning-rate schedules, planning and instance noise run on the HIP library only', {
+                         'learning-rate schedules, planning, instance noise and the latent posterior run on the HIP library only', {
         'acg_dna_bwd_image': (STATUS, [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, c_float] + [c_int32] * 6 + [_P]),
         'acg_action_grad': (STATUS, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_float, _P]),
         'acg_grad_clip_norm_workspace_bytes': (c_size_t, [c_int64, ctypes.POINTER(NormSegments)]),
@@ -260,6 +261,10 @@ EXTENSIONS = {
         'acg_inst_noise_prepare': (STATUS, [_P, _P, _P, _P, c_float, c_float, c_int64, c_int64, c_int32, _P]),
         'acg_inst_noise_add': (STATUS, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
         'acg_logit_stats': (STATUS, [_P, _P, c_int32, _P, _P]),
+        # the learned latent posterior of the noise input: the reparameterised draw with its KL term, and the gradient of both
+        # (ops.LatentOp / LatentBwdOp, train.Trainer posterior)
+        'acg_latent_fwd': (STATUS, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+        'acg_latent_bwd': (STATUS, [_P, _P, _P, _P, c_float, _P, _P, c_int32, c_int32, c_int32, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)

@@ -25,6 +25,14 @@ are Z channels wider).  ``--noise zero`` (default) predicts with z = 0; ``--nois
 best-of-N protocol of stochastic video prediction - for each sequence and each metric separately the sample whose mean over
 the steps is best, then the same reductions over sequences.  metrics.json also holds ``noise_dim``, ``noise`` and
 ``noise_samples``.  Not with ``--bn_stats stored`` / ``calibrate``.
+
+``--posterior`` (with ``--noise_dim Z``, float32): the checkpoint is of a run trained with ``--posterior``; the encoder
+``g/posterior`` is built and restored, and ``--noise posterior`` / ``posterior_mean`` draw z from q(z | x_t, x_{t+1}) - every step
+of the rollout encodes its current input frame (the prediction, from the second step on) and the TRUE next frame, so these two
+modes score a reconstruction that has seen the target, the VAE's upper bound, not a prediction.  ``--noise_samples`` applies to
+``posterior`` as to ``sample``; metrics.json then also holds ``posterior: true``.  Without the flag such a checkpoint predicts
+from the prior like any ``--noise_dim`` run: its extra ``g/posterior/*`` keys are ignored, and so are the G optimizers' flat slots,
+which are laid out with the encoder and which predicting does not read (``--weights ema`` reads such a buffer: it needs ``--posterior``).
 """
 import argparse
 import json
@@ -119,15 +127,33 @@ def _use_ema_weights(trainer, ckpt):
     return updates
 
 
+def _slots_to_skip(path, posterior, weights):
+    """A checkpoint of a run trained with --posterior, read into a graph without the encoder (prior predictions from a plain
+    --noise_dim graph): its ``g/posterior/*`` variables are extra keys the Saver ignores, but the flat buffers laid out over scope
+    ``g`` - the G optimizers' slots - hold the encoder too and fit no buffer of this graph.  A session that predicts reads none of
+    them: -> the Saver.restore ``skip_state`` that leaves them out (None for every other checkpoint).  The weight average is such
+    a buffer as well and IS read by ``--weights ema``: that needs --posterior."""
+    with np.load(path if path.endswith('.npz') else path + '.npz') as data:
+        extra = any(k.startswith('var:g/posterior/') for k in data.files)
+    if posterior or not extra:
+        return None
+    if weights == 'ema':
+        raise ValueError('--weights ema: checkpoint %s is of a run trained with --posterior, whose weight average is laid out with the '
+                         'encoder: add --posterior' % os.path.abspath(path))
+    return lambda name: name.startswith(('g_opt/', 'g_pretrain_opt/', 'g/ema/'))
+
+
 def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn_stats='batch', weights='raw',
-                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate', pixel_maps=0, canvas=False):
+                       noise_dim=None, noise_seed=0, restore_from=None, calibrate_with='--bn_stats calibrate', pixel_maps=0, canvas=False,
+                       posterior=False):
     """A checkpoint as a Trainer that predicts: a fresh graph and session, the generator ``transform`` / ``ksize`` / ``num_masks`` at
     ``batch_size`` with what the modes need and nothing else - ``bn_stats`` 'stored' or 'calibrate': the stored-statistics instances;
     ``weights='ema'``: the average (then copied into the variables, _use_ema_weights); ``noise_dim`` > 0: the noise input, its stream
     restarted at ``noise_seed`` - initialised and restored from ``restore_from`` (default: ``ckpt``, which the messages name).  An int
     ``noise_dim`` also makes the Saver's shape refusal ask about --noise_dim.  'stored' needs calibrated rows in the checkpoint (the
     error names ``calibrate_with``).  ``pixel_maps`` > 0: the map path of plan.Planner's designated-pixel cost (DNA generator).
-    ``canvas``: the CDNA / affine generator with its painted candidate (Trainer ``canvas``).
+    ``canvas``: the CDNA / affine generator with its painted candidate (Trainer ``canvas``).  ``posterior``: the encoder of the
+    latent posterior (Trainer ``posterior``; the KL weight plays no part in predicting).
     -> (trainer, updates of the average or None, calibrated rows or None); the caller closes
     ``trainer.sess``."""
     from . import graph as G
@@ -142,6 +168,8 @@ def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, devi
         extra['pixel_maps'] = pixel_maps
     if canvas:
         extra['canvas'] = True
+    if posterior:
+        extra['posterior'] = True
     G.reset_default_graph()
     sess = G.Session(device=device, dtype=dtype)
     try:
@@ -149,7 +177,7 @@ def predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, devi
                           num_masks=num_masks, **extra)
         sess.run(G.global_variables_initializer())
         try:
-            Saver().restore(sess, restore_from or ckpt)
+            Saver().restore(sess, restore_from or ckpt, skip_state=_slots_to_skip(restore_from or ckpt, posterior, weights))
         except ValueError as e:
             if noise_dim is not None and 'has shape' in str(e):        # the Saver's shape refusal: the bottleneck layers are noise_dim channels wider
                 raise ValueError('%s - the generator is built with --noise_dim %d: does that match the run that wrote the checkpoint?'
@@ -201,14 +229,15 @@ def set_psnr(sqerr, valid, count_per_frame):
 def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, ksize=5, img_size=64, dtype='f32', batch_size=32,
              seq_len=8, num_sequences=None, samples=16, gif=False, dump=False, device='cuda:0', cdna=False, num_masks=10, bn_stats='batch',
              calibrate_batch_size=32, calibrate_batches=16, calibrate_input=None, calibrate_actions=None, weights='raw', noise_dim=0,
-             noise='zero', noise_samples=1, noise_seed=0, affine=False, canvas=False):
+             noise='zero', noise_samples=1, noise_seed=0, affine=False, canvas=False, posterior=False):
     """Restore ``model_path`` (a checkpoint directory - its latest checkpoint - or a checkpoint prefix) into the generator
     ``dna`` / ``cdna`` / ``affine`` (with ``num_masks``) / ``ksize`` / ``img_size`` / ``dtype`` describe, roll it out over the sequences of
     ``input_path`` and write ``output_path``/metrics.json (module docstring), ``samples`` sample videos (util.save_samples, GIFs
     with ``gif``) and with ``dump`` the predictions as ``predictions.npy`` [N, steps, H, W, 3].  ``bn_stats`` 'batch', 'stored' or 'calibrate' and the
     ``calibrate_*`` arguments: the module docstring (``calibrate_actions``: the actions of a ``calibrate_input`` .npy).
     ``weights``: 'raw' or 'ema' (module docstring); 'ema' on a checkpoint without an average is a ValueError.
-    ``noise_dim`` / ``noise`` ('zero' or 'sample') / ``noise_samples`` / ``noise_seed``: the module docstring.
+    ``noise_dim`` / ``noise`` ('zero', 'sample', and with ``posterior`` 'posterior' or 'posterior_mean') / ``noise_samples`` /
+    ``noise_seed`` / ``posterior``: the module docstring.
     ``canvas``: the checkpoint is of a ``cdna`` / ``affine`` generator trained with its painted candidate (Trainer ``canvas``);
     metrics.json then holds ``canvas: true``.
     -> the metrics dict."""
@@ -220,15 +249,19 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
         raise ValueError("weights must be 'raw' or 'ema', got %r" % (weights,))
     if bn_stats == 'calibrate' and (calibrate_batch_size < 1 or calibrate_batches < 1):
         raise ValueError('calibrate_batch_size and calibrate_batches must be >= 1')
-    from .train import check_canvas, check_noise
+    from .train import NOISE_MODES, check_canvas, check_noise, check_posterior
     canvas = check_canvas(canvas, M.model_kind(transform), ksize, num_masks)
     noise_dim = check_noise(noise_dim, noise_seed, 1, bn_stats != 'batch', batch_size)
-    if noise not in ('zero', 'sample'):
-        raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
+    posterior, _ = check_posterior(posterior, 1.0, noise_dim, bf16=dtype != 'f32')
+    if noise not in NOISE_MODES:
+        raise ValueError("noise must be 'zero', 'sample', 'posterior' or 'posterior_mean', got %r" % (noise,))
     if noise == 'sample' and not noise_dim:
         raise ValueError("noise 'sample' needs noise_dim > 0")
-    if int(noise_samples) < 1 or (noise == 'zero' and int(noise_samples) != 1):
-        raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' (got %r)" % (noise_samples,))
+    if NOISE_MODES[noise][1] and not posterior:
+        raise ValueError('noise %r needs posterior (the encoder it draws from)' % (noise,))
+    drawn = noise in ('sample', 'posterior')         # the modes that draw: several rollouts per sequence differ
+    if int(noise_samples) < 1 or (not drawn and int(noise_samples) != 1):
+        raise ValueError("noise_samples must be >= 1, and 1 unless noise is 'sample' or 'posterior' (got %r)" % (noise_samples,))
     n_draws = int(noise_samples)
     from .metrics import SSIM_DEFINITION
     from .saver import latest_checkpoint
@@ -250,7 +283,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
     bn = 'stored' if stored else 'batch'
     trainer, ema_updates, calibration_rows = predicting_trainer(ckpt, transform, batch_size, ksize, img_size, dtype, device, num_masks, bn,
                                                                 weights, noise_dim, noise_seed, restore_from=restore_from,
-                                                                **({'canvas': True} if canvas else {}))
+                                                                **({'canvas': True} if canvas else {}),
+                                                                **({'posterior': True} if posterior else {}))
     sess = trainer.sess
     try:
         keys =('ssim', 'sqerr', 'identity_ssim', 'identity_sqerr')
@@ -267,7 +301,7 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             t0 = time.perf_counter()
             m = trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), return_frames=want, **({'bn': bn} if stored else {}),
                                         **({'noise': noise} if noise_dim else {}))
-            if noise == 'sample':        # the first draw is the one that is kept as a sample video; the others are scored only
+            if drawn:        # the first draw is the one that is kept as a sample video; the others are scored only
                 more = [trainer.rollout_metrics(_pad(frames, batch_size), _pad(acts, batch_size), identity=False, noise=noise)
                         for _ in range(n_draws - 1)]
                 for k in draws:
@@ -305,8 +339,8 @@ def evaluate(model_path, input_path, output_path, actions_path=None, dna=False, 
             'frames_per_s': float(valid.size * steps * n_draws / rollout_s),
         }
         if noise_dim:
-            result.update(noise_dim=noise_dim, noise=noise, noise_samples=n_draws)
-        if noise == 'sample':
+            result.update(noise_dim=noise_dim, noise=noise, noise_samples=n_draws, **({'posterior': True} if posterior else {}))
+        if drawn:
             result.update(best_of_n(np.concatenate(draws['ssim'], axis=1)[:, valid], np.concatenate(draws['sqerr'], axis=1)[:, valid], count))
         if stored:
             result['bn_statistics'] = bn_stats
@@ -392,21 +426,27 @@ def main(argv=None):
     parser.add_argument('--calibrate_actions', type=str, default=None, help='actions .npy of a --calibrate_input frames .npy')
     parser.add_argument('--weights', type=str, default='raw', choices=['raw', 'ema'],
                         help="the generator weights as trained, or their moving average (a checkpoint of a run trained with --g_ema)")
-    from .train import add_noise_args, check_noise_args
+    from .train import add_noise_args, add_posterior_args, check_noise_args, check_posterior_args
     add_noise_args(parser)
-    parser.add_argument('--noise', type=str, default='zero', choices=['zero', 'sample'],
-                        help="predict with z = 0, or roll every sequence out --noise_samples times with fresh noise (needs --noise_dim)")
-    parser.add_argument('--noise_samples', type=int, default=None, metavar='N', help="rollouts per sequence with --noise sample (default 1)")
+    add_posterior_args(parser, training=False)
+    parser.add_argument('--noise', type=str, default='zero', choices=['zero', 'sample', 'posterior', 'posterior_mean'],
+                        help="predict with z = 0, or roll every sequence out --noise_samples times with fresh noise (needs --noise_dim); "
+                             "with --posterior also: z drawn from the encoder's q(z | x_t, x_t+1), or its mean")
+    parser.add_argument('--noise_samples', type=int, default=None, metavar='N',
+                        help="rollouts per sequence with --noise sample or posterior (default 1)")
     args = parser.parse_args(argv)
     check_model_args(parser, args)
     check_bn_args(parser, args)
     check_noise_args(parser, args)
+    check_posterior_args(parser, args)
+    if args.noise.startswith('posterior') and not args.posterior:
+        parser.error('--noise %s needs --posterior' % args.noise)
     if args.noise_dim > 0 and args.bn_stats != 'batch':
         parser.error('--noise_dim > 0 predicts with batch statistics (--bn_stats %s)' % args.bn_stats)
     if args.noise == 'sample' and args.noise_dim < 1:
         parser.error('--noise sample needs --noise_dim > 0')
-    if args.noise_samples is not None and (args.noise != 'sample' or args.noise_samples < 1):
-        parser.error('--noise_samples N >= 1 goes with --noise sample')
+    if args.noise_samples is not None and (args.noise not in ('sample', 'posterior') or args.noise_samples < 1):
+        parser.error('--noise_samples N >= 1 goes with --noise sample' + (' or posterior' if args.posterior else ''))
     if args.noise_samples is None:
         args.noise_samples = 1
     if args.batch_size < 1:
@@ -435,7 +475,7 @@ def main(argv=None):
                     **({'weights': args.weights} if args.weights != 'raw' else {}), **{flag: getattr(args, flag) for flag in M.flags()},
                     **({'canvas': True} if args.canvas else {}),
                     **({'noise_dim': args.noise_dim, 'noise': args.noise, 'noise_samples': args.noise_samples, 'noise_seed': args.noise_seed}
-                       if args.noise_dim else {}))
+                       if args.noise_dim else {}), **({'posterior': True} if args.posterior else {}))
 
 
 if __name__ == '__main__':

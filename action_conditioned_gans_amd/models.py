@@ -25,6 +25,7 @@ G_DNA = {'encoder': (('conv1', 32), ('conv2', 64), ('conv3', 128), ('conv4', 256
          'decoder_a': (('tconv1', 128), ('tconv2', 128)),
          'state': (('sconv3', 32), ('sconv4', 16)),
          'decoder_b': (('tconv3', 128),)}
+Q_NET = (('conv1', 32), ('conv2', 64), ('conv3', 128), ('conv4', 256))
 D_NET = {'pre': (('conv1', 64), ('conv2', 128)), 'post': (('conv3', 128), ('conv4', 256), ('conv5', 512))}
 
 
@@ -177,6 +178,29 @@ def build_discriminator(inputs, actions, reuse=False):
         net = _with_actions(net, actions, 'actions')
         net = _stack(net, D_NET['post'], O.conv2d)
         return O.conv2d(net, 1, [2, 2], activation_fn=None, stride=1, scope='conv6')
+
+
+def build_posterior(frames6, z, reuse=False):
+    """The encoder of the latent posterior q(z | x_t, x_{t+1}) (no reference counterpart; the inference network of SV2P / SAVP
+    cut down to one transition): ``frames6`` = concat([x_t, x_{t+1}]), 6 channels at pitch 8 as the discriminator's inputs are
+    stored -> stats [B, 2 z] = [mu, logvar].
+
+    Four conv 5x5 / 2 + BatchNorm + lrelu layers (Q_NET) and a VALID stride-1 head over the whole remaining map with bias, no
+    BatchNorm and no activation - sized as ``g/sconv5`` sizes itself - under scope ``g/posterior``: the variables are the
+    generator's to every optimizer, average, clip and schedule that acts on scope ``g``.  The head starts from the default
+    initializer and a zero bias; nothing clamps logvar."""
+    if len(frames6.shape) != 4 or (frames6.valid_c or frames6.shape[3]) != 6:
+        raise ValueError('posterior: [B, H, W, 6] frames (concat([x_t, x_t+1])) expected, got %s' % (frames6.shape,))
+    if O.half_mode():
+        raise NotImplementedError('the latent posterior is float32 only (the action gradient it is trained through is)')
+    with O.variable_scope('g', reuse=reuse), O.variable_scope('posterior'), \
+            O.arg_scope([O.conv2d], activation_fn=O.lrelu, stride=2, padding='SAME', normalizer_fn=O.batch_norm, reuse=reuse):
+        net = _stack(frames6, Q_NET, O.conv2d)
+        sk = net.shape[1]
+        if net.shape[2] != sk:
+            raise ValueError('posterior: square frames expected, got a %s map' % (net.shape[1:3],))
+        stats = O.conv2d(net, 2 * int(z), [sk, sk], activation_fn=None, stride=1, padding='VALID', normalizer_fn=None, scope='head')
+        return O.squeeze(stats, axis=(1, 2))       # [B, 1, 1, 2 z] -> [B, 2 z], also at B = 1
 
 
 # ================================================================================================

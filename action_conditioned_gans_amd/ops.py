@@ -1278,6 +1278,17 @@ class NoiseOp(G.Op):
         return [SliceOp(gouts[0], 0, a.shape[-1], a.shape, self.name + '/bwd').outputs[0] if needs[0] else None]
 
 
+def latent_state(seed=0):
+    """The state every LatentOp of the graph shares, created by the first call: -> (state, mode).  ``state`` IS noise_state()'s
+    ``g/noise/state`` (``seed`` is read by whichever of the two calls comes first): the prior and the posterior draw one stream
+    under one checkpoint key.  ``mode``: float32 [2] = {scale, posterior}, initialised to {1, 1}, unnamed (no checkpoint key):
+    whoever runs the programs writes it between them (include/acgan_rollout.h, acg_latent_fwd)."""
+    g = G.get_default_graph()
+    if 'latent' not in g.collections:
+        g.collections['latent'] = (noise_state(seed)[0], g.new_state((2,), (1.0, 1.0), None))
+    return g.collections['latent']
+
+
 SCHED_SAMPLING_STATE = 'g/sched_sampling/state'
 SCHED_SAMPLING_KINDS = _lib.SsSched.KINDS
 
@@ -1930,6 +1941,14 @@ def sched_sample(mask_row, pred, truth, pred_state=None, true_state=None, name='
     return outs[0], (outs[1] if len(outs) > 1 else None)
 
 
+def append_latent(actions, stats, name='latent'):
+    """actions [B, A], stats [B, 2 Z] = [mu, logvar] -> (vec [B, A + Z], kl): the generator's latent input drawn from the posterior
+    the stats describe - or from the prior, as latent_state()'s mode says - and KL(q || N(0, 1)) summed over the batch as a
+    Scalar that goes into a loss like any head's value (LatentOp)."""
+    op = LatentOp(actions, stats, _scope_name(name))
+    return op.outputs[0], Scalar([(op, 1, 1.0)])
+
+
 def append_noise(actions, noise_dim, name='noise'):
     """actions [B, A] -> [B, A + noise_dim]: the generator's latent input, appended to its action vector (NoiseOp)."""
     return NoiseOp(actions, noise_dim, _scope_name(name)).outputs[0]
@@ -2234,6 +2253,88 @@ class PsnrOp(LossHead):
 
     def seed(self, weights, needs):
         raise NotImplementedError('psnr is a metric (ops.py:19-20), not a training loss')
+
+
+class _KlSeed:
+    """What LatentOp.seed hands build_gradients as the 'gradient' of the kl output: the weight of kl in the loss, nothing on the
+    device.  The reverse walk gives it back to LatentOp.grad, which puts it into the one backward launch."""
+
+    def __init__(self, weight):
+        self.weight = float(weight)
+
+
+class LatentOp(LossHead):
+    """[actions [B, A], z [B, Z]] -> vec [B, A + Z] float32 and kl [1], with stats [B, 2 Z] = [mu, logvar] of a posterior
+    q(z | .) (acg_latent_fwd): z = mu + scale * exp(logvar / 2) * eps under mode {scale, 1}, the prior's scale * eps - NoiseOp's
+    bits - under {scale, 0}; kl = KL(q || N(0, 1)) summed over the batch, in both modes.  eps is drawn from the graph's noise
+    state, which the launch advances (latent_state); the stream id of the draw is the data-parallel rank.
+
+    An op with a gradient AND a loss head: ``kl`` goes into a Scalar like any head's output, and its weight reaches the backward
+    launch through ``seed``, which launches nothing - it marks the kl output with the weight (_KlSeed), the reverse walk then
+    calls ``grad`` with the generator's gradient of ``vec`` (None where no loss reads the generator) and that mark, and ONE
+    LatentBwdOp writes d stats of both.  The gradient of the action columns is their slice, produced when needed."""
+
+    def __init__(self, actions, stats, name):
+        if len(actions.shape) != 2 or actions.dtype != torch.float32:
+            raise ValueError('append_latent: actions must be float32 [batch, A], got %s %s' % (actions.dtype, actions.shape))
+        b, a = actions.shape
+        if len(stats.shape) != 2 or stats.shape[0] != b or stats.shape[1] % 2 or stats.dtype != torch.float32 or stats.valid_c:
+            raise ValueError('append_latent: stats must be dense float32 [%d, 2 Z], got %s %s' % (b, stats.dtype, stats.shape))
+        z = stats.shape[1] // 2
+        if not (1 <= z <= _lib.NOISE_DIM_MAX and 1 <= a <= _lib.NOISE_DIM_MAX and b * z <= _lib.NOISE_VALUES_MAX):
+            raise ValueError('append_latent: %d latent values on actions %s (1 <= A, Z <= %d and B * Z <= %d)'
+                             % (z, actions.shape, _lib.NOISE_DIM_MAX, _lib.NOISE_VALUES_MAX))
+        self.latent_dim = z
+        self.extras = list(latent_state())
+        super().__init__(G.get_default_graph(), name, [actions, stats], [_new((b, a + z), name + ':0'), _new((1,), name + ':kl')])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'latent_fwd')
+        actions, stats = self.inputs
+        out, kl = self.outputs
+        state, mode = self.extras
+        args = (_p(actions.buf), _p(stats.buf), _p(state.buf), _p(mode.buf), _p(out.buf), _p(kl.buf), actions.shape[0], actions.shape[1],
+                self.latent_dim, int(rt.rank))
+        return lambda s: fn(*args, s)
+
+    def seed(self, weights, needs):
+        unknown = set(weights) - {1}
+        if unknown:
+            raise ValueError('latent: output(s) %s are no loss values (kl is output 1)' % sorted(unknown))
+        return [(self.outputs[1], _KlSeed(weights[1]))] if needs[1] else []
+
+    def grad(self, gouts, needs, ctx):
+        dvec, mark = gouts
+        if not needs[1]:
+            a = self.inputs[0]
+            return [SliceOp(dvec, 0, a.shape[-1], a.shape, self.name + '/bwd_actions').outputs[0] if needs[0] and dvec is not None else None,
+                    None]
+        op = LatentBwdOp(self, dvec, mark.weight if mark is not None else 0.0, needs[0], self.name + '/bwd')
+        return [op.dactions, op.dstats]
+
+
+class LatentBwdOp(G.Op):
+    """acg_latent_bwd: d stats of  L(vec) + kl_weight * kl  in one launch - the generator's gradient through the
+    reparameterisation (``dvec``; None: the KL term alone) and the KL gradient - and, when asked for, the action columns of
+    ``dvec``.  z is read from the forward op's output: nothing is redrawn."""
+
+    def __init__(self, fwd, dvec, kl_weight, want_actions, name):
+        actions, stats = fwd.inputs
+        self.kl_weight, self.has_dvec, self.latent_dim = float(kl_weight), dvec is not None, fwd.latent_dim
+        self.dstats = _new(stats.shape, name + ':0')
+        self.dactions = _new(actions.shape, name + ':actions') if want_actions else None
+        self.extras = [fwd.extras[1]]
+        super().__init__(G.get_default_graph(), name, ([dvec] if dvec is not None else []) + [fwd.outputs[0], stats],
+                         [self.dstats] + ([self.dactions] if want_actions else []))
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'latent_bwd')
+        out, stats = self.inputs[-2:]
+        dvec = self.inputs[0] if self.has_dvec else None
+        b, p = out.shape
+        args = (_p(dvec.buf) if dvec is not None else None, _p(out.buf), _p(stats.buf), _p(self.extras[0].buf), self.kl_weight,
+                _p(self.dstats.buf), _p(self.dactions.buf) if self.dactions is not None else None, b, p - self.latent_dim, self.latent_dim)
+        return lambda s: fn(*args, s)
 
 
 def build_psnr(true, pred):

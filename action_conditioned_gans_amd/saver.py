@@ -119,11 +119,16 @@ class Saver:
             err, self._error = self._error, None
             raise err
 
-    def restore(self, sess, save_path):
+    def restore(self, sess, save_path, skip_state=None):
+        """``skip_state``: a predicate on state names; the named state it accepts stays as initialised.  For a session that only
+        predicts from a checkpoint whose scope holds more variables than its graph (extra variable keys are ignored, but the
+        scope's flat optimizer slots then have another length and layout: evaluate.predicting_trainer)."""
         self.wait()
         path = save_path if save_path.endswith('.npz') else save_path + '.npz'
         data = np.load(path)
         items = self._tensors()
+        if skip_state is not None:
+            items = {k: t for k, t in items.items() if not (k.startswith('state:') and skip_state(k[len('state:'):]))}
         missing = [k for k in items if k.startswith('var:') and k not in data]
         if missing:
             raise ValueError('checkpoint %s lacks variables: %s' % (path, ', '.join(missing)))

@@ -45,7 +45,8 @@ class Trainer:
                  ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False, noise_dim=0, noise_seed=0,
                  g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
                  sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0,
-                 d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False, canvas=False):
+                 d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False, canvas=False,
+                 posterior=False, kl_weight=1.0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -179,13 +180,33 @@ class Trainer:
         ``g/tconv4_canvas/*`` is new, with their optimizer and average slots: a checkpoint of one setting does not restore into
         the other.  Everything these generators take they take with it (the look-ahead pair pass, HIP-graph replay, noise_dim,
         ema_decay, ssim_weight, the clip norms, the schedules, bn_inference), and what they decline stays declined.  A generator
-        without masks (plain, DNA) is a ValueError before anything is created."""
-        self.canvas = check_canvas(canvas, model_kind(arg_transform), ksize, num_masks)      # (before anything is created)
+        without masks (plain, DNA) is a ValueError before anything is created.
+
+        ``posterior`` / ``kl_weight`` W (no reference counterpart; False builds nothing: ops, op order, variables, state names and
+        summaries are those of a Trainer without the arguments; needs ``noise_dim`` Z > 0): the VAE half of a VAE-GAN (SV2P,
+        Babaeizadeh et al. 2018; SAVP, Lee et al. 2018).  Nothing in L1 + GDL + the adversarial term ties z to the frame, so a
+        generator that ignores its noise input minimises them.  With ``posterior`` an encoder under scope ``g/posterior``
+        (models.build_posterior) sees (x_t, x_{t+1}) and emits mu, logvar; the generator reads z = mu + exp(logvar / 2) * eps -
+        eps the draw of ``noise_dim``, from the same ``g/noise/state`` - and  W / B * KL(q(z | x_t, x_{t+1}) || N(0, 1))  joins
+        the G loss AND the pretraining loss (ops.append_latent: one launch forward, one backward for the generator's gradient
+        and the KL gradient together).  The encoder's variables are the generator's to the optimizers, the weight average, the
+        clip norm and the lr schedule.  The summary ``g_kl`` is KL / B.  The training steps run with the posterior;
+        ``test`` / ``test_sequence`` / ``rollout_metrics`` take ``noise`` in NOISE_MODES: 'zero' (z = 0) and 'sample' (z ~ N(0, 1),
+        the prior) as before, 'posterior' (z ~ q) and 'posterior_mean' (z = mu), which encode the frames the placeholders
+        hold - the current input frame and the fed next frame.  The mode is a device-side float32 [2] written between programs,
+        only when it changes.  New checkpoint keys are the ``g/posterior/*`` variables and their optimizer slots: a posterior
+        checkpoint restores into a plain ``noise_dim`` Trainer (the Saver ignores extra keys), a plain one into a posterior
+        Trainer is refused (it lacks variables).  Declined before anything is created (check_posterior): no ``noise_dim``, a
+        bf16 graph (the action gradient is float32 only), a negative or non-finite ``kl_weight``; ``rollout_steps`` > 1 and
+        ``bn_inference`` are ``noise_dim``'s refusals.  More than one rank is allowed and not verified (the stream id is the rank)."""
+        self.canvas =check_canvas(canvas, model_kind(arg_transform), ksize, num_masks)      # (before anything is created)
         self.d_noise = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, d_noise_offset, d_noise_seed, rollout_steps,
                                      arg_adv)         # (before anything is created; None: off)
         self.pixel_maps = check_pixel_maps(pixel_maps, model_kind(arg_transform))      # (before anything is created)
         self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
+        self.posterior, self.kl_weight = check_posterior(posterior, kl_weight, self.noise_dim,
+                                                         bf16=G.get_default_graph().act_dtype != torch.float32)      # (the same)
         self.sched_sampling = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, ss_offset, ss_seed, rollout_steps,
                                                    batch_size)      # (None: off)
         self.ema_decay = ema_decay = check_ema_decay(ema_decay)         # (before anything is created)
@@ -220,8 +241,16 @@ class Trainer:
             and self.d_noise is None
         self._noise = None            # the [B, 10 + Z] vector the generator reads (noise_dim > 0)
 
+        self._kl = None               # KL(q || N(0, 1)) summed over the batch, a Scalar (posterior)
+
         def build_g(images, actions, batch, reuse):
-            if self.noise_dim:
+            if self.posterior:
+                # the encoder reads (x_t, x_{t+1}) as the discriminator reads its real pairs: 6 channels at a pitch of 8
+                O.latent_state(noise_seed)
+                pair = O.concat([self.img_ph, self.next_frame_ph], axis=3, name='posterior_in', pitch=8, act=True)
+                actions, self._kl = O.append_latent(actions, M.build_posterior(pair, self.noise_dim, reuse=reuse))
+                self._noise = actions
+            elif self.noise_dim:
                 O.noise_state(noise_seed)
                 actions = self._noise = O.append_noise(actions, self.noise_dim)
             return M.KINDS[self.model].build_with(images, actions, batch, reuse, ksize, num_masks, self.canvas)
@@ -298,6 +327,11 @@ class Trainer:
         self.summaries = {}
         g_l2_loss, self.g_ssim_loss, adv_loss, self.g_loss = self._step_losses(self.g_out, self.g_state_out, self.next_frame_ph, self.next_state,
                                                                                self.d_out_gen, '', mean_ssim=True)
+        if self._kl is not None:
+            # the ELBO's KL term, per sample like the L1 term it stands against: in the G loss and in the pretraining loss
+            kl_term = self._kl * (self.kl_weight / B)
+            g_l2_loss, self.g_loss = g_l2_loss + kl_term, self.g_loss + kl_term
+            self.summaries['g_kl'] = self._kl / B
         self.g_l2_loss = g_l2_loss
         if self.g_ssim_loss is not None:
             self.summaries['g_ssim_loss'] = self.g_ssim_loss
@@ -357,7 +391,7 @@ class Trainer:
         self.merged_summaries = [self.summaries[k] for k in self._summary_names]
         self._zero_state = np.zeros((B, STATE_DIM), np.float32)
         self._announced = None          # (images, actions) of the G step a look-ahead D step has prepared
-        self._noise_on = None           # the 0 / 1 factor of the noise as last written (_noise_switch; None: not yet)
+        self._noise_on = None           # the mode of the noise as last written (_noise_switch; None: not yet)
         self._skip_d = self._skip_g = None
         if self.rollout_steps > 1:
             self._build_rollout(build_g, minimize_g)
@@ -407,12 +441,21 @@ class Trainer:
 
     # ---- the generator's noise input (noise_dim > 0)
     def _noise_switch(self, on, always=False):
-        """Write the 0 / 1 factor of the noise the next generator pass reads (ops.noise_state: outside the programs, on their
-        stream).  The training steps switch it on and write only when they last wrote something else; a predicting call always
-        writes (the initializer, run again, resets the factor behind this object's back)."""
-        if self.noise_dim and (always or on is not self._noise_on):
-            self.sess._materialize(O.noise_state()[1]).fill_(1.0 if on else 0.0)
-            self._noise_on = on
+        """Write the mode of the noise the next generator pass reads (outside the programs, on their stream): ``on`` is True -
+        what the training steps read: the posterior where there is one, else the prior - or one of NOISE_MODES.  Without
+        ``posterior`` that is the 0 / 1 factor of ops.noise_state, with it the {scale, posterior} pair of ops.latent_state.  The
+        training steps write only when something else was written last; a predicting call always writes (the initializer, run
+        again, resets the value behind this object's back)."""
+        mode = ('posterior' if self.posterior else 'sample') if on is True else 'zero' if on is False else on
+        if self.noise_dim and (always or mode != self._noise_on):
+            scale, post = NOISE_MODES[mode]
+            if self.posterior:
+                buf = self.sess._materialize(O.latent_state()[1])
+                buf[0:1].fill_(scale)
+                buf[1:2].fill_(post)
+            else:
+                self.sess._materialize(O.noise_state()[1]).fill_(scale)
+            self._noise_on = mode
 
     def last_noise(self):
         """-> [B, noise_dim] float32: the z the last generator pass read (zeros after a ``noise='zero'`` pass, and before the
@@ -574,14 +617,16 @@ class Trainer:
             raise ValueError("bn must be 'batch' or 'stored', got %r" % (bn,))
         if bn == 'stored':
             self._require_calibrated()
-        if noise not in ('zero', 'sample'):
-            raise ValueError("noise must be 'zero' or 'sample', got %r" % (noise,))
+        if noise not in NOISE_MODES:
+            raise ValueError("noise must be 'zero', 'sample', 'posterior' or 'posterior_mean', got %r" % (noise,))
         if noise == 'sample' and not self.noise_dim:
             raise RuntimeError("noise='sample': this Trainer was built without noise_dim, its generator reads no noise")
+        if NOISE_MODES[noise][1] and not self.posterior:
+            raise RuntimeError('noise=%r: this Trainer was built without posterior, it has no encoder to draw from' % (noise,))
         with self.ema_weights() if weights == 'ema' else contextlib.nullcontext():
             self._announced = None
             if switch:
-                self._noise_switch(noise == 'sample', always=True)
+                self._noise_switch(noise, always=True)
             yield bn == 'stored'
 
     def _build_bn_inference(self, build_g):
@@ -825,7 +870,8 @@ class Trainer:
         return None
 
     def test(self, input_images, next_frame, actions, bn='batch', weights='raw', noise='zero'):
-        """``noise`` (a Trainer built with ``noise_dim``): 'zero' - z = 0 - or 'sample' - a fresh z, see ``last_noise``.
+        """``noise`` (a Trainer built with ``noise_dim``): 'zero' - z = 0 - or 'sample' - a fresh z, see ``last_noise``; with
+        ``posterior`` also 'posterior' - z drawn from q(z | input_images, next_frame) - and 'posterior_mean' - its mean.
         ``bn='stored'`` (a Trainer built with ``bn_inference``, after calibration): the stored-statistics generator; the
         summaries then hold ``g_psnr`` alone (the other six read the discriminator on the batch-statistics frames).
         ``weights='ema'`` (a Trainer built with ``ema_decay``): the same call inside ``ema_weights()``."""
@@ -1030,6 +1076,22 @@ def check_noise_seed(seed, what='noise_seed'):
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
         raise ValueError('%s must be an integer in [0, 2^64), got %r' % (what, seed))
     return int(seed)
+
+
+# ``noise`` of a predicting call -> the {scale, posterior} mode of acg_latent_fwd (without a posterior: scale alone)
+NOISE_MODES = {'zero': (0.0, 0.0), 'sample': (1.0, 0.0), 'posterior': (1.0, 1.0), 'posterior_mean': (0.0, 1.0)}
+
+
+def check_posterior(posterior=False, kl_weight=1.0, noise_dim=0, bf16=False):
+    """ValueError for ``posterior`` / ``kl_weight`` the Trainer does not take: a ``kl_weight`` that is not a finite number >= 0,
+    ``posterior`` without ``noise_dim`` > 0 or in a bf16 graph.  ``noise_dim`` is the checked one (check_noise, whose refusals
+    of rollout_steps > 1 and bn_inference cover the posterior too).  -> (posterior as a bool, kl_weight as a float)."""
+    w = _number(kl_weight, 'kl_weight', 'a finite number >= 0', 'be finite and >= 0', lambda x: 0.0 <= x <= F32_MAX)
+    if posterior and not noise_dim:
+        raise ValueError('posterior needs noise_dim > 0 (the latent it is the posterior of)')
+    if posterior and bf16:
+        raise ValueError('posterior does not go with a bf16 graph (the action gradient the encoder is trained through is float32 only)')
+    return bool(posterior), w
 
 
 def check_noise(noise_dim, noise_seed=0, rollout_steps=1, bn_inference=False, batch_size=1):
@@ -1314,7 +1376,7 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
           noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
           lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0, d_noise=0.0, d_noise_final=0.0,
-          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False, canvas=False):
+          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False, canvas=False, posterior=False, kl_weight=1.0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1343,7 +1405,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     ``g_grad_norm`` / ``g_clip_scale`` / ``d_grad_norm`` / ``d_clip_scale`` of the iteration's last updates at every log
     interval (the scopes that are measured) and the configured bounds once, in its first record.  Checkpoints are unchanged.
     ``noise_dim`` Z > 0 / ``noise_seed``: the generator reads Z noise values drawn on the device (Trainer, same keywords); the loop
-    takes the plain call path (no look-ahead pass), checkpoints hold ``g/noise/state``, ``train.jsonl`` records ``noise_dim`` and
+    takes the plain call path (no look-ahead pass; ``posterior`` / ``kl_weight``: the latent posterior and its KL weight, Trainer,
+    same keywords - ``train.jsonl`` then records ``g_kl``), checkpoints hold ``g/noise/state``, ``train.jsonl`` records ``noise_dim`` and
     the evaluation block predicts with z = 0.
     ``g_lr`` / ``d_lr`` / ``beta1``: the rates of the G and D updates and Adam's beta1 (Trainer, same keywords; None: the
     reference's).  ``lr_schedule`` / ``lr_warmup`` / ``lr_decay_steps`` / ``lr_final``: a learning-rate schedule (Trainer, same
@@ -1385,6 +1448,9 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, False, batch_size)
     if noise_dim:
         options.update(noise_dim=noise_dim, noise_seed=noise_seed)
+    posterior, kl_weight = check_posterior(posterior, kl_weight, noise_dim, bf16=dtype != 'f32')
+    if posterior:
+        options.update(posterior=True, kl_weight=kl_weight)
     ss = check_sched_sampling(sched_sampling, ss_start, ss_final, ss_decay_steps, max(int(pretrain_iter), 0), ss_seed, rollout_steps,
                               batch_size)           # (the pretraining updates count too: the decay begins behind them)
     if ss is not None:
@@ -1645,6 +1711,29 @@ def check_noise_args(parser, args):
         parser.error('--noise_dim / --noise_seed: %s' % e)
 
 
+def add_posterior_args(parser, training=True):
+    """The flags of the latent posterior, beside the noise flags: --posterior, shared by this CLI and evaluate's, and --kl_weight
+    (``training``: this CLI alone)."""
+    parser.add_argument('--posterior', nargs='?', const=True, default=False, type=_flag,
+                        help='train an encoder q(z | x_t, x_t+1) of the noise input with a KL term towards the N(0, 1) prior (the VAE '
+                             'half of a VAE-GAN; needs --noise_dim; float32); evaluate takes the same --posterior' if training else
+                             'build the encoder of a run trained with --posterior (needs --noise_dim): --noise posterior / '
+                             'posterior_mean then draw z from it')
+    if training:
+        parser.add_argument('--kl_weight', type=float, default=1.0, metavar='W',
+                            help="weight of KL / batch in the G loss and the pretraining loss (1 = the ELBO's own weight against the "
+                                 'summed-L1 reconstruction term: a starting point, not a tuned value)')
+
+
+def check_posterior_args(parser, args):
+    """parser.error for a --posterior / --kl_weight the Trainer does not take (before anything is created; behind
+    check_noise_args, whose refusals of --rollout_steps > 1 cover the posterior too)."""
+    try:
+        check_posterior(args.posterior, getattr(args, 'kl_weight', 1.0), args.noise_dim, bf16=getattr(args, 'dtype', 'f32') != 'f32')
+    except ValueError as e:
+        parser.error('--posterior / --kl_weight: %s' % e)
+
+
 def add_sched_sampling_args(parser):
     """The scheduled-sampling flags of --rollout_steps > 1."""
     parser.add_argument('--sched_sampling', type=str, default='off', metavar='KIND',
@@ -1739,6 +1828,7 @@ def main(argv=None):
                         help='record the gradient norms of G and D in train.jsonl (g_grad_norm, d_grad_norm, ..._clip_scale), also '
                              'where no bound is set')
     add_noise_args(parser)
+    add_posterior_args(parser)
     add_lr_args(parser)
     add_sched_sampling_args(parser)
     add_d_noise_args(parser)
@@ -1748,6 +1838,7 @@ def main(argv=None):
     transform = check_model_args(parser, args)
     check_rollout_args(parser, args)
     check_noise_args(parser, args)
+    check_posterior_args(parser, args)
     # every other option: the check train() makes, its ValueError reported under the flags' names ({}: the check's own words)
     for message, check in (
             ('--g_lr / --d_lr / --beta1 / --lr_*: {}', lambda: check_lr(args.g_lr, args.d_lr, args.beta1, args.opt, args.lr_schedule,

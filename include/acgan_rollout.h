@@ -34,6 +34,12 @@
  * The fourth draw of that generator is the one on the other network: instance noise on every frame the discriminator judges
  * (acg_inst_noise_prepare / acg_inst_noise_add), and, to choose its level by, the statistics of D's logits (acg_logit_stats).
  * Same conventions, same table, no atomics.
+ *
+ * The noise input's learned posterior (the VAE half of a VAE-GAN; SV2P, Babaeizadeh et al. 2018; SAVP, Lee et al. 2018) is the
+ * last pair: acg_latent_fwd, acg_noise_concat's draw reparameterised as z = mu + exp(logvar / 2) * eps with
+ * KL(N(mu, exp(logvar)) || N(0, 1)) summed in the same launch, and acg_latent_bwd, the one launch that carries the gradient of
+ * both back into (mu, logvar).  They read acg_noise_concat's state and its limits, which is why they are declared here and not in
+ * a header of their own.  Same conventions, same table, no atomics.
  */
 #ifndef ACGAN_ROLLOUT_H
 #define ACGAN_ROLLOUT_H
@@ -318,6 +324,42 @@ int32_t acg_inst_noise_prepare(uint64_t* state, uint64_t* updates, uint64_t* key
 int32_t acg_inst_noise_add(const void* in, void* out, const uint64_t* key, const float* sigma, int64_t pixels, int32_t c, int32_t pitch,
                            int32_t c0, int32_t cn, int32_t dtype, int32_t stream_id, acg_stream_t stream);
 int32_t acg_logit_stats(const float* fake, const float* real, int32_t n, float* out4, acg_stream_t stream);
+
+/* The learned latent posterior of the noise input.  eps is the draw of acg_noise_concat above - the same Philox4x32-10 counter
+ * words (lo32(counter), hi32(counter), block, stream_id) and key, uniform and Box-Muller pairing; element e = b * Z + j is lane
+ * e % 4 of block e / 4 and the tail of the last block is dropped - and `state` uint64 [2] = {seed, counter} is the SAME state
+ * acg_noise_concat reads (g/noise/state): the two entries draw one stream.  A refused call writes nothing.
+ *
+ * acg_latent_fwd: actions [B, A], stats [B, 2 Z] (stats[b, 0:Z] = mu, stats[b, Z:2Z] = logvar), out [B, A + Z], all dense float32; state
+ * uint64 [2]; mode float32 [2] = {scale, posterior} in device memory (whoever runs the programs writes it between them);
+ * kl float32 [1] or NULL.
+ *   out[b, :A]    = actions[b, :]                                                      (bit for bit)
+ *   posterior == 0:  out[b, A + j] = scale == 0 ? 0 : scale * eps                      (the prior: bit-identical to
+ *                    acg_noise_concat given the same state, scale and stream id; stats is not read for out)
+ *   posterior != 0:  out[b, A + j] = scale == 0 ? mu : fmaf(scale * expf(0.5f * logvar), eps, mu)
+ *                    (scale == 0: the posterior mean, bit for bit, -0.0 included)
+ *   kl[0] = (float)(0.5 * sum_{b, j} (mu^2 + exp(logvar) - logvar - 1))                (when kl is not NULL, in BOTH modes)
+ * The KL terms are evaluated in double and summed in double in a fixed order (each thread its strided share in ascending order,
+ * the lanes of a wave by shuffles, the waves in order) and the sum is rounded to float32 once: the same stats give the same bits
+ * in every launch.  With kl == NULL and posterior == 0 stats is not read at all.
+ * There is NO clamp on logvar: one large enough for expf to overflow gives z = +-inf (and a kl of inf), as the formula says;
+ * whoever produces stats keeps them in range.
+ * After the draw the kernel stores counter + 1 (in both modes, and when scale == 0): every thread has read the pair, a barrier,
+ * thread 0 stores - no atomics, no workspace.  One launch of one block; 1 <= A, Z <= ACG_NOISE_DIM_MAX and
+ * B * Z <= ACG_NOISE_VALUES_MAX.  Calls that share a state must be stream-ordered. */
+int32_t acg_latent_fwd(const float* actions, const float* stats, uint64_t* state, const float* mode, float* out, float* kl,
+                       int32_t batch, int32_t action_dim, int32_t latent_dim, int32_t stream_id, acg_stream_t stream);
+
+/* acg_latent_bwd: the gradient of  L(out) + kl_weight * kl  with respect to stats, dout = dL/dout [B, A + Z] (NULL: zeros - the KL term alone).
+ * With p = (mode[1] != 0), z = out[b, A + j] (read, never redrawn: no state is touched) and dz = dout[b, A + j]:
+ *   dstats[b, j]     = p * dz                  + kl_weight * mu
+ *   dstats[b, Z + j] = p * 0.5 * (z - mu) * dz + kl_weight * 0.5 * expm1f(logvar)
+ * (sigma * eps = z - mu, so d z / d logvar = 0.5 * (z - mu)).  p == 0 leaves the z path out exactly and kl_weight == 0 the KL
+ * path: with p != 0 and kl_weight == 0, dstats[b, j] is dz bit for bit.  dactions [B, A], when not NULL, is the copy of dout[:, :A] (zeros for
+ * a NULL dout).  out, stats and mode are read only.  One launch of one block, plain vector stores, the limits of
+ * acg_latent_fwd. */
+int32_t acg_latent_bwd(const float* dout, const float* out, const float* stats, const float* mode, float kl_weight, float* dstats,
+                       float* dactions, int32_t batch, int32_t action_dim, int32_t latent_dim, acg_stream_t stream);
 
 #ifdef __cplusplus
 }
