@@ -543,12 +543,33 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
   auto put = [&](f4* tile, int width, int kq, int col, const f4& q) { tile[kq * width + pcol(col, kq)] = q; };
 
   // write k-rows sub..sub+L-1 of quad `kq` of tile column `col` (L = 4, 2, 1: a whole, half or quarter quad)
+  // The values of a part come from L different load registers.  A ds_write_b64 wants them in a consecutive register pair, which
+  // costs one v_mov per value in the K-loop; ds_write2_b32 takes its two dwords from any two registers (same LDS slots, same
+  // bytes, same bank pattern), so the half quad is stored with it, in inline assembly: written as two float stores the compiler
+  // proves the 8-byte alignment and re-forms the b64 store together with the moves.  The compiler's wait-count insertion does
+  // not see LDS traffic issued from inline assembly: lds_pair_wait() below is what orders these stores before the barrier.
+  // The whole quad (L == 4, the gathered side of a 128-row weight gradient) keeps its ds_write_b128 and its 16 moves: as two
+  // ds_write2_b32 per column the 128x32 weight gradients measured slower (profiles/lds_pair_store).
+  // ACG_LDS_PAIR_B64 (tools only, `make pairb64`; never in the shipped library) keeps the paired store for A/B runs.
+#ifdef ACG_LDS_PAIR_B64
+  constexpr bool PAIR_ASM = false;
+#else
+  constexpr bool PAIR_ASM = true;
+#endif
+  constexpr bool ASM_STORES = PAIR_ASM && ((MODE == MODE_WGRAD && LPA == 2) || (MODE != MODE_DGRAD && NVEC && LPB == 2));      // store_tiles issues some
   auto put_part = [&](f4* tile, int width, int kq, int sub, int col, auto lc, const float* v) {
     constexpr int L = decltype(lc)::value;
     char* dst = reinterpret_cast<char*>(tile + kq * width + pcol(col, kq)) + sub * 4;
     if constexpr (L == 4) *reinterpret_cast<f4*>(dst) = f4{v[0], v[1], v[2], v[3]};
-    else if constexpr (L == 2) *reinterpret_cast<f2*>(dst) = f2{v[0], v[1]};
+    else if constexpr (L == 2 && PAIR_ASM) {
+      const unsigned at = (unsigned)reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) char*)dst);      // LDS byte address
+      asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" : : "v"(at), "v"(v[0]), "v"(v[1]) : "memory");
+    } else if constexpr (L == 2) *reinterpret_cast<f2*>(dst) = f2{v[0], v[1]};
     else *reinterpret_cast<float*>(dst) = v[0];
+  };
+  // every LDS store issued so far, the inline-assembly ones included, has completed
+  auto lds_pair_wait = [] {
+    if constexpr (ASM_STORES) __builtin_amdgcn_s_waitcnt(0xc07f);      // gfx9 encoding of lgkmcnt(0) alone: vmcnt and expcnt fields at their maxima
   };
 
   auto store_tiles = [&](auto stage, int buf) {
@@ -674,6 +695,7 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
       load_tiles(jc, ks_begin + J, ks_begin + J < ks_end);
     });
     store_tiles(std::integral_constant<int, 0>{}, 0);
+    lds_pair_wait();
     __syncthreads();
   }
   // iteration ks: LDS[buf] holds step ks; stage J (its source) is free; stage J+1 holds step ks+1.
@@ -697,6 +719,9 @@ __device__ __forceinline__ void conv_body(const ConvArgs& p, const int bx, const
     __builtin_amdgcn_sched_barrier(0);
     static_for<0, NM>([&](auto ic) {
       constexpr int I = decltype(ic)::value;
+      // the last fragment group is waited for here with the LDS counter at zero anyway; said in the source, the same wait also
+      // covers this iteration's inline-assembly stores, and no more of them follow before the barrier
+      if constexpr (I == (NT - 1) * GM) lds_pair_wait();
       mfma(ic);
       if constexpr (I % GM == 0 && I / GM + 1 < NT) frag_read(buf, std::integral_constant<int, I / GM + 1>{});
       static_for<0, NLD>([&](auto pc) {
