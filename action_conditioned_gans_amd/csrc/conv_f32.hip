@@ -846,7 +846,18 @@ int32_t acg_conv2d_pair_path(const acg_conv_desc* d, int32_t transposed, int32_t
   float* const p = const_cast<float*>(probe);
   const int whichA = transposed ? ACG_CONV_FWD : ACG_CONV_DGRAD;
   if (d == nullptr || validate(d, "conv2d_pair_path") != ACG_OK) return 0;
-  if (pair_merged(whichA, d, dtype, "conv2d_pair_path")) return ACG_PAIR_MERGED;
+  if (pair_merged(whichA, d, dtype, "conv2d_pair_path")) {
+    // run_pair runs the merged input gradient and the weight gradient as launches of their own, and each refuses what its own entry
+    // refuses: a storage type no weight gradient has, bf16 tensors off the round8 pitch, a slabs-only flag on a contraction that does
+    // not split (the merged form splits as its stride-1 forward problem does), and the quad slab layout, which run_merged does not write
+    if (dtype != ACG_F32 && dtype != ACG_BF16) return 0;
+    const bool h = dtype == ACG_BF16;
+    if (h && !((d->in_pitch == 0 || d->in_pitch == ((d->in_c + 7) & ~7)) && (d->out_pitch == 0 || d->out_pitch == ((d->out_c + 7) & ~7)))) return 0;
+    if (flags & 4) return 0;
+    if ((flags & 2) && make_plan(merged_dgrad(*d, h).syn, ACG_CONV_FWD, h).splits <= 1) return 0;
+    if ((flags & 1) && make_plan(*d, ACG_CONV_WGRAD, h).splits <= 1) return 0;
+    return ACG_PAIR_MERGED;
+  }
   Job ja, jb;
   if (prepare_pair(ja, jb, whichA, p, p, p, p, p, p, 0.f, d, dtype, p, ~(size_t)0, p, ~(size_t)0, flags, "conv2d_pair_path") != ACG_OK) return 0;
   return pair_kind(whichA, ja, jb);

@@ -23,6 +23,7 @@ that are left without a row.
 
 Run as a script, this file prints the table as the queries tools/conv_path_sweep.hip reads."""
 import collections
+import contextlib
 import ctypes
 
 import torch
@@ -129,6 +130,9 @@ ROWS = [
         _sq(4, 16, 16, 6, 64, 5, 2), dict(fwd='mfma_f32 64x64 s1 ragged', dgrad='mfma_f32 128x32 s4 lin merged red=plain', wgrad='mfma_f32 64x64 s2 ragged red=plain', pair={0: 'merged', 1: 'merged'})),
     row('f32_merged_unsplit', 'merged input gradient, unsplit (256 tiles or more)',
         _sq(32, 64, 64, 1, 16, 5, 2), dict(dgrad='mfma_f32 128x32 s1 lin merged')),
+    row('f32_merged_pair_refusals', 'found by the random sweep (tests/conv_random_cases.py): neither contraction splits, so the pair entry refuses the slabs-only '
+        'flag words 1 and 2 - and acg_conv2d_pair_path answered "merged" for them, without looking at the flag word',
+        _sq(8, 8, 6, 4, 16, 5, 2), dict(fwd='mfma_f32 128x32 s1 lin', dgrad='mfma_f32 128x32 s1 lin merged', wgrad='mfma_f32 128x32 s1', pair={0: 'merged', 1: 'refused', 2: 'refused'})),
     # B2: pairs - the A tile x B tile combinations beyond the rows above, MODE_FWD A (transposed layers), the flag words
     row('pair_t_narrow_narrow_lin', 'conv_pair_f32 MODE_FWD A 128x32 LIN, B 128x32',
         _sq(2, 16, 16, 24, 16, 5, 2), dict(fwd='mfma_f32 128x32 s1', dgrad='mfma_f32 128x32 s4 lin red=plain', wgrad='mfma_f32 128x32 s1', pair={0: 'conv_pair_f32', 2: 'conv_pair_f32', 6: 'conv_pair_f32'}), transposed=True),
@@ -436,9 +440,10 @@ class Runner:
     """A row's contractions through the full-descriptor entries of abi_call.Abi, each against float64, with the pad channels and the
     channels beyond a limit held to the sentinel and every workspace's canary checked."""
 
-    def __init__(self, abi, r, figures=None):
+    def __init__(self, abi, r, figures=None, dy_pad=X_PAD):
+        """``dy_pad``: what the fp32 pad channels of the out-side tensors hold (acgan_hip.h wants zeros in those of dy)."""
         from abi_call import Abi
-        self.r, self.d, self.half = r, desc_of(r), r.storage != 'f32'
+        self.r, self.d, self.half, self.dy_pad = r, desc_of(r), r.storage != 'f32', dy_pad
         self.abi = Abi(abi.lib, abi.device, conv_dtype=L.ACG_BF16 if self.half else L.ACG_F32)
         self.store = torch.bfloat16 if self.half else torch.float32
         self.lay = layer(r, abi.device)
@@ -450,7 +455,7 @@ class Runner:
         return _r8(c) if self.half else (p or c)
 
     def tensor(self, side, t):
-        out = torch.full(t.shape[:-1] + (self.pitch(side),), 0.0 if self.half else X_PAD, dtype=self.store, device=t.device)
+        out = torch.full(t.shape[:-1] + (self.pitch(side),), 0.0 if self.half else (X_PAD if side == 'in' else self.dy_pad), dtype=self.store, device=t.device)
         out[..., :t.shape[-1]] = t.to(self.store)
         return out
 
@@ -576,6 +581,17 @@ class Runner:
             self.bitwise(dw, dw_sep, '%s %s: dw vs the separate weight gradient' % (self.r.name, tag))
             self.close(dw, acc * dw0.double() + self.lay.dW.to(dw.device), TOL_CONV, tag + ' dw')
 
+    def pair_refused(self, flags):
+        """A flag word for which acg_conv2d_pair_path answers 'refused': the entry must say so too (an error, not a launch of something else)."""
+        dy, _, side, _, _ = self.dgrad_io()
+        x, _ = self.wgrad_io()
+        try:
+            self.keep(*self.abi.bwd_pair_d(self.d, self.r.transposed, dy, self.lay.w, x, None if flags & 2 else self.output(side), None if flags & 1 else self.dw0(13), 0.0, flags))
+        except L.AcgError:
+            self.abi.sync()
+            return
+        raise AssertionError('%s pair flags %d: acg_conv2d_pair_path answers "refused", the entry ran' % (self.r.name, flags))
+
 
 def case_row(abi, r, figures=None, pair_flags=None):
     """Every contraction the row lists.  ``pair_flags``: the flag words to run (None: all the row lists; the C oracle knows 0 and 1)."""
@@ -587,27 +603,125 @@ def case_row(abi, r, figures=None, pair_flags=None):
         run.dgrad()
     if 'wgrad' in r.expect:
         run.wgrad()
-    for flags in r.expect.get('pair', {}):
+    for flags, kind in r.expect.get('pair', {}).items():
         if pair_flags is None or flags in pair_flags:
-            run.pair(flags)
+            run.pair_refused(flags) if kind == 'refused' else run.pair(flags)
+
+
+def planned(lib, r, pair_flags=(0,)):
+    """What the planner answers for a row (acg_conv2d_path / acg_conv2d_pair_path; nothing is launched): the ConvPath of the layer's
+    three contractions under 'fwd', 'dgrad', 'wgrad', and {flag word: kind} under 'pair'.  A valid descriptor the planner refuses
+    raises (AcgError)."""
+    d = desc_of(r)
+    out = {c: query(lib, r, c) for c in ('fwd', 'dgrad', 'wgrad')}
+    out['pair'] = {f: L.PAIR_KINDS[lib.conv2d_pair_path(ctypes.byref(d), 1 if r.transposed else 0, dtype_of(r), f)] for f in pair_flags}
+    return out
+
+
+def case_planned(abi, lib, r, figures=None, pair_flags=(0,), max_flop=MAX_FLOP, dy_pad=0.0):
+    """A row WITHOUT expectations (tests/conv_random_cases.py): all three contractions, and the paired entry at every flag word of
+    ``pair_flags`` - as case_row runs it where acg_conv2d_pair_path of ``lib`` names a kind, and held to its refusal where the query
+    answers 'refused'.  ``lib`` answers the queries (libacgan_hip.so; they need no GPU), ``abi`` runs the row (the library on a GPU,
+    or the C oracle, which knows the flag words 0 and 1).  The out-side pad channels hold ``dy_pad``: zeros, as acgan_hip.h asks of
+    dy.  -> ``planned``."""
+    assert not r.expect and flop(r) <= max_flop, '%s: %.1f MFLOP' % (r.name, flop(r) / 1e6)
+    plan = planned(lib, r, pair_flags)
+    run = Runner(abi, r, figures, dy_pad=dy_pad)
+    run.fwd()
+    run.dgrad()
+    run.wgrad()
+    for flags, kind in plan['pair'].items():
+        run.pair_refused(flags) if kind == 'refused' else run.pair(flags)
+    return plan
+
+
+# ---- the uniform_k / uniform_w switches (acgan_conv_plan.h): shared by the variant tests and the random sweep -----------------------
+PLAN_FIELDS = ('family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce', 'direct_nb')
+
+
+@contextlib.contextmanager
+def switches(lib, uk=1, uw=1):
+    """acg_conv2d_uniform_k(uk) and acg_conv2d_uniform_w(uw) for the block; both back on afterwards, whatever happens inside."""
+    lib.conv2d_uniform_k(uk)
+    lib.conv2d_uniform_w(uw)
+    try:
+        yield
+    finally:
+        lib.conv2d_uniform_k(1)
+        lib.conv2d_uniform_w(1)
+
+
+def same_plan(on, off, tag, fields=PLAN_FIELDS):
+    """Two answers of the path query for one contraction, under different switches: no plan field may move."""
+    for f in fields:
+        assert getattr(on, f) == getattr(off, f), '%s: the switch moved %s from %d to %d' % (tag, f, getattr(off, f), getattr(on, f))
+
+
+def same_bits(a, b, tag, how):
+    """Two {name: tensor or None} results of one launch: the same names, and every tensor bit for bit."""
+    assert sorted(a) == sorted(b), (tag, sorted(a), sorted(b))
+    for k in a:
+        if a[k] is not None or b[k] is not None:
+            Runner.bitwise(a[k], b[k], '%s: %s %s' % (tag, k, how))
+
+
+def both_ways(lib, tag, fn, on, off):
+    """``fn()`` -> {name: tensor} under switches(**on), then under switches(**off): bit-identical.  -> the result with ``on``."""
+    with switches(lib, **on):
+        a = fn()
+    with switches(lib, **off):
+        b = fn()
+    same_bits(a, b, tag, 'with the variant on vs off')
+    return a
+
+
+def run_once(run, contraction, acc=0.5):
+    """One contraction of a Runner's row through its plain entry, checked against float64 -> {name: tensor}: the result and the
+    workspace (the slabs of a split plan).  Outputs start at SENTINEL, so pad channels are part of what is compared; a weight gradient
+    accumulates ``acc`` times a seeded dw0, or with ``acc`` 0 writes into a sentinel-filled dw (the launch owns every bit)."""
+    abi, d, t, w = run.abi, run.d, run.r.transposed, run.lay.w
+    if contraction == 'fwd':
+        x, ref, side = run.fwd_io()
+        y = run.output(side)
+        ws = abi.fwd_d(d, t, x, w, y)
+        run.keep(ws)
+        run.done()
+        run.check_out(y, ref, ref.shape[-1], ref.shape[-1], 'fwd')
+        return dict(y=y, ws=ws)
+    if contraction == 'dgrad':
+        dy, ref, side, c, n = run.dgrad_io()
+        dx = run.output(side)
+        ws = abi.dgrad_d(d, t, dy, w, dx)
+        run.keep(ws)
+        run.done()
+        run.check_out(dx, ref, c, n, 'dgrad')
+        return dict(dx=dx, ws=ws)
+    x, dy = run.wgrad_io()
+    dw0 = run.dw0(23) if acc else torch.full(w.shape, SENTINEL, device=abi.device)
+    dw = dw0.clone()
+    ws = abi.wgrad_d(d, t, x, dy, dw, acc)
+    run.keep(ws)
+    run.done()
+    run.close(dw, acc * dw0.double() + run.lay.dW.to(dw.device), TOL_CONV, 'wgrad accumulate %g' % acc)
+    return dict(dw=dw, ws=ws)
 
 
 def _act(t, act, leak=0.2):
     return {None: lambda v: v, 'relu': torch.relu, 'lrelu': lambda v: torch.where(v > 0, v, leak * v), 'tanh': torch.tanh}[act](t)
 
 
-def case_epi(abi, name, desc, storage, fused, figures=None):
+def case_epi(abi, name, desc, storage, fused, figures=None, dy_pad=X_PAD):
     """acg_deconv2d_fwd_bias_act on an adjoint descriptor: every activation against float64 where acg_deconv2d_fwd_bias_act_ok says
     yes; where it says no the entry must refuse (ACG_ERR_UNSUPPORTED) and leave y alone."""
     r = row(name, 'fused bias + activation', desc, {}, transposed=True, storage=storage)
-    run = Runner(abi, r, figures)
+    run = Runner(abi, r, figures, dy_pad=dy_pad)
     d, lay = run.d, run.lay
     ok = run.abi.lib.deconv2d_fwd_bias_act_ok(ctypes.byref(d), dtype_of(r))
     assert bool(ok) == fused, 'row %s: acg_deconv2d_fwd_bias_act_ok answers %d.  %s' % (name, ok, HOW)
     x = run.tensor('out', lay.B)
     bias = (torch.randn((d.in_c,), generator=torch.Generator().manual_seed(5)) * 0.5).to(abi.device)
     for act in ACTS:
-        y = torch.full((d.batch, d.in_h, d.in_w, d.in_c), SENTINEL, device=abi.device)
+        y = torch.full((d.batch, d.in_h, d.in_w, d.in_pitch or d.in_c), SENTINEL, device=abi.device)      # fp32 rows at the adjoint's in_pitch
         if not fused:
             try:
                 run.abi.fwd_bias_act_d(d, x, lay.w, bias, y, act, 0.2)
@@ -619,15 +733,15 @@ def case_epi(abi, name, desc, storage, fused, figures=None):
             raise AssertionError(name + ': the entry launched a shape acg_deconv2d_fwd_bias_act_ok refuses')
         run.abi.fwd_bias_act_d(d, x, lay.w, bias, y, act, 0.2)
         run.done()
-        run.close(y, _act(lay.CtB + bias.double().to(lay.CtB.device), act), TOL_CONV, 'bias + %s' % act)
+        run.check_out(y, _act(lay.CtB + bias.double().to(lay.CtB.device), act), d.in_c, d.in_c, 'bias + %s' % act, TOL_CONV)
 
 
-def case_stats(abi, name, desc, transposed, groups, provided, figures=None):
+def case_stats(abi, name, desc, transposed, groups, provided, figures=None, dy_pad=X_PAD):
     """acg_(de)conv2d_fwd_stats + acg_bn_act_fwd_partials against float64 BatchNorm of the conv output as stored (the bars of
     op_cases.case_conv_bn_stats); where acg_conv2d_stats_blocks returns 0 the entry must refuse."""
     from abi_call import _p
     r = row(name, 'statistics epilogue', desc, {}, transposed=transposed)
-    run = Runner(abi, r, figures)
+    run = Runner(abi, r, figures, dy_pad=dy_pad)
     d, lay, lib = run.d, run.lay, run.abi.lib
     which = L.CONV_DGRAD if transposed else L.CONV_FWD
     nblk = lib.conv2d_stats_blocks(ctypes.byref(d), which, L.ACG_F32, groups)

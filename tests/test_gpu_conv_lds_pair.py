@@ -15,7 +15,6 @@ Shapes are the smallest that reach each instantiation; most are the cases of tes
 The 128x32 weight gradient (whole-quad stores on its gathered side, single dwords on its dense side) is here as the neighbour
 whose stores did not change."""
 import collections
-import contextlib
 import ctypes
 
 import pytest
@@ -57,18 +56,9 @@ CASES = [
          P._sq(2, 13, 11, 32, 128, 5, 2), dict(wgrad=(W64, (), 0, 1)), transposed=True, pair=(W64, 1)),
 ]
 
-PLAN_FIELDS = ('family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce', 'direct_nb')
-
-
-@contextlib.contextmanager
 def variants(lib, on):
-    lib.conv2d_uniform_k(on)
-    lib.conv2d_uniform_w(on)
-    try:
-        yield
-    finally:
-        lib.conv2d_uniform_k(1)
-        lib.conv2d_uniform_w(1)
+    """Both switches for a block (conv_path_cases.switches, shared with the other variant tests and the random sweep)."""
+    return P.switches(lib, uk=on, uw=on)
 
 
 def row_of(c):
@@ -92,8 +82,7 @@ def premise(lib, c, r):
         assert (on.uniform_k, on.uniform_w) == (uk, uw), '%s %s: uniform_k %d uniform_w %d, the case is there for %d %d (%s).  %s' % (
             c.name, contraction, on.uniform_k, on.uniform_w, uk, uw, s, P.HOW)
         assert (off.uniform_k, off.uniform_w) == (0, 0), '%s %s: a variant is reported with the switches off' % (c.name, contraction)
-        for f in PLAN_FIELDS:
-            assert getattr(on, f) == getattr(off, f), '%s %s: the switches moved %s' % (c.name, contraction, f)
+        P.same_plan(on, off, '%s %s' % (c.name, contraction))
         out[contraction] = on
     if c.pair is not None:
         d = P.desc_of(r)
@@ -142,10 +131,7 @@ def run_pair(run):
 
 def twice(name, what, fn):
     a, b = fn(), fn()
-    assert sorted(a) == sorted(b)
-    for k in a:
-        if a[k] is not None or b[k] is not None:
-            P.Runner.bitwise(a[k], b[k], '%s %s: %s of two runs of the same launch' % (name, what, k))
+    P.same_bits(a, b, '%s %s' % (name, what), 'of two runs of the same launch')
     return a
 
 

@@ -12,7 +12,6 @@ Shapes are (b, h, w, cin, cout, k, stride) layers with SAME padding, a few MFLOP
 (in side = the layer's output), so its forward is the descriptor's DGRAD - stride classes, tap subsets - and its input gradient the
 descriptor's FWD."""
 import collections
-import contextlib
 import ctypes
 
 import pytest
@@ -59,16 +58,9 @@ CASES = [
          P._sq(2, 8, 8, 138, 64, 3, 1, dgrad_c=128), dict(fwd=0, dgrad=1)),
 ]
 
-PLAN_FIELDS = ('family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce', 'direct_nb')
-
-
-@contextlib.contextmanager
 def variant(lib, on):
-    lib.conv2d_uniform_k(on)
-    try:
-        yield
-    finally:
-        lib.conv2d_uniform_k(1)
+    """acg_conv2d_uniform_k(on) for a block (conv_path_cases.switches: the helper the variant tests and the random sweep share)."""
+    return P.switches(lib, uk=on)
 
 
 def row_of(c):
@@ -81,40 +73,13 @@ def paths(lib, r, contraction, as_pair_a=False):
         on = P.query(lib, r, contraction, as_pair_a)
     with variant(lib, 0):
         off = P.query(lib, r, contraction, as_pair_a)
-    for f in PLAN_FIELDS:
-        assert getattr(on, f) == getattr(off, f), '%s %s: the switch moved %s from %d to %d' % (r.name, contraction, f, getattr(off, f), getattr(on, f))
+    P.same_plan(on, off, '%s %s' % (r.name, contraction))
     assert off.uniform_k == 0, '%s %s: the variant is reported with the switch off' % (r.name, contraction)
     assert on.family == L.ConvPath.FAMILIES.index('mfma_f32'), '%s %s: not on the fp32 MFMA kernels.  %s' % (r.name, contraction, P.HOW)
     return on
 
 
-def run_once(run, contraction):
-    """One contraction of the row through its plain entry -> {tag: tensor}: the result and the workspace (the slabs of a split plan)."""
-    abi, d, t, w = run.abi, run.d, run.r.transposed, run.lay.w
-    if contraction == 'fwd':
-        x, ref, side = run.fwd_io()
-        y = run.output(side)
-        ws = abi.fwd_d(d, t, x, w, y)
-        run.keep(ws)
-        run.done()
-        run.check_out(y, ref, ref.shape[-1], ref.shape[-1], 'fwd')
-        return dict(y=y, ws=ws)
-    if contraction == 'dgrad':
-        dy, ref, side, c, n = run.dgrad_io()
-        dx = run.output(side)
-        ws = abi.dgrad_d(d, t, dy, w, dx)
-        run.keep(ws)
-        run.done()
-        run.check_out(dx, ref, c, n, 'dgrad')
-        return dict(dx=dx, ws=ws)
-    x, dy = run.wgrad_io()
-    dw0 = run.dw0(23)
-    dw = dw0.clone()
-    ws = abi.wgrad_d(d, t, x, dy, dw, 0.5)
-    run.keep(ws)
-    run.done()
-    run.close(dw, 0.5 * dw0.double() + run.lay.dW.to(dw.device), P.TOL_CONV, 'wgrad accumulate 0.5')
-    return dict(dw=dw, ws=ws)
+run_once = P.run_once      # one contraction through its plain entry -> {tag: tensor}: the result and the workspace; a weight gradient at accumulate 0.5
 
 
 def run_pair(run):
@@ -132,13 +97,7 @@ def run_pair(run):
 
 
 def both_ways(lib, name, what, fn):
-    with variant(lib, 1):
-        on = fn()
-    with variant(lib, 0):
-        off = fn()
-    assert sorted(on) == sorted(off)
-    for k in on:
-        P.Runner.bitwise(on[k], off[k], '%s %s: %s with the variant on vs off' % (name, what, k))
+    P.both_ways(lib, '%s %s' % (name, what), fn, dict(uk=1), dict(uk=0))
 
 
 @pytest.mark.parametrize('c', CASES, ids=lambda c: c.name)

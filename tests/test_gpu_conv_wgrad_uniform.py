@@ -25,7 +25,6 @@ acg_conv_path.uniform_w answers (conv_f32_pair.hip: launch_b; no query reports w
 64x64 A - the premise test asserts it - so their B does run the variant; for the left-out combination an on / off comparison would compare
 the generic loaders with themselves."""
 import collections
-import contextlib
 import ctypes
 
 import pytest
@@ -71,19 +70,12 @@ CASES = [
     case('novec_25', 'N = 25: dY rows are not float4-able (nvec off)', P._sq(2, 9, 7, 32, 25, 3, 1), 0),
 ]
 
-PLAN_FIELDS = ('family', 'tile_rows', 'tile_cols', 'tiles', 'classes', 'nk', 'splits', 'ragged', 'nvec', 'lin', 'compact', 'merged', 'reduce', 'direct_nb',
-               'uniform_k')
+PLAN_FIELDS = P.PLAN_FIELDS + ('uniform_k',)
 
 
-@contextlib.contextmanager
 def variant(lib, on, uk=1):
-    lib.conv2d_uniform_w(on)
-    lib.conv2d_uniform_k(uk)
-    try:
-        yield
-    finally:
-        lib.conv2d_uniform_w(1)
-        lib.conv2d_uniform_k(1)
+    """acg_conv2d_uniform_w(on) and acg_conv2d_uniform_k(uk) for a block (conv_path_cases.switches, shared with the other variant tests)."""
+    return P.switches(lib, uk=uk, uw=on)
 
 
 def row_of(c):
@@ -96,8 +88,7 @@ def paths(lib, r):
         on = P.query(lib, r, 'wgrad')
     with variant(lib, 0):
         off = P.query(lib, r, 'wgrad')
-    for f in PLAN_FIELDS:
-        assert getattr(on, f) == getattr(off, f), '%s: the switch moved %s from %d to %d' % (r.name, f, getattr(off, f), getattr(on, f))
+    P.same_plan(on, off, r.name, PLAN_FIELDS)
     assert off.uniform_w == 0, '%s: the variant is reported with the switch off' % r.name
     assert on.uniform_k == 0, '%s: a weight gradient reports uniform_k' % r.name
     assert on.family == L.ConvPath.FAMILIES.index('mfma_f32'), '%s: not on the fp32 MFMA kernels.  %s' % (r.name, P.HOW)
@@ -131,14 +122,7 @@ def run_pair(run):
 
 
 def both_ways(lib, name, what, fn, uk=1):
-    with variant(lib, 1, uk):
-        on = fn()
-    with variant(lib, 0, uk):
-        off = fn()
-    assert sorted(on) == sorted(off)
-    for k in on:
-        P.Runner.bitwise(on[k], off[k], '%s %s: %s with the variant on vs off' % (name, what, k))
-    return on
+    return P.both_ways(lib, '%s %s' % (name, what), fn, dict(uk=uk, uw=1), dict(uk=uk, uw=0))
 
 
 @pytest.mark.parametrize('c', CASES, ids=lambda c: c.name)
