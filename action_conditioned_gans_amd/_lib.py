@@ -265,6 +265,12 @@ EXTENSIONS = {
         # (ops.LatentOp / LatentBwdOp, train.Trainer posterior)
         'acg_latent_fwd': (STATUS, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
         'acg_latent_bwd': (STATUS, [_P, _P, _P, _P, c_float, _P, _P, c_int32, c_int32, c_int32, _P]),
+        # differentiable augmentation of the discriminator's inputs (ops.DAugmentDrawOp / DAugmentOp / DAugmentBwdOp,
+        # train.Trainer d_augment): the parameter draw, the transform and its adjoint
+        'acg_d_augment_draw': (STATUS, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+        'acg_d_augment_workspace_bytes': (c_int64, [c_int32] * 5),
+        'acg_d_augment_fwd': (STATUS, [_P, _P, _P] + [c_int32] * 6 + [_P, c_int64, _P]),
+        'acg_d_augment_bwd': (STATUS, [_P, _P, _P] + [c_int32] * 6 + [_P, c_int64, _P]),
     }),
     # BatchNorm with stored statistics: the apply pass on its own and the calibration pass that pools the moments of the batches
     # it is shown (ops.BnInferOp / BnCollectOp)
@@ -312,6 +318,9 @@ PLAN_ACTION_DIM_MAX = 8
 PLAN_STATE_DIM_MAX = 16
 PLAN_PIXEL_MAPS_MAX = 4       # acgan_rollout.h ACG_PLAN_PIXEL_MAPS_MAX / ACG_PLAN_MAP_SIDE_MAX
 PLAN_MAP_SIDE_MAX = 1024
+DA_STREAM_TAG = 0x44415547    # acgan_rollout.h ACG_DA_STREAM_TAG / ACG_DA_ROWS_MAX / ACG_DA_COLOR, _TRANSLATION, _CUTOUT
+DA_ROWS_MAX = 1024
+DA_POLICY_BITS = {'color': 1, 'translation': 2, 'cutout': 4}
 
 
 def dtype2(first, second):

@@ -1464,6 +1464,107 @@ class InstNoiseOp(G.Op):
         return [gouts[0] if needs[0] else None, None, None]
 
 
+D_AUGMENT_STATE = 'd/augment/state'
+D_AUGMENT_NAMES = tuple(_lib.DA_POLICY_BITS)      # the canonical order: color, translation, cutout
+
+
+def d_augment_state(seed=0):
+    """The augmentation state of the graph, created by the first call (``seed`` is read by that call alone): ``d/augment/state``
+    (new_draw_state: {seed, counter}, the counter is the number of draws so far); a checkpoint key."""
+    g = G.get_default_graph()
+    if 'd_augment' not in g.collections:
+        g.collections['d_augment'] = new_draw_state(D_AUGMENT_STATE, seed, 'd_augment')
+    return g.collections['d_augment']
+
+
+class DAugmentDrawOp(G.Op):
+    """The augmentation parameters of one D instance (acg_d_augment_draw): -> ``params`` float32 [rows, 8], row r =
+    (b, s, c, ty, tx, cy0, cx0, n) for images of ``h`` x ``w`` under ``policy`` (the ACG_DA_* bits), drawn from the graph's
+    augmentation state (d_augment_state), whose counter the launch advances - a program that holds this op draws fresh parameters
+    every time it runs, replayed from a captured graph or not.  ``slot`` in 0..63 is the slot of the D instance: the draw's stream id
+    is rank * 64 + slot, so instances and ranks draw different parameters.  params is a plain tensor, not state: no checkpoint
+    key.  No inputs, no gradient."""
+
+    def __init__(self, rows, h, w, policy, slot, name):
+        self.rows, self.h, self.w, self.policy, self.slot = int(rows), int(h), int(w), int(policy), int(slot)
+        if not (1 <= self.rows <= _lib.DA_ROWS_MAX and 1 <= self.h <= 1024 and 1 <= self.w <= 1024):
+            raise ValueError('d_augment_draw: %d rows of %d x %d (1 <= rows <= %d, 1 <= h, w <= 1024)' % (self.rows, self.h, self.w, _lib.DA_ROWS_MAX))
+        if not 0 <= self.policy <= sum(_lib.DA_POLICY_BITS.values()):
+            raise ValueError('d_augment_draw: policy must be in 0..%d, got %d' % (sum(_lib.DA_POLICY_BITS.values()), self.policy))
+        if not 0 <= self.slot < INST_NOISE_SLOTS:
+            raise ValueError('d_augment_draw: slot (the instance slot) must be in 0..%d, got %d' % (INST_NOISE_SLOTS - 1, self.slot))
+        self.extras = [d_augment_state()]
+        self.params = _new((self.rows, 8), name + ':params')
+        super().__init__(G.get_default_graph(), name, [], [self.params])
+
+    def bind(self, rt):
+        fn = _lib.entry(rt.lib, 'd_augment_draw')
+        args = (_p(self.extras[0].buf), _p(self.params.buf), self.rows, self.h, self.w, self.policy, int(rt.rank) * INST_NOISE_SLOTS + self.slot)
+        return lambda s: fn(*args, s)
+
+
+def _d_augment_geometry(x, params, frames, cf, who):
+    frames, cf = int(frames), int(cf)
+    if x.dtype != torch.float32 or params.dtype != torch.float32:
+        raise ValueError('%s: float32 input and parameters, got %s and %s' % (who, x.dtype, params.dtype))
+    if len(x.shape) != 4:
+        raise ValueError('%s: input [rows, h, w, pitch], got %s' % (who, x.shape))
+    rows, h, w, pitch = x.shape
+    c = x.valid_c or pitch
+    if not (1 <= frames <= 2 and 1 <= cf <= 4 and frames * cf <= c):
+        raise ValueError('%s: %d frames of %d channels in %d (1 <= frames <= 2, 1 <= cf <= 4)' % (who, frames, cf, c))
+    if not (1 <= rows <= _lib.DA_ROWS_MAX and 1 <= h <= 1024 and 1 <= w <= 1024):
+        raise ValueError('%s: %d rows of %d x %d (1 <= rows <= %d, 1 <= h, w <= 1024)' % (who, rows, h, w, _lib.DA_ROWS_MAX))
+    if params.shape != (rows, 8):
+        raise ValueError('%s: parameters %s, expected [%d, 8]' % (who, params.shape, rows))
+    return rows, h, w, pitch, frames, cf
+
+
+def _d_augment_bind(op, rt, which, src, params, dst):
+    fn, size = _lib.entry(rt.lib, which), _lib.entry(rt.lib, 'd_augment_workspace_bytes')
+    rows, h, w, pitch, frames, cf = op.geometry
+    ws, n = rt.workspace(size(rows, h, w, frames, cf))
+    op._keep = ws
+    args = (_p(src.buf), _p(params.buf), _p(dst.buf), rows, h, w, pitch, frames, cf, _p(ws), n)
+    return lambda s: fn(*args, s)
+
+
+class DAugmentOp(G.Op):
+    """The differentiable augmentation of a D input (acg_d_augment_fwd): x float32 [rows, h, w, pitch] with ``frames`` frames of
+    ``cf`` channels -> a new activation tensor with the shape, pitch and ``valid_c`` of ``x``: colour, translation and cutout
+    under ``params`` [rows, 8] (a DAugmentDrawOp's), both frames of a row alike; the pad channels are copied.  The gradient of
+    ``x`` is the transform's adjoint (DAugmentBwdOp), a tensor in ``x``'s layout: the window acg_dna_bwd reads stays where it is.
+    ``params`` has no gradient."""
+
+    def __init__(self, x, params, frames, cf, name):
+        self.geometry = _d_augment_geometry(x, params, frames, cf, 'd_augment')
+        y = _new(x.shape, name + ':0', x.dtype)
+        y.valid_c = x.valid_c
+        super().__init__(G.get_default_graph(), name, [x, params], [y])
+
+    def bind(self, rt):
+        return _d_augment_bind(self, rt, 'd_augment_fwd', self.inputs[0], self.inputs[1], self.outputs[0])
+
+    def grad(self, gouts, needs, ctx):
+        if not needs[0] or gouts[0] is None:
+            return [None, None]
+        return [DAugmentBwdOp(gouts[0], self.inputs[1], self.geometry[4], self.geometry[5], self.inputs[0].valid_c, self.name + '/bwd').outputs[0], None]
+
+
+class DAugmentBwdOp(G.Op):
+    """acg_d_augment_bwd: the adjoint of a DAugmentOp under the same ``params`` - dout [rows, h, w, pitch] -> the gradient of the
+    op's input in the same layout, pad channels +0."""
+
+    def __init__(self, dout, params, frames, cf, valid_c, name):
+        self.geometry = _d_augment_geometry(dout, params, frames, cf, 'd_augment_bwd')
+        din = _new(dout.shape, name + ':0', dout.dtype)
+        din.valid_c = valid_c
+        super().__init__(G.get_default_graph(), name, [dout, params], [din])
+
+    def bind(self, rt):
+        return _d_augment_bind(self, rt, 'd_augment_bwd', self.inputs[0], self.inputs[1], self.outputs[0])
+
+
 class LogitStatsOp(G.Op):
     """acg_logit_stats: -> float32 [4] = {mean D(fake) logit, mean D(real) logit, share of fake logits < 0, share of real logits
     > 0} of two equally long float32 logit tensors.  One launch of one block; no gradient."""

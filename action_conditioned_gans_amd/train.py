@@ -46,7 +46,7 @@ class Trainer:
                  g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0, lr_final=0.0,
                  sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_offset=0, ss_seed=0, pixel_maps=0,
                  d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, d_stats=False, canvas=False,
-                 posterior=False, kl_weight=1.0):
+                 posterior=False, kl_weight=1.0, d_augment=None, d_augment_seed=0):
         """``lookahead`` (no reference counterpart, off the reference's call path unless asked for): builds a second generator
         instance on a batch of 2 B - the pair (generator-step samples ; discriminator-step samples), BatchNorm statistics per half -
         that ``train_d(..., next_g=...)`` runs INSTEAD of the batch-B instance; the ``train_g`` call that follows with the announced
@@ -168,6 +168,21 @@ class Trainer:
         take it; more than one rank is allowed - the rank is part of the stream id - and not verified.  The look-ahead
         pair pass is switched off, as it is for noise_dim.  Declined before anything is created: ``rollout_steps`` > 1 (the K-step
         programs' D(fake) instances read no noise), ``arg_adv=False``, a negative or non-finite level.
+        ``d_augment`` LIST, ``d_augment_seed`` (no reference counterpart; None or '' builds nothing: ops, op order, variables, state
+        names, checkpoint keys, summaries and ``graph.collections`` are those of a Trainer without the arguments): differentiable
+        augmentation (DiffAugment, Zhao et al. 2020) of every pair the discriminator judges.  LIST is a comma-separated subset of
+        ``color``, ``translation``, ``cutout`` in any order.  D(both) - D(real) and D(fake) with ``batched_d=False`` - and the G
+        step's D(fake) read a transformed copy of their 6-channel input, both frames of a row under the same parameters, the
+        rows (the fake and the real row of a sample too) under independent ones (ops.DAugmentOp, acg_d_augment_fwd), and G's
+        gradient goes back through the transform's adjoint (ops.DAugmentBwdOp).  The parameters are drawn on the device inside
+        the program, one ops.DAugmentDrawOp per D instance (stream id rank * 64 + slot: gen 0, real 1, both 2) from the graph
+        state ``d/augment/state`` = {``d_augment_seed``, counter}; every program that runs a D instance runs its draw once - the
+        D step, the G step and the summaries alike - so the counter counts draws.  That state is the only new checkpoint key (a
+        checkpoint without it starts at 0); no variable, optimizer slot or summary is added.  With ``d_noise`` the noise is
+        added to the augmented input.  ``d_augment_last()`` reads the parameters of the last program, ``d_augment_state()`` the
+        state.  The look-ahead pair pass is switched off, as it is for ``d_noise``.  Declined before anything is created
+        (check_d_augment): an unknown or repeated name, ``rollout_steps`` > 1, ``arg_adv=False``, a bf16 graph.  More than one
+        rank is allowed - the rank is part of the stream id - and not verified.
         ``d_stats=True`` (False adds nothing): the summaries ``d_fake_logit`` / ``d_real_logit`` - the mean logit of D on the
         generated and on the real half - and ``d_fake_acc`` / ``d_real_acc`` - the share of fake logits < 0 and of real logits > 0 -
         computed on the device from the logits the D loss reads (ops.LogitStatsOp), and with ``d_noise`` > 0 ``d_noise_sigma``, the
@@ -202,6 +217,8 @@ class Trainer:
         self.canvas =check_canvas(canvas, model_kind(arg_transform), ksize, num_masks)      # (before anything is created)
         self.d_noise = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, d_noise_offset, d_noise_seed, rollout_steps,
                                      arg_adv)         # (before anything is created; None: off)
+        self.d_augment = check_d_augment(d_augment, d_augment_seed, rollout_steps, arg_adv,
+                                         bf16=G.get_default_graph().act_dtype != torch.float32)      # (the same)
         self.pixel_maps = check_pixel_maps(pixel_maps, model_kind(arg_transform))      # (before anything is created)
         self.lr_args = check_lr(g_lr, d_lr, beta1, arg_opt, lr_schedule, lr_warmup, lr_decay_steps, lr_final)   # (before anything is created)
         self.noise_dim = check_noise(noise_dim, noise_seed, rollout_steps, bn_inference, batch_size)        # (before anything is created)
@@ -238,7 +255,7 @@ class Trainer:
         dp = graph.collections.get('data_parallel')
         # (synchronised BatchNorm builds other ops per layer and is a validation mode: it keeps the plain call path)
         self.lookahead = bool(lookahead) and batched_d and not (dp is not None and dp.active and dp.sync_bn) and not self.noise_dim \
-            and self.d_noise is None
+            and self.d_noise is None and self.d_augment is None
         self._noise = None            # the [B, 10 + Z] vector the generator reads (noise_dim > 0)
 
         self._kl = None               # KL(q || N(0, 1)) summed over the batch, a Scalar (posterior)
@@ -300,19 +317,34 @@ class Trainer:
         else:
             d_in_gen = O.concat([self.img_ph, self.g_next_frame], axis=3, name='d_in_gen', pitch=8, act=True)
             d_in_real = O.concat([self.img_ph, self.next_frame_ph], axis=3, name='d_in_real', pitch=8, act=True)
-        # what the D instances read: their inputs, or (d_noise) a noisy copy each, drawn under the instance's own stream id
+        # what the D instances read: their inputs, or (d_augment) a transformed and / or (d_noise) a noisy copy each - the noise
+        # behind the augmentation - drawn under the instance's own stream id
         d_x_gen, d_x_real, d_x_both = d_in_gen, d_in_real, d_in_both if batched_d else None
+        self._d_augment_params = {}           # slot name -> the params tensor of that D instance's draw (d_augment)
+        if self.d_augment is not None:
+            da = self.d_augment
+            O.d_augment_state(da['seed'])
+
+            def augmented(t, slot, name):
+                draw = O.DAugmentDrawOp(t.shape[0], S, S, da['policy'], D_SLOTS[slot], name + '/draw')
+                self._d_augment_params[slot] = draw.params
+                return O.DAugmentOp(t, draw.params, 2, 3, name).outputs[0]
+            d_x_gen = augmented(d_in_gen, 'gen', 'd_in_gen/augmented')
+            if batched_d:
+                d_x_both = augmented(d_in_both, 'both', 'd_in_both/augmented')
+            else:
+                d_x_real = augmented(d_in_real, 'real', 'd_in_real/augmented')
         self._d_noise_prep, self.d_noisy = None, {}
         if self.d_noise is not None:
             dn = self.d_noise
             O.inst_noise_state(dn['seed'])
             prep = self._d_noise_prep = O.InstNoisePrepareOp(dn['start'], dn['final'], dn['decay_steps'], dn['offset'], 0, 'd/inst_noise/prepare')
             noisy = lambda t, slot, name: O.InstNoiseOp(t, prep.key, prep.sigma, 3, 3, slot, name).outputs[0]     # noqa: E731
-            d_x_gen = self.d_noisy['gen'] = noisy(d_in_gen, 0, 'd_in_gen/noisy')
+            d_x_gen = self.d_noisy['gen'] = noisy(d_x_gen, 0, 'd_in_gen/noisy')
             if batched_d:
-                d_x_both = self.d_noisy['both'] = noisy(d_in_both, 2, 'd_in_both/noisy')
+                d_x_both = self.d_noisy['both'] = noisy(d_x_both, 2, 'd_in_both/noisy')
             else:
-                d_x_real = self.d_noisy['real'] = noisy(d_in_real, 1, 'd_in_real/noisy')
+                d_x_real = self.d_noisy['real'] = noisy(d_x_real, 1, 'd_in_real/noisy')
         self.d_out_gen = M.build_discriminator(d_x_gen, self.action_ph, reuse=False)
         if batched_d:
             with O.arg_scope([O.batch_norm], groups=2):
@@ -497,6 +529,23 @@ class Trainer:
         self._require_d_noise()
         state, updates = O.inst_noise_state()
         return O.read_draw_state(self.sess._materialize(state)) + (int(self.sess._materialize(updates).item()) % 2 ** 64,)
+
+    # ---- differentiable augmentation of the discriminator's inputs (d_augment)
+    def _require_d_augment(self):
+        if self.d_augment is None:
+            raise RuntimeError('this Trainer was built without d_augment: its discriminator reads no augmented input')
+
+    def d_augment_last(self):
+        """-> {slot name ('gen', 'real', 'both'): params float32 [rows, 8] as numpy} - the parameters every D instance's draw
+        holds: those of the last program that ran the instance (zeros before the first).  One device-to-host copy per
+        instance (a synchronisation)."""
+        self._require_d_augment()
+        return {slot: self.sess._materialize(t).detach().cpu().numpy().copy() for slot, t in self._d_augment_params.items()}
+
+    def d_augment_state(self):
+        """-> (seed, counter) of ``d/augment/state`` as Python ints in [0, 2^64): the counter is the number of draws so far."""
+        self._require_d_augment()
+        return O.read_draw_state(self.sess._materialize(O.d_augment_state()))
 
     # ---- scheduled sampling of the K-step programs (sched_sampling != 'off')
     def _require_sched_sampling(self):
@@ -1142,6 +1191,35 @@ def check_sched_sampling(sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_de
             'offset': counts['ss_offset'], 'seed': seed}
 
 
+D_SLOTS = {'gen': 0, 'real': 1, 'both': 2}      # the D instances' slots in a draw's stream id (instance noise, d_augment)
+
+
+def check_d_augment(d_augment=None, d_augment_seed=0, rollout_steps=1, arg_adv=True, bf16=False):
+    """The differentiable-augmentation arguments of Trainer / train(), checked before anything is created.  ``d_augment``: None or
+    '' (off), or a comma-separated subset of ``color``, ``translation``, ``cutout`` in any order.  Declined (ValueError): an unknown
+    or repeated name, a bad ``d_augment_seed``, and an augmentation together with ``rollout_steps`` > 1, without ``arg_adv`` or in
+    a bf16 graph.  -> None (off, whatever the other arguments are), else {'names': the names in canonical order, 'policy': the
+    ACG_DA_* bits, 'seed'}."""
+    if d_augment is None or d_augment == '':
+        return None
+    if not isinstance(d_augment, str):
+        raise ValueError('d_augment is not a valid policy: a comma-separated subset of %s, got %r' % (', '.join(O.D_AUGMENT_NAMES), d_augment))
+    names = [n.strip() for n in d_augment.split(',')]
+    for n in names:
+        if n not in O.D_AUGMENT_NAMES or names.count(n) > 1:
+            raise ValueError('d_augment %r is not a valid policy: %r is %s (a comma-separated subset of %s)'
+                             % (d_augment, n, 'repeated' if n in O.D_AUGMENT_NAMES else 'unknown', ', '.join(O.D_AUGMENT_NAMES)))
+    seed = check_noise_seed(d_augment_seed, 'd_augment_seed')
+    if rollout_steps > 1:
+        raise ValueError("d_augment does not go with rollout_steps > 1 (the K-step programs' D instances are not augmented)")
+    if not arg_adv:
+        raise ValueError('d_augment needs an adversarial trainer (arg_adv): without one nothing is trained against the discriminator')
+    if bf16:
+        raise ValueError('d_augment does not go with a bf16 graph (the augmentation kernels are float32 only)')
+    names = [n for n in O.D_AUGMENT_NAMES if n in names]
+    return {'names': names, 'policy': sum(_lib.DA_POLICY_BITS[n] for n in names), 'seed': seed}
+
+
 def check_d_noise(d_noise=0.0, d_noise_final=0.0, d_noise_decay_steps=0, d_noise_offset=0, d_noise_seed=0, rollout_steps=1, arg_adv=True):
     """ValueError for instance-noise arguments the Trainer does not take: a level that is not a finite number >= 0 (in float32
     too), a negative or non-integer ``d_noise_decay_steps`` / ``d_noise_offset``, a bad ``d_noise_seed``, and ``d_noise`` > 0 together
@@ -1339,18 +1417,20 @@ class _PairSelections:
 
 
 def train_record(summ, iteration, wall_s, rollout_steps, ema_decay=0.0, ssim_weight=0.0, grad_stats=None, clip_bounds=None, noise_dim=0,
-                 rates=None, ss_prob=None, canvas=False):
+                 rates=None, ss_prob=None, canvas=False, d_augment=None):
     """One ``train.jsonl`` record.  ``grad_stats``: {scope: Trainer.grad_norm_stats(scope)} of the scopes that are measured (none:
     the record is what it was before gradient norms existed) -> ``<scope>_grad_norm`` / ``<scope>_clip_scale``;
     ``clip_bounds``: {scope: bound} -> ``<scope>_clip_norm`` (the first record of a run).  ``noise_dim`` is recorded when > 0.
     ``rates``: Trainer.learning_rates() of a run with a learning-rate schedule (None: no field is added) -> ``g_lr`` / ``d_lr``, the
     rates the iteration's last updates used.  ``ss_prob``: the probability of truth of the iteration's K-step update in a run with
-    scheduled sampling (None: no field is added) -> ``ss_prob``.  ``canvas`` is recorded when on."""
+    scheduled sampling (None: no field is added) -> ``ss_prob``.  ``canvas`` is recorded when on, and so is ``d_augment``, the
+    canonical policy string of a run with differentiable augmentation (None: no field is added)."""
     record = dict(summ, iteration=iteration, wall_s=wall_s, rollout_steps=rollout_steps,
                   **({'g_ema': ema_decay} if ema_decay else {}),
                   **({'ssim_weight': ssim_weight} if ssim_weight else {}),
                   **({'noise_dim': noise_dim} if noise_dim else {}),
-                  **({'canvas': True} if canvas else {}))
+                  **({'canvas': True} if canvas else {}),
+                  **({'d_augment': d_augment} if d_augment else {}))
     for scope in sorted(grad_stats or {}, reverse=True):             # g, then d
         record[scope + '_grad_norm'] = grad_stats[scope]['norm']
         record[scope + '_clip_scale'] = grad_stats[scope]['scale']
@@ -1376,7 +1456,8 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
           num_masks=10, rollout_steps=1, ema_decay=0.0, ssim_weight=0.0, g_clip_norm=0.0, d_clip_norm=0.0, grad_norms=False,
           noise_dim=0, noise_seed=0, g_lr=None, d_lr=None, beta1=None, lr_schedule='constant', lr_warmup=0, lr_decay_steps=0,
           lr_final=0.0, sched_sampling='off', ss_start=1.0, ss_final=0.0, ss_decay_steps=0, ss_seed=0, d_noise=0.0, d_noise_final=0.0,
-          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False, canvas=False, posterior=False, kl_weight=1.0):
+          d_noise_decay_steps=0, d_noise_seed=0, d_stats=False, canvas=False, posterior=False, kl_weight=1.0, d_augment=None,
+          d_augment_seed=0):
     """Training loop of train.py:179-309.  ``input_path``: 'synthetic' (seeded random sequences) or a directory of
     push-dataset TFRecords, read by push_data.PushDataset (the reference's build_tfrecord_input, ops.py:140-223).
     ``dtype``: 'f32', or 'bf16' for the bf16 pipeline of BASELINE configs 3 and 5 (bf16 activations, float32 master weights).
@@ -1428,7 +1509,11 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     ``d_real_acc`` of the interval's last D step and, with ``d_noise`` > 0, its ``d_noise_sigma`` (Trainer ``d_stats``: they are
     summaries).  With both off all of this is unchanged.
     ``canvas``: the CDNA / affine generator composites an image it paints itself (Trainer ``canvas``); ``train.jsonl`` records
-    ``canvas`` and checkpoints hold ``g/tconv4_canvas/*``.  Off, all of this is unchanged."""
+    ``canvas`` and checkpoints hold ``g/tconv4_canvas/*``.  Off, all of this is unchanged.
+    ``d_augment`` / ``d_augment_seed``: differentiable augmentation of the discriminator's inputs (Trainer, same keywords; needs
+    ``arg_adv``, ``rollout_steps`` = 1 and ``dtype`` 'f32').  The loop takes the plain call path (no look-ahead pass), checkpoints
+    hold ``d/augment/state`` and ``train.jsonl`` records ``d_augment``, the policy in canonical order.  Off, all of this is
+    unchanged."""
     for what, v in (('lr_warmup', lr_warmup), ('lr_decay_steps', lr_decay_steps)):
         if isinstance(v, (tuple, list)):
             raise ValueError('%s is a number of training iterations here, got %r' % (what, v))
@@ -1459,6 +1544,9 @@ def train(input_path, output_path, test_output_path, log_dir, model_dir, arg_adv
     dn = check_d_noise(d_noise, d_noise_final, d_noise_decay_steps, 0, d_noise_seed, rollout_steps, arg_adv)
     if dn is not None:                  # iterations -> D updates
         options.update(d_noise=dn['start'], d_noise_final=dn['final'], d_noise_decay_steps=dn['decay_steps'] * D_per_G, d_noise_seed=dn['seed'])
+    da = check_d_augment(d_augment, d_augment_seed, rollout_steps, arg_adv, bf16=dtype != 'f32')
+    if da is not None:
+        options.update(d_augment=','.join(da['names']), d_augment_seed=da['seed'])
     if d_stats:
         options['d_stats'] = True
     for key, value in (('ema_decay', check_ema_decay(ema_decay)), ('ssim_weight', check_ssim_weight(ssim_weight))):
@@ -1592,7 +1680,8 @@ def _train_loop(sess, data, input_path, synthetic, boolean_mask, log_dir, model_
                 _log_jsonl(log_file, train_record(summ, i, time.time() - t0, rollout_steps, trainer.ema_decay, trainer.ssim_weight, stats, bounds,
                                                     trainer.noise_dim, trainer.learning_rates() if scheduled else None,
                                                     ss_prob=trainer.sched_sampling_last()['prob'] if sampling else None,
-                                                    canvas=trainer.canvas))
+                                                    canvas=trainer.canvas,
+                                                    d_augment=','.join(trainer.d_augment['names']) if trainer.d_augment else None))
                 bounds_logged = True
             if model_dir:
                 saver.save(sess, os.path.join(model_dir, 'model{:d}'.format(i)), background=True)      # train.py:274; written by a writer thread
@@ -1761,6 +1850,15 @@ def add_d_noise_args(parser):
                              '(d_fake_logit, d_real_logit, d_fake_acc, d_real_acc) and, with --d_noise, d_noise_sigma')
 
 
+def add_d_augment_args(parser):
+    """The flags of the differentiable augmentation of the discriminator's inputs."""
+    parser.add_argument('--d_augment', type=str, default=None, metavar='LIST',
+                        help='put every pair the discriminator judges, real and generated, through random transforms drawn on the '
+                             'device inside the step, and the generator\'s gradient through their adjoint (DiffAugment): a '
+                             'comma-separated subset of color, translation, cutout (needs --adv; float32 only)')
+    parser.add_argument('--d_augment_seed', type=int, default=0, metavar='SEED', help='seed of the augmentation parameters (0 <= SEED < 2^64)')
+
+
 def add_lr_args(parser):
     """The learning-rate flags: the rates of G and D, Adam's beta1 and the schedule."""
     parser.add_argument('--g_lr', type=float, default=None, metavar='LR', help='learning rate of the generator updates (default: 1e-3 for adam, 5e-5 for rmsprop)')
@@ -1832,6 +1930,7 @@ def main(argv=None):
     add_lr_args(parser)
     add_sched_sampling_args(parser)
     add_d_noise_args(parser)
+    add_d_augment_args(parser)
     args = parser.parse_args(argv)
     if args.buckets < 0:
         parser.error('--buckets must be >= 0')
@@ -1850,7 +1949,9 @@ def main(argv=None):
             ('--sched_sampling / --ss_*: {}', lambda: check_sched_sampling(args.sched_sampling, args.ss_start, args.ss_final, args.ss_decay_iters,
                                                                            0, args.ss_seed, args.rollout_steps, args.batch_size)),
             ('--d_noise / --d_noise_*: {}', lambda: check_d_noise(args.d_noise, args.d_noise_final, args.d_noise_decay_iters, 0,
-                                                                   args.d_noise_seed, args.rollout_steps, args.adv))):
+                                                                   args.d_noise_seed, args.rollout_steps, args.adv)),
+            ('--d_augment / --d_augment_seed: {}', lambda: check_d_augment(args.d_augment, args.d_augment_seed, args.rollout_steps, args.adv,
+                                                                           bf16=args.dtype != 'f32'))):
         try:
             check()
         except ValueError as e:

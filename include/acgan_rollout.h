@@ -361,6 +361,67 @@ int32_t acg_latent_fwd(const float* actions, const float* stats, uint64_t* state
 int32_t acg_latent_bwd(const float* dout, const float* out, const float* stats, const float* mode, float kl_weight, float* dstats,
                        float* dactions, int32_t batch, int32_t action_dim, int32_t latent_dim, acg_stream_t stream);
 
+/* Differentiable augmentation of the discriminator's inputs (DiffAugment, Zhao et al., NeurIPS 2020): every pair D judges, real
+ * and generated, goes through a random colour / translation / cutout transform, and the generator's gradient goes back through
+ * its adjoint.  x float32 [rows, h, w, pitch] holds `frames` frames of `cf` channels each at the channels [f * cf, (f + 1) * cf);
+ * the channels [frames * cf, pitch) are pad.  params float32 [rows, 8], row r = (b, s, c, ty, tx, cy0, cx0, n): both frames of a
+ * row get the same parameters, the rows of a launch independent ones.
+ *
+ * acg_d_augment_fwd.  Per frame of a row, with X[y, x, ch] its values:
+ *   pm[y, x]      = mean over ch of X[y, x, .]          fm = mean over y, x, ch of X
+ *   col[y, x, ch] = c * s * X[y, x, ch] + c * (1 - s) * pm[y, x] + (1 - c) * fm + b
+ *     (brightness + b, then saturation about the pixel's channel mean by s, then contrast about the frame mean by c)
+ *   out[y, x, ch] = 0                          if (y - ty, x - tx) is outside the image
+ *                 = 0                          if cy0 <= y < cy0 + n and cx0 <= x < cx0 + n
+ *                 = col[y - ty, x - tx, ch]    otherwise
+ * and out[y, x, ch] for ch >= frames * cf is a copy of the bits of in[y, x, ch].  In float32: k1 = c * s, k2 = c * (1 - s),
+ * out = fmaf(k1, X, fmaf(k2, pm, fmaf(1 - c, fm, b))), pm the channels summed in ascending order over cf, fm a sum in double
+ * rounded to float32 once.  The identity (0, 1, 1, 0, 0, 0, 0, 0) therefore gives 1 * X + 0: the valid channels of a frame of
+ * finite values come back bit for bit, except that -0.0 becomes +0.0.
+ *
+ * acg_d_augment_bwd, the adjoint.  Per frame, t = (ty, tx):
+ *   g'[q]      = dout[q + t]   if q + t is inside the image and not in the cut rectangle, else 0
+ *   din[q, ch] = c * s * g'[q, ch] + c * (1 - s) * mean_ch g'[q, .] + (1 - c) * mean_frame g'
+ * and the pad channels of din are written as +0.
+ *
+ * The shift and cut fields are integer-valued.  They are range-checked in float before any conversion (|v| <= 4096, false for a
+ * NaN) and then truncated towards zero; a row with one of the five outside that range has no source pixel that is provably
+ * inside: its valid channels come out as 0 (forward) and its g' is 0 (backward).  No index is formed from an unchecked value,
+ * so no access leaves the tensors whatever params holds.  b, s, c are used as they are.
+ *
+ * Two launches each: per-block double partial sums of every (row, frame) - the frame for the forward pass, the live pixels of
+ * dout for the adjoint - into the workspace, in a fixed order (each thread its strided share in ascending order, the lanes of a
+ * wave by shuffles, the waves in order), then one thread per pixel, which adds the partials in the same fixed way and streams
+ * the pixel.  No atomics: the same call gives the same bits.  16-byte accesses where pitch * 4 is a multiple of 16 and both
+ * bases are 16-byte aligned, element accesses otherwise, the same bits either way.  acg_d_augment_workspace_bytes is what both
+ * need (0 for arguments a launch would refuse); the workspace is 8-byte aligned and holds nothing between calls.
+ *
+ * acg_d_augment_draw: state uint64 [2] = {seed, counter} (laid out as the noise state above).  Row r uses the Philox4x32-10 blocks
+ * 2 r and 2 r + 1 with the counter words (lo32(counter), hi32(counter), block, stream_id ^ ACG_DA_STREAM_TAG) and the key
+ * (lo32(seed), hi32(seed)); with x0..x7 their eight words and m_i = x_i >> 9 (23 bits):
+ *   ACG_DA_COLOR        b = (m0 - 2^22) * 2^-23 in [-0.5, 0.5),  s = m1 * 2^-22 in [0, 2),  c = 0.5 + m2 * 2^-23 in [0.5, 1.5)
+ *   ACG_DA_TRANSLATION  Ry = (h + 4) / 8, Rx = (w + 4) / 8;  ty = ((m3 * (2 Ry + 1)) >> 23) - Ry,  tx likewise from m4 and Rx
+ *   ACG_DA_CUTOUT       n = (min(h, w) + 1) / 2;  cy0 = ((m5 * (h + 1)) >> 23) - n / 2,  cx0 = ((m6 * (w + 1)) >> 23) - n / 2
+ * (integer divisions, 64-bit products; m7 is not used); a group whose policy bit is clear gets (0, 1, 1), (0, 0), (0, 0, 0).  All
+ * of it is integer arithmetic or exact in float32.  Then state[1] = counter + 1: every thread has read the pair, a barrier,
+ * thread 0 stores.  One launch of one block.  Calls that share a state must be stream-ordered.
+ *
+ * 1 <= rows <= ACG_DA_ROWS_MAX, 1 <= frames <= 2, 1 <= cf <= 4, frames * cf <= pitch, 1 <= h, w <= 1024, 0 <= policy <= 7,
+ * in != out: a NULL pointer, a workspace that is NULL, misaligned or too small, or a value below its range is
+ * ACG_ERR_INVALID_ARG, a value above its range ACG_ERR_UNSUPPORTED; nothing is launched and nothing is written then. */
+#define ACG_DA_STREAM_TAG 0x44415547u
+#define ACG_DA_ROWS_MAX 1024
+#define ACG_DA_COLOR 1
+#define ACG_DA_TRANSLATION 2
+#define ACG_DA_CUTOUT 4
+int32_t acg_d_augment_draw(uint64_t* state, float* params, int32_t rows, int32_t h, int32_t w, int32_t policy, int32_t stream_id,
+                           acg_stream_t stream);
+int64_t acg_d_augment_workspace_bytes(int32_t rows, int32_t h, int32_t w, int32_t frames, int32_t cf);
+int32_t acg_d_augment_fwd(const float* in, const float* params, float* out, int32_t rows, int32_t h, int32_t w, int32_t pitch,
+                          int32_t frames, int32_t cf, void* workspace, int64_t workspace_bytes, acg_stream_t stream);
+int32_t acg_d_augment_bwd(const float* dout, const float* params, float* din, int32_t rows, int32_t h, int32_t w, int32_t pitch,
+                          int32_t frames, int32_t cf, void* workspace, int64_t workspace_bytes, acg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
